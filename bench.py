@@ -1,15 +1,19 @@
 #!/usr/bin/env python3
 """bench.py -- throughput of the batched voice chain on MI355X (one process per GPU).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
 
 A "step" is one pass of the hot path over one batch of synthetic input that is already
 resident in HBM: `--streams` independent 48 kHz mono streams x `--seconds` of audio
 through the chain (default: BASELINE.json configs[2] shape, batch 4096 x 10 s).  Rank 0
-prints ONE JSON line with BASELINE.json's metric (48 kHz mono frames/s, whole job), the
-roofline object for the dominant kernel (HIP-event timing taken inside this script on the
-stream the kernel runs on) and the CPU baseline (the KAT-pinned oracle timed on this
-host's cores on a bounded sample of the same workload).
+prints ONE JSON line with BASELINE.json's metric (48 kHz mono frames/s, whole job),
+`ms_per_step` and the roofline object for the dominant kernel (HIP-event timing taken
+inside this script on the stream the kernel runs on, during the timed steps).
+`--full` adds what needs runs of its own: the CPU baseline (the KAT-pinned oracle timed on
+this host's cores on a bounded sample of the same workload).
+`--dump-outputs DIR` writes a fixed sample of what the last timed step returned (see
+dump_outputs) so that two builds can be compared output for output; the input is the
+same deterministic synthetic batch on every run with the same arguments.
 """
 from __future__ import annotations
 
@@ -255,6 +259,47 @@ def cpu_baseline(seconds: float, full: bool, chain_settings: dict | None = None)
     }
 
 
+DUMP_SEED = 0x5EED
+DUMP_AUDIO_ROWS_BYTES = 32 << 20     # whole streams of output audio
+DUMP_AUDIO_COLUMNS_BYTES = 16 << 20  # every stream at a few sample positions
+DUMP_STATS_BYTES = 8 << 20           # per-block statistics of the whole streams above (64 MB in all at most)
+
+
+def dump_outputs(out_dir: pathlib.Path, audio: torch.Tensor, rows: np.ndarray) -> dict:
+    """`--dump-outputs`: what a caller of the timed path receives from its last step, sampled to fit 64 MB.
+
+      output_audio_streams.npy  f32 [S, L]  the output audio of S streams drawn with a fixed seed (whole streams, or
+                                            their first L samples when one stream alone is over the budget)
+      output_audio_columns.npy  f32 [B, P]  every stream's output (B = all streams) at P sample positions drawn with the
+                                            same seed
+      block_stats.npy           f64 [K, S, F] the engine's per-block statistics (STATS_DTYPE's fields but `reserved`, in
+                                            its order) of the same S streams, first K blocks
+
+    The draw depends on the shape alone, so two runs with the same arguments write the same positions."""
+    out_dir.mkdir(parents=True, exist_ok=True)
+    n_streams, n = audio.shape
+    rng = np.random.default_rng(DUMP_SEED)
+    s = min(n_streams, max(1, DUMP_AUDIO_ROWS_BYTES // (4 * n)))
+    length = min(n, DUMP_AUDIO_ROWS_BYTES // 4)
+    streams = np.sort(rng.choice(n_streams, size=s, replace=False))
+    p = min(n, max(1, DUMP_AUDIO_COLUMNS_BYTES // (4 * n_streams)))
+    columns = np.sort(rng.choice(n, size=p, replace=False))
+    b = min(n_streams, DUMP_AUDIO_COLUMNS_BYTES // (4 * p))  # (all of them below 4 M streams)
+    rows_t = torch.from_numpy(streams).to(audio.device)
+    cols_t = torch.from_numpy(columns).to(audio.device)
+    arrays = {
+        "output_audio_streams": audio.index_select(0, rows_t)[:, :length].to(torch.float32).cpu().numpy(),
+        "output_audio_columns": audio[:b].index_select(1, cols_t).to(torch.float32).cpu().numpy(),
+    }
+    fields = [f for f in rows.dtype.names if f != "reserved"]
+    k = min(rows.shape[0], max(1, DUMP_STATS_BYTES // (8 * s * len(fields))))
+    arrays["block_stats"] = np.stack([rows[:k, streams][f].astype(np.float64) for f in fields], axis=-1)
+    for name, arr in arrays.items():
+        np.save(out_dir / f"{name}.npy", np.ascontiguousarray(arr))
+    return {"dir": str(out_dir), "files": sorted(f"{name}.npy" for name in arrays),
+            "bytes": int(sum(a.nbytes for a in arrays.values())), "streams_sampled": int(s), "positions_sampled": int(p)}
+
+
 def launch_ranks(n: int) -> int:
     """`python bench.py --gpus N` without a launcher: start N ranks of this script (one per GPU, LOCAL_RANK = RANK) with a
     fresh rendezvous port and wait for them.  Runs BEFORE anything in this process touches a GPU (the parent never does:
@@ -312,7 +357,13 @@ def main() -> None:
     ap.add_argument("--seconds", type=float, default=10.0)
     ap.add_argument("--kernel", type=int, default=0)
     ap.add_argument("--variant", type=str, default="", help="lane | ring-<waves>x<chunk> (tuning)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what needs runs of its own: the CPU baseline (cpu_baseline); off by default, so that a "
+                         "plain run only sets up, warms up, times the steps and prints the line")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave the CPU baseline out")
+    ap.add_argument("--dump-outputs", type=pathlib.Path, default=None, metavar="DIR",
+                    help="after the timed steps, write a fixed sample of the last step's outputs to DIR/<name>.npy "
+                         "(float32 / float64, 64 MB at most; rank 0's shard)")
     ap.add_argument("--chain", choices=["full", "dynamics"], default="full",
                     help="full = DC/HP prefilter + RNNoise + EQ + compressor + limiter + true-peak (configs[2]); "
                          "dynamics = EQ + compressor + limiter + true-peak only (configs[1] chain)")
@@ -330,6 +381,8 @@ def main() -> None:
     args = ap.parse_args()
     if args.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("--steps must be >= 1 and --warmup >= 0")
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         # no launcher around us: become the launcher (nothing has touched a GPU yet)
@@ -437,6 +490,7 @@ def main() -> None:
     elapsed_max = merged["elapsed_s"]
     total_frames = int(merged["samples"])
     value = total_frames / elapsed_max
+    dumped = dump_outputs(args.dump_outputs, y, rows) if args.dump_outputs is not None and rank == 0 else None
     collective = None
     if distributed:
         collective = {"backend": dist.get_backend(), "world_size": dist.get_world_size(),
@@ -533,10 +587,13 @@ def main() -> None:
                        "max_compressor_gr_db": merged["compressor_gain_reduction_db"],
                        "true_peak_limited_blocks": int(merged["true_peak_limited_events"])},
         }
-        if not args.no_cpu_baseline and world == 1:  # the CPU baseline is a single-GPU-run artefact (rank 0, N = 1)
-            line["cpu_baseline"] = cpu_baseline(args.seconds, full, chain_settings)
-        elif world > 1:
-            line["cpu_baseline"] = None
+        if dumped is not None:
+            line["dump_outputs"] = dumped
+        if args.full:
+            if not args.no_cpu_baseline and world == 1:  # the CPU baseline is a single-GPU-run artefact (rank 0, N = 1)
+                line["cpu_baseline"] = cpu_baseline(args.seconds, full, chain_settings)
+            elif world > 1:
+                line["cpu_baseline"] = None
         print(json.dumps(line))
     engine.close()
     if distributed:
@@ -565,6 +622,9 @@ def run_stub(args, world: int, rank: int, streams: int, n: int, first_stream: in
     elapsed = time.perf_counter() - t0
     sums, maxes = sharding.local_metrics(engine.rows, streams * n * args.steps, elapsed)
     merged = sharding.reduce_metrics(sums, maxes, torch.device("cpu"))
+    dumped = None
+    if args.dump_outputs is not None and rank == 0:  # the stub passes its input through
+        dumped = dump_outputs(args.dump_outputs, torch.from_numpy(engine.x), engine.rows)
     if rank == 0:
         print(json.dumps({
             "metric": "48 kHz mono frames/s (real-time-factor x streams), voice chain", "stub": True,
@@ -575,6 +635,7 @@ def run_stub(args, world: int, rank: int, streams: int, n: int, first_stream: in
                        "sharding": f"streams x{world}, no data-path collective"},
             "collective": ({"backend": dist.get_backend(), "world_size": dist.get_world_size()} if dist.is_initialized() else None),
             "checks": {"total_samples": int(merged["samples"]), "input_square_sum": merged["input_square_sum"]},
+            **({"dump_outputs": dumped} if dumped is not None else {}),
         }))
     if dist.is_initialized():
         dist.destroy_process_group()

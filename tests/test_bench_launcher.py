@@ -56,3 +56,25 @@ def test_force_distributed_runs_the_collectives_with_one_gloo_rank():
     line = json.loads([ln for ln in proc.stdout.splitlines() if ln.startswith("{")][0])
     assert line["n_gpus"] == 1 and line["collective"]["backend"] == "gloo" and line["collective"]["world_size"] == 1
     assert line["checks"]["total_samples"] == 8 * 9600
+
+
+def test_dump_outputs_are_float_arrays_under_64_mb_and_reproducible(tmp_path):
+    """--dump-outputs DIR: the last step's outputs (the stub passes its input through) as float32 / float64 .npy files, the
+    same bytes from two runs with the same arguments."""
+    import numpy as np
+
+    dumps = []
+    for run in ("a", "b"):
+        out = tmp_path / run
+        proc = _run(["--gpus", "1", "--steps", "2", "--warmup", "1", "--streams", "8", "--seconds", "0.2", "--stub-engine",
+                     "--dump-outputs", str(out)])
+        assert proc.returncode == 0, proc.stderr[-2000:]
+        line = json.loads([ln for ln in proc.stdout.splitlines() if ln.startswith("{")][0])
+        files = sorted(p.name for p in out.glob("*.npy"))
+        assert files == line["dump_outputs"]["files"] and files
+        dumps.append({pathlib.Path(name).stem: np.load(out / name) for name in files})
+    assert sum(a.nbytes for a in dumps[0].values()) <= 64 << 20
+    for name, arr in dumps[0].items():
+        assert arr.dtype in (np.float32, np.float64), name
+        assert np.array_equal(arr, dumps[1][name]), name
+    assert np.any(dumps[0]["output_audio_streams"] != 0)

@@ -308,16 +308,15 @@ def test_dynamics_aliasing_report_pins(oracle):
 
 
 def test_fir_table_matches_reference_text_if_present():
-    """Only where the reference checkout exists (this container); skipped on the GPU box."""
+    """Both copies of the table against the reference's TRUE_PEAK_FIR coefficients (true_peak.rs), stored as data in
+    tests/golden/true_peak_fir.json."""
+    import json
     import pathlib
     import re
 
-    src = pathlib.Path("/root/reference/rust-core/src/dsp/true_peak.rs")
-    if not src.exists():
-        pytest.skip("reference checkout not present")
-    body = re.search(r"TRUE_PEAK_FIR[^=]*=\s*\[(.*?)\];\s*\n\s*#\[derive", src.read_text(), re.S).group(1)
-    ref = np.array([float(v) for v in re.findall(r"-?\d+\.\d+(?:e-?\d+)?", body)]).reshape(4, 32).astype(np.float32)
     root = pathlib.Path(__file__).resolve().parents[1]
+    fixture = json.loads((root / "tests" / "golden" / "true_peak_fir.json").read_text())
+    ref = np.array(fixture["coefficients"], dtype=np.float64).reshape(4, 32).astype(np.float32)
     for header in (root / "oracle" / "tp_fir_table.h", root / "audio-forge_amd" / "csrc" / "tp_fir_table.h"):
         vals = re.findall(r"-?0x[0-9a-f.]+p[-+]?\d+", header.read_text())
         mine = np.array([float.fromhex(v) for v in vals]).reshape(4, 32).astype(np.float32)
