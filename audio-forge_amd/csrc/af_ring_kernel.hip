@@ -70,9 +70,9 @@ __host__ __device__ inline size_t ring_lds_bytes(int n_sections, int lookahead, 
 // unit past the unit's token wait (earlier loads and pure arithmetic may legally move below an acquire), where it lengthens the
 // time the token is held -- the kernel's period is its longest unit.  -DAF_NO_FF_PINS builds without (A/B).
 // AF_PIN_MASK (A/B builds): 1 = in front of the peak-envelope unit, 2 = gain-reduction smoothing, 4 = limiter, 8 = true-peak
-// limiter, 16 = final fold, 32 = the linear gains in front of the auto-makeup build's meter unit.
+// limiter, 16 = final fold, 32 = the linear gains in front of the auto-makeup build's meter unit, 64 = the limiter's ring position.
 #ifndef AF_PIN_MASK
-#define AF_PIN_MASK (2 | 16 | 32)
+#define AF_PIN_MASK (2 | 16 | 32 | 64)
 #endif
 #define AF_PIN(bit, v) do { if constexpr (((AF_PIN_MASK) & (bit)) != 0) asm volatile("" : "+v"(v)); } while (0)
 constexpr int kAbortSlot = 32;
@@ -83,6 +83,16 @@ __shared__ unsigned g_prof[2][16][12];
 __shared__ long long g_prof_acq[16];
 __shared__ long long g_prof_ready[16];
 #endif
+// Assembly comments at a serial unit's edges (no instructions): tools/chain_unit_isa.py cuts the kernel's listing at them.  A unit whose
+// token is a loop variable (the EQ groups) is marked "eq".
+__device__ __forceinline__ void unit_marker_begin(int tok) {
+  if (__builtin_constant_p(tok)) asm volatile(";;#af-unit-begin %0" ::"i"(tok));
+  else asm volatile(";;#af-unit-begin eq");
+}
+__device__ __forceinline__ void unit_marker_end(int tok) {
+  if (__builtin_constant_p(tok)) asm volatile(";;#af-unit-end %0" ::"i"(tok));
+  else asm volatile(";;#af-unit-end eq");
+}
 __device__ __forceinline__ void token_wait(int *turn_base, int tok, int q) {
   __builtin_amdgcn_sched_barrier(0);
 #ifdef AF_TOKEN_PROFILE
@@ -102,6 +112,7 @@ __device__ __forceinline__ void token_wait(int *turn_base, int tok, int q) {
   // a wave inside a serial unit is on the workgroup's critical path: it issues ahead of the three feed-forward waves
   // that share its SIMD (measured: 257 -> 240 ms of chain time per bench step)
   __builtin_amdgcn_s_setprio(3);
+  unit_marker_begin(tok);
 #ifdef AF_TOKEN_PROFILE
   if ((threadIdx.x & 63) == 0) {
     const long long t1 = clock64();
@@ -113,6 +124,7 @@ __device__ __forceinline__ void token_wait(int *turn_base, int tok, int q) {
 }
 __device__ __forceinline__ void token_pass(int *turn_base, int tok, int q) {
   __builtin_amdgcn_sched_barrier(0);  // ... and nothing that can wait until after the hand-over delays it
+  unit_marker_end(tok);
 #ifdef AF_TOKEN_PROFILE
   if ((threadIdx.x & 63) == 0) g_prof[1][threadIdx.x >> 6][tok] += (unsigned)(clock64() - g_prof_acq[threadIdx.x >> 6]);
 #endif
@@ -565,13 +577,17 @@ __global__ __launch_bounds__(kRingWaves *kLanes) void chain_ring_kernel(LaunchAr
   #pragma unroll
         for (int k = 0; k < kChunk; ++k)
           if (kFull || k < len) AF_PIN(1, inst_peak_db[k]);
+        // Both coefficients as values, selected per lane.  Written as `cond ? cp.attack_coeff : cp.detector_release_coeff`,
+        // LLVM folds the two scalar loads into ONE load from a per-lane address -- a global load behind s_waitcnt vmcnt(0) on
+        // every sample of the unit, four dependent round trips to L2 while the token is held.
+        const double pe_attack = cp.attack_coeff, pe_release = cp.detector_release_coeff;
         token_wait(turn, kTokCompC, q);
         {
           double pe = L64(kR64PeakEnvDb);
   #pragma unroll
           for (int k = 0; k < kChunk; ++k)
             if (kFull || k < len) {
-              const double pk = inst_peak_db[k] > pe ? cp.attack_coeff : cp.detector_release_coeff;
+              const double pk = inst_peak_db[k] > pe ? pe_attack : pe_release;
               pe = pk * pe + (1.0 - pk) * inst_peak_db[k];
               peak_db[k] = pe;
             }
@@ -776,12 +792,14 @@ __global__ __launch_bounds__(kRingWaves *kLanes) void chain_ring_kernel(LaunchAr
   #pragma unroll
         for (int k = 0; k < kChunk; ++k)
           if (kFull || k < len) AF_PIN(4, x[k]);  // (the compressor's gain applied: an exp10 per sample)
+        // the ring position: a 64-bit remainder (~100 instructions) that LLVM would otherwise sink into the unit
+        int j = (int)((n0 + t0) % W);
+        AF_PIN(64, j);
         token_wait(turn, kTokLim, q);
         {
           double g = L64(kR64LimGain);
           double gmin = first_in_block ? 1.0 : L64(kR64LimGmin);
           float prefix = L32(kR32LimPrefix);
-          int j = (int)((n0 + t0) % W);
   #pragma unroll
           for (int k = 0; k < kChunk; ++k)
             if (kFull || k < len) {
@@ -815,7 +833,13 @@ __global__ __launch_bounds__(kRingWaves *kLanes) void chain_ring_kernel(LaunchAr
                 }
               }
               j = jn;
-              const double tg = peak > ceil_lin ? ceil_lin / peak : 1.0;
+              // (limiter.rs: the quotient only where the peak is over the ceiling; a wave with no lane over it skips the f64
+              // division sequence -- a scalar branch -- and the lanes that take it get the same quotient as before)
+              double tg = 1.0;
+              if (__builtin_amdgcn_ballot_w64(peak > ceil_lin) != 0) {
+                tg = peak > ceil_lin ? ceil_lin / peak : 1.0;
+                asm volatile("" : "+v"(tg));  // (or LLVM speculates the division above the branch and selects)
+              }
               if (tg < g) {
                 g = tg;
               } else {
