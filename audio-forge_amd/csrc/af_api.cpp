@@ -1758,11 +1758,15 @@ int af_engine_process_device(af_engine *e, const float *in, float *out, int64_t 
       }();
       const bool auto_mk = (hp.flags & af::kFlagCompressor) && hp.comp.auto_makeup_enabled;
       const int64_t window = (int64_t)cb * std::max<int64_t>(1, 9600 / cb);
+      // (the chain launch lays out its LDS for a crossfade only when one is pending at the call's start, as
+      // launch_chain_segment sizes it: checking the crossfade layout always kept 15 and 16 sections off this form)
+      bool xf_now = false;
+      for (int j = 0; j < hp.n_eq_sections; ++j) xf_now = xf_now || hp.eq[j].xf_remaining > 0;
       bool offload = one_launch_calls_enabled() && eq_offload_on && (e->kernel == AF_KERNEL_AUTO || e->kernel == AF_KERNEL_PHASED) &&
                      (e->ring_variant == 0 || e->ring_variant == 1604) && e->extra_presets.empty() && roles_mode() == 0 &&
                      layout == AF_LAYOUT_STREAM_MAJOR && (hp.flags & af::kFlagEq) && hp.n_eq_sections > 0 && hp.n_eq_sections <= 16 &&
                      !(hp.flags & (af::kFlagDeesser | af::kFlagDcBlock | af::kFlagPreHighpass | af::kFlagPrePass)) &&
-                     af::ring_kernel_dynamic_lds(hp.n_eq_sections, hp.lim.lookahead_samples, true) <= af::kMaxLdsBytes &&
+                     af::ring_kernel_dynamic_lds(hp.n_eq_sections, hp.lim.lookahead_samples, xf_now) <= af::kMaxLdsBytes &&
                      n_samples >= 2 * window && !std::getenv("AF_SERIAL_STREAMS");
       if (offload) {
         if (int rc = ensure_side_streams(e, stream)) return rc;

@@ -300,3 +300,104 @@ def aliasing_case_metrics(base_output: np.ndarray, reference_output: np.ndarray,
         reference, candidate = reference[trim:-trim], candidate[trim:-trim]
     return {"alignment_lag_samples": lag, "relative_waveform_error_db": relative_error_db(reference, candidate),
             "folded_out_of_expected_error_db": folded_error_db(reference, candidate, carrier_hz, modulation_hz)}
+
+
+# ------------------------------------------------------------------------------------------------------------------
+# Mixed-lane stimulus for the chain kernels, whose lanes are streams: one wave holds 64 streams, and the limiter's
+# division runs under a wave-wide branch (any lane over the ceiling).  Built so that waves split at the same sample.
+LANE_MIX_GROUP = 64
+LANE_MIX_UNDER_GROUP, LANE_MIX_OVER_GROUP = 1, 2  # group kinds by index; every other group is a mixed one
+
+
+def lane_mix_kind(group: int) -> str:
+    return {LANE_MIX_UNDER_GROUP: "under", LANE_MIX_OVER_GROUP: "over"}.get(group, "mixed")
+
+
+def _lane_mix_roles() -> list[tuple[str, int]]:
+    """The 64 lanes of a mixed group before the group's own permutation: (role, index within the role)."""
+    counts = (("voiced", 37), ("loud_section", 12), ("square", 2), ("clipped", 2), ("impulses", 3), ("silent", 2),
+              ("dc", 2), ("out_of_range", 2), ("non_finite", 2))
+    roles = [(role, k) for role, count in counts for k in range(count)]
+    assert len(roles) == LANE_MIX_GROUP
+    return roles
+
+
+def _edge_positions(n: int) -> np.ndarray:
+    """Samples on both sides of 4-sample chunk, 480-sample control-block and 9600-sample window edges."""
+    chunk = np.arange(4 * 97, n, 4 * 997)
+    block = np.arange(480 * 7, n, 480 * 11)
+    window = np.arange(9600, n, 9600)
+    edges = np.concatenate([chunk, block, window])
+    edges = np.concatenate([edges - 1, edges])
+    return np.unique(edges[(edges >= 0) & (edges < n)])
+
+
+def lane_mix_batch(n_streams: int, n_samples: int, seed: int = 0) -> np.ndarray:
+    """[n_streams, n_samples] float32, deterministic in `seed`.  Every group of 64 streams is one of three kinds
+    (`lane_mix_kind`): "mixed" groups hold voiced streams whose peak levels spread from -60 to +12 dBFS, voiced streams
+    with a loud section starting at staggered offsets, full-scale squares and clipped two-tones (inter-sample overs),
+    impulses at chunk / control-block / window edges, silence, DC offsets, +-4.0 samples and, in every eighth mixed group,
+    NaN / +-Inf samples; in the "under" group every stream stays well under a -1.5 dBFS ceiling; in the "over" group every
+    stream is loud (over the ceiling) during a span whose ends are staggered, so that the group's lanes are all under,
+    some over and all over at different times.  Lanes are permuted differently in every group."""
+    rng = np.random.default_rng(seed)
+    n = int(n_samples)
+    n_blocks = max(1, -(-n // 480))
+    bases = []
+    for i in range(16):  # voiced material, normalised to a peak of 1.0 (a gain in dB is then the peak level in dBFS)
+        v = kat_signal(n_blocks, *stream_params(i)).astype(np.float64)[:n]
+        bases.append(v / max(float(np.max(np.abs(v))), 1e-12))
+    t = np.arange(n, dtype=np.float64)
+    db = lambda g: 10.0 ** (np.asarray(g, dtype=np.float64) / 20.0)  # noqa: E731
+    roles = _lane_mix_roles()
+    edges = _edge_positions(n)
+    out = np.empty((n_streams, n), dtype=np.float32)
+    for g0 in range(0, n_streams, LANE_MIX_GROUP):
+        group = g0 // LANE_MIX_GROUP
+        kind = lane_mix_kind(group)
+        lanes = min(LANE_MIX_GROUP, n_streams - g0)
+        order = rng.permutation(LANE_MIX_GROUP)
+        voiced_gain = rng.permutation(np.linspace(-60.0, 12.0, 37))
+        offsets = rng.permutation(np.linspace(0.08, 0.72, 12)) * n + rng.integers(0, 480, 12)
+        for lane in range(lanes):
+            k_all = int(order[lane])
+            base = bases[(k_all + 5 * group) % 16]
+            if kind == "under":
+                x = base * db(-60.0 + 54.0 * k_all / (LANE_MIX_GROUP - 1))  # -60 .. -6 dBFS
+            elif kind == "over":
+                start = (0.10 + 0.15 * k_all / LANE_MIX_GROUP) * n + 37 * k_all
+                stop = (0.65 + 0.15 * ((k_all * 29) % LANE_MIX_GROUP) / LANE_MIX_GROUP) * n
+                loud = (t >= start) & (t < stop)
+                x = base * np.where(loud, db(6.0 + 6.0 * k_all / LANE_MIX_GROUP), db(-30.0 + 12.0 * k_all / LANE_MIX_GROUP))
+            else:
+                role, k = roles[k_all]
+                if role == "voiced":
+                    x = base * db(voiced_gain[k])
+                elif role == "loud_section":
+                    loud = (t >= offsets[k]) & (t < offsets[k] + n // 6)
+                    x = base * np.where(loud, db(3.0 + k * 0.75), db(-24.0))
+                elif role == "square":
+                    x = np.where(np.sin(2.0 * np.pi * (997.0 + 2004.0 * k) * t / SAMPLE_RATE + 0.3 * group) >= 0.0, 1.0, -1.0)
+                elif role == "clipped":
+                    x = np.clip(0.9 * np.sin(2.0 * np.pi * (180.0 + 40.0 * k) * t / SAMPLE_RATE)
+                                + 0.6 * np.sin(2.0 * np.pi * (2300.0 + 700.0 * k) * t / SAMPLE_RATE + group), -1.0, 1.0)
+                elif role == "impulses":
+                    x = base * db(-40.0)
+                    x[edges] = np.where(np.arange(edges.size) % 2 == 0, 1.3, -0.95) * (1.0 - 0.2 * k)
+                elif role == "silent":
+                    x = np.zeros(n)
+                elif role == "dc":
+                    x = (0.5 if k == 0 else -0.95) + base * db(-26.0)
+                elif role == "out_of_range":
+                    x = base * db(-6.0)
+                    x[(997 * (k + 1)) % 1553 :: 1553] = 4.0
+                    x[(499 + 331 * k) % 2039 :: 2039] = -4.0
+                else:  # non_finite
+                    x = base * db(-3.0 * k)
+                    if group % 8 == 0:
+                        x = x.copy()
+                        x[edges[k::9]] = np.nan
+                        x[edges[3 + k :: 11]] = np.inf
+                        x[edges[5 + k :: 13]] = -np.inf
+            out[g0 + lane] = x
+    return out

@@ -368,3 +368,28 @@ def test_auto_makeup_inside_full_chain(mi, oracle):
         max_abs, rms = _err(out[s], want["output_audio"])
         assert max_abs <= 5e-7 and rms <= 5e-8, (s, max_abs, rms)
         _compare_dicts(results[s], want)
+
+
+_LANE_MIX_ORACLE = {}
+
+
+def test_lane_mix_batch_matches_oracle(mi, oracle):
+    """The mixed-lane stimulus (signals.lane_mix_batch: waves split over / under the limiter ceiling at the same sample,
+    squares, edge impulses, silence, DC, +-4.0 and non-finite samples), compressor off: every one of the 130 streams
+    bit-exact, rows and summaries as in test_limiter_and_true_peak_without_compressor_bit_exact."""
+    n_streams, n = 130, 24_000
+    audio = S.lane_mix_batch(n_streams, n, 7)
+    settings = dict(S.limiter_settings(2.0), compressor_enabled=False)
+    if not _LANE_MIX_ORACLE:  # (computed once, for every variant)
+        from concurrent.futures import ThreadPoolExecutor
+
+        with ThreadPoolExecutor(max_workers=16) as pool:
+            wants = list(pool.map(lambda s: oracle.simulate_auto_eq_chain(audio[s], 48_000, S.LIMITER_BANDS, settings),
+                                  range(n_streams)))
+        _LANE_MIX_ORACLE["want"] = wants
+    wants = _LANE_MIX_ORACLE["want"]
+    out, results = mi.simulate_auto_eq_chain_batch(audio, 48_000, S.LIMITER_BANDS, settings)
+    differ = [s for s in range(n_streams) if not np.array_equal(out[s].view(np.uint32), wants[s]["output_audio"].view(np.uint32))]
+    assert not differ, (differ[:8], [_err(out[s], wants[s]["output_audio"]) for s in differ[:4]])
+    for s in range(n_streams):
+        _compare_dicts(results[s], wants[s], exact_keys=("true_peak_limited_events", "processed_samples"))
