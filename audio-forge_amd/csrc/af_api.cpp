@@ -214,8 +214,16 @@ struct af_engine {
   // 12 -> 165.2, 14 -> 166.1, 16 -> 163.2, 18 -> 164.5, 20 -> 165.0, 24 -> 166.7, 32 -> 169.2
   int supp_window_frames = 16;
   hipEvent_t ev_start = nullptr, ev_stop = nullptr, ev_mid = nullptr;  // start | suppressor done | chain done
+  // the noise gate stage (realtime stage 1, dsp_loop.rs:1371-1435): engine-wide parameters, live between calls; per-stream
+  // state in `d_gate` ([af::kGateFields][stream], zero = NoiseGate's initial state), allocated at the first gated call and
+  // touched only by the pre-pass that gates
+  bool gate_enabled = false;
+  double gate_threshold_db = -40.0, gate_attack_ms = 10.0, gate_release_ms = 100.0;  // NoiseGate::new(-40, 10, 100, fs)
+  int gate_mode = 0;                 // 0 ThresholdOnly, 1 VadAssisted, 2 VadOnly
+  int64_t *d_gate = nullptr;
+  double sample_rate;
 
-  af_engine(double fs, int n, int dev) : proto(fs), n_streams(n), device(dev) {}
+  af_engine(double fs, int n, int dev) : proto(fs), n_streams(n), device(dev), sample_rate(fs) {}
 };
 
 namespace {
@@ -523,6 +531,33 @@ void advance_crossfades(af_engine *e, int64_t n) {
     }
   }
  }
+}
+
+// The gate's parameters and state pointer on a pre-pass launch (gate.rs:158-225 for the derived constants).
+void gate_args(const af_engine *e, af::SuppArgs &sa) {
+  const double fs = e->sample_rate;
+  sa.gate = 1;
+  sa.gate_state = e->d_gate;
+  sa.gate_thr = e->gate_threshold_db;
+  sa.gate_rms_c = af::time_constant_to_coeff(8.0, fs);
+  sa.gate_rms_omc = 1.0 - sa.gate_rms_c;
+  sa.gate_atk = af::time_constant_to_coeff(e->gate_attack_ms, fs);
+  sa.gate_atk_omc = 1.0 - sa.gate_atk;
+  sa.gate_rel = af::time_constant_to_coeff(e->gate_release_ms, fs);
+  sa.gate_rel_omc = 1.0 - sa.gate_rel;
+  sa.gate_hold = (int32_t)std::round(fs * 50.0 / 1000.0);
+  sa.gate_window = (int32_t)std::round(fs * 500.0 / 1000.0);
+  sa.gate_cooldown = (int32_t)std::round(fs * 1000.0 / 1000.0);
+  sa.gate_relax = (int32_t)std::round(fs * 700.0 / 1000.0);
+  sa.gate_vad_mode = e->gate_mode != 0 ? 1 : 0;
+}
+
+// Without the suppressor, the front end runs in the gated pre-pass when the gate is on -- and for the whole stream when the
+// chain's form was chosen with the front end stripped: the stage pipeline does not build the DC block / high-pass, and the
+// choice holds until a reset, while the gate can be switched off between calls.
+bool front_end_in_gate_prepass(const af_engine *e) {
+  if (e->supp.enabled) return false;
+  return e->gate_enabled || (e->pipe.active && (e->host_params.flags & (af::kFlagDcBlock | af::kFlagPreHighpass)));
 }
 
 // Several presets in one engine: one launch of the token-ring kernel, the workgroup of every 64-stream group reading its
@@ -1345,6 +1380,10 @@ void af_engine_destroy(af_engine *e) {
     (void)hipSetDevice(e->device);
     e->supp.release_all();
   }
+  if (e->d_gate) {
+    (void)hipSetDevice(e->device);
+    (void)hipFree(e->d_gate);
+  }
   delete e;
 }
 
@@ -1364,6 +1403,10 @@ int af_engine_reset(af_engine *e) {
   e->pending = 0;
   e->last_output_samples = 0;
   e->trace_frames = 0;
+  if (e->d_gate) {  // NoiseGate::reset, gate.rs:759-785: every state field back to its initial value
+    AF_HIP(hipSetDevice(e->device));
+    AF_HIP(hipMemset(e->d_gate, 0, sizeof(int64_t) * af::kGateFields * e->n_streams));
+  }
   return AF_OK;
 }
 
@@ -1498,6 +1541,75 @@ int af_engine_set_suppressor_strength(af_engine *e, float strength) {  // rnnois
   e->supp.strength = af::clampf(strength, 0.0f, 1.0f);
   return AF_OK;
 }
+// ---- noise gate stage: live between calls, like the realtime apply_gate_control (processor/control.rs:851-865); the
+// ranges are the realtime processor's (audio/processor.rs:77-82), a non-finite value leaves the setting as it is
+// (clamp_control_value, control.rs:50-52)
+namespace {
+void gate_control(double v, double lo, double hi, double *dst) {
+  if (std::isfinite(v)) *dst = v < lo ? lo : (v > hi ? hi : v);
+}
+}  // namespace
+int af_engine_set_gate_enabled(af_engine *e, int32_t on) {
+  if (!e) return fail(AF_ERR_INVALID_ARGUMENT, "engine is null");
+  e->gate_enabled = on != 0;
+  return AF_OK;
+}
+int32_t af_engine_gate_enabled(const af_engine *e) { return e && e->gate_enabled ? 1 : 0; }
+int af_gate_set_threshold(af_engine *e, double threshold_db) {
+  if (!e) return fail(AF_ERR_INVALID_ARGUMENT, "engine is null");
+  gate_control(threshold_db, -80.0, -10.0, &e->gate_threshold_db);
+  return AF_OK;
+}
+int af_gate_set_attack_time(af_engine *e, double attack_ms) {
+  if (!e) return fail(AF_ERR_INVALID_ARGUMENT, "engine is null");
+  gate_control(attack_ms, 0.1, 100.0, &e->gate_attack_ms);
+  return AF_OK;
+}
+int af_gate_set_release_time(af_engine *e, double release_ms) {
+  if (!e) return fail(AF_ERR_INVALID_ARGUMENT, "engine is null");
+  gate_control(release_ms, 10.0, 1000.0, &e->gate_release_ms);
+  return AF_OK;
+}
+int af_gate_set_mode(af_engine *e, int32_t mode) {  // gate_controls.rs:75-81; gate.rs:812-821
+  if (!e) return fail(AF_ERR_INVALID_ARGUMENT, "engine is null");
+  if (mode < 0 || mode > 2) return fail(AF_ERR_INVALID_ARGUMENT, "Invalid gate mode");
+  e->gate_mode = mode;
+  if (mode == 0 && e->d_gate) {  // set_gate_mode(ThresholdOnly) clears the auto-relax counter at once
+    AF_HIP(hipSetDevice(e->device));
+    AF_HIP(hipDeviceSynchronize());
+    AF_HIP(hipMemset(e->d_gate + (int64_t)af::kGateRelax * e->n_streams, 0, sizeof(int64_t) * e->n_streams));
+  }
+  return AF_OK;
+}
+double af_gate_threshold_db(const af_engine *e) { return e ? e->gate_threshold_db : 0.0; }
+int af_engine_read_gate_state(af_engine *e, float *current_gain, uint64_t *chatter_events, int32_t *flags, int32_t n_streams) {
+  if (!e) return fail(AF_ERR_INVALID_ARGUMENT, "engine is null");
+  if (n_streams < 0 || n_streams > e->n_streams)
+    return fail(AF_ERR_INVALID_ARGUMENT, "n_streams %d is outside [0, %d]", n_streams, e->n_streams);
+  const int64_t NS = e->n_streams;
+  std::vector<int64_t> rows;
+  if (e->d_gate) {
+    rows.resize((size_t)(af::kGateFields * NS));
+    AF_HIP(hipSetDevice(e->device));
+    AF_HIP(hipDeviceSynchronize());
+    AF_HIP(hipMemcpy(rows.data(), e->d_gate, sizeof(int64_t) * rows.size(), hipMemcpyDeviceToHost));
+  }
+  for (int32_t s = 0; s < n_streams; ++s) {
+    double gain = 0.0;
+    int64_t events = 0, open = 0, relax = 0;
+    if (!rows.empty()) {
+      std::memcpy(&gain, &rows[(size_t)(af::kGateGain * NS + s)], sizeof(double));
+      events = rows[(size_t)(af::kGateEvents * NS + s)];
+      open = rows[(size_t)(af::kGateOpen * NS + s)];
+      relax = rows[(size_t)(af::kGateRelax * NS + s)];
+    }
+    if (current_gain) current_gain[s] = (float)gain;  // NoiseGate::current_gain
+    if (chatter_events) chatter_events[s] = (uint64_t)events;
+    if (flags) flags[s] = (open ? 1 : 0) | (relax > 0 ? 2 : 0);
+  }
+  return AF_OK;
+}
+
 int af_suppressor_set_raw_protocol(af_engine *e, int32_t on) { AF_SETTER(e->supp.raw_protocol = on != 0); }
 int af_suppressor_set_synthetic_weights(af_engine *e, uint64_t seed) {
   AF_SETTER((af::synthetic_weights(e->supp.weights, seed), e->supp.weights_dirty = true));
@@ -1603,6 +1715,7 @@ int af_engine_process_device(af_engine *e, const float *in, float *out, int64_t 
   int64_t src_stride = stream_stride;
   const int64_t n_in = n_samples;
   int64_t n_run = n_samples, rem = 0;
+  if (e->gate_enabled && layout != AF_LAYOUT_STREAM_MAJOR) return fail(AF_ERR_UNSUPPORTED, "the noise gate needs stream-major audio");
   if (e->supp.enabled) {
     if (layout != AF_LAYOUT_STREAM_MAJOR) return fail(AF_ERR_UNSUPPORTED, "the suppressor needs stream-major audio");
     const int64_t total = e->pending + n_in;
@@ -1620,7 +1733,7 @@ int af_engine_process_device(af_engine *e, const float *in, float *out, int64_t 
                 (long long)blocks, (long long)e->vad_blocks);
   if (n_run > 0 && !e->pipe.decided) {  // first call after a reset: which form of the chain this engine runs
     af::ChainParams probe = e->host_params;
-    if (e->supp.enabled) probe.flags &= ~(af::kFlagInputClamp | af::kFlagDcBlock | af::kFlagPreHighpass | af::kFlagInputScrub);
+    if (e->supp.enabled || e->gate_enabled) probe.flags &= ~(af::kFlagInputClamp | af::kFlagDcBlock | af::kFlagPreHighpass | af::kFlagInputScrub);
     const bool serves = stage_pipe_serves(e, probe, layout);
     static const int env_staged = [] {  // AF_STAGED=0 / 1: keep AUTO off / on the stage pipeline (A/B runs)
       const char *env = std::getenv("AF_STAGED");
@@ -1640,7 +1753,13 @@ int af_engine_process_device(af_engine *e, const float *in, float *out, int64_t 
     if (e->pipe.active)
       if (int rc = stage_pipe_clear(e)) return rc;
   }
+  if (front_end_in_gate_prepass(e) && layout != AF_LAYOUT_STREAM_MAJOR)
+    return fail(AF_ERR_UNSUPPORTED, "this engine runs its front end in the noise gate's pre-pass, which needs stream-major audio");
   // ---- accepted: from here on the call only fails on a backend error
+  if (e->gate_enabled && !e->d_gate) {
+    AF_HIP(hipMalloc(&e->d_gate, sizeof(int64_t) * af::kGateFields * e->n_streams));
+    AF_HIP(hipMemset(e->d_gate, 0, sizeof(int64_t) * af::kGateFields * e->n_streams));
+  }
   e->last_stream = stream;
   (void)collect_retired(e, false);
   if (e->supp.enabled) {
@@ -1695,6 +1814,36 @@ int af_engine_process_device(af_engine *e, const float *in, float *out, int64_t 
   for (auto &pr : e->chain_ms_events) { (void)hipEventDestroy(pr.first); (void)hipEventDestroy(pr.second); }
   e->chain_ms_events.clear();
 
+  // ---- The noise gate without the suppressor: the front end and the gate run as the pre-pass (`in` -> `out`, on this stream),
+  // and the chain then runs on `out` in place with the front end's flags stripped, as it does behind the suppressor.
+  const uint32_t gate_strip = front_end_in_gate_prepass(e)
+                                  ? (af::kFlagInputScrub | af::kFlagInputClamp | af::kFlagDcBlock | af::kFlagPreHighpass) : 0u;
+  const float *chain_in = in;
+  if (gate_strip) {
+    const af::ChainParams &hp = e->host_params;
+    af::SuppArgs sa{};
+    sa.in = in;
+    sa.in_stride = stream_stride;
+    sa.out = out;
+    sa.stream_stride = stream_stride;
+    sa.n_streams = e->n_streams;
+    sa.n_samples = n_samples;
+    sa.front_scrub = (hp.flags & af::kFlagInputScrub) ? 1 : 0;
+    sa.front_clamp = (hp.flags & af::kFlagInputClamp) ? 1 : 0;
+    sa.front_dc = (hp.flags & af::kFlagDcBlock) ? 1 : 0;
+    sa.front_hp = (hp.flags & af::kFlagPreHighpass) ? 1 : 0;
+    sa.hp_b0 = hp.pre_hp.b0; sa.hp_b1 = hp.pre_hp.b1; sa.hp_b2 = hp.pre_hp.b2;
+    sa.hp_a1 = hp.pre_hp.a1; sa.hp_a2 = hp.pre_hp.a2;
+    sa.chain_st64 = e->d_st64;
+    sa.chain_st32 = e->d_st32;
+    sa.f64_pre_z1 = af::kPreZ1;
+    sa.f32_dc_x1 = af::kDcX1;
+    if (e->gate_enabled) gate_args(e, sa);  // (else the pass runs the front end alone and leaves the gate's state alone)
+    AF_HIP(af::launch_gate_prepass(sa, stream));
+    e->last_launches += 1;
+    if (e->timing) AF_HIP(hipEventRecord(e->ev_mid, stream));  // the pre-pass counts as suppressor-side time
+    chain_in = out;
+  }
   if (!e->supp.enabled && e->pipe.active) {
     // ---- the chain as a pipeline of stage kernels over windows of whole control blocks (af_stages.hip)
     // (a launch step costs ~20 us, the pipeline's fill is depth x window time: 960 samples 45.7 ms per 10 s at 256 streams,
@@ -1702,7 +1851,7 @@ int af_engine_process_device(af_engine *e, const float *in, float *out, int64_t 
     int64_t tw = (int64_t)cb * std::max<int64_t>(1, 2880 / cb);
     if (const char *env = std::getenv("AF_STAGE_WINDOW")) tw = (int64_t)cb * std::max<int64_t>(1, std::atoll(env) / cb);
     if (int rc = stage_pipe_prepare(e, std::max<int64_t>(tw, e->pipe.tw_max))) return rc;
-    e->pipe.strip = 0;
+    e->pipe.strip = e->host_params.flags & gate_strip;
     if (int rc = stage_chain_params(e, stream)) return rc;  // what the stage kernels read (everything but the EQ sections)
     e->last_kernel_used = AF_KERNEL_STAGED;
     {
@@ -1719,7 +1868,7 @@ int af_engine_process_device(af_engine *e, const float *in, float *out, int64_t 
         wd.mk = e->pipe.d_mk + ((e->pipe.windows + (int64_t)wins.size()) % af_engine::StagePipe::kMkSets) * e->pipe.mk_rows;
         wd.bp = e->pipe.d_bp + ((e->pipe.windows + (int64_t)wins.size()) % af_engine::StagePipe::kBpSets) * e->pipe.mk_rows;
         wd.vad = e->has_evidence ? e->d_vad + blocks_at * e->n_streams : nullptr;
-        wd.in = in + t0;
+        wd.in = chain_in + t0;
         wd.out = out + t0;
         wins.push_back(wd);
         blocks_at += (n_w + cb - 1) / cb;
@@ -1738,7 +1887,7 @@ int af_engine_process_device(af_engine *e, const float *in, float *out, int64_t 
       }
       e->pipe.windows += (int64_t)wins.size();
       if (e->timing) {
-        AF_HIP(hipEventRecord(e->ev_mid, stream));
+        if (!gate_strip) AF_HIP(hipEventRecord(e->ev_mid, stream));
         AF_HIP(hipEventRecord(e->ev_stop, stream));
       }
       e->samples_processed += n_samples;
@@ -1751,7 +1900,8 @@ int af_engine_process_device(af_engine *e, const float *in, float *out, int64_t 
     // window, and the chain is ONE launch that follows it through the ready counter (the form the suppressor's pipeline
     // uses).  Taken when the streams can be CU-partitioned and the EQ kernel serves the configuration.
     {
-      const af::ChainParams &hp = e->host_params;
+      af::ChainParams hp = e->host_params;  // (a copy: with the gate on, the front end is the pre-pass's)
+      hp.flags &= ~gate_strip;
       static const bool eq_offload_on = [] {
         const char *env = std::getenv("AF_EQ_OFFLOAD");
         return !env || std::atoi(env) != 0;
@@ -1803,13 +1953,14 @@ int af_engine_process_device(af_engine *e, const float *in, float *out, int64_t 
         for (int64_t seg0 = 0; seg0 < n_samples; seg0 += window) {
           const int64_t seg_n = std::min<int64_t>(window, n_samples - seg0);
           std::vector<af::ChainParams> run_eq(1, e->host_params);  // (as the crossfade counters stand at this window)
+          run_eq[0].flags &= ~gate_strip;
           bool xf_w = false;
           for (int j = 0; j < run_eq[0].n_eq_sections; ++j) xf_w = xf_w || run_eq[0].eq[j].xf_remaining > 0;
           if (e->uploaded_eq.size() != 1 || std::memcmp(e->uploaded_eq.data(), run_eq.data(), sizeof(af::ChainParams)) != 0) {
             e->uploaded_eq = run_eq;
             if (int rc = stage_upload(e, e->d_params_eq, run_eq.data(), 1, e->eq_stream)) return rc;
           }
-          AF_HIP(af::launch_eq_systolic(e->d_params_eq, nullptr, e->d_st64, in + seg0, out + seg0, nullptr, nullptr, 0, 0,
+          AF_HIP(af::launch_eq_systolic(e->d_params_eq, nullptr, e->d_st64, chain_in + seg0, out + seg0, nullptr, nullptr, 0, 0,
                                         e->d_stats + blocks_done * e->n_streams, xf_w, seg_n, stream_stride, e->n_streams, e->eq_stream,
                                         auto_mk ? e->d_block_power + blocks_done * e->n_streams : nullptr));  // (the systolic form: here the EQ's own latency per window is what the chain follows)
           AF_HIP(af::launch_chain_publish_ready(e->d_ready, seg0 + seg_n, e->eq_stream));
@@ -1823,18 +1974,26 @@ int af_engine_process_device(af_engine *e, const float *in, float *out, int64_t 
           AF_HIP(hipStreamWaitEvent(stream, ev, 0));
         }
         if (e->timing) {
-          AF_HIP(hipEventRecord(e->ev_mid, stream));
+          if (!gate_strip) AF_HIP(hipEventRecord(e->ev_mid, stream));
           AF_HIP(hipEventRecord(e->ev_stop, stream));
         }
         e->samples_processed += n_samples;
         return AF_OK;
       }
     }
-    int rc = launch_chain_segment(e, e->host_params, false, in, out, n_samples, stream_stride, layout, e->samples_processed,
-                                  e->d_stats, e->has_evidence ? e->d_vad : nullptr, stream, stream);
+    int rc;
+    if (gate_strip) {
+      af::ChainParams run_g = e->host_params;
+      run_g.flags &= ~gate_strip;
+      rc = launch_chain_segment(e, run_g, true, chain_in, out, n_samples, stream_stride, layout, e->samples_processed,
+                                e->d_stats, e->has_evidence ? e->d_vad : nullptr, stream, stream);
+    } else {
+      rc = launch_chain_segment(e, e->host_params, false, in, out, n_samples, stream_stride, layout, e->samples_processed,
+                                e->d_stats, e->has_evidence ? e->d_vad : nullptr, stream, stream);
+    }
     if (rc) return rc;
     if (e->timing) {
-      AF_HIP(hipEventRecord(e->ev_mid, stream));  // no suppressor: everything is chain time
+      if (!gate_strip) AF_HIP(hipEventRecord(e->ev_mid, stream));  // no suppressor: everything is chain time
       AF_HIP(hipEventRecord(e->ev_stop, stream));
     }
     e->samples_processed += n_samples;
@@ -1855,7 +2014,8 @@ int af_engine_process_device(af_engine *e, const float *in, float *out, int64_t 
   bool run_modified = false;
   const uint32_t front = af::kFlagInputClamp | af::kFlagDcBlock | af::kFlagPreHighpass;
   const uint32_t front_flags = run.flags & front;
-  if (front_flags) {
+  const bool strip_front = front_flags || e->gate_enabled;  // the gate runs in the pre-pass too, after the front end
+  if (strip_front) {
     // the realtime front end (clamp + DC block + 80 Hz HP, routing.rs:802-843) runs inside the suppressor's
     // own sample-serial pre-pass, so the chain launches must not repeat it
     run.flags &= ~(front | af::kFlagInputScrub);
@@ -2060,6 +2220,10 @@ int af_engine_process_device(af_engine *e, const float *in, float *out, int64_t 
     sa.chain_st32 = e->d_st32;
     sa.f64_pre_z1 = af::kPreZ1;
     sa.f32_dc_x1 = af::kDcX1;
+    if (e->gate_enabled) {
+      sa.front_scrub = (front_flags || (e->host_params.flags & af::kFlagInputScrub)) ? 1 : 0;
+      gate_args(e, sa);
+    }
     if (index > 0) {  // history = tail of the previous window's buffer
       sa.xh_prev = e->supp.d_xh + (size_t)((index - 1) % kXh) * e->supp.xh_floats;
       sa.xh_prev_stride = af::kPitchBuf + win_nf[index - 1] * af::kRnnFrame;
@@ -2189,7 +2353,7 @@ int af_engine_process_device(af_engine *e, const float *in, float *out, int64_t 
         sub_blocks += (n_sub + cb - 1) / cb;
       }
       run = e->host_params;  // crossfade bookkeeping may have moved on
-      if (front_flags) run.flags &= ~(front | af::kFlagInputScrub);
+      if (strip_front) run.flags &= ~(front | af::kFlagInputScrub);
       blocks_done += (seg_n + cb - 1) / cb;
       continue;
     }
@@ -2282,7 +2446,7 @@ int af_engine_process_device(af_engine *e, const float *in, float *out, int64_t 
           AF_HIP(af::launch_chain_publish_ready(e->d_ready, seg0 + seg_n, es));
           advance_crossfades(e, seg_n);
           run = e->host_params;
-          if (front_flags) run.flags &= ~(front | af::kFlagInputScrub);
+          if (strip_front) run.flags &= ~(front | af::kFlagInputScrub);
           blocks_done += (seg_n + cb - 1) / cb;
           continue;
         }
@@ -2296,7 +2460,7 @@ int af_engine_process_device(af_engine *e, const float *in, float *out, int64_t 
           AF_HIP(af::launch_chain_publish_ready(e->d_ready, seg0 + seg_n, es));
           advance_crossfades(e, seg_n);  // (the one chain launch did not: the EQ's counters move window by window)
           run = e->host_params;
-          if (front_flags) run.flags &= ~(front | af::kFlagInputScrub);
+          if (strip_front) run.flags &= ~(front | af::kFlagInputScrub);
           blocks_done += (seg_n + cb - 1) / cb;
           continue;
         }
@@ -2320,7 +2484,7 @@ int af_engine_process_device(af_engine *e, const float *in, float *out, int64_t 
                                 /*stats_cleared=*/!clear_per_window || eq_offloaded, power_w);
     if (rc) return rc;
     run = e->host_params;  // crossfade bookkeeping may have moved on
-    if (front_flags) run.flags &= ~(front | af::kFlagInputScrub);
+    if (strip_front) run.flags &= ~(front | af::kFlagInputScrub);
     blocks_done += (seg_n + cb - 1) / cb;
   }
   if (e->timing) AF_HIP(hipEventRecord(e->ev_mid, (fin && fin != syn) ? fin : syn));  // last suppressor kernel done

@@ -30,6 +30,7 @@
 #include <hip/hip_runtime.h>
 #include <cstdlib>
 
+#include "af_dsp.h"
 #include "af_fft_consts.h"
 #include "af_suppressor.h"
 
@@ -240,6 +241,310 @@ __global__ __launch_bounds__(64 * kPreWaves) void supp_prefilter_kernel(SuppArgs
     a.chain_st32[(int64_t)(a.f32_dc_x1 + 1) * NS + s] = dc_y1;
     a.chain_st64[(int64_t)a.f64_pre_z1 * NS + s] = z1;
     a.chain_st64[(int64_t)(a.f64_pre_z1 + 1) * NS + s] = z2;
+  }
+}
+
+// ---- The same pre-pass with the noise gate (dsp/gate.rs, realtime stage 1: dsp_loop.rs:1371-1435) after the front end.
+// The gate is split so that no wave walks its whole per-sample chain (sqrt, log10, exp10 and the smoothing, ~100 dependent
+// f64 instructions) as gate_lane_kernel does:
+//   R1 (lane = stream, in the front-end wave)  rms_sq = c rms_sq + (1 - c) x^2                       (update_detector)
+//   F1 (lane = TIME, four waves)               level = lin2db(sqrt(rms_sq)); bits level >= thr, level <= thr - 4, d > 24;
+//                                              g36 = db_to_linear(-d), d = clamp((thr - level) 0.75, 0, 36)
+//   R2 (lane = stream)                         hold / open / chatter / auto-relax state machine (track_gate_transition),
+//                                              target 1, g36 or db_to_linear(-24) (= g36 whenever d <= 24: bit-identical
+//                                              to clamping at 24 directly), attack / release smoothing, x gain
+// Tiles are 32 samples (64 streams x 32 samples, rows of 65): the f64 tile R1 fills, F1 overwrites in place and R2 reads is
+// in flight for three steps, the f32 tile for five (load, front end and gate work on it in place), which at 64-sample tiles
+// would not fit the CU's LDS.  131 040 bytes: x[5] f32, g[3] f64, bits[3] u8, model input[2] + [2] f32.
+// kSupp = false compiles the RNNoise roles out: scrub / clamp / DC / HP / gate over `n_samples`, result to `out`.  There
+// `a.gate` = 0 runs the front end alone (the gate roles idle, the gate state is neither read nor written): the engine keeps
+// the front end in this pass for the whole stream when the chain's route was chosen with it stripped.
+constexpr int kGateTileT = 32;
+constexpr int kGateRow = kPreGroup + 1;
+constexpr int kGateTileElems = kGateTileT * kGateRow;
+constexpr int kGateF1Waves = 4;
+constexpr size_t kGateLds = sizeof(float) * 5 * kGateTileElems + sizeof(double) * 3 * kGateTileElems + 3 * kGateTileElems +
+                            sizeof(float) * 4 * kGateTileElems;
+static_assert(kGateLds <= 160 * 1024, "the gated pre-pass must fit one CU's LDS");
+template <bool kSupp>
+constexpr int gate_prepass_waves() { return kSupp ? 11 : 8; }
+template <bool kSupp, bool kRaw>
+__global__ __launch_bounds__(64 * gate_prepass_waves<kSupp>()) void supp_prefilter_gate_kernel(SuppArgs a) {
+  extern __shared__ double gate_lds[];
+  constexpr int T = kGateTileT;
+  constexpr int kF1 = 2, kR2 = kF1 + kGateF1Waves, kSoft = kR2 + 1, kModelHp = kSoft + 1, kDryOut = kSupp ? kModelHp + 1 : kR2 + 1,
+                kXhOut = kDryOut + 1;
+  double *t_g = gate_lds;                                                                // [3]
+  float *t_x = reinterpret_cast<float *>(t_g + 3 * kGateTileElems);                      // [5]
+  float *t_sc = t_x + 5 * kGateTileElems, *t_xh = t_sc + 2 * kGateTileElems;             // [2], [2] (kSupp)
+  uint8_t *t_b = reinterpret_cast<uint8_t *>(t_xh + 2 * kGateTileElems);                  // [3]
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int tl = lane & (T - 1), half = lane >> 5;  // lane = time roles: sample tl of rows half * 32 + r
+  const int s0 = blockIdx.x * kPreGroup;
+  const int s = s0 + lane;
+  const bool valid = s < a.n_streams;
+  const int sc = valid ? s : a.n_streams - 1;
+  const int64_t NS = a.n_streams;
+  const int64_t n = kSupp ? (int64_t)a.n_frames * kRnnFrame : a.n_samples;
+  const int64_t col0 = kSupp ? a.frame0 * kRnnFrame : 0;
+  const int64_t xh_stride = kPitchBuf + n;
+  float *st = kSupp ? a.state + (int64_t)sc * SuppState::kCount : nullptr;
+  const int64_t ntiles = (n + T - 1) / T;
+  auto tile_len = [&](int64_t ti) { return (int)((n - ti * T) < T ? (n - ti * T) : T); };
+  auto row_of = [&](int r) { return (s0 + r) < a.n_streams ? (s0 + r) : a.n_streams - 1; };
+
+  if (kSupp) {  // model-input history, as supp_prefilter_kernel
+    constexpr int kWaves = gate_prepass_waves<kSupp>();
+    for (int r = wave; r < kPreGroup; r += kWaves) {
+      const int sr = row_of(r);
+      const float *hist = a.xh_prev ? a.xh_prev + (int64_t)sr * a.xh_prev_stride + (a.xh_prev_stride - kPitchBuf)
+                                    : a.state + (int64_t)sr * SuppState::kCount + SuppState::kHist;
+      for (int i = lane; i < kPitchBuf; i += 64) a.xh[(int64_t)sr * xh_stride + i] = hist[i];
+    }
+  }
+
+  int64_t *gs = a.gate_state;
+  const bool gate_on = kSupp || a.gate != 0;
+  float m0 = 0.0f, m1 = 0.0f, dc_x1 = 0.0f, dc_y1 = 0.0f;
+  double z1 = 0.0, z2 = 0.0, rms = 0.0, gain = 0.0;
+  int hold = 0, window = 0, trans = 0, cooldown = 0, relax = 0;
+  bool open = false, eff = false, has_eff = false;
+  int64_t events = 0;
+  if (wave == kModelHp && kSupp) {
+    m0 = st[SuppState::kHpMem];
+    m1 = st[SuppState::kHpMem + 1];
+  }
+  if (wave == 1) {
+    if (a.front_dc) {
+      dc_x1 = a.chain_st32[(int64_t)a.f32_dc_x1 * NS + sc];
+      dc_y1 = a.chain_st32[(int64_t)(a.f32_dc_x1 + 1) * NS + sc];
+      z1 = a.chain_st64[(int64_t)a.f64_pre_z1 * NS + sc];
+      z2 = a.chain_st64[(int64_t)(a.f64_pre_z1 + 1) * NS + sc];
+    }
+    if (gate_on) rms = __longlong_as_double(gs[kGateRms * NS + sc]);
+  }
+  if (wave == kR2 && gate_on) {
+    gain = __longlong_as_double(gs[kGateGain * NS + sc]);
+    hold = (int)gs[kGateHold * NS + sc];
+    window = (int)gs[kGateWindow * NS + sc];
+    trans = (int)gs[kGateTrans * NS + sc];
+    cooldown = (int)gs[kGateCooldown * NS + sc];
+    relax = (int)gs[kGateRelax * NS + sc];
+    open = gs[kGateOpen * NS + sc] != 0;
+    eff = gs[kGateEff * NS + sc] != 0;
+    has_eff = gs[kGateHasEff * NS + sc] != 0;
+    events = gs[kGateEvents * NS + sc];
+  }
+  const float b0 = -2.0f, b1 = 1.0f, a0 = -1.99599f, a1 = 0.99600f;  // RNNoise input high-pass
+  const double hb0 = a.hp_b0, hb1 = a.hp_b1, hb2 = a.hp_b2, ha1 = a.hp_a1, ha2 = a.hp_a2;
+  const bool scrub = a.front_scrub != 0, clamp = a.front_clamp != 0, dc = a.front_dc != 0, hp_on = a.front_hp != 0;
+  const double thr = a.gate_thr, thr_low = a.gate_thr - 4.0;
+  // the two constant targets, evaluated by the same device routine as every other target
+  const double g_open = db2lin(-0.0), g24 = db2lin(-24.0);
+  constexpr int kLast = kSupp ? 6 : 4;  // the last role's lag in tiles
+
+  for (int64_t it = 0; it < ntiles + kLast; ++it) {
+    if (wave == 0) {  // ---- load tile `it` into x[it % 5]
+      const int64_t ti = it;
+      if (ti < ntiles) {
+        const int len = tile_len(ti);
+        const int64_t col = col0 + ti * T + (tl < len ? tl : len - 1);
+        float *tile = t_x + (ti % 5) * kGateTileElems;
+#pragma unroll 1
+        for (int r0 = half * 32; r0 < half * 32 + 32; r0 += 16) {  // (two batches of 16 loads in flight: the VGPR budget of 11 waves)
+          float v[16];
+#pragma unroll
+          for (int r = 0; r < 16; ++r) v[r] = a.in[(int64_t)row_of(r0 + r) * a.in_stride + col];
+#pragma unroll
+          for (int r = 0; r < 16; ++r) tile[tl * kGateRow + r0 + r] = v[r];
+        }
+      }
+    } else if (wave == 1) {  // ---- front end (routing.rs:802-843) + R1 on tile it - 1, in place (lane = stream)
+      const int64_t ti = it - 1;
+      if (ti >= 0 && ti < ntiles) {
+        const int len = tile_len(ti);
+        float *x = t_x + (ti % 5) * kGateTileElems;
+        double *g = t_g + (ti % 3) * kGateTileElems;
+#pragma unroll 4
+        for (int t = 0; t < T; ++t) {
+          if (t < len) {
+            float v = x[t * kGateRow + lane];
+            if (scrub && !finite32(v)) v = 0.0f;
+            if (clamp) v = v < -1.0f ? -1.0f : (v > 1.0f ? 1.0f : v);
+            if (dc) {
+              const float o = v - dc_x1 + 0.995f * dc_y1;
+              dc_x1 = v;
+              dc_y1 = o;
+              v = o;
+              if (hp_on) {
+                const double xin = (double)o;
+                const double y = hb0 * xin + z1;
+                z1 = hb1 * xin - ha1 * y + z2;
+                z2 = hb2 * xin - ha2 * y;
+                v = (float)y;
+              }
+            }
+            x[t * kGateRow + lane] = v;
+            if (gate_on) {
+              const double xd = (double)v;  // update_detector, gate.rs:265-285
+              rms = a.gate_rms_c * rms + a.gate_rms_omc * xd * xd;
+              g[t * kGateRow + lane] = rms;
+            }
+          }
+        }
+      }
+    } else if (wave >= kF1 && wave < kR2) {  // ---- F1 on tile it - 2 (lane = time): 16 streams per wave
+      const int64_t ti = it - 2;
+      if (gate_on && ti >= 0 && ti < ntiles && tl < tile_len(ti)) {
+        double *g = t_g + (ti % 3) * kGateTileElems;
+        uint8_t *bits = t_b + (ti % 3) * kGateTileElems;
+        const int rb = (wave - kF1) * 16 + half * 8;
+#pragma unroll 2
+        for (int r = rb; r < rb + 8; ++r) {
+          const int k = tl * kGateRow + r;
+          const double level = lin2db(sqrt(g[k]), 1e-10);                        // gate.rs:280-284
+          const double d = dclamp((thr - level) * (1.0 - 1.0 / 4.0), 0.0, 36.0);  // gate.rs:298-306
+          g[k] = db2lin(-d);
+          bits[k] = (uint8_t)((level >= thr ? 1 : 0) | (level <= thr_low ? 2 : 0) | (d > 24.0 ? 4 : 0));
+        }
+      }
+    } else if (wave == kR2) {  // ---- R2 on tile it - 3, in place (lane = stream): gate.rs:265-285 (decision), 578-637
+      const int64_t ti = it - 3;
+      if (gate_on && ti >= 0 && ti < ntiles) {
+        const int len = tile_len(ti);
+        float *x = t_x + (ti % 5) * kGateTileElems;
+        const double *g = t_g + (ti % 3) * kGateTileElems;
+        const uint8_t *bits = t_b + (ti % 3) * kGateTileElems;
+#pragma unroll 4
+        for (int t = 0; t < T; ++t) {
+          if (t < len) {
+            const int k = t * kGateRow + lane;
+            const int b = bits[k];
+            if (b & 1) {
+              open = true;
+              hold = a.gate_hold;
+            } else if (hold > 0) {
+              hold -= 1;
+              open = true;
+            } else if (b & 2) {
+              open = false;
+            }
+            // detector_gain_reduction_db: the range is the one in force BEFORE this sample's transition is tracked
+            const double target = open ? g_open : ((relax > 0 && (b & 4)) ? g24 : g[k]);
+            if (!has_eff) {  // track_gate_transition, gate.rs:578-611
+              eff = open;
+              has_eff = true;
+            } else if (open != eff) {
+              eff = open;
+              if (window == 0) {
+                window = a.gate_window;
+                trans = 1;
+              } else {
+                trans += 1;
+              }
+              if (trans >= 4 && cooldown == 0) {
+                events += 1;
+                cooldown = a.gate_cooldown;
+                if (a.gate_vad_mode) relax = a.gate_relax;
+                window = 0;
+                trans = 0;
+              }
+            }
+            if (relax > 0) relax -= 1;  // advance_chatter_timers, gate.rs:562-575
+            if (window > 0) {
+              window -= 1;
+              if (window == 0) trans = 0;
+            }
+            if (cooldown > 0) cooldown -= 1;
+            const bool up = target > gain;  // apply_gain, gate.rs:613-623
+            gain = (up ? a.gate_atk : a.gate_rel) * gain + (up ? a.gate_atk_omc : a.gate_rel_omc) * target;
+            x[k] = (float)((double)x[k] * gain);
+          }
+        }
+      }
+    } else if (kSupp && wave == kSoft) {  // ---- model-input scaling of tile it - 4 (lane = time)
+      const int64_t ti = it - 4;
+      if (ti >= 0 && ti < ntiles) {
+        const float *src = t_x + (ti % 5) * kGateTileElems;
+        float *dst = t_sc + (ti & 1) * kGateTileElems;
+#pragma unroll 8
+        for (int r = half * 32; r < half * 32 + 32; ++r) {
+          float v = src[tl * kGateRow + r];
+          if (kRaw) {
+            v = (v < -1.0f ? -1.0f : (v > 1.0f ? 1.0f : v)) * 32768.0f;
+          } else {
+            v = scale_for_model(v);
+          }
+          dst[tl * kGateRow + r] = v;
+        }
+      }
+    } else if (kSupp && wave == kModelHp) {  // ---- the model's own high-pass on tile it - 5 (lane = stream)
+      const int64_t ti = it - 5;
+      if (ti >= 0 && ti < ntiles) {
+        const int len = tile_len(ti);
+        const float *src = t_sc + (ti & 1) * kGateTileElems;
+        float *dst = t_xh + (ti & 1) * kGateTileElems;
+#pragma unroll 8
+        for (int t = 0; t < T; ++t) {
+          if (t < len) {
+            const float v = src[t * kGateRow + lane];
+            const float y = v + m0;
+            m0 = m1 + (b0 * v - a0 * y);
+            m1 = (b1 * v - a1 * y);
+            dst[t * kGateRow + lane] = y;
+          }
+        }
+      }
+    } else if (wave == kDryOut) {  // ---- the gated signal of tile it - 4 to `out` (the suppressor's dry signal)
+      const int64_t ti = it - 4;
+      if (ti >= 0 && ti < ntiles) {
+        const int len = tile_len(ti);
+        const float *src = t_x + (ti % 5) * kGateTileElems;
+#pragma unroll 8
+        for (int r = half * 32; r < half * 32 + 32; ++r) {
+          const int sr = s0 + r;
+          if (sr < a.n_streams && tl < len) a.out[(int64_t)sr * a.stream_stride + col0 + ti * T + tl] = src[tl * kGateRow + r];
+        }
+      }
+    } else if (kSupp && wave == kXhOut) {  // ---- the model input of tile it - 6
+      const int64_t ti = it - 6;
+      if (ti >= 0 && ti < ntiles) {
+        const int len = tile_len(ti);
+        const float *src = t_xh + (ti & 1) * kGateTileElems;
+#pragma unroll 8
+        for (int r = half * 32; r < half * 32 + 32; ++r) {
+          const int sr = s0 + r;
+          if (sr < a.n_streams && tl < len) a.xh[(int64_t)sr * xh_stride + kPitchBuf + ti * T + tl] = src[tl * kGateRow + r];
+        }
+      }
+    }
+    __syncthreads();
+  }
+  if (!valid) return;
+  if (kSupp && wave == kModelHp) {
+    st[SuppState::kHpMem] = m0;
+    st[SuppState::kHpMem + 1] = m1;
+  }
+  if (wave == 1) {
+    if (a.front_dc) {
+      a.chain_st32[(int64_t)a.f32_dc_x1 * NS + s] = dc_x1;
+      a.chain_st32[(int64_t)(a.f32_dc_x1 + 1) * NS + s] = dc_y1;
+      a.chain_st64[(int64_t)a.f64_pre_z1 * NS + s] = z1;
+      a.chain_st64[(int64_t)(a.f64_pre_z1 + 1) * NS + s] = z2;
+    }
+    if (gate_on) gs[kGateRms * NS + s] = __double_as_longlong(rms);
+  }
+  if (wave == kR2 && gate_on) {
+    gs[kGateGain * NS + s] = __double_as_longlong(gain);
+    gs[kGateHold * NS + s] = hold;
+    gs[kGateWindow * NS + s] = window;
+    gs[kGateTrans * NS + s] = trans;
+    gs[kGateCooldown * NS + s] = cooldown;
+    gs[kGateRelax * NS + s] = relax;
+    gs[kGateOpen * NS + s] = open ? 1 : 0;
+    gs[kGateEff * NS + s] = eff ? 1 : 0;
+    gs[kGateHasEff * NS + s] = has_eff ? 1 : 0;
+    gs[kGateEvents * NS + s] = events;
   }
 }
 
@@ -2016,7 +2321,7 @@ extern "C" __global__ __launch_bounds__(64 * kFftWaves, 3) void supp_synth_kerne
   float prev[8];  // the previous frame's second half: sample 480 + lane + 64 j
 #pragma unroll
   for (int j = 0; j < 8; ++j) prev[j] = (lane + 64 * j) < kRnnFrame ? st[SuppState::kSynthMem + lane + 64 * j] : 0.0f;
-  const bool dry_from_out = a.front_clamp || a.front_dc;
+  const bool dry_from_out = a.front_clamp || a.front_dc || a.gate;
   for (int f = 0; f < a.n_frames; ++f) {
     const int64_t cell = (int64_t)f * a.n_streams + s;
     const SuppFrameRec *rec = a.rec + cell;
@@ -2141,7 +2446,7 @@ extern "C" __global__ __launch_bounds__(64) void supp_overlap_kernel(SuppArgs a)
     for (int i = lane; i < kRnnFrame; i += 64) {
       float wet = (y[i] + prev[i]) / 32768.0f;
       if (!a.raw_protocol && smoothed < 1.0f) {
-        const float dry = (a.front_clamp || a.front_dc) ? a.out[base + i] : a.in[(int64_t)s * a.in_stride + (a.frame0 + f) * kRnnFrame + i];
+        const float dry = (a.front_clamp || a.front_dc || a.gate) ? a.out[base + i] : a.in[(int64_t)s * a.in_stride + (a.frame0 + f) * kRnnFrame + i];
         wet = (smoothed * wet) + ((1.0f - smoothed) * dry);
       }
       a.out[base + i] = wet;
@@ -2169,7 +2474,23 @@ static hipError_t launch_prefilter_variant(const SuppArgs &a, hipStream_t stream
   hipLaunchKernelGGL((supp_prefilter_kernel<kClamp, kDcHp, kRaw>), grid, block, lds, stream, a);
   return hipGetLastError();
 }
+template <bool kSupp, bool kRaw>
+static hipError_t launch_prefilter_gate_variant(const SuppArgs &a, hipStream_t stream) {
+  static bool attr_set = false;
+  if (!attr_set) {
+    hipError_t err = hipFuncSetAttribute(reinterpret_cast<const void *>(supp_prefilter_gate_kernel<kSupp, kRaw>),
+                                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)kGateLds);
+    if (err != hipSuccess) return err;
+    attr_set = true;
+  }
+  const dim3 grid((a.n_streams + kPreGroup - 1) / kPreGroup), block(64 * gate_prepass_waves<kSupp>());
+  hipLaunchKernelGGL((supp_prefilter_gate_kernel<kSupp, kRaw>), grid, block, kGateLds, stream, a);
+  return hipGetLastError();
+}
+// the gated front end without the suppressor: `in` -> `out` over a.n_samples
+hipError_t launch_gate_prepass(const SuppArgs &a, hipStream_t stream) { return launch_prefilter_gate_variant<false, false>(a, stream); }
 hipError_t launch_suppressor_prefilter(const SuppArgs &a, hipStream_t stream) {
+  if (a.gate) return a.raw_protocol ? launch_prefilter_gate_variant<true, true>(a, stream) : launch_prefilter_gate_variant<true, false>(a, stream);
   const int sel = (a.front_clamp ? 4 : 0) | (a.front_dc ? 2 : 0) | (a.raw_protocol ? 1 : 0);
   switch (sel) {
     case 0: return launch_prefilter_variant<false, false, false>(a, stream);

@@ -112,6 +112,18 @@ struct SuppArgs {
   double *chain_st64;         // chain state planes (pre-filter memories live there)
   float *chain_st32;
   int32_t f64_pre_z1, f32_dc_x1;  // field indices inside those planes
+  // optional noise gate after the front end (dsp/gate.rs, dsp_loop.rs:1371-1435): supp_prefilter_gate_kernel
+  int32_t gate;               // 1: the pass gates (and then writes the dry signal to `out`); see supp_prefilter_gate_kernel
+  int32_t front_scrub;        // non-finite input -> 0 (with the gate on it runs here, not in the chain)
+  int64_t n_samples;          // samples of the pass when it runs without the suppressor (not whole frames), else 0
+  int64_t *gate_state;        // [kGateFields][stream] (rows 0-1 f64 bits, the rest int64)
+  double gate_thr, gate_rms_c, gate_rms_omc, gate_atk, gate_atk_omc, gate_rel, gate_rel_omc;
+  int32_t gate_hold, gate_window, gate_cooldown, gate_relax;  // samples
+  int32_t gate_vad_mode;
 };
+// gate state rows (af_engine::d_gate): rms_envelope_sq, current_gain (f64); hold, chatter window, transition count,
+// cooldown, auto-relax, is_open, effective_open, has_effective, chatter events (int64)
+enum GateField { kGateRms, kGateGain, kGateHold, kGateWindow, kGateTrans, kGateCooldown, kGateRelax, kGateOpen, kGateEff,
+                 kGateHasEff, kGateEvents, kGateFields };
 
 }  // namespace af

@@ -16,6 +16,7 @@ hipError_t launch_suppressor_synthesis(const SuppArgs &a, const SuppTables &tb, 
                                        hipEvent_t after_network, hipStream_t finish_stream, hipStream_t network_stream = nullptr,
                                        hipEvent_t after_spectra = nullptr);
 hipError_t launch_suppressor_prefilter(const SuppArgs &a, hipStream_t stream);
+hipError_t launch_gate_prepass(const SuppArgs &a, hipStream_t stream);  // the gated front end without the suppressor
 hipError_t launch_scale_probe(const float *in, float *out, int64_t n, hipStream_t stream);
 
 // int8 network weights in the layout of the public RNNoise model (dense: [in][out]; GRU: [in][3*units],

@@ -166,6 +166,15 @@ SIGNATURES = {
     "af_engine_set_timing_enabled": (C.c_int, [_vp, _i32]),
     "af_engine_last_kernel_ms": (C.c_int, [_vp, _dp, C.POINTER(_i32)]),
     "af_engine_last_stage_ms": (C.c_int, [_vp, _dp, _dp]),
+    # noise gate stage
+    "af_engine_set_gate_enabled": (C.c_int, [_vp, _i32]),
+    "af_gate_set_threshold": (C.c_int, [_vp, _d]),
+    "af_gate_set_attack_time": (C.c_int, [_vp, _d]),
+    "af_gate_set_release_time": (C.c_int, [_vp, _d]),
+    "af_gate_set_mode": (C.c_int, [_vp, _i32]),
+    "af_gate_threshold_db": (_d, [_vp]),
+    "af_engine_gate_enabled": (_i32, [_vp]),
+    "af_engine_read_gate_state": (C.c_int, [_vp, _fp, C.POINTER(C.c_uint64), C.POINTER(_i32), _i32]),
     "af_engine_last_chain_launch_ms": (C.c_int, [_vp, _dp, _dp, C.POINTER(_i32)]),
     # product resampler
     "af_engine_last_kernel": (C.c_int, [_vp]),
@@ -200,6 +209,7 @@ VALUE_FUNCTIONS = {
     "af_noise_suppressor_latency_samples", "af_noise_suppressor_backend_available", "af_noise_suppressor_backend_failed",
     "af_noise_suppressor_backend_error",
     "af_resampler_destroy", "af_resampler_output_delay", "af_resampler_expected_frames", "af_resampler_sinc_len",
+    "af_gate_threshold_db", "af_engine_gate_enabled",
 }
 
 _lib = None

@@ -155,6 +155,18 @@ class Engine:
         _lib.check(self._lib.af_engine_process_device(self._h, C.c_void_p(in_ptr), C.c_void_p(out_ptr), int(n_samples),
                                                       int(stream_stride), int(layout), C.c_void_p(hip_stream)))
 
+    def gate_state(self) -> dict:
+        """Each stream's noise gate as of the end of the last call: ``current_gain`` (float32), ``chatter_events``
+        (uint64, since reset), ``is_open`` and ``auto_relax_active`` (bool)."""
+        gain = np.zeros(self.n_streams, dtype=np.float32)
+        events = np.zeros(self.n_streams, dtype=np.uint64)
+        flags = np.zeros(self.n_streams, dtype=np.int32)
+        _lib.check(self._lib.af_engine_read_gate_state(self._h, gain.ctypes.data_as(C.POINTER(C.c_float)),
+                                                        events.ctypes.data_as(C.POINTER(C.c_uint64)),
+                                                        flags.ctypes.data_as(C.POINTER(C.c_int32)), self.n_streams))
+        return {"current_gain": gain, "chatter_events": events, "is_open": (flags & 1) != 0,
+                "auto_relax_active": (flags & 2) != 0}
+
     def block_stats(self) -> np.ndarray:
         """Structured array [blocks, n_streams] of the last process call."""
         blocks = int(self._lib.af_engine_last_block_count(self._h))

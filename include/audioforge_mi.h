@@ -119,6 +119,34 @@ int af_engine_set_input_clamp_enabled(af_engine *e, int32_t enabled);
 /* apply_input_pre_filter: DC block + 80 Hz high-pass, routing.rs:826-843 */
 int af_engine_set_prefilter_enabled(af_engine *e, int32_t enabled, int32_t apply_fixed_highpass);
 
+/* ---- noise gate stage: rust-core/src/dsp/gate.rs (NoiseGate) as stage 1 of the realtime loop -------------------
+ * Realtime order (dsp_loop.rs:1371-1435, built at :478-487 as NoiseGate::new(-40, 10, 100, fs)): input scrub / clamp ->
+ * DC block + 80 Hz high-pass -> GATE -> suppressor (whose dry signal is the gated one) -> de-esser / EQ / compressor /
+ * limiter / true peak.  Per stream, process_block_inplace on the path without a VadAutoGate: update_detector
+ * (gate.rs:265-285), detector_gain_reduction_db with the auto-relax range (:298-306), track_gate_transition (:578-611),
+ * apply_gain (:613-623), process_sample (:626-637).  Modes 1 (VadAssisted) and 2 (VadOnly) arm the chatter auto-relax
+ * (24 dB floor) as that path does; the realtime loop also attaches VadAutoGate::without_backend, whose fused-probability
+ * path is NOT built here.
+ * Off by default.  Parameters are engine-wide (presets do not carry them) and live between process calls, like
+ * apply_gate_control (processor/control.rs:851-865): threshold [-80, -10] dB, attack [0.1, 100] ms, release [10, 1000] ms
+ * (audio/processor.rs:77-82); a non-finite value leaves the setting unchanged (control.rs:50-52).  Mode 0/1/2, anything
+ * else is AF_ERR_INVALID_ARGUMENT "Invalid gate mode" (gate_controls.rs:75-81); mode 0 clears the auto-relax counter
+ * (gate.rs:812-821).  State is per stream: disabling freezes it, re-enabling resumes from it, af_engine_reset restores
+ * NoiseGate::reset (gate.rs:759-785).  Stream-major audio only (AF_ERR_UNSUPPORTED otherwise; also for a gate-off call of an
+ * engine whose stage-pipeline route was chosen with the gate on and the front end in the gate's pre-pass).  With the suppressor off
+ * the chain receives the gated front-end output, and the block input statistics describe that signal. */
+int af_engine_set_gate_enabled(af_engine *e, int32_t enabled);
+int af_gate_set_threshold(af_engine *e, double threshold_db);
+int af_gate_set_attack_time(af_engine *e, double attack_ms);
+int af_gate_set_release_time(af_engine *e, double release_ms);
+int af_gate_set_mode(af_engine *e, int32_t mode);
+double af_gate_threshold_db(const af_engine *e);      /* VALUE */
+int32_t af_engine_gate_enabled(const af_engine *e);   /* VALUE */
+/* each stream's gate as of the end of the last call (synchronises): current_gain = NoiseGate::current_gain, chatter
+ * events since reset, flags bit 0 is_open, bit 1 auto_relax_active -- what dsp_loop.rs:1397-1409 publishes to the
+ * meters.  Any pointer may be null; n_streams <= the engine's. */
+int af_engine_read_gate_state(af_engine *e, float *current_gain, uint64_t *chatter_events, int32_t *flags, int32_t n_streams);
+
 /* ---- RNNoise suppressor: rust-core/src/dsp/rnnoise.rs (RNNoiseProcessor) -------------------------
  * Runs between the front end and the EQ (dsp_loop.rs:1521-1599).  48 kHz only.  The suppressor eats whole
  * 480-sample frames: what a process call leaves over waits in the engine for the next call (rnnoise.rs:114-164), and a
