@@ -427,6 +427,22 @@ def suppressor_process_traced(audio, strength: float = 1.0, weight_seed: int = 0
     return out[:n], pitch, silence
 
 
+def suppressor_pitch_filter_margins(audio, strength: float = 1.0, weight_seed: int = 0x5EED) -> np.ndarray:
+    """Per frame of suppressor_process: min over bands of |Exp - g|, the distance of pitch_filter's one discontinuous
+    decision (`Exp > g`: the filter strength jumps to 1) from its edge; 1e30 on a silent frame."""
+    audio = np.ascontiguousarray(audio, dtype=np.float32)
+    L = lib()
+    L.afo_suppressor_process_margins.restype = C.c_size_t
+    L.afo_suppressor_process_margins.argtypes = [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_size_t,
+                                                 C.POINTER(C.c_float)]
+    state = C.create_string_buffer(1 << 18)
+    L.afo_suppressor_init(state, float(strength), C.c_uint64(weight_seed))
+    out = np.zeros_like(audio)
+    margin = np.zeros(audio.size // 480, dtype=np.float32)
+    L.afo_suppressor_process_margins(state, _fptr(out), _fptr(audio), audio.size, _fptr(margin))
+    return margin
+
+
 def scale_sample_for_model(sample: float) -> float:
     """RNNoiseProcessor::scale_sample_for_model (rnnoise.rs:89-111)."""
     L = lib()

@@ -741,6 +741,7 @@ float afo_rnn_process_frame(const afo_rnn_weights *w, afo_rnn_state *st, float *
     E += Ex[i];
   }
   int silence = 0;
+  afo_rnn_last.pf_margin = 1e30f;
   if (E < 0.04f) {
     memset(features, 0, sizeof features);
     silence = 1;
@@ -776,6 +777,8 @@ float afo_rnn_process_frame(const afo_rnn_weights *w, afo_rnn_state *st, float *
   }
   if (!silence) {
     compute_rnn(w, st, g, &vad_prob, features);
+    afo_rnn_last.pf_margin = 1e30f;
+    for (int i = 0; i < NB; ++i) afo_rnn_last.pf_margin = fminf(afo_rnn_last.pf_margin, fabsf(Exp[i] - g[i]));
     pitch_filter(X, P, Ex, Ep, Exp, g);
     for (int i = 0; i < NB; ++i) {
       g[i] = fmaxf(g[i], 0.6f * st->lastg[i]);
@@ -865,6 +868,16 @@ size_t afo_suppressor_process_traced(afo_suppressor *s, float *out, const float 
     afo_suppressor_process_frame(s, out + f * FRAME, in + f * FRAME);
     if (pitch) pitch[f] = afo_rnn_last.pitch_index;
     if (silence) silence[f] = afo_rnn_last.silence;
+  }
+  return frames * FRAME;
+}
+
+/* the same with each frame's pitch-filter margin (afo_rnn_debug.pf_margin): how close its one discontinuous decision was */
+size_t afo_suppressor_process_margins(afo_suppressor *s, float *out, const float *in, size_t n, float *margin) {
+  size_t frames = n / FRAME;
+  for (size_t f = 0; f < frames; ++f) {
+    afo_suppressor_process_frame(s, out + f * FRAME, in + f * FRAME);
+    margin[f] = afo_rnn_last.pf_margin;
   }
   return frames * FRAME;
 }

@@ -40,6 +40,7 @@ typedef struct {
   float X[962], P[962];
   int pitch_index, silence;
   float pitch_gain;
+  float pf_margin; /* min over bands of |Exp - g| where pitch_filter branches (Exp > g); 1e30 on a silent frame */
 } afo_rnn_debug;
 extern __thread afo_rnn_debug afo_rnn_last;
 
@@ -58,6 +59,7 @@ void afo_suppressor_init(afo_suppressor *s, float strength, uint64_t weight_seed
 void afo_suppressor_process_frame(afo_suppressor *s, float *out, const float *dry);
 size_t afo_suppressor_process(afo_suppressor *s, float *out, const float *in, size_t n);
 size_t afo_suppressor_process_traced(afo_suppressor *s, float *out, const float *in, size_t n, int32_t *pitch, int32_t *silence);
+size_t afo_suppressor_process_margins(afo_suppressor *s, float *out, const float *in, size_t n, float *margin);
 void afo_rnnoise_benchmark_frames(const float *in, float *out, size_t n, uint64_t weight_seed);
 
 

@@ -401,3 +401,101 @@ def lane_mix_batch(n_streams: int, n_samples: int, seed: int = 0) -> np.ndarray:
                         x[edges[5 + k :: 13]] = -np.inf
             out[g0 + lane] = x
     return out
+
+
+# ------------------------------------------------------------------------------------------------------------------
+# Lane-role stimulus for the gated pre-pass (supp_prefilter_gate_kernel): every 64-stream group moves through 32-sample
+# tiles, and each wave role maps rows differently (the load wave 32 rows per half-wave in batches of 16, F1 eight rows per
+# half-wave, the state machine and the front end one lane per row).  Built so that the gate opens, closes and chatters on
+# some rows of every eight-row octet and not on others in the same tile.
+GATE_LANE_GROUP = 64
+GATE_LANE_TILE = 32
+
+
+def _gate_lane_roles() -> list[tuple[str, int]]:
+    """The 64 lanes of a group before the group's own permutation: (role, index within the role)."""
+    counts = (("flutter", 54), ("non_finite", 2), ("out_of_range", 2), ("dc", 2), ("noise", 2), ("silent", 1), ("steady", 1))
+    roles = [(role, k) for role, count in counts for k in range(count)]
+    assert len(roles) == GATE_LANE_GROUP
+    return roles
+
+
+def _gate_lane_envelope(rng: np.random.Generator, n: int, centre_db: float) -> np.ndarray:
+    """Per-sample RMS level in dB: episodes of level flutter across `centre_db` (loud segments of 12-60 ms, quiet ones of
+    65-140 ms that outlast the 50 ms hold, so that the 8 ms detector follows them and four transitions fall inside the
+    500 ms chatter window), each followed either by a quiet gap of 0.25-0.5 s 34-55 dB under the centre (the 24 dB
+    auto-relax floor's case: the relax still armed) or by a loud span.  Starts at a random point of its first episode."""
+    fs = SAMPLE_RATE
+    levels, lengths = [], []
+    total = 0
+    skip = int(rng.integers(0, int(0.4 * fs)))
+    while total < n + skip:
+        for i in range(int(rng.integers(6, 13))):  # the flutter (a quiet segment outlasts the 50 ms hold)
+            loud = i % 2 == 0
+            levels.append(centre_db + (rng.uniform(3.0, 18.0) if loud else -rng.uniform(6.0, 28.0)))
+            lengths.append(int((rng.uniform(0.012, 0.06) if loud else rng.uniform(0.065, 0.14)) * fs))
+        if rng.uniform() < 0.4:  # a quiet gap
+            levels.append(centre_db - rng.uniform(34.0, 55.0))
+            lengths.append(int(rng.uniform(0.25, 0.5) * fs))
+        else:  # or a loud span
+            levels.append(centre_db + rng.uniform(4.0, 20.0))
+            lengths.append(int(rng.uniform(0.05, 0.4) * fs))
+        total = int(np.sum(lengths))
+    env = np.repeat(np.asarray(levels), np.asarray(lengths))
+    return env[skip : skip + n]
+
+
+def gate_lane_batch(n_streams: int, n_samples: int, seed: int = 0) -> np.ndarray:
+    """[n_streams, n_samples] float32, deterministic in `seed`; a group's rows depend on (seed, group) only, so a batch's
+    first streams do not depend on how many follow.  Lanes are permuted differently in every group of 64.  Most rows are
+    a tone (120-900 Hz) under a level flutter around the -40 dB default threshold (a sixth of them around -60 and -20 dB,
+    for the other threshold settings); a few carry NaN / +-Inf, samples beyond +-1.0 (up to +-4.0), a DC offset, white
+    noise instead of the tone, digital silence, or a steady tone just over the threshold."""
+    n = int(n_samples)
+    t = np.arange(n, dtype=np.float64) / SAMPLE_RATE
+    roles = _gate_lane_roles()
+    out = np.empty((n_streams, n), dtype=np.float32)
+    for g0 in range(0, n_streams, GATE_LANE_GROUP):
+        group = g0 // GATE_LANE_GROUP
+        rng = np.random.default_rng([int(seed), group])
+        order = rng.permutation(GATE_LANE_GROUP)
+        # every role's parameters are drawn for all 64 lanes, whether or not the group is complete
+        params = []
+        for role, k in roles:
+            centre = -40.0 + rng.uniform(-2.0, 2.0)
+            pick = rng.uniform()
+            if role == "flutter" and pick < 1 / 12:
+                centre -= 20.0
+            elif role == "flutter" and pick < 1 / 6:
+                centre += 20.0
+            params.append(dict(centre=centre, f=rng.uniform(120.0, 900.0), phase=rng.uniform(0.0, 2.0 * np.pi),
+                               env_seed=int(rng.integers(0, 2**63)), noise=rng.uniform(1e-6, 3e-5)))
+        for lane in range(min(GATE_LANE_GROUP, n_streams - g0)):
+            role, k = roles[int(order[lane])]
+            p = params[int(order[lane])]
+            r = np.random.default_rng(p["env_seed"])
+            if role == "silent":
+                out[g0 + lane] = 0.0
+                continue
+            if role == "steady":
+                env = np.full(n, p["centre"] + 2.0)
+            else:
+                env = _gate_lane_envelope(r, n, p["centre"])
+            amp = np.sqrt(2.0) * 10.0 ** (env / 20.0)
+            if role == "noise":
+                x = 10.0 ** (env / 20.0) * r.standard_normal(n)
+            else:
+                x = amp * np.sin(2.0 * np.pi * p["f"] * t + p["phase"]) + p["noise"] * r.standard_normal(n)
+            if role == "dc":
+                x = x + (0.3 if k == 0 else -0.6)
+            elif role == "out_of_range":
+                x = x.copy()
+                x[int(r.integers(0, 977)) :: 977] = 4.0 if k == 0 else 1.5
+                x[int(r.integers(0, 1231)) :: 1231] = -4.0 if k == 0 else -1.25
+            elif role == "non_finite":
+                x = x.copy()
+                x[int(r.integers(0, 1409)) :: 1409] = np.nan
+                x[int(r.integers(0, 2083)) :: 2083] = np.inf
+                x[int(r.integers(0, 2801)) :: 2801] = -np.inf
+            out[g0 + lane] = x
+    return out

@@ -29,7 +29,8 @@ def test_gate_matches_oracle(mi, oracle):
     audio = np.stack([S.kat_signal(150, *S.stream_params(s)) * np.float32(0.02 + 0.03 * (s % 5)) for s in range(n_streams)])
     audio[:, 20_000:30_000] *= np.float32(0.01)  # a pause: the expander closes, then reopens
     out, trace, chatter = core.gate_batch(audio, -40.0, 10.0, 100.0, 48_000.0, True, 480)
-    for s in (0, 1, 63, 64, 66):
+    worst = 0.0
+    for s in range(n_streams):  # every stream: rows of both workgroups, the second one partial
         g = oracle.Gate(-40.0, 10.0, 100.0, 48_000.0, vad_mode=True)
         want = np.empty_like(audio[s])
         gains = []
@@ -38,8 +39,10 @@ def test_gate_matches_oracle(mi, oracle):
             gains.append(g.current_gain)
         max_abs, rms = _err(out[s], want)
         assert max_abs <= 2e-7 and rms <= 2e-8, (s, max_abs, rms)
+        worst = max(worst, max_abs)
         assert np.max(np.abs(trace[:, s] - np.asarray(gains, dtype=np.float32))) <= 1e-6
         assert int(chatter[s]) == g.chatter_event_count
+    print(f"gate_lane_kernel: {n_streams} streams, worst max abs {worst:.3e}")
     assert trace.min() < 0.2 < 0.8 < trace.max()  # the gate really closed and opened
 
 

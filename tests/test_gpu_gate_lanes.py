@@ -1,0 +1,410 @@
+"""The gated pre-pass (`supp_prefilter_gate_kernel`) against the oracle on EVERY stream and every stream's gate state, on
+the lane-role stimulus (`signals.gate_lane_batch`: in every 64-stream group and every eight-row octet of the F1 waves, rows
+open, close and chatter in the same 32-sample tile).  Each case first asserts which kernel ran.  The oracle is the front
+half of the realtime chain composed per stream (tests/gate_oracle.py) over the engine's own call lengths.
+
+Tolerances: without the suppressor max abs 1e-6 per stream after the chain, 2e-7 on the gated signal itself; behind the
+suppressor the output is bit-identical to the engine's own suppressor fed the oracle's gated signal (gate off), and within
+RMS 1e-5 and worst sample 1e-5 of the oracle on every stream but the named SUPPRESSOR_EXCEPTIONS; gate state: current_gain
+within 1e-6, events, is_open, relax equal."""
+import numpy as np
+import pytest
+
+import gate_oracle as GO
+import signals as S
+
+pytestmark = pytest.mark.gpu
+
+N_STREAMS, N, SEED = 130, 96_000, 2  # three groups, the last with 2 rows (tests/test_gate_lane_stimulus.py checks this stimulus)
+CALLS = (1, 31, 33, 4799, 19_213, N - 24_077)  # boundaries mid-tile and mid-control-block
+SUPP_CALLS = (1_000, 20_011, 33_333, N - 54_344)  # not multiples of 480: the engine keeps the remainder
+KERNEL_AUTO, KERNEL_LANE, KERNEL_PHASED, KERNEL_QUAD, KERNEL_STAGED = 0, 1, 2, 3, 4
+CHAIN = (S.LIMITER_BANDS, S.limiter_settings(2.0))
+OTHER = dict(attack_ms=0.5, release_ms=500.0)
+# name: (gate parameters per call (one dict: every call), input clamp)
+SETTINGS = {
+    "default_mode0": (GO.DEFAULT_GATE, False),
+    "default_mode1_clamp": (dict(GO.DEFAULT_GATE, mode=1), True),
+    "thr-60_mode1": (dict(GO.DEFAULT_GATE, threshold_db=-60.0, mode=1, **OTHER), False),
+    # live: the default for three calls, then threshold -20, attack 0.5 ms, release 500 ms
+    "thr-20_live": ([GO.DEFAULT_GATE] * 3 + [dict(GO.DEFAULT_GATE, threshold_db=-20.0, **OTHER)] * 3, False),
+}
+# Streams of this stimulus whose suppressor output is off the oracle's by more than 1e-5 in one or two frames (2e-5 .. 6e-5;
+# RMS under 1e-6) WITHOUT the gate as well: the suppressor's own deviation on this input, not the gate stage's -- with the gate
+# on, the engine's output is bit-identical to its suppressor on the oracle's gated signal.  Pitch decisions and silence flags
+# equal the oracle's there, and pitch_filter's Exp > g branch is >= 5e-3 from its edge (test_gate_lane_stimulus.py).
+# Recorded by the strict xfail test_suppressor_alone_on_the_lane_stimulus; the set must match exactly (a stream that leaves
+# or joins it fails).
+SUPPRESSOR_EXCEPTIONS = {N_STREAMS: (29, 68, 82, 93), 4096: (1992,)}
+REPORT = {}
+
+
+@pytest.fixture(scope="module", autouse=True)
+def _report():
+    yield
+    for name, line in sorted(REPORT.items()):
+        print(f"gate-lanes {name}: {line}")
+
+
+@pytest.fixture(scope="module")
+def core():
+    import mic_eq_mi
+    from mic_eq_mi import mic_eq_core
+
+    assert mic_eq_mi.CORE_AVAILABLE, "HIP library missing: GPU tests never fall back to the CPU"
+    return mic_eq_core
+
+
+_AUDIO, _ORACLE = {}, {}
+
+
+def _audio(n_streams=N_STREAMS, n=N):
+    if (n_streams, n) not in _AUDIO:
+        _AUDIO[(n_streams, n)] = S.gate_lane_batch(n_streams, n, SEED)
+    return _AUDIO[(n_streams, n)]
+
+
+def _oracle(key, audio, fs, calls, params, **kw):
+    if key not in _ORACLE:
+        _ORACLE[key] = GO.run_batch(audio, fs, calls, params, **kw)
+    return _ORACLE[key]
+
+
+def _per_call(params, i):
+    return params if isinstance(params, dict) else params[i]
+
+
+def _apply(eng, p):
+    eng.gate_set_threshold(float(p["threshold_db"]))
+    eng.gate_set_attack_time(float(p["attack_ms"]))
+    eng.gate_set_release_time(float(p["release_ms"]))
+    eng.gate_set_mode(int(p["mode"]))
+
+
+def _engine(core, n_streams, fs=48_000.0, kernel=KERNEL_AUTO, chain=True, suppressor=False, clamp=False, raw=False):
+    eng = core.Engine(float(fs), n_streams)
+    if chain:
+        core.configure_auto_eq_chain(eng, float(fs), *CHAIN)
+    else:
+        eng.set_eq_enabled(0)
+        eng.set_compressor_enabled(0)
+        eng.set_limiter_enabled(0)
+    eng.set_prefilter_enabled(1, 1)
+    if clamp:
+        eng.set_input_clamp_enabled(1)
+    if suppressor:
+        eng.set_suppressor_enabled(1)
+        eng.suppressor_set_raw_protocol(int(raw))
+        eng.suppressor_set_trace_enabled(1)
+    eng.set_kernel(kernel)
+    eng.set_gate_enabled(1)
+    eng.set_timing_enabled(1)
+    return eng
+
+
+def _run(eng, audio, calls, params, device=None, frames=False, traces=None):
+    """`calls` through `eng`, the gate parameters set before each call.  device: None (host arrays), "stride" (device
+    pointers, rows n + 3 apart -- n + 483 behind the suppressor (`frames`), whose calls may return up to 479 samples more
+    than they take -- the padding checked untouched) or "inplace" (in == out).  Returns (output, forms per call,
+    samples each call returned)."""
+    outs, forms, lengths = [], [], []
+    at = 0
+    for i, n in enumerate(calls):
+        _apply(eng, _per_call(params, i))
+        x = audio[:, at : at + n]
+        at += n
+        if device is None:
+            y = eng.process(x)
+        else:
+            import torch
+
+            stride = (n + 3 + (480 if frames else 0)) if device == "stride" else n + 480
+            buf = torch.full((x.shape[0], stride), 7.0, dtype=torch.float32, device="cuda")
+            buf[:, :n] = torch.from_numpy(np.ascontiguousarray(x)).cuda()
+            out = torch.full_like(buf, 7.0) if device == "stride" else buf
+            eng.process_device(buf.data_ptr(), out.data_ptr(), n, stride, 0, torch.cuda.current_stream().cuda_stream)
+            torch.cuda.synchronize()
+            m = int(eng.last_output_samples())
+            host = out.cpu().numpy()
+            # nothing written between rows: past the output (and, in place, past the input) every row keeps its padding
+            assert (host[:, max(m, 0 if device == "stride" else n) :] == 7.0).all(), "the engine wrote past a row's samples"
+            y = host[:, :m]
+        outs.append(y)
+        lengths.append(y.shape[1])
+        forms.append((eng.last_kernel(), eng.last_chain_launch_ms()[2], eng.last_kernel_ms()[1]))
+        if traces is not None:
+            traces.append(eng.suppressor_trace().copy())
+    return np.concatenate(outs, axis=1), forms, lengths
+
+
+def _check_state(name, eng, want, streams=None):
+    st = eng.gate_state()
+    sel = slice(None) if streams is None else np.asarray(streams)
+    gain_err = np.abs(st["current_gain"][sel].astype(np.float64) - want["current_gain"].astype(np.float64))
+    bad = np.flatnonzero(gain_err > 1e-6)
+    assert bad.size == 0, f"{name}: current_gain off in streams {bad[:8].tolist()} (worst {gain_err.max():.3e})"
+    for field in ("chatter_events", "is_open", "auto_relax_active"):
+        bad = np.flatnonzero(st[field][sel] != want[field])
+        assert bad.size == 0, f"{name}: {field} differs in streams {bad[:8].tolist()}"
+    return float(gain_err.max())
+
+
+def _max_abs(name, got, want, tol, gain_err):
+    assert got.shape == want.shape, (got.shape, want.shape)
+    d = np.abs(got.astype(np.float64) - want.astype(np.float64)).max(axis=1)
+    REPORT[name] = f"{got.shape[0]} streams, worst max abs {d.max():.3e}, worst gain {gain_err:.3e}"
+    bad = np.flatnonzero(~(d <= tol))
+    assert bad.size == 0, f"{name}: streams {bad[:8].tolist()} exceed {tol:g} (worst {d.max():.3e})"
+
+
+def _gate_free(core, gated, calls, chain=True, raw=False):
+    """The engine's suppressor (and chain) with the gate and the front end off, fed the oracle's gated signal."""
+    eng = core.Engine(48_000.0, gated.shape[0])
+    if chain:
+        core.configure_auto_eq_chain(eng, 48_000.0, *CHAIN)
+    else:
+        eng.set_eq_enabled(0)
+        eng.set_compressor_enabled(0)
+        eng.set_limiter_enabled(0)
+    eng.set_suppressor_enabled(1)
+    eng.suppressor_set_raw_protocol(int(raw))
+    try:
+        return np.concatenate([eng.process(gated[:, a : a + c]) for a, c in zip(np.cumsum((0,) + tuple(calls[:-1])), calls)], axis=1)
+    finally:
+        eng.close()
+
+
+def _suppressor_bounds(name, got, want, same, gain_err, exceptions, streams=None, tol=1e-5):
+    """Behind the suppressor: `got` bit-identical to `same` (_gate_free on the oracle's gated signal: the gate stage adds
+    nothing); against the oracle RMS <= tol on every stream and worst sample <= tol on every stream but `exceptions`,
+    which must be exactly the streams over it."""
+    assert got.shape == want.shape == same.shape, (got.shape, want.shape, same.shape)
+    differ = np.flatnonzero((got.view(np.uint32) != same.view(np.uint32)).any(axis=1))
+    assert differ.size == 0, f"{name}: streams {differ[:8].tolist()} differ from the suppressor on the oracle's gated signal"
+    d = got.astype(np.float64) - want.astype(np.float64)
+    rms, worst = np.sqrt(np.mean(d * d, axis=1)), np.abs(d).max(axis=1)
+    streams = np.arange(got.shape[0]) if streams is None else np.asarray(streams)
+    over = sorted(int(s) for s in streams[worst > tol])
+    inside = worst[~np.isin(streams, exceptions)]
+    REPORT[name] = (f"{got.shape[0]} streams, bit-identical to the gate-free suppressor; vs oracle worst rms {rms.max():.3e}, "
+                    f"worst sample {inside.max():.3e} (named exceptions {over}: {worst.max():.3e}), worst gain {gain_err:.3e}")
+    bad = np.flatnonzero(~(rms <= tol))
+    assert bad.size == 0, f"{name}: streams {streams[bad[:8]].tolist()} exceed rms {tol:g} (rms {rms.max():.3e})"
+    assert over == sorted(s for s in exceptions if s in set(streams.tolist())), f"{name}: streams over {tol:g}: {over}"
+
+
+def _gate_acted(want_state):
+    assert (want_state["chatter_events"] > 0).any() and (~want_state["is_open"]).any(), "the stimulus never made the gate act"
+
+
+# ----------------------------------------------------------------------------------------------------- no suppressor
+@pytest.mark.parametrize("setting", list(SETTINGS))
+@pytest.mark.parametrize("kernel", [KERNEL_AUTO, KERNEL_LANE, KERNEL_PHASED, KERNEL_QUAD])
+def test_no_suppressor_every_stream(core, kernel, setting):
+    params, clamp = SETTINGS[setting]
+    audio = _audio()
+    want, want_st = _oracle(("chain", setting), audio, 48_000.0, CALLS, params, clamp=clamp, chain=CHAIN)
+    eng = _engine(core, N_STREAMS, kernel=kernel, clamp=clamp)
+    try:
+        got, forms, _ = _run(eng, audio, CALLS, params)
+        assert all(f[0] == (KERNEL_STAGED if kernel == KERNEL_AUTO else kernel) for f in forms), forms
+        gain_err = _check_state(f"{kernel}/{setting}", eng, want_st)
+    finally:
+        eng.close()
+    _gate_acted(want_st)
+    _max_abs(f"no suppressor, kernel {kernel}, {setting}", got, want, 1e-6, gain_err)
+
+
+@pytest.mark.parametrize("setting", ["default_mode0", "default_mode1_clamp"])
+@pytest.mark.parametrize("kernel", [KERNEL_AUTO, KERNEL_PHASED])
+def test_chain_disabled_gated_signal(core, kernel, setting):
+    """EQ, compressor and limiter off: what the engine returns is the front end's and the gate's output itself."""
+    params, clamp = SETTINGS[setting]
+    audio = _audio()
+    want, want_st = _oracle(("gated", setting), audio, 48_000.0, CALLS, params, clamp=clamp)
+    eng = _engine(core, N_STREAMS, kernel=kernel, chain=False, clamp=clamp)
+    try:
+        got, forms, _ = _run(eng, audio, CALLS, params)
+        assert all(f[0] == (KERNEL_STAGED if kernel == KERNEL_AUTO else kernel) for f in forms), forms
+        gain_err = _check_state(f"gated/{kernel}/{setting}", eng, want_st)
+    finally:
+        eng.close()
+    _max_abs(f"chain disabled, kernel {kernel}, {setting}", got, want, 2e-7, gain_err)
+
+
+@pytest.mark.parametrize("fs", [44_100.0, 96_000.0])
+def test_other_sample_rates(core, fs):
+    """Hold, window, cooldown and relax are sample counts rounded from fs; the 8 ms RMS and the smoothing coefficients too."""
+    params = dict(GO.DEFAULT_GATE, mode=1)
+    audio = _audio()
+    want, want_st = _oracle(("fs", fs), audio, fs, CALLS, params, chain=CHAIN)
+    eng = _engine(core, N_STREAMS, fs=fs)
+    try:
+        got, forms, _ = _run(eng, audio, CALLS, params)
+        assert all(f[0] == KERNEL_STAGED for f in forms), forms
+        gain_err = _check_state(f"fs {fs}", eng, want_st)
+    finally:
+        eng.close()
+    _gate_acted(want_st)
+    _max_abs(f"fs {fs:g}", got, want, 1e-6, gain_err)
+
+
+@pytest.mark.parametrize("device", ["stride", "inplace"])
+def test_process_device_no_suppressor(core, device):
+    params, clamp = SETTINGS["default_mode1_clamp"]
+    audio = _audio()
+    want, want_st = _oracle(("chain", "default_mode1_clamp"), audio, 48_000.0, CALLS, params, clamp=clamp, chain=CHAIN)
+    eng = _engine(core, N_STREAMS, clamp=clamp)
+    try:
+        got, _, _ = _run(eng, audio, CALLS, params, device=device)
+        gain_err = _check_state(f"device {device}", eng, want_st)
+    finally:
+        eng.close()
+    _max_abs(f"process_device {device}, no suppressor", got, want, 1e-6, gain_err)
+
+
+def test_4096_streams_auto_one_launch_ring(core):
+    """AUTO at 4096 streams: the one-launch token-ring form behind the gated pre-pass (calls of at least 19 200 samples)."""
+    n_streams, calls = 4096, (19_213, 24_000)
+    audio = _audio(n_streams, sum(calls))
+    params = dict(GO.DEFAULT_GATE, mode=1)
+    want, want_st = GO.run_batch(audio, 48_000.0, calls, params, chain=CHAIN)
+    eng = _engine(core, n_streams)
+    try:
+        got, forms, _ = _run(eng, audio, calls, params)
+        assert all(f[0] == KERNEL_PHASED and f[1] == 1 for f in forms), forms
+        gain_err = _check_state("4096 auto", eng, want_st)
+    finally:
+        eng.close()
+    _gate_acted(want_st)
+    _max_abs("4096 streams, AUTO one-launch ring", got, want, 1e-6, gain_err)
+
+
+# ----------------------------------------------------------------------------------------------------- suppressor
+def _gated(audio, calls, params):
+    """The oracle's front end and gate over every sample (what the gated pre-pass hands the suppressor)."""
+    return _oracle(("gate only", audio.shape[0], calls), audio, 48_000.0, calls, params)[0]
+
+
+def _assert_suppressor_ran(forms, traces, lengths):
+    for (kernel, chain, launches), trace, n in zip(forms, traces, lengths):
+        assert trace.shape[0] == n // GO.FRAME and launches >= 4, (kernel, chain, launches, trace.shape, n)
+
+
+@pytest.mark.parametrize("kernel", [KERNEL_AUTO, KERNEL_PHASED])
+def test_behind_the_suppressor_every_stream(core, kernel):
+    params = dict(GO.DEFAULT_GATE, mode=1)
+    audio = _audio()
+    want, want_st = _oracle(("supp",), audio, 48_000.0, SUPP_CALLS, params, suppressor="wrapper", chain=CHAIN)
+    eng = _engine(core, N_STREAMS, kernel=kernel, suppressor=True)
+    try:
+        traces = []
+        got, forms, lengths = _run(eng, audio, SUPP_CALLS, params, traces=traces)
+        assert lengths == GO.output_calls(SUPP_CALLS, "wrapper"), lengths
+        assert all(f[0] == (KERNEL_STAGED if kernel == KERNEL_AUTO else kernel) for f in forms[1:]), forms
+        _assert_suppressor_ran(forms, traces, lengths)
+        gain_err = _check_state(f"supp {kernel}", eng, want_st)
+    finally:
+        eng.close()
+    _gate_acted(want_st)
+    same = _gate_free(core, _gated(audio, SUPP_CALLS, params), SUPP_CALLS)
+    _suppressor_bounds(f"suppressor, kernel {kernel}", got, want, same, gain_err, SUPPRESSOR_EXCEPTIONS[N_STREAMS])
+
+
+def test_raw_protocol_with_the_gate(core):
+    """supp_prefilter_gate_kernel<true, true>: prefilter -> gate -> the benchmark protocol (clamp(+-1) * 32768, no wet/dry
+    mix), the dynamics chain off."""
+    params = dict(GO.DEFAULT_GATE, mode=1)
+    audio = _audio()
+    want, want_st = _oracle(("raw",), audio, 48_000.0, SUPP_CALLS, params, suppressor="raw")
+    eng = _engine(core, N_STREAMS, chain=False, suppressor=True, raw=True)
+    try:
+        traces = []
+        got, forms, lengths = _run(eng, audio, SUPP_CALLS, params, traces=traces)
+        assert lengths == GO.output_calls(SUPP_CALLS, "raw"), lengths
+        _assert_suppressor_ran(forms, traces, lengths)
+        gain_err = _check_state("raw", eng, want_st)
+    finally:
+        eng.close()
+    same = _gate_free(core, _gated(audio, SUPP_CALLS, params), SUPP_CALLS, chain=False, raw=True)
+    _suppressor_bounds("raw protocol + gate", got, want, same, gain_err, SUPPRESSOR_EXCEPTIONS[N_STREAMS])
+
+
+@pytest.mark.parametrize("device", ["stride", "inplace"])
+def test_process_device_behind_the_suppressor(core, device):
+    params = dict(GO.DEFAULT_GATE, mode=1)
+    audio = _audio()
+    want, want_st = _oracle(("supp",), audio, 48_000.0, SUPP_CALLS, params, suppressor="wrapper", chain=CHAIN)
+    eng = _engine(core, N_STREAMS, suppressor=True)
+    try:
+        traces = []
+        got, forms, lengths = _run(eng, audio, SUPP_CALLS, params, device=device, frames=True, traces=traces)
+        _assert_suppressor_ran(forms, traces, lengths)
+        gain_err = _check_state(f"supp device {device}", eng, want_st)
+    finally:
+        eng.close()
+    same = _gate_free(core, _gated(audio, SUPP_CALLS, params), SUPP_CALLS)
+    _suppressor_bounds(f"process_device {device}, suppressor", got, want, same, gain_err, SUPPRESSOR_EXCEPTIONS[N_STREAMS])
+
+
+def test_4096_streams_behind_the_suppressor(core):
+    """Every stream bit-identical to the gate-free suppressor on the oracle's gated signal.  Against the oracle, sampled:
+    row position p of groups p and (p + 23) % 64 (every position twice, in different groups), plus the first 16 rows of
+    the first, a middle and the last group."""
+    n_streams, calls = 4096, (20_011, 23_213)
+    audio = _audio(n_streams, sum(calls))
+    params = dict(GO.DEFAULT_GATE, mode=1)
+    sample = sorted({64 * (p % 64) + p for p in range(64)} | {64 * ((p + 23) % 64) + p for p in range(64)}
+                    | set(range(0, 16)) | set(range(2048, 2064)) | set(range(4080, 4096)))
+    eng = _engine(core, n_streams, suppressor=True)
+    traces = []
+    try:
+        got, forms, lengths = _run(eng, audio, calls, params, traces=traces)
+        _assert_suppressor_ran(forms, traces, lengths)
+        st = eng.gate_state()
+    finally:
+        eng.close()
+    want, want_st = GO.run_batch(audio, 48_000.0, calls, params, suppressor="wrapper", chain=CHAIN, streams=sample)
+    # row positions covered twice, the first, a middle and the last group
+    assert all(sum(1 for s in sample if s % 64 == p) >= 2 for p in range(64))
+    assert {0, 32, 63} <= {s // 64 for s in sample}
+    gain = np.abs(st["current_gain"][sample].astype(np.float64) - want_st["current_gain"].astype(np.float64))
+    assert gain.max() <= 1e-6 and np.array_equal(st["chatter_events"][sample], want_st["chatter_events"])
+    assert np.array_equal(st["is_open"][sample], want_st["is_open"])
+    assert np.array_equal(st["auto_relax_active"][sample], want_st["auto_relax_active"])
+    assert lengths == GO.output_calls(calls, "wrapper")
+    same = _gate_free(core, _gated(audio, calls, params), calls)
+    differ = np.flatnonzero((got.view(np.uint32) != same.view(np.uint32)).any(axis=1))
+    assert differ.size == 0, f"streams {differ[:8].tolist()} differ from the suppressor on the oracle's gated signal"
+    _suppressor_bounds("4096 suppressor (sampled)", got[sample], want, same[sample], float(gain.max()),
+                       SUPPRESSOR_EXCEPTIONS[n_streams], streams=sample)
+
+
+@pytest.mark.xfail(strict=True, reason="the suppressor alone (no gate) is off the oracle by 2e-5 .. 6e-5 in one or two frames "
+                                       "of streams 29, 68, 82 and 93 of this stimulus (SUPPRESSOR_EXCEPTIONS); cause not found")
+def test_suppressor_alone_on_the_lane_stimulus(core):
+    """Prefilter -> suppressor, no gate, chain off, against the oracle at the suppressor's bound (test_gpu_suppressor.py)."""
+    audio = _audio()
+    eng = core.Engine(48_000.0, N_STREAMS)
+    eng.set_eq_enabled(0)
+    eng.set_compressor_enabled(0)
+    eng.set_limiter_enabled(0)
+    eng.set_prefilter_enabled(1, 1)
+    eng.set_suppressor_enabled(1)
+    try:
+        got = np.concatenate([eng.process(audio[:, a : a + c])
+                              for a, c in zip(np.cumsum((0,) + SUPP_CALLS[:-1]), SUPP_CALLS)], axis=1)
+    finally:
+        eng.close()
+    m = got.shape[1]
+    want = np.stack([_suppressor_oracle(audio[s, :m]) for s in range(N_STREAMS)])
+    worst = np.abs(got.astype(np.float64) - want).max(axis=1)
+    print(f"suppressor alone on the lane stimulus: worst {worst.max():.3e}, streams over 1e-5 {np.flatnonzero(worst > 1e-5).tolist()}")
+    assert worst.max() <= 1e-5
+
+
+def _suppressor_oracle(x):
+    import af_oracle_py as O
+    import chain_oracle as CO
+
+    return O.suppressor_process(O.prefilter(CO.sanitize(x, False)), 1.0)

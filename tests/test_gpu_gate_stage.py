@@ -4,6 +4,7 @@ simulate_auto_eq_chain), with gate state carried across calls."""
 import numpy as np
 import pytest
 
+import gate_oracle as GO
 import signals as S
 
 pytestmark = pytest.mark.gpu
@@ -40,6 +41,16 @@ def gate_signal(n_streams: int, n: int, seed: int = 7) -> np.ndarray:
 def oracle_gate(oracle, x, vad_mode=False):
     g = oracle.Gate(vad_mode=vad_mode)
     return g.process(x), g
+
+
+def check_all_states(eng, want):
+    """Every stream's gate state against the batched oracle's (tests/gate_oracle.py)."""
+    st = eng.gate_state()
+    gain = np.abs(st["current_gain"].astype(np.float64) - want["current_gain"].astype(np.float64))
+    assert gain.max() <= 1e-6, (int(np.argmax(gain)), gain.max())
+    for field in ("chatter_events", "is_open", "auto_relax_active"):
+        assert np.array_equal(st[field], want[field]), (field, np.flatnonzero(st[field] != want[field])[:8])
+    return st
 
 
 def check_state(eng, gates, streams):
@@ -84,6 +95,16 @@ def test_full_realtime_chain_with_the_gate(core, oracle, kernel):
     eng.close()
     assert any(g.chatter_event_count > 0 for g in gates), "the stimulus never made the gate chatter"
     assert float(st["current_gain"].min()) < 0.5 or not all(st["is_open"])
+    # every stream, through the batched oracle
+    want, want_st = GO.run_batch(x, FS, (frames_a * 480, n - frames_a * 480), suppressor="wrapper",
+                                 chain=(S.LIMITER_BANDS, settings))
+    d = got.astype(np.float64) - want.astype(np.float64)
+    rms, worst = np.sqrt(np.mean(d * d, axis=1)), np.abs(d).max(axis=1)
+    print(f"gate stage + suppressor, kernel {kernel}: {n_streams} streams, worst rms {rms.max():.3e}, worst {worst.max():.3e}")
+    assert rms.max() <= 1e-5, (int(np.argmax(rms)), rms.max())
+    assert np.array_equal(st["chatter_events"], want_st["chatter_events"])
+    assert np.abs(st["current_gain"].astype(np.float64) - want_st["current_gain"]).max() <= 1e-6
+    assert np.array_equal(st["is_open"], want_st["is_open"])
 
 
 def _dyn_engine(core, n_streams, kernel=0, presets=1):
@@ -125,8 +146,14 @@ def test_gate_without_the_suppressor(core, oracle, kernel):
         assert np.allclose(rows["input_square_sum"][:, s], want_sq, rtol=1e-5, atol=1e-12), s
         assert not np.allclose(want_sq, raw_sq, rtol=1e-2), "the gate never acted on this stream"
     check_state(eng, gates, (0, 1, 63, 64, 69))
+    # every stream, through the batched oracle
+    want, want_st = GO.run_batch(x, FS, (20_000, x.shape[1] - 20_000), chain=(S.LIMITER_BANDS, settings))
+    check_all_states(eng, want_st)
     eng.close()
+    every = float(np.abs(got.astype(np.float64) - want.astype(np.float64)).max())
+    print(f"gate stage, kernel {kernel}: {n_streams} streams, worst max abs {every:.3e}")
     assert worst <= 1e-6, (kernel, worst)
+    assert every <= 1e-6, (kernel, every)
 
 
 def test_gate_without_the_suppressor_with_the_deesser(core, oracle):
@@ -145,7 +172,7 @@ def test_gate_without_the_suppressor_with_the_deesser(core, oracle):
     rows = eng.block_stats()
     eng.close()
     assert float(rows["deesser_gain_reduction_db"].max()) > 0.5, "the de-esser never acted"
-    for s in (0, 1, 63, 64, 69):
+    for s in range(n_streams):
         gated, _ = oracle_gate(oracle, oracle.prefilter(x[s]))
         want = oracle.simulate_auto_eq_chain(gated, FS, S.LIMITER_BANDS, dict(settings))["output_audio"]
         assert float(np.max(np.abs(got[s].astype(np.float64) - np.asarray(want, dtype=np.float64)))) <= 1e-6, s
@@ -157,7 +184,7 @@ def test_gate_without_the_suppressor_two_presets(core, oracle):
     eng, settings = _dyn_engine(core, n_streams, 0, presets=2)
     got = eng.process(x)
     eng.close()
-    for s in (0, 64, 127):
+    for s in range(n_streams):
         gated, _ = oracle_gate(oracle, oracle.prefilter(x[s]))
         want = oracle.simulate_auto_eq_chain(gated, FS, S.LIMITER_BANDS, settings)["output_audio"]
         assert float(np.max(np.abs(got[s].astype(np.float64) - np.asarray(want, dtype=np.float64)))) <= 1e-6, s
@@ -224,7 +251,7 @@ def test_live_parameter_changes_match_the_oracle(core, oracle):
     eng.gate_set_release_time(250.0)
     b = eng.process(x[:, n1:])
     eng.close()
-    for s in (0, 64):
+    for s in range(n_streams):
         g = oracle.Gate()
         first = g.process(x[s, :n1])
         g.s.threshold_db = -35.0
@@ -257,9 +284,9 @@ def test_modes_and_the_auto_relax_floor(core, oracle, mode):
     eng = _gate_only(core, n_streams)
     eng.gate_set_mode(mode)
     a = eng.process(x[:, :n1])
-    gates = [oracle.Gate(vad_mode=mode != 0) for _ in range(3)]
-    firsts = [g.process(x[s, :n1]) for g, s in zip(gates, (0, 31, 63))]
-    st = check_state(eng, gates, (0, 31, 63))
+    gates = [oracle.Gate(vad_mode=mode != 0) for _ in range(n_streams)]  # every stream
+    firsts = [g.process(x[s, :n1]) for g, s in zip(gates, range(n_streams))]
+    st = check_state(eng, gates, range(n_streams))
     other = oracle.Gate(vad_mode=mode == 0)
     other.process(x[0, :n1])
     assert (gates[0].s.auto_relax_remaining_samples > 0) == (mode == 1)
@@ -269,10 +296,10 @@ def test_modes_and_the_auto_relax_floor(core, oracle, mode):
     else:
         assert not st["auto_relax_active"].any()
     b = eng.process(x[:, n1:])
-    for g, first, s in zip(gates, firsts, (0, 31, 63)):
+    for g, first, s in zip(gates, firsts, range(n_streams)):
         want = _chain(oracle, np.concatenate([first, g.process(x[s, n1:])]))
         assert _tp_free_err(np.concatenate([a[s], b[s]]), want) <= 1e-6, s
-    st = check_state(eng, gates, (0, 31, 63))
+    st = check_state(eng, gates, range(n_streams))
     assert st["chatter_events"].max() > 1
     eng.close()
 
@@ -306,7 +333,7 @@ def test_disable_freezes_and_reset_restores(core, oracle):
     b = eng.process(x[:, n : 2 * n])
     eng.set_gate_enabled(1)
     c = eng.process(x[:, 2 * n :])
-    for s in (0, 63):
+    for s in range(n_streams):
         g = oracle.Gate()
         gated = np.concatenate([g.process(x[s, :n]), x[s, n : 2 * n], g.process(x[s, 2 * n :])])  # skipped in the middle
         want = _chain(oracle, gated)
@@ -336,7 +363,7 @@ def test_disable_with_the_front_end_on_the_stage_pipeline(core, oracle):
     eng.set_gate_enabled(1)
     c = eng.process(x[:, 2 * n :])
     eng.close()
-    for s in (0, 64, 69):
+    for s in range(n_streams):
         pre = oracle.prefilter(x[s])
         g = oracle.Gate()
         gated = np.concatenate([g.process(pre[:n]), pre[n : 2 * n], g.process(pre[2 * n :])])
