@@ -221,6 +221,33 @@ struct af_engine {
   double gate_threshold_db = -40.0, gate_attack_ms = 10.0, gate_release_ms = 100.0;  // NoiseGate::new(-40, 10, 100, fs)
   int gate_mode = 0;                 // 0 ThresholdOnly, 1 VadAssisted, 2 VadOnly
   int64_t *d_gate = nullptr;
+  // the VAD-fused modes (gate.rs:652-741): a VadAutoGate::without_backend attached to the gate.  Its settings are engine-wide
+  // and kept across a detach; its state and the fused gate's own fields live in `d_gate_vad` ([af::kVadFields][stream],
+  // allocated at the first fused call).  `vad_ctl_fresh` / `vad_fused_fresh`: that part of the plane has to be (re)initialised
+  // before the next fused pass (attach, reset, first use).
+  bool gate_vad_attached = false, vad_ctl_fresh = true, vad_fused_fresh = true;
+  float vad_threshold = 0.48f;       // ControlState's default, processor/control.rs:89
+  float vad_hold_ms = 200.0f, vad_margin_db = 10.0f;  // vad.rs:667, 675
+  bool vad_auto_threshold = true;
+  uint32_t *d_gate_vad = nullptr;
+  uint32_t *d_vad_dec = nullptr;     // [block][af::kVadDecWords][stream] decision rows of the running call
+  int64_t vad_dec_capacity = 0;      // bytes
+  int64_t vad_dec_blocks = 0;        // rows the last fused call wrote (af_engine_read_gate_vad_decisions)
+  // evidence for the next fused call: one probability and one availability flag per control block, shared or per stream
+  std::vector<float> vad_ev_prob;
+  std::vector<uint8_t> vad_ev_avail;
+  int64_t vad_ev_blocks = 0;
+  bool vad_ev_per_stream = false;
+  uint8_t *d_vad_ev = nullptr;       // [probabilities f32 | flags u8] of the running call
+  int64_t vad_ev_capacity = 0;       // bytes
+  struct EvidenceStager {            // pinned slots, as ParamStager: the host never waits for a stream
+    static constexpr int kSlots = 8;
+    uint8_t *pinned[kSlots] = {};
+    size_t bytes[kSlots] = {};
+    hipEvent_t done[kSlots] = {};
+    bool used[kSlots] = {};
+    int next = 0;
+  } ev_stager;
   double sample_rate;
 
   af_engine(double fs, int n, int dev) : proto(fs), n_streams(n), device(dev), sample_rate(fs) {}
@@ -550,6 +577,88 @@ void gate_args(const af_engine *e, af::SuppArgs &sa) {
   sa.gate_cooldown = (int32_t)std::round(fs * 1000.0 / 1000.0);
   sa.gate_relax = (int32_t)std::round(fs * 700.0 / 1000.0);
   sa.gate_vad_mode = e->gate_mode != 0 ? 1 : 0;
+}
+
+void drop_vad_evidence(af_engine *e) {
+  e->vad_ev_blocks = 0;
+  e->vad_ev_prob.clear();
+  e->vad_ev_avail.clear();
+}
+bool gate_vad_fused(const af_engine *e) { return e->gate_enabled && e->gate_vad_attached && e->gate_mode != 0; }
+
+// What the fused passes read beside gate_args (every f32 evaluated as the reference evaluates it, in f32)
+void vad_gate_args(const af_engine *e, af::VadGateArgs &va) {
+  const double fs = e->sample_rate;
+  const float fs32 = (float)(uint32_t)fs;  // VadAutoGate::sample_rate is a u32
+  va.plane = e->d_gate_vad;
+  va.dec = e->d_vad_dec;
+  va.block = e->host_params.control_block;
+  va.mode = e->gate_mode;
+  va.auto_threshold = e->vad_auto_threshold ? 1 : 0;
+  va.vad_threshold = e->vad_threshold;
+  va.margin_db = e->vad_margin_db;
+  va.manual_threshold_db = (float)e->gate_threshold_db;  // set_manual_threshold, vad.rs:996-999 (already inside [-80, -10])
+  va.hold_samples = e->vad_hold_ms / 1000.0f * fs32;      // vad.rs:940
+  va.debounce_samples = 50.0f / 1000.0f * fs32;           // vad.rs:929
+  va.smooth_c = af::time_constant_to_coeff(35.0, fs);     // gate.rs:217-220
+  va.smooth_omc = 1.0 - va.smooth_c;
+  auto clampf32 = [](float x, float lo, float hi) { return x < lo ? lo : (x > hi ? hi : x); };
+  va.open_thr = clampf32(e->vad_threshold, 0.05f, 0.95f);                                // gate.rs:392
+  va.close_norm = clampf32(va.open_thr - 0.12f, 0.02f, va.open_thr);                     // gate.rs:393
+  va.close_relax = clampf32(va.open_thr - 0.20f, 0.02f, va.open_thr);
+  va.conf_close = clampf32(va.open_thr - 0.20f, 0.02f, std::max(va.open_thr - 0.02f, 0.02f));  // gate.rs:489-490
+  va.conf_span = std::max(va.open_thr - va.conf_close, 1.0e-3f);                          // gate.rs:491
+  va.tail_thr = e->vad_threshold - 0.20f;                                                // gate.rs:517
+}
+
+// Before a fused call's first pass, on the caller's stream: the state plane (allocated / re-initialised when due), room for
+// the call's decision rows, and the pending evidence through a pinned slot.  Fills `va` but for block0.
+int vad_gate_prepare(af_engine *e, int64_t blocks, hipStream_t stream, af::VadGateArgs &va) {
+  const int64_t NS = e->n_streams;
+  if (!e->d_gate_vad) {
+    AF_HIP(hipMalloc(&e->d_gate_vad, sizeof(uint32_t) * af::kVadFields * NS));
+    e->vad_ctl_fresh = e->vad_fused_fresh = true;
+  }
+  if (e->vad_ctl_fresh || e->vad_fused_fresh) {
+    AF_HIP(af::launch_vad_plane_init(e->d_gate_vad, e->n_streams, (float)(uint32_t)e->sample_rate * 0.05f, e->vad_ctl_fresh,
+                                     e->vad_fused_fresh, stream));
+    e->vad_ctl_fresh = e->vad_fused_fresh = false;
+  }
+  if (int rc = grow_device(e, reinterpret_cast<void **>(&e->d_vad_dec), &e->vad_dec_capacity,
+                           blocks * af::kVadDecWords * NS * (int64_t)sizeof(uint32_t), stream)) return rc;
+  vad_gate_args(e, va);
+  va.prob = nullptr;
+  va.avail = nullptr;
+  va.ev_stride = 0;
+  if (e->vad_ev_blocks > 0) {
+    const size_t count = e->vad_ev_prob.size(), bytes = count * (sizeof(float) + 1);
+    if (int rc = grow_device(e, reinterpret_cast<void **>(&e->d_vad_ev), &e->vad_ev_capacity, (int64_t)bytes, stream)) return rc;
+    auto &st = e->ev_stager;
+    const int slot = st.next;
+    st.next = (st.next + 1) % af_engine::EvidenceStager::kSlots;
+    if (!st.done[slot]) AF_HIP(hipEventCreateWithFlags(&st.done[slot], hipEventDisableTiming));
+    if (st.used[slot]) AF_HIP(hipEventSynchronize(st.done[slot]));  // kSlots calls ago: long done
+    if (st.bytes[slot] < bytes) {
+      if (st.pinned[slot]) AF_HIP(hipHostFree(st.pinned[slot]));
+      st.pinned[slot] = nullptr;
+      AF_HIP(hipHostMalloc(reinterpret_cast<void **>(&st.pinned[slot]), bytes, hipHostMallocDefault));
+      st.bytes[slot] = bytes;
+    }
+    std::memcpy(st.pinned[slot], e->vad_ev_prob.data(), count * sizeof(float));
+    std::memcpy(st.pinned[slot] + count * sizeof(float), e->vad_ev_avail.data(), count);
+    AF_HIP(hipMemcpyAsync(e->d_vad_ev, st.pinned[slot], bytes, hipMemcpyHostToDevice, stream));
+    AF_HIP(hipEventRecord(st.done[slot], stream));
+    st.used[slot] = true;
+    va.prob = reinterpret_cast<const float *>(e->d_vad_ev);
+    va.avail = e->d_vad_ev + count * sizeof(float);
+    va.ev_stride = e->vad_ev_per_stream ? NS : 0;
+    e->vad_ev_blocks = 0;  // consumed: evidence is for ONE call
+    e->vad_ev_prob.clear();
+    e->vad_ev_avail.clear();
+  }
+  va.dec = e->d_vad_dec;
+  e->vad_dec_blocks = blocks;
+  return AF_OK;
 }
 
 // Without the suppressor, the front end runs in the gated pre-pass when the gate is on -- and for the whole stream when the
@@ -1384,6 +1493,16 @@ void af_engine_destroy(af_engine *e) {
     (void)hipSetDevice(e->device);
     (void)hipFree(e->d_gate);
   }
+  if (e->d_gate_vad || e->d_vad_dec || e->d_vad_ev) {
+    (void)hipSetDevice(e->device);
+    (void)hipFree(e->d_gate_vad);
+    (void)hipFree(e->d_vad_dec);
+    (void)hipFree(e->d_vad_ev);
+  }
+  for (int k = 0; k < af_engine::EvidenceStager::kSlots; ++k) {
+    if (e->ev_stager.pinned[k]) (void)hipHostFree(e->ev_stager.pinned[k]);
+    if (e->ev_stager.done[k]) (void)hipEventDestroy(e->ev_stager.done[k]);
+  }
   delete e;
 }
 
@@ -1407,6 +1526,13 @@ int af_engine_reset(af_engine *e) {
     AF_HIP(hipSetDevice(e->device));
     AF_HIP(hipMemset(e->d_gate, 0, sizeof(int64_t) * af::kGateFields * e->n_streams));
   }
+  // ... + VadAutoGate::reset (vad.rs:1017-1031): the plane is rewritten in front of the next fused pass; pending evidence is
+  // dropped with vad_external_probability / _available (gate.rs:775-776)
+  e->vad_ctl_fresh = e->vad_fused_fresh = true;
+  e->vad_ev_blocks = 0;
+  e->vad_ev_prob.clear();
+  e->vad_ev_avail.clear();
+  e->vad_dec_blocks = 0;
   return AF_OK;
 }
 
@@ -1574,14 +1700,152 @@ int af_gate_set_mode(af_engine *e, int32_t mode) {  // gate_controls.rs:75-81; g
   if (!e) return fail(AF_ERR_INVALID_ARGUMENT, "engine is null");
   if (mode < 0 || mode > 2) return fail(AF_ERR_INVALID_ARGUMENT, "Invalid gate mode");
   e->gate_mode = mode;
+  if (mode == 0) drop_vad_evidence(e);  // (as on a detach: no fused call can follow until the mode changes again)
   if (mode == 0 && e->d_gate) {  // set_gate_mode(ThresholdOnly) clears the auto-relax counter at once
     AF_HIP(hipSetDevice(e->device));
     AF_HIP(hipDeviceSynchronize());
     AF_HIP(hipMemset(e->d_gate + (int64_t)af::kGateRelax * e->n_streams, 0, sizeof(int64_t) * e->n_streams));
+    // ... and puts gate_state back to Closed (gate.rs:814-815)
+    if (e->d_gate_vad)
+      AF_HIP(hipMemset(e->d_gate_vad + (int64_t)af::kVadGateState * e->n_streams, 0, sizeof(uint32_t) * e->n_streams));
   }
   return AF_OK;
 }
 double af_gate_threshold_db(const af_engine *e) { return e ? e->gate_threshold_db : 0.0; }
+// ---- the VAD-fused modes: NoiseGate::set_vad_auto_gate (gate.rs:829-836) and the controller's live controls
+// (apply_gate_control, control.rs:856-864, over vad.rs:984, 1002, 1043, 1054)
+namespace {
+void vad_control(double v, float lo, float hi, float *dst) {
+  if (std::isfinite(v)) *dst = (float)v < lo ? lo : ((float)v > hi ? hi : (float)v);
+}
+}  // namespace
+int af_gate_set_vad_auto_gate_enabled(af_engine *e, int32_t on) {
+  if (!e) return fail(AF_ERR_INVALID_ARGUMENT, "engine is null");
+  if ((on != 0) == e->gate_vad_attached) return AF_OK;
+  e->gate_vad_attached = on != 0;
+  if (!on) drop_vad_evidence(e);  // evidence is for a fused call: none can follow until the controller is back
+  if (on) e->vad_ctl_fresh = true;  // a newly attached controller starts from VadAutoGate::without_backend's state
+  return AF_OK;
+}
+int af_gate_set_vad_threshold(af_engine *e, double threshold) {
+  if (!e) return fail(AF_ERR_INVALID_ARGUMENT, "engine is null");
+  vad_control(threshold, 0.0f, 1.0f, &e->vad_threshold);
+  return AF_OK;
+}
+int af_gate_set_hold_time(af_engine *e, double hold_ms) {
+  if (!e) return fail(AF_ERR_INVALID_ARGUMENT, "engine is null");
+  vad_control(hold_ms, 0.0f, 500.0f, &e->vad_hold_ms);
+  return AF_OK;
+}
+int af_gate_set_margin(af_engine *e, double margin_db) {
+  if (!e) return fail(AF_ERR_INVALID_ARGUMENT, "engine is null");
+  vad_control(margin_db, 0.0f, 20.0f, &e->vad_margin_db);
+  return AF_OK;
+}
+int af_gate_set_auto_threshold(af_engine *e, int32_t on) {
+  if (!e) return fail(AF_ERR_INVALID_ARGUMENT, "engine is null");
+  e->vad_auto_threshold = on != 0;  // (vad.rs:1005-1008 repairs a floor <= -100 dB, which the clamp at :747 never lets arise)
+  return AF_OK;
+}
+int af_gate_read_vad_controls(const af_engine *e, double *vad_threshold, double *hold_ms, double *margin_db, int32_t *auto_threshold,
+                              int32_t *attached) {
+  if (!e) return fail(AF_ERR_INVALID_ARGUMENT, "engine is null");
+  if (vad_threshold) *vad_threshold = e->vad_threshold;
+  if (hold_ms) *hold_ms = e->vad_hold_ms;
+  if (margin_db) *margin_db = e->vad_margin_db;
+  if (auto_threshold) *auto_threshold = e->vad_auto_threshold ? 1 : 0;
+  if (attached) *attached = e->gate_vad_attached ? 1 : 0;
+  return AF_OK;
+}
+int af_gate_set_vad_evidence(af_engine *e, const float *probabilities, const uint8_t *available, int64_t n_blocks, int32_t per_stream) {
+  if (!e) return fail(AF_ERR_INVALID_ARGUMENT, "engine is null");
+  if (n_blocks < 0 || (n_blocks > 0 && (!probabilities || !available))) return fail(AF_ERR_INVALID_ARGUMENT, "bad VAD evidence arrays");
+  const size_t count = (size_t)n_blocks * (per_stream ? (size_t)e->n_streams : 1);
+  e->vad_ev_prob.assign(probabilities, probabilities + count);
+  for (float &p : e->vad_ev_prob) p = std::isfinite(p) ? p : 0.0f;  // (the clamp to [0, 1] is the control pass's, gate.rs:841)
+  e->vad_ev_avail.assign(available, available + count);
+  e->vad_ev_blocks = n_blocks;
+  e->vad_ev_per_stream = per_stream != 0;
+  return AF_OK;
+}
+int af_engine_read_gate_vad_decisions(af_engine *e, float *probability, float *noise_floor_db, int32_t *flags, int64_t n_blocks) {
+  if (!e) return fail(AF_ERR_INVALID_ARGUMENT, "engine is null");
+  if (n_blocks != e->vad_dec_blocks)
+    return fail(AF_ERR_INVALID_ARGUMENT, "the last fused call left %lld decision rows, not %lld", (long long)e->vad_dec_blocks,
+                (long long)n_blocks);
+  if (n_blocks == 0) return AF_OK;
+  const int64_t NS = e->n_streams;
+  std::vector<uint32_t> rows((size_t)(n_blocks * af::kVadDecWords * NS));
+  AF_HIP(hipSetDevice(e->device));
+  AF_HIP(hipDeviceSynchronize());
+  AF_HIP(hipMemcpy(rows.data(), e->d_vad_dec, sizeof(uint32_t) * rows.size(), hipMemcpyDeviceToHost));
+  for (int64_t b = 0; b < n_blocks; ++b)
+    for (int64_t s = 0; s < NS; ++s) {
+      const uint32_t *row = rows.data() + b * af::kVadDecWords * NS + s;
+      if (probability) std::memcpy(&probability[b * NS + s], &row[af::kVadDecProb * NS], sizeof(float));
+      if (noise_floor_db) std::memcpy(&noise_floor_db[b * NS + s], &row[af::kVadDecFloor * NS], sizeof(float));
+      if (flags) flags[b * NS + s] = ((row[af::kVadDecFlags * NS] & af::kVadDecHeld) ? 1 : 0) | ((row[af::kVadDecFlags * NS] & af::kVadDecAvail) ? 4 : 0);
+    }
+  return AF_OK;
+}
+int af_engine_read_gate_vad_state(af_engine *e, float *noise_floor_db, float *noise_floor_reliability, float *fused_score,
+                                  float *probability, int32_t *gate_state, int32_t *flags, int32_t n_streams) {
+  if (!e) return fail(AF_ERR_INVALID_ARGUMENT, "engine is null");
+  if (n_streams < 0 || n_streams > e->n_streams)
+    return fail(AF_ERR_INVALID_ARGUMENT, "n_streams %d is outside [0, %d]", n_streams, e->n_streams);
+  const int64_t NS = e->n_streams;
+  std::vector<uint32_t> rows;
+  const bool ctl_live = e->d_gate_vad && !e->vad_ctl_fresh, fused_live = e->d_gate_vad && !e->vad_fused_fresh;
+  if (ctl_live || fused_live) {
+    rows.resize((size_t)(af::kVadFields * NS));
+    AF_HIP(hipSetDevice(e->device));
+    AF_HIP(hipDeviceSynchronize());
+    AF_HIP(hipMemcpy(rows.data(), e->d_gate_vad, sizeof(uint32_t) * rows.size(), hipMemcpyDeviceToHost));
+  }
+  auto word = [&](int field, int32_t s) { return rows[(size_t)(field * NS + s)]; };
+  auto f32 = [&](int field, int32_t s) { float v; const uint32_t w = word(field, s); std::memcpy(&v, &w, sizeof v); return v; };
+  for (int32_t s = 0; s < n_streams; ++s) {
+    float floor_db = -60.0f, reliability = 0.0f, score = 0.0f, prob = 0.0f;  // gate.rs:935-951 without a controller
+    int32_t state = 0, fl = 0;
+    if (ctl_live && e->gate_vad_attached) {
+      floor_db = f32(af::kVadFloor, s);
+      // noise_floor_reliability, vad.rs:805-821 over noise_floor_percentile :786-802
+      const int len = (int)word(af::kVadHistLen, s);
+      if (len > 0) {
+        auto percentile = [&](float pct) {
+          size_t target = (size_t)std::floor((float)len * pct);
+          target = std::min<size_t>(target, (size_t)len - 1);
+          size_t cumulative = 0;
+          for (int b = 0; b < af::kVadBinCount; ++b) {
+            cumulative += word(af::kVadBins + b, s);
+            if (cumulative > target) return -80.0f + (float)b * 1.0f;
+          }
+          return floor_db;
+        };
+        const float maturity = std::min(std::max((float)len / (float)af::kVadHistory, 0.0f), 1.0f);
+        const float spread = std::max(percentile(0.80f) - percentile(0.20f), 0.0f);
+        const float t = std::min(std::max((spread - 3.0f) / 7.0f, 0.0f), 1.0f);
+        const float stationarity = 1.0f - t * t * (3.0f - 2.0f * t);
+        reliability = std::min(std::max(maturity * stationarity, 0.0f), 1.0f);
+      }
+      fl |= (word(af::kVadLastFlags, s) & af::kVadDecHeld) ? 1 : 0;
+      fl |= (word(af::kVadLastFlags, s) & af::kVadDecAvail) ? 4 : 0;
+    }
+    if (fused_live) {
+      score = f32(af::kVadFusedScore, s);
+      prob = f32(af::kVadSmoothed, s);
+      state = (int32_t)word(af::kVadGateState, s);
+      fl |= word(af::kVadFusedOpen, s) ? 2 : 0;
+    }
+    if (noise_floor_db) noise_floor_db[s] = floor_db;
+    if (noise_floor_reliability) noise_floor_reliability[s] = reliability;
+    if (fused_score) fused_score[s] = score;
+    if (probability) probability[s] = prob;
+    if (gate_state) gate_state[s] = state;
+    if (flags) flags[s] = fl;
+  }
+  return AF_OK;
+}
 int af_engine_read_gate_state(af_engine *e, float *current_gain, uint64_t *chatter_events, int32_t *flags, int32_t n_streams) {
   if (!e) return fail(AF_ERR_INVALID_ARGUMENT, "engine is null");
   if (n_streams < 0 || n_streams > e->n_streams)
@@ -1731,6 +1995,9 @@ int af_engine_process_device(af_engine *e, const float *in, float *out, int64_t 
       e->vad_blocks != blocks)
     return fail(AF_ERR_INVALID_ARGUMENT, "expected %lld VAD probabilities at the control cadence, got %lld",
                 (long long)blocks, (long long)e->vad_blocks);
+  if (n_run > 0 && gate_vad_fused(e) && e->vad_ev_blocks > 0 && e->vad_ev_blocks != blocks)
+    return fail(AF_ERR_INVALID_ARGUMENT, "expected %lld VAD evidence blocks at the control cadence, got %lld", (long long)blocks,
+                (long long)e->vad_ev_blocks);
   if (n_run > 0 && !e->pipe.decided) {  // first call after a reset: which form of the chain this engine runs
     af::ChainParams probe = e->host_params;
     if (e->supp.enabled || e->gate_enabled) probe.flags &= ~(af::kFlagInputClamp | af::kFlagDcBlock | af::kFlagPreHighpass | af::kFlagInputScrub);
@@ -1762,6 +2029,10 @@ int af_engine_process_device(af_engine *e, const float *in, float *out, int64_t 
   }
   e->last_stream = stream;
   (void)collect_retired(e, false);
+  const bool fused_gate = n_run > 0 && gate_vad_fused(e);
+  af::VadGateArgs vad_args{};
+  if (fused_gate)
+    if (int rc = vad_gate_prepare(e, blocks, stream, vad_args)) return rc;
   if (e->supp.enabled) {
     const int64_t B = e->n_streams;
     if (e->pending > 0 || rem > 0) {
@@ -1839,7 +2110,12 @@ int af_engine_process_device(af_engine *e, const float *in, float *out, int64_t 
     sa.f64_pre_z1 = af::kPreZ1;
     sa.f32_dc_x1 = af::kDcX1;
     if (e->gate_enabled) gate_args(e, sa);  // (else the pass runs the front end alone and leaves the gate's state alone)
-    AF_HIP(af::launch_gate_prepass(sa, stream));
+    if (fused_gate) {  // modes 1 / 2 with the controller attached: control pass + fused per-sample pass
+      AF_HIP(af::launch_vad_gate_pass(sa, vad_args, stream));
+      e->last_launches += 1;
+    } else {
+      AF_HIP(af::launch_gate_prepass(sa, stream));
+    }
     e->last_launches += 1;
     if (e->timing) AF_HIP(hipEventRecord(e->ev_mid, stream));  // the pre-pass counts as suppressor-side time
     chain_in = out;
@@ -2244,7 +2520,14 @@ int af_engine_process_device(af_engine *e, const float *in, float *out, int64_t 
   auto enqueue_pre = [&](int64_t w) -> int {
     const int64_t f0 = win_f0[w], nf = win_nf[w];
     if (w >= kXh) AF_HIP(hipStreamWaitEvent(e->pre_stream, syn_done[w - kXh], 0));  // its model-input buffer is free
-    AF_HIP(af::launch_suppressor_prefilter(window_args(f0, nf, w), e->pre_stream));
+    if (fused_gate) {  // (a window holds whole control blocks: its first block is f0 x 480 / cb)
+      af::VadGateArgs va = vad_args;
+      va.block0 = f0 * af::kRnnFrame / cb;
+      AF_HIP(af::launch_vad_gate_pass(window_args(f0, nf, w), va, e->pre_stream));
+      e->last_launches += 1;  // the control pass (the per-sample pass stands where the expander pre-pass is counted)
+    } else {
+      AF_HIP(af::launch_suppressor_prefilter(window_args(f0, nf, w), e->pre_stream));
+    }
     AF_HIP(hipEventRecord(pre_done[w], e->pre_stream));
     return AF_OK;
   };

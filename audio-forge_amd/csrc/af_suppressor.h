@@ -126,4 +126,48 @@ struct SuppArgs {
 enum GateField { kGateRms, kGateGain, kGateHold, kGateWindow, kGateTrans, kGateCooldown, kGateRelax, kGateOpen, kGateEff,
                  kGateHasEff, kGateEvents, kGateFields };
 
+// ---- the VAD-fused gate modes (gate.rs:652-741 with a VadAutoGate::without_backend attached, vad.rs:714-966).
+// State plane af_engine::d_gate_vad, 32-bit words, [kVadFields][stream]: the controller's noise-floor ring (250 x f32) and
+// its 1 dB histogram (61 counts; the reference's u16 cannot saturate at 250 entries), its scalars, and the fused gate's own
+// fields.  The control pass owns rows kVadHist .. kVadLastFlags, wave R1 of the per-sample pass owns kVadSmoothed, wave R2
+// kVadFusedScore .. kVadGateState.  vad_plane_init_kernel writes VadAutoGate::without_backend / reset + NoiseGate::reset.
+constexpr int kVadHistory = 250, kVadBinCount = 61;
+enum VadField {
+  kVadHist = 0,
+  kVadBins = kVadHist + kVadHistory,
+  kVadFloor = kVadBins + kVadBinCount,  // f32 noise_floor (dB)
+  kVadHoldTimer,                        // f32 samples
+  kVadClosed,                           // f32 closed_counter_samples
+  kVadTimerRunning, kVadPrevOpen, kVadHistLen, kVadCursor,
+  kVadPrevProb,                         // f32 previous_vad_probability
+  kVadLastFlags,                        // the last block's decision flags (kVadDecHeld | kVadDecAvail)
+  kVadSmoothed,                         // f32 vad_smoothed_probability
+  kVadFusedScore,                       // f32
+  kVadFusedOpen, kVadGateState,         // 0 Closed, 1 Opening, 2 Open, 3 Uncertain, 4 Releasing
+  kVadFields
+};
+// decision row of one (block, stream): what process_with_external_probability hands the per-sample loop
+enum VadDecWord { kVadDecProb, kVadDecDelta, kVadDecFlags, kVadDecFloor /* noise_floor after the block: read-out only */, kVadDecWords };
+constexpr uint32_t kVadDecHeld = 1u, kVadDecAvail = 2u;
+
+struct VadGateArgs {
+  uint32_t *plane;          // [kVadFields][stream]
+  uint32_t *dec;            // [block][kVadDecWords][stream] decision rows of the call
+  const float *prob;        // evidence of the call, [block] (ev_stride 0) or [block][stream], or null: probability 0, not available
+  const uint8_t *avail;
+  int64_t ev_stride;
+  int64_t block0;           // the pass's first block inside the call
+  int32_t block;            // control block, samples
+  int32_t mode;             // 1 VadAssisted, 2 VadOnly
+  int32_t auto_threshold;
+  float vad_threshold, margin_db, manual_threshold_db;
+  float hold_samples;       // hold_time_ms / 1000 * fs, in f32 as vad.rs:940
+  float debounce_samples;   // 50 ms
+  double smooth_c, smooth_omc;  // 35 ms one-pole of the posterior
+  // update_probabilistic_gate_state's and probability_speech_confidence's thresholds (gate.rs:392-393, 488-491, 517), in f32
+  // from vad_threshold: clamp(t, .05, .95); clamp(open - .12 | .20, .02, open); clamp(open - .20, .02, max(open - .02, .02));
+  // max(open - conf_close, 1e-3); t - .20
+  float open_thr, close_norm, close_relax, conf_close, conf_span, tail_thr;
+};
+
 }  // namespace af

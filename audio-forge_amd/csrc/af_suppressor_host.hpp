@@ -17,6 +17,9 @@ hipError_t launch_suppressor_synthesis(const SuppArgs &a, const SuppTables &tb, 
                                        hipEvent_t after_spectra = nullptr);
 hipError_t launch_suppressor_prefilter(const SuppArgs &a, hipStream_t stream);
 hipError_t launch_gate_prepass(const SuppArgs &a, hipStream_t stream);  // the gated front end without the suppressor
+// the VAD-fused gate modes: control pass + per-sample pass (a.n_samples > 0: without the suppressor, else one window of frames)
+hipError_t launch_vad_gate_pass(const SuppArgs &a, const VadGateArgs &v, hipStream_t stream);
+hipError_t launch_vad_plane_init(uint32_t *plane, int32_t n_streams, float closed_counter, bool controller, bool fused, hipStream_t stream);
 hipError_t launch_scale_probe(const float *in, float *out, int64_t n, hipStream_t stream);
 
 // int8 network weights in the layout of the public RNNoise model (dense: [in][out]; GRU: [in][3*units],

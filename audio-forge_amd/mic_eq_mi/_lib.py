@@ -175,6 +175,16 @@ SIGNATURES = {
     "af_gate_threshold_db": (_d, [_vp]),
     "af_engine_gate_enabled": (_i32, [_vp]),
     "af_engine_read_gate_state": (C.c_int, [_vp, _fp, C.POINTER(C.c_uint64), C.POINTER(_i32), _i32]),
+    # the VAD-fused gate modes
+    "af_gate_set_vad_auto_gate_enabled": (C.c_int, [_vp, _i32]),
+    "af_gate_set_vad_threshold": (C.c_int, [_vp, _d]),
+    "af_gate_set_hold_time": (C.c_int, [_vp, _d]),
+    "af_gate_set_margin": (C.c_int, [_vp, _d]),
+    "af_gate_set_auto_threshold": (C.c_int, [_vp, _i32]),
+    "af_gate_read_vad_controls": (C.c_int, [_vp, _dp, _dp, _dp, C.POINTER(_i32), C.POINTER(_i32)]),
+    "af_gate_set_vad_evidence": (C.c_int, [_vp, _fp, C.POINTER(C.c_uint8), _i64, _i32]),
+    "af_engine_read_gate_vad_decisions": (C.c_int, [_vp, _fp, _fp, C.POINTER(_i32), _i64]),
+    "af_engine_read_gate_vad_state": (C.c_int, [_vp, _fp, _fp, _fp, _fp, C.POINTER(_i32), C.POINTER(_i32), _i32]),
     "af_engine_last_chain_launch_ms": (C.c_int, [_vp, _dp, _dp, C.POINTER(_i32)]),
     # product resampler
     "af_engine_last_kernel": (C.c_int, [_vp]),

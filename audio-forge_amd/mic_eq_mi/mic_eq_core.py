@@ -167,6 +167,52 @@ class Engine:
         return {"current_gain": gain, "chatter_events": events, "is_open": (flags & 1) != 0,
                 "auto_relax_active": (flags & 2) != 0}
 
+    def gate_set_vad_evidence(self, probabilities=None, available=None) -> None:
+        """Speech probability and availability per control block of the NEXT call's gate pass: [blocks] (shared by all
+        streams) or [blocks, n_streams].  ``None`` clears it (every block then runs with probability 0, not available)."""
+        if probabilities is None:
+            _lib.check(self._lib.af_gate_set_vad_evidence(self._h, None, None, 0, 0))
+            return
+        p = np.ascontiguousarray(probabilities, dtype=np.float32)
+        a = np.ascontiguousarray(np.ones(p.shape, bool) if available is None else available).astype(np.uint8)
+        if a.shape != p.shape or p.ndim not in (1, 2) or (p.ndim == 2 and p.shape[1] != self.n_streams):
+            raise ValueError("evidence must be [blocks] or [blocks, n_streams], probabilities and flags alike")
+        _lib.check(self._lib.af_gate_set_vad_evidence(self._h, p.ctypes.data_as(C.POINTER(C.c_float)),
+                                                       a.ctypes.data_as(C.POINTER(C.c_uint8)), p.shape[0], int(p.ndim == 2)))
+
+    def gate_vad_controls(self) -> dict:
+        """The VAD controller's settings: ``vad_threshold``, ``hold_ms``, ``margin_db``, ``auto_threshold``, ``attached``."""
+        thr, hold, margin = C.c_double(0.0), C.c_double(0.0), C.c_double(0.0)
+        auto, attached = C.c_int32(0), C.c_int32(0)
+        _lib.check(self._lib.af_gate_read_vad_controls(self._h, C.byref(thr), C.byref(hold), C.byref(margin), C.byref(auto),
+                                                        C.byref(attached)))
+        return {"vad_threshold": thr.value, "hold_ms": hold.value, "margin_db": margin.value,
+                "auto_threshold": bool(auto.value), "attached": bool(attached.value)}
+
+    def gate_vad_decisions(self, n_blocks: int) -> dict:
+        """The per-block decisions of the last fused call, [n_blocks, n_streams]: ``probability`` (clamped), ``noise_floor_db``
+        after the block, ``held_open`` and ``available``."""
+        prob = np.zeros((n_blocks, self.n_streams), dtype=np.float32)
+        floor = np.zeros((n_blocks, self.n_streams), dtype=np.float32)
+        flags = np.zeros((n_blocks, self.n_streams), dtype=np.int32)
+        fp = C.POINTER(C.c_float)
+        _lib.check(self._lib.af_engine_read_gate_vad_decisions(self._h, prob.ctypes.data_as(fp), floor.ctypes.data_as(fp),
+                                                                flags.ctypes.data_as(C.POINTER(C.c_int32)), int(n_blocks)))
+        return {"probability": prob, "noise_floor_db": floor, "held_open": (flags & 1) != 0, "available": (flags & 4) != 0}
+
+    def gate_vad_state(self) -> dict:
+        """Each stream's VAD-fused gate as of the end of the last call: ``noise_floor_db``, ``noise_floor_reliability``,
+        ``fused_score``, ``probability`` (the smoothed posterior) (float32), ``gate_state`` (0 Closed, 1 Opening, 2 Open,
+        3 Uncertain, 4 Releasing), ``held_open`` / ``available`` (the last block's decision) and ``fused_open`` (bool)."""
+        f = [np.zeros(self.n_streams, dtype=np.float32) for _ in range(4)]
+        state = np.zeros(self.n_streams, dtype=np.int32)
+        flags = np.zeros(self.n_streams, dtype=np.int32)
+        fp, ip = C.POINTER(C.c_float), C.POINTER(C.c_int32)
+        _lib.check(self._lib.af_engine_read_gate_vad_state(self._h, *(x.ctypes.data_as(fp) for x in f), state.ctypes.data_as(ip),
+                                                            flags.ctypes.data_as(ip), self.n_streams))
+        return {"noise_floor_db": f[0], "noise_floor_reliability": f[1], "fused_score": f[2], "probability": f[3],
+                "gate_state": state, "held_open": (flags & 1) != 0, "fused_open": (flags & 2) != 0, "available": (flags & 4) != 0}
+
     def block_stats(self) -> np.ndarray:
         """Structured array [blocks, n_streams] of the last process call."""
         blocks = int(self._lib.af_engine_last_block_count(self._h))

@@ -126,7 +126,7 @@ int af_engine_set_prefilter_enabled(af_engine *e, int32_t enabled, int32_t apply
  * (gate.rs:265-285), detector_gain_reduction_db with the auto-relax range (:298-306), track_gate_transition (:578-611),
  * apply_gain (:613-623), process_sample (:626-637).  Modes 1 (VadAssisted) and 2 (VadOnly) arm the chatter auto-relax
  * (24 dB floor) as that path does; the realtime loop also attaches VadAutoGate::without_backend, whose fused-probability
- * path is NOT built here.
+ * path runs once the controller is attached (af_gate_set_vad_auto_gate_enabled, below).
  * Off by default.  Parameters are engine-wide (presets do not carry them) and live between process calls, like
  * apply_gate_control (processor/control.rs:851-865): threshold [-80, -10] dB, attack [0.1, 100] ms, release [10, 1000] ms
  * (audio/processor.rs:77-82); a non-finite value leaves the setting unchanged (control.rs:50-52).  Mode 0/1/2, anything
@@ -146,6 +146,48 @@ int32_t af_engine_gate_enabled(const af_engine *e);   /* VALUE */
  * events since reset, flags bit 0 is_open, bit 1 auto_relax_active -- what dsp_loop.rs:1397-1409 publishes to the
  * meters.  Any pointer may be null; n_streams <= the engine's. */
 int af_engine_read_gate_state(af_engine *e, float *current_gain, uint64_t *chatter_events, int32_t *flags, int32_t n_streams);
+/* ---- the VAD-fused gate modes: the gate with a VadAutoGate::without_backend attached, as the realtime loop runs it -------
+ * dsp_loop.rs:478-487 attaches VadAutoGate::without_backend(fs, vad_threshold) to stage 1 and hands the gate one speech
+ * probability per block (set_external_vad_probability, dsp_loop.rs:1381-1397).  With the controller attached and mode 1 or 2
+ * the gate takes the branch at gate.rs:657-741: per control block the controller (vad.rs:714-966: block RMS in f32, noise-floor
+ * histogram with auto-threshold, debounce and hold time), per sample the fused score (gate.rs:315-366), the five-state
+ * probabilistic gate (:374-483) and the continuous posterior reduction (:485-553).  The probability comes from the caller: no
+ * Silero, no model.  Detached (the default) every mode behaves as described above; attached and mode 0 is the expander, and the
+ * controller is not stepped (gate.rs:659, 743-745).
+ * af_gate_set_vad_auto_gate_enabled: NoiseGate::set_vad_auto_gate (gate.rs:829-836).  A newly attached controller starts from
+ *   without_backend's state (vad.rs:663-690); its manual threshold IS the gate's threshold (af_gate_set_threshold feeds both,
+ *   gate.rs:227-233).  The controller's SETTINGS below are engine-wide and kept while detached (the reference's setters are
+ *   no-ops without a controller and a new controller starts from its defaults: set them again after attaching to get that).
+ * af_gate_set_vad_threshold [0, 1] (vad.rs:1043; default 0.48, control.rs:89), af_gate_set_hold_time [0, 500] ms (vad.rs:1054;
+ *   200), af_gate_set_margin [0, 20] dB (vad.rs:984; 10), af_gate_set_auto_threshold (vad.rs:1002; on): live between calls like
+ *   apply_gate_control (control.rs:856-864); a non-finite value leaves the setting as it is.  set_vad_pre_gain is LEFT OUT: it
+ *   only reaches a Silero instance (vad.rs:1069-1073), which this engine does not have.
+ * af_gate_set_vad_evidence: for the NEXT process call whose gate pass runs the fused path, one probability (clamped to [0, 1],
+ *   gate.rs:841) and one availability flag per control block of the samples that pass covers (the call, or behind the suppressor
+ *   the whole frames it completes; last block short: the cut of the block statistics), shared by all streams or
+ *   [block][stream].  Consumed by that call.  n_blocks = 0 clears it; without evidence every block runs with probability 0, not
+ *   available (dsp_loop.rs:1387-1395 with a stale worker).  Detaching the controller or selecting mode 0 drops it.  A call whose block count differs is refused with
+ *   AF_ERR_INVALID_ARGUMENT before anything is touched.
+ * af_engine_read_gate_vad_state (synchronises): what dsp_loop.rs:1410-1431 publishes -- noise_floor(), noise_floor_reliability(),
+ *   fused_gate_score(), get_vad_probability() (the smoothed posterior) -- plus gate_state (0 Closed, 1 Opening, 2 Open,
+ *   3 Uncertain, 4 Releasing) and flags: bit 0 the last block's held-open decision, bit 1 fused_gate_open, bit 2 the last
+ *   block's availability.  Null pointers are skipped.  Detached: -60, 0 (gate.rs:935-951).
+ * af_engine_reset restores NoiseGate::reset + VadAutoGate::reset (the closed counter restarts at 50 ms, vad.rs:1022) and drops
+ * pending evidence; af_gate_set_mode(0) also puts gate_state back to Closed (gate.rs:814-817). */
+int af_gate_set_vad_auto_gate_enabled(af_engine *e, int32_t enabled);
+int af_gate_set_vad_threshold(af_engine *e, double threshold);
+int af_gate_set_hold_time(af_engine *e, double hold_ms);
+int af_gate_set_margin(af_engine *e, double margin_db);
+int af_gate_set_auto_threshold(af_engine *e, int32_t enabled);
+int af_gate_read_vad_controls(const af_engine *e, double *vad_threshold, double *hold_ms, double *margin_db, int32_t *auto_threshold,
+                              int32_t *attached);
+int af_gate_set_vad_evidence(af_engine *e, const float *probabilities, const uint8_t *available, int64_t n_blocks, int32_t per_stream);
+/* the decision rows of the last call that ran the fused path (synchronises), [block][stream]: the clamped probability, the
+ * noise floor after the block's controller step, and flags (bit 0 held-open, bit 2 available) -- what
+ * process_with_external_probability handed the per-sample loop (gate.rs:662-669).  n_blocks must be that call's block count. */
+int af_engine_read_gate_vad_decisions(af_engine *e, float *probability, float *noise_floor_db, int32_t *flags, int64_t n_blocks);
+int af_engine_read_gate_vad_state(af_engine *e, float *noise_floor_db, float *noise_floor_reliability, float *fused_score,
+                                  float *probability, int32_t *gate_state, int32_t *flags, int32_t n_streams);
 
 /* ---- RNNoise suppressor: rust-core/src/dsp/rnnoise.rs (RNNoiseProcessor) -------------------------
  * Runs between the front end and the EQ (dsp_loop.rs:1521-1599).  48 kHz only.  The suppressor eats whole

@@ -1,8 +1,10 @@
 """Cost of the noise gate stage: 4096 streams x 10 s with the gate off and on, for the full realtime chain (front end +
 suppressor + dynamics) and for the dynamics chain without the suppressor.  One JSON line per case: the call's kernel time
-(af_engine_last_kernel_ms) and its split at the pre-pass | chain boundary (af_engine_last_stage_ms).
+(af_engine_last_kernel_ms) and its split at the pre-pass | chain boundary (af_engine_last_stage_ms).  --fused adds the
+VAD-fused modes (controller attached, mode 1 and 2, one shared probability per control block that follows the talk spurts):
+"gate": "fused1" / "fused2", beside the expander path ("gate": 1) of the same run.
 
-    python tools/bench_gate.py [--streams 4096] [--seconds 10] [--steps 3]
+    python tools/bench_gate.py [--streams 4096] [--seconds 10] [--steps 3] [--fused]
 """
 from __future__ import annotations
 
@@ -22,7 +24,9 @@ def main() -> None:
     ap.add_argument("--streams", type=int, default=4096)
     ap.add_argument("--seconds", type=float, default=10.0)
     ap.add_argument("--steps", type=int, default=3)
+    ap.add_argument("--fused", action="store_true")
     args = ap.parse_args()
+    import numpy as np
     import torch
 
     import signals as S
@@ -37,16 +41,24 @@ def main() -> None:
     y = torch.empty_like(x)
     stream = torch.cuda.current_stream().cuda_stream
     for chain in ("full", "dynamics"):
-        for gate in (0, 1):
+        for gate in (0, 1) + (("fused1", "fused2") if args.fused else ()):
             eng = core.Engine(48_000.0, args.streams)
             core.configure_auto_eq_chain(eng, 48_000.0, S.LIMITER_BANDS, S.limiter_settings(2.0))
             eng.set_prefilter_enabled(1, 1)
             if chain == "full":
                 eng.set_suppressor_enabled(1)
-            eng.set_gate_enabled(gate)
+            eng.set_gate_enabled(int(gate != 0))
+            prob = None
+            if isinstance(gate, str):
+                eng.gate_set_vad_auto_gate_enabled(1)
+                eng.gate_set_mode(int(gate[-1]))
+                tb = (np.arange(-(-n // 960)) + 0.5) * 960 / 48_000.0  # (configure_auto_eq_chain: control blocks of 960)
+                prob = np.where(((tb + 0.037) % 2.0) < 1.0, 0.9, 0.05).astype(np.float32)
             eng.set_timing_enabled(1)
             best = None
             for _ in range(args.steps + 1):  # the first call is warm-up
+                if prob is not None:
+                    eng.gate_set_vad_evidence(prob, np.ones(prob.size, bool))
                 eng.process_device(x.data_ptr(), y.data_ptr(), n, n, 0, stream)
                 torch.cuda.synchronize()
                 ms, launches = eng.last_kernel_ms()
