@@ -38,6 +38,13 @@ hipError_t launch_resample(const double *in, double *out, const ResamplePos *pos
                            int64_t n_out, int64_t in_stride, int64_t out_stride, int32_t n_streams, int32_t sinc_len,
                            double ratio, int variant, hipStream_t stream);
 int resample_segment_outputs(double ratio, int sinc_len);
+hipError_t launch_resample_stream(const float *plane, const float *in, float *out, const ResamplePos *pos, const double *table,
+                                  int64_t split, int64_t n_in, int64_t n_out, int64_t in_stride, int64_t out_stride,
+                                  int32_t plane_stride, int32_t n_streams, int32_t sinc_len, double ratio, int variant,
+                                  hipStream_t stream);
+hipError_t launch_resample_stream_advance(const float *plane, float *next, const float *in, int64_t split, int64_t n_in,
+                                          int64_t shift, int64_t in_stride, int32_t count, int32_t plane_stride, int32_t n_streams,
+                                          hipStream_t stream);
 hipError_t launch_kweight_energy(const float *audio, double *partial, int32_t *non_finite, const double b[5],
                                  const double a5[5], int64_t n_samples, int64_t stride, int64_t n100, int32_t n_streams,
                                  int32_t s100, hipStream_t stream);
@@ -249,6 +256,11 @@ struct af_engine {
     int next = 0;
   } ev_stager;
   double sample_rate;
+  // Device-rate I/O (dsp_loop.rs:274-317): a streaming product resampler in front of and / or behind the chain, built by
+  // af_engine_set_io_sample_rates.  Null = that side runs at the engine's rate; both null = the engine as it always was.
+  af_stream_resampler *rs_in = nullptr, *rs_out = nullptr;
+  float *d_rs_in = nullptr, *d_rs_mid = nullptr, *d_rs_out = nullptr;  // af_engine_stream_host: device-rate input | engine-rate audio | device-rate output
+  int64_t rs_in_capacity = 0, rs_mid_capacity = 0, rs_out_capacity = 0;  // bytes
 
   af_engine(double fs, int n, int dev) : proto(fs), n_streams(n), device(dev), sample_rate(fs) {}
 };
@@ -1503,6 +1515,14 @@ void af_engine_destroy(af_engine *e) {
     if (e->ev_stager.pinned[k]) (void)hipHostFree(e->ev_stager.pinned[k]);
     if (e->ev_stager.done[k]) (void)hipEventDestroy(e->ev_stager.done[k]);
   }
+  af_stream_resampler_destroy(e->rs_in);
+  af_stream_resampler_destroy(e->rs_out);
+  if (e->d_rs_in || e->d_rs_mid || e->d_rs_out) {
+    (void)hipSetDevice(e->device);
+    (void)hipFree(e->d_rs_in);
+    (void)hipFree(e->d_rs_mid);
+    (void)hipFree(e->d_rs_out);
+  }
   delete e;
 }
 
@@ -1533,6 +1553,8 @@ int af_engine_reset(af_engine *e) {
   e->vad_ev_prob.clear();
   e->vad_ev_avail.clear();
   e->vad_dec_blocks = 0;
+  if (e->rs_in) (void)af_stream_resampler_reset(e->rs_in);    // fresh resamplers on both sides: zero history, nothing queued
+  if (e->rs_out) (void)af_stream_resampler_reset(e->rs_out);
   return AF_OK;
 }
 
@@ -1958,8 +1980,24 @@ int af_engine_set_timing_enabled(af_engine *e, int32_t on) {
   return AF_OK;
 }
 
-int af_engine_process_device(af_engine *e, const float *in, float *out, int64_t n_samples, int64_t stream_stride,
-                             int32_t layout, void *hip_stream) {
+// a call that runs n_run samples per stream needs evidence, where evidence is pending, for exactly its control blocks
+static int check_evidence_blocks(const af_engine *e, int64_t n_run) {
+  const int cb = e->host_params.control_block;
+  const int64_t blocks = (n_run + cb - 1) / cb;
+  if (n_run > 0 && (e->host_params.flags & af::kFlagCompressor) && e->host_params.comp.auto_makeup_enabled && e->has_evidence &&
+      e->vad_blocks != blocks)
+    return fail(AF_ERR_INVALID_ARGUMENT, "expected %lld VAD probabilities at the control cadence, got %lld",
+                (long long)blocks, (long long)e->vad_blocks);
+  if (n_run > 0 && gate_vad_fused(e) && e->vad_ev_blocks > 0 && e->vad_ev_blocks != blocks)
+    return fail(AF_ERR_INVALID_ARGUMENT, "expected %lld VAD evidence blocks at the control cadence, got %lld", (long long)blocks,
+                (long long)e->vad_ev_blocks);
+  return AF_OK;
+}
+
+static bool io_resampled(const af_engine *e) { return e->rs_in || e->rs_out; }
+
+static int process_device_impl(af_engine *e, const float *in, float *out, int64_t n_samples, int64_t stream_stride, int32_t layout,
+                               void *hip_stream) {
   if (!e) return fail(AF_ERR_INVALID_ARGUMENT, "engine is null");
   if (n_samples < 0) return fail(AF_ERR_INVALID_ARGUMENT, "n_samples must be >= 0");
   if (layout != AF_LAYOUT_STREAM_MAJOR && layout != AF_LAYOUT_TIME_MAJOR)
@@ -1991,13 +2029,7 @@ int af_engine_process_device(af_engine *e, const float *in, float *out, int64_t 
   }
   const int cb = e->host_params.control_block;
   const int64_t blocks = (n_run + cb - 1) / cb;
-  if (n_run > 0 && (e->host_params.flags & af::kFlagCompressor) && e->host_params.comp.auto_makeup_enabled && e->has_evidence &&
-      e->vad_blocks != blocks)
-    return fail(AF_ERR_INVALID_ARGUMENT, "expected %lld VAD probabilities at the control cadence, got %lld",
-                (long long)blocks, (long long)e->vad_blocks);
-  if (n_run > 0 && gate_vad_fused(e) && e->vad_ev_blocks > 0 && e->vad_ev_blocks != blocks)
-    return fail(AF_ERR_INVALID_ARGUMENT, "expected %lld VAD evidence blocks at the control cadence, got %lld", (long long)blocks,
-                (long long)e->vad_ev_blocks);
+  if (int rc = check_evidence_blocks(e, n_run)) return rc;
   if (n_run > 0 && !e->pipe.decided) {  // first call after a reset: which form of the chain this engine runs
     af::ChainParams probe = e->host_params;
     if (e->supp.enabled || e->gate_enabled) probe.flags &= ~(af::kFlagInputClamp | af::kFlagDcBlock | af::kFlagPreHighpass | af::kFlagInputScrub);
@@ -2798,6 +2830,13 @@ int af_engine_process_device(af_engine *e, const float *in, float *out, int64_t 
   return AF_OK;
 }
 
+int af_engine_process_device(af_engine *e, const float *in, float *out, int64_t n_samples, int64_t stream_stride,
+                             int32_t layout, void *hip_stream) {
+  if (e && io_resampled(e))
+    return fail(AF_ERR_UNSUPPORTED, "this engine resamples its input or output (af_engine_set_io_sample_rates): use af_engine_stream_host");
+  return process_device_impl(e, in, out, n_samples, stream_stride, layout, hip_stream);
+}
+
 // host buffers in, host buffers out: `in` is [streams][n_in] (stream-major) or [n_in][streams] (time-major), `out` gets
 // *n_out samples per stream at out_stride (stream-major) -- n_out differs from n_in only with the suppressor on
 static int process_host_impl(af_engine *e, const float *in, int64_t n_in, float *out, int64_t out_stride, int32_t layout,
@@ -2828,7 +2867,7 @@ static int process_host_impl(af_engine *e, const float *in, int64_t n_in, float 
     else
       AF_HIP(hipMemcpy(e->d_io, in, sizeof(float) * total, hipMemcpyHostToDevice));
   }
-  if (int rc = af_engine_process_device(e, e->d_io, e->d_io, n_in, io_stride, layout, nullptr)) return rc;
+  if (int rc = process_device_impl(e, e->d_io, e->d_io, n_in, io_stride, layout, nullptr)) return rc;
   AF_HIP(hipStreamSynchronize(nullptr));
   if (produced > 0) {
     if (stream_major)
@@ -2840,14 +2879,120 @@ static int process_host_impl(af_engine *e, const float *in, int64_t n_in, float 
   return check_device_status(e);
 }
 
+// ---- device-rate I/O: dsp_loop.rs:274-317 (the two resamplers), 963-1011 (input side), 843-895 (output side)
+int af_engine_set_io_sample_rates(af_engine *e, uint32_t input_rate, uint32_t output_rate) {
+  if (int rc = require_config(e)) return rc;
+  const uint32_t fs = (uint32_t)e->sample_rate;
+  const bool want_in = input_rate != 0 && (double)input_rate != e->sample_rate;    // dsp_loop.rs:274
+  const bool want_out = output_rate != 0 && (double)output_rate != e->sample_rate;  // dsp_loop.rs:292
+  if ((want_in || want_out) && (double)fs != e->sample_rate)
+    return fail(AF_ERR_INVALID_ARGUMENT, "the I/O resamplers need an integer engine sample rate");
+  // build_sinc_resampler (resampling.rs:140-156): the product configuration, chunks of 1024
+  af_stream_resampler *rin = nullptr, *rout = nullptr;
+  if (want_in)
+    if (int rc = af_stream_resampler_create(input_rate, fs, 1024, 128, AF_WINDOW_BLACKMAN, e->n_streams, e->device, &rin)) return rc;
+  if (want_out)
+    if (int rc = af_stream_resampler_create(fs, output_rate, 1024, 128, AF_WINDOW_BLACKMAN, e->n_streams, e->device, &rout)) {
+      af_stream_resampler_destroy(rin);
+      return rc;
+    }
+  af_stream_resampler_destroy(e->rs_in);
+  af_stream_resampler_destroy(e->rs_out);
+  e->rs_in = rin;
+  e->rs_out = rout;
+  return AF_OK;
+}
+
+int af_engine_io_resampler_delay(const af_engine *e, int32_t *input_frames, int32_t *output_frames) {  // dsp_loop.rs:310-313
+  if (!e) return fail(AF_ERR_INVALID_ARGUMENT, "engine is null");
+  if (input_frames) *input_frames = af_stream_resampler_output_delay(e->rs_in);
+  if (output_frames) *output_frames = af_stream_resampler_output_delay(e->rs_out);
+  return AF_OK;
+}
+
+int af_engine_io_resampler_pending(const af_engine *e, int64_t *input_frames, int64_t *output_frames) {
+  if (!e) return fail(AF_ERR_INVALID_ARGUMENT, "engine is null");
+  if (input_frames) *input_frames = af_stream_resampler_pending_input(e->rs_in);
+  if (output_frames) *output_frames = af_stream_resampler_pending_input(e->rs_out);
+  return AF_OK;
+}
+
+// host arithmetic only: what the next af_engine_stream_host call of n_in frames will do
+int af_engine_stream_plan(const af_engine *e, int64_t n_in, int64_t *engine_frames_in, int64_t *engine_frames_out, int64_t *n_out) {
+  if (!e) return fail(AF_ERR_INVALID_ARGUMENT, "engine is null");
+  if (n_in < 0) return fail(AF_ERR_INVALID_ARGUMENT, "n_samples must be >= 0");
+  const int64_t m1 = e->rs_in ? af_stream_resampler_output_frames(e->rs_in, n_in) : n_in;
+  int64_t m2 = m1;
+  if (e->supp.enabled) m2 = (e->rs_in && m1 == 0) ? 0 : ((e->pending + m1) / af::kRnnFrame) * af::kRnnFrame;  // (no chunk: no engine call)
+  const int64_t m3 = e->rs_out ? (m2 > 0 ? af_stream_resampler_output_frames(e->rs_out, m2) : 0) : m2;
+  if (engine_frames_in) *engine_frames_in = m1;
+  if (engine_frames_out) *engine_frames_out = m2;
+  if (n_out) *n_out = m3;
+  return AF_OK;
+}
+
+// af_engine_stream_host with a rate set: input resampler -> the engine's device path on an internal buffer -> output
+// resampler, all on the null stream.  Everything that can refuse the call is checked before either resampler or the engine is
+// touched.  DEVIATION: non-finite host input refuses the call.  The reference resamples first and scrubs afterwards
+// (dsp_loop.rs:963-1011, then routing.rs:802-823), which smears one NaN over the 2 * sinc_len frames whose windows hold it
+// before zeroing them all; here the padded sinc rows would spread it further (a NaN times a zero pad tap is a NaN).
+static int stream_host_resampled(af_engine *e, const float *in, int64_t n_in, float *out, int64_t out_stride, int64_t *n_out) {
+  if (n_in < 0) return fail(AF_ERR_INVALID_ARGUMENT, "n_samples must be >= 0");
+  if (n_in > 0 && !in) return fail(AF_ERR_INVALID_ARGUMENT, "audio pointers are null");
+  int64_t m1 = 0, m2 = 0, m3 = 0;
+  if (int rc = af_engine_stream_plan(e, n_in, &m1, &m2, &m3)) return rc;
+  if (m3 > 0 && !out) return fail(AF_ERR_INVALID_ARGUMENT, "audio pointers are null");
+  if (out_stride < m3)
+    return fail(AF_ERR_INVALID_ARGUMENT, "this call produces %lld frames per stream (af_engine_stream_plan) but out_stride is %lld",
+                (long long)m3, (long long)out_stride);
+  const int64_t B = e->n_streams;
+  for (int64_t i = 0; i < B * n_in; ++i)
+    if (!std::isfinite(in[i])) return fail(AF_ERR_NON_FINITE, "samples must be finite");
+  if (int rc = ensure_started(e)) return rc;
+  if (int rc = check_evidence_blocks(e, m2)) return rc;
+  // ---- accepted
+  const int64_t f4 = sizeof(float);
+  const int64_t mid_stride = std::max<int64_t>(m1, 1) + af::kRnnFrame;  // the engine may return up to 479 frames more than it got
+  if (int rc = grow_device(e, reinterpret_cast<void **>(&e->d_rs_in), &e->rs_in_capacity, f4 * B * std::max<int64_t>(n_in, 1), nullptr)) return rc;
+  if (int rc = grow_device(e, reinterpret_cast<void **>(&e->d_rs_mid), &e->rs_mid_capacity, f4 * B * mid_stride, nullptr)) return rc;
+  if (int rc = grow_device(e, reinterpret_cast<void **>(&e->d_rs_out), &e->rs_out_capacity, f4 * B * std::max<int64_t>(m3, 1), nullptr)) return rc;
+  int64_t got = 0;
+  if (e->rs_in) {
+    if (n_in > 0) AF_HIP(hipMemcpy(e->d_rs_in, in, f4 * B * n_in, hipMemcpyHostToDevice));
+    if (int rc = af_stream_resampler_push_device(e->rs_in, e->d_rs_in, n_in, std::max<int64_t>(n_in, 1), e->d_rs_mid, m1, mid_stride, &got, nullptr)) return rc;
+  } else if (n_in > 0) {
+    AF_HIP(hipMemcpy2D(e->d_rs_mid, f4 * mid_stride, in, f4 * n_in, f4 * n_in, B, hipMemcpyHostToDevice));
+  }
+  if (m1 > 0) {  // (no chunk completed: the engine is not called, dsp_loop.rs:1013)
+    if (int rc = process_device_impl(e, e->d_rs_mid, e->d_rs_mid, m1, mid_stride, AF_LAYOUT_STREAM_MAJOR, nullptr)) return rc;
+  } else {
+    e->last_output_samples = 0;
+    e->last_blocks = 0;
+  }
+  const float *res = e->d_rs_mid;
+  int64_t res_stride = mid_stride;
+  if (e->rs_out && m2 > 0) {
+    if (int rc = af_stream_resampler_push_device(e->rs_out, e->d_rs_mid, m2, mid_stride, e->d_rs_out, m3, std::max<int64_t>(m3, 1), &got, nullptr)) return rc;
+    res = e->d_rs_out;
+    res_stride = std::max<int64_t>(m3, 1);
+  }
+  AF_HIP(hipStreamSynchronize(nullptr));
+  if (m3 > 0) AF_HIP(hipMemcpy2D(out, f4 * out_stride, res, f4 * res_stride, f4 * m3, B, hipMemcpyDeviceToHost));
+  if (n_out) *n_out = m3;
+  return check_device_status(e);
+}
+
 int af_engine_process_host(af_engine *e, const float *in, float *out, int64_t n_samples, int32_t layout) {
   if (layout != AF_LAYOUT_STREAM_MAJOR && layout != AF_LAYOUT_TIME_MAJOR)
     return fail(AF_ERR_INVALID_ARGUMENT, "unknown layout %d", layout);
+  if (e && io_resampled(e))
+    return fail(AF_ERR_UNSUPPORTED, "this engine resamples its input or output (af_engine_set_io_sample_rates): use af_engine_stream_host");
   return process_host_impl(e, in, n_samples, out, layout == AF_LAYOUT_STREAM_MAJOR ? n_samples : (e ? e->n_streams : 0), layout, nullptr);
 }
 
 int af_engine_stream_host(af_engine *e, const float *in, int64_t n_in, float *out, int64_t out_stride, int64_t *n_out) {
   if (n_out) *n_out = 0;
+  if (e && io_resampled(e)) return stream_host_resampled(e, in, n_in, out, out_stride, n_out);
   return process_host_impl(e, in, n_in, out, out_stride, AF_LAYOUT_STREAM_MAJOR, n_out);
 }
 
@@ -3052,6 +3197,23 @@ int resampler_upload(af_resampler *r) {
   r->uploaded_n_in = r->planned_n_in;
   return AF_OK;
 }
+// the argument checks of simulate_product_resampler, resampling.rs:187-214, and what the kernels' LDS tiles hold; host only
+int resampler_check_arguments(uint32_t input_rate, uint32_t output_rate, int64_t chunk_size, int32_t sinc_len, int32_t window,
+                              int32_t device) {
+  if (input_rate == 0 || output_rate == 0) return fail(AF_ERR_INVALID_ARGUMENT, "sample rates must be positive");
+  if (chunk_size < 1 || chunk_size > 1024) return fail(AF_ERR_INVALID_ARGUMENT, "chunk_size must be between 1 and 1024");
+  if (sinc_len < 32 || sinc_len > 2048 || (sinc_len & (sinc_len - 1)) != 0)
+    return fail(AF_ERR_INVALID_ARGUMENT, "sinc_len must be a power of two between 32 and 2048");
+  if (window < 0 || window > af::kWinHann2) return fail(AF_ERR_INVALID_ARGUMENT, "unsupported resampler window %d", window);
+  if (device < 0) return fail(AF_ERR_INVALID_ARGUMENT, "device must be >= 0");
+  const double ratio = (double)output_rate / (double)input_rate;
+  if (chunk_size <= (int64_t)sinc_len + 1 + (int64_t)std::ceil(1.0 / ratio))
+    return fail(AF_ERR_UNSUPPORTED, "chunk_size %lld is too short for sinc_len %d: the reference's chunk loop would produce no frames",
+                (long long)chunk_size, sinc_len);
+  if (af::resample_segment_outputs(ratio, sinc_len) == 0)
+    return fail(AF_ERR_UNSUPPORTED, "sinc_len %d at ratio %.4f needs a longer input span than the LDS tile holds", sinc_len, ratio);
+  return AF_OK;
+}
 }  // namespace
 
 extern "C" {
@@ -3067,19 +3229,7 @@ int af_resampler_create(uint32_t input_rate, uint32_t output_rate, int64_t chunk
                         int32_t device, af_resampler **out) {
   if (!out) return fail(AF_ERR_INVALID_ARGUMENT, "out is null");
   *out = nullptr;
-  // the argument checks of simulate_product_resampler, resampling.rs:187-214
-  if (input_rate == 0 || output_rate == 0) return fail(AF_ERR_INVALID_ARGUMENT, "sample rates must be positive");
-  if (chunk_size < 1 || chunk_size > 1024) return fail(AF_ERR_INVALID_ARGUMENT, "chunk_size must be between 1 and 1024");
-  if (sinc_len < 32 || sinc_len > 2048 || (sinc_len & (sinc_len - 1)) != 0)
-    return fail(AF_ERR_INVALID_ARGUMENT, "sinc_len must be a power of two between 32 and 2048");
-  if (window < 0 || window > af::kWinHann2) return fail(AF_ERR_INVALID_ARGUMENT, "unsupported resampler window %d", window);
-  if (device < 0) return fail(AF_ERR_INVALID_ARGUMENT, "device must be >= 0");
-  const double ratio = (double)output_rate / (double)input_rate;
-  if (chunk_size <= (int64_t)sinc_len + 1 + (int64_t)std::ceil(1.0 / ratio))
-    return fail(AF_ERR_UNSUPPORTED, "chunk_size %lld is too short for sinc_len %d: the reference's chunk loop would produce no frames",
-                (long long)chunk_size, sinc_len);
-  if (af::resample_segment_outputs(ratio, sinc_len) == 0)
-    return fail(AF_ERR_UNSUPPORTED, "sinc_len %d at ratio %.4f needs a longer input span than the LDS tile holds", sinc_len, ratio);
+  if (int rc = resampler_check_arguments(input_rate, output_rate, chunk_size, sinc_len, window, device)) return rc;
   af_resampler *r = new af_resampler();
   r->device = device;
   r->plan.build(input_rate, output_rate, chunk_size, sinc_len, window);
@@ -3182,6 +3332,286 @@ int af_resampler_process_host(af_resampler *r, const double *in, double *out, in
 }
 
 int af_resampler_last_kernel_ms(af_resampler *r, double *ms) {
+  if (!r || !ms) return fail(AF_ERR_INVALID_ARGUMENT, "null argument");
+  *ms = 0.0;
+  if (!r->timed) return AF_OK;
+  AF_HIP(hipEventSynchronize(r->ev1));
+  float t = 0.0f;
+  AF_HIP(hipEventElapsedTime(&t, r->ev0, r->ev1));
+  *ms = t;
+  return AF_OK;
+}
+
+}  // extern "C"
+
+// ------------------------------------------------------------------------------------------
+// The product resampler as a stream (dsp_loop.rs:274-317, 843-895, 963-1011): state carried across calls, f32 in and out.
+// Kernels and the layout of the carried plane: af_resampler_stream.hip.
+struct af_stream_resampler {
+  af::ResamplePlan plan;
+  int device = 0, n_streams = 0;
+  int variant = 0;             // as af_resampler::variant
+  int32_t plane_stride = 0;    // 2 * sinc_len + chunk - 1 frames per stream
+  // host state: all streams advance in lock step
+  double last_index = 0.0;     // SincFixedIn::last_index, advanced by the crate's repeated addition
+  int64_t pending = 0;         // frames queued behind the history that do not fill a chunk yet
+  int64_t chunks = 0, frames_in = 0, frames_out = 0;
+  bool fresh = true;           // the history has to be zeroed in front of the next launch (create, reset)
+  // device state
+  double *d_table = nullptr;
+  float *d_plane[2] = {nullptr, nullptr};  // ping-pong pair, [n_streams][plane_stride]
+  int cur = 0;
+  // per-call scratch: the position records of the chunks the call completes
+  std::vector<af::ResamplePos> pos;
+  af::ResamplePos *d_pos = nullptr;
+  int64_t pos_capacity = 0;    // bytes
+  struct Retired { void *p; hipEvent_t ev; };
+  std::vector<Retired> retired;
+  struct Stager {              // pinned slots, as af_engine::ParamStager: the host never waits for a stream
+    static constexpr int kSlots = 8;
+    void *pinned[kSlots] = {};
+    size_t bytes[kSlots] = {};
+    hipEvent_t done[kSlots] = {};
+    bool used[kSlots] = {};
+    int next = 0;
+  } stager;
+  float *d_in = nullptr, *d_out = nullptr;  // staging of the host entry point
+  int64_t in_capacity = 0, out_capacity = 0;
+  hipEvent_t ev0 = nullptr, ev1 = nullptr;
+  bool timed = false;
+};
+
+namespace {
+
+struct StreamReplay { int64_t chunks, n_out, rem; double last_index; };
+// What a push of n_in frames does, replayed on the host: changes nothing.  With `pos`, the position records of the frames
+// it produces, on the call's virtual axis (chunk j's buffer starts at axis frame j * chunk, its input 2 * sinc_len later).
+StreamReplay stream_replay(const af_stream_resampler *r, int64_t n_in, std::vector<af::ResamplePos> *pos) {
+  const int64_t total = r->pending + n_in, chunk = r->plan.chunk;
+  StreamReplay p{total / chunk, 0, total % chunk, r->last_index};
+  if (pos) pos->clear();
+  for (int64_t j = 0; j < p.chunks; ++j)
+    p.n_out += r->plan.chunk_positions(p.last_index, j * chunk + 2 * (int64_t)r->plan.sinc_len, pos);
+  return p;
+}
+
+int stream_collect_retired(af_stream_resampler *r, bool all) {
+  size_t kept = 0;
+  for (auto &x : r->retired) {
+    hipError_t q = all ? hipEventSynchronize(x.ev) : hipEventQuery(x.ev);
+    if (q == hipSuccess) {
+      (void)hipFree(x.p);
+      (void)hipEventDestroy(x.ev);
+    } else {
+      if (q != hipErrorNotReady) (void)hipGetLastError();
+      r->retired[kept++] = x;
+    }
+  }
+  r->retired.resize(kept);
+  return AF_OK;
+}
+
+// the call's position records -> d_pos behind everything queued on `stream`, through a pinned slot
+int stream_upload_positions(af_stream_resampler *r, hipStream_t stream) {
+  const int64_t need = (int64_t)(sizeof(af::ResamplePos) * r->pos.size());
+  if (need > r->pos_capacity) {  // per-call scratch: grown geometrically, the old buffer retired behind an event
+    const int64_t cap = std::max<int64_t>(need, r->pos_capacity + r->pos_capacity / 2);
+    void *fresh = nullptr;
+    AF_HIP(hipMalloc(&fresh, (size_t)cap));
+    if (r->d_pos) {
+      hipEvent_t ev;
+      AF_HIP(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
+      AF_HIP(hipEventRecord(ev, stream));
+      r->retired.push_back({r->d_pos, ev});
+    }
+    r->d_pos = static_cast<af::ResamplePos *>(fresh);
+    r->pos_capacity = cap;
+  }
+  auto &st = r->stager;
+  const int slot = st.next;
+  st.next = (st.next + 1) % af_stream_resampler::Stager::kSlots;
+  if (!st.done[slot]) AF_HIP(hipEventCreateWithFlags(&st.done[slot], hipEventDisableTiming));
+  if (st.used[slot]) AF_HIP(hipEventSynchronize(st.done[slot]));  // kSlots pushes ago: normally long done
+  if ((size_t)need > st.bytes[slot]) {
+    if (st.pinned[slot]) AF_HIP(hipHostFree(st.pinned[slot]));
+    st.pinned[slot] = nullptr;
+    const size_t cap = std::max<size_t>((size_t)need, st.bytes[slot] + st.bytes[slot] / 2);
+    st.bytes[slot] = 0;
+    AF_HIP(hipHostMalloc(&st.pinned[slot], cap, hipHostMallocDefault));
+    st.bytes[slot] = cap;
+  }
+  std::memcpy(st.pinned[slot], r->pos.data(), (size_t)need);
+  AF_HIP(hipMemcpyAsync(r->d_pos, st.pinned[slot], (size_t)need, hipMemcpyHostToDevice, stream));
+  AF_HIP(hipEventRecord(st.done[slot], stream));
+  st.used[slot] = true;
+  return AF_OK;
+}
+
+// The device half of a push whose replay `p` (with r->pos filled) has been accepted: enqueues on `stream`, commits the host state.
+int stream_push_enqueue(af_stream_resampler *r, const StreamReplay &p, const float *d_in, int64_t n_in, int64_t in_stride,
+                        float *d_out, int64_t out_stride, hipStream_t stream) {
+  AF_HIP(hipSetDevice(r->device));
+  (void)stream_collect_retired(r, false);
+  const size_t plane_bytes = sizeof(float) * (size_t)r->plane_stride * r->n_streams;
+  if (!r->d_table) {
+    AF_HIP(hipMalloc(&r->d_table, sizeof(double) * r->plan.table.size()));
+    AF_HIP(hipMemcpyAsync(r->d_table, r->plan.table.data(), sizeof(double) * r->plan.table.size(), hipMemcpyHostToDevice, stream));
+    AF_HIP(hipMalloc(&r->d_plane[0], plane_bytes));
+    AF_HIP(hipMalloc(&r->d_plane[1], plane_bytes));
+    AF_HIP(hipEventCreate(&r->ev0));
+    AF_HIP(hipEventCreate(&r->ev1));
+    r->fresh = true;
+  }
+  if (r->fresh) {  // SincFixedIn::new / reset: a history of zeros
+    AF_HIP(hipMemsetAsync(r->d_plane[r->cur], 0, plane_bytes, stream));
+    r->fresh = false;
+  }
+  const int64_t split = 2 * (int64_t)r->plan.sinc_len + r->pending;
+  if (p.n_out > 0)
+    if (int rc = stream_upload_positions(r, stream)) return rc;
+  AF_HIP(hipEventRecord(r->ev0, stream));
+  if (p.n_out > 0)
+    AF_HIP(af::launch_resample_stream(r->d_plane[r->cur], d_in, d_out, r->d_pos, r->d_table, split, n_in, p.n_out, in_stride,
+                                      out_stride, r->plane_stride, r->n_streams, r->plan.sinc_len, r->plan.ratio, r->variant, stream));
+  if (n_in > 0) {  // the plane of the next call: the last 2 * sinc_len frames consumed + the remainder, into the other plane
+    AF_HIP(af::launch_resample_stream_advance(r->d_plane[r->cur], r->d_plane[r->cur ^ 1], d_in, split, n_in, p.chunks * r->plan.chunk,
+                                              in_stride, (int32_t)(2 * r->plan.sinc_len + p.rem), r->plane_stride, r->n_streams, stream));
+    r->cur ^= 1;
+  }
+  AF_HIP(hipEventRecord(r->ev1, stream));
+  r->timed = true;
+  r->last_index = p.last_index;
+  r->pending = p.rem;
+  r->chunks += p.chunks;
+  r->frames_in += n_in;
+  r->frames_out += p.n_out;
+  return AF_OK;
+}
+
+// everything that can refuse a push, before anything is touched; fills r->pos
+int stream_push_check(af_stream_resampler *r, const float *in, int64_t n_in, int64_t in_stride, const float *out, int64_t out_capacity,
+                      int64_t out_stride, StreamReplay *p) {
+  if (!r) return fail(AF_ERR_INVALID_ARGUMENT, "resampler is null");
+  if (n_in < 0 || in_stride < n_in) return fail(AF_ERR_INVALID_ARGUMENT, "in_stride must cover n_in frames");
+  if (!in && n_in > 0) return fail(AF_ERR_INVALID_ARGUMENT, "null buffer");
+  *p = stream_replay(r, n_in, &r->pos);
+  if (out_capacity < p->n_out || out_stride < p->n_out)
+    return fail(AF_ERR_INVALID_ARGUMENT, "this push produces %lld frames per stream: out_capacity %lld / out_stride %lld is too small",
+                (long long)p->n_out, (long long)out_capacity, (long long)out_stride);
+  if (!out && p->n_out > 0) return fail(AF_ERR_INVALID_ARGUMENT, "null buffer");
+  return AF_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int af_stream_resampler_create(uint32_t input_rate, uint32_t output_rate, int64_t chunk_size, int32_t sinc_len, int32_t window,
+                               int32_t n_streams, int32_t device, af_stream_resampler **out) {
+  if (!out) return fail(AF_ERR_INVALID_ARGUMENT, "out is null");
+  *out = nullptr;
+  if (int rc = resampler_check_arguments(input_rate, output_rate, chunk_size, sinc_len, window, device)) return rc;
+  if (n_streams <= 0) return fail(AF_ERR_INVALID_ARGUMENT, "n_streams must be positive");
+  af_stream_resampler *r = new af_stream_resampler();
+  r->device = device;
+  r->n_streams = n_streams;
+  r->plan.build(input_rate, output_rate, chunk_size, sinc_len, window);
+  r->plane_stride = (int32_t)(2 * r->plan.sinc_len + chunk_size - 1);
+  r->last_index = r->plan.initial_index();
+  if (const char *env = std::getenv("AF_RESAMPLER_VARIANT")) r->variant = std::strcmp(env, "valu") == 0 ? 1 : (std::strcmp(env, "mfma32") == 0 ? 2 : 0);
+  *out = r;
+  return AF_OK;
+}
+
+void af_stream_resampler_destroy(af_stream_resampler *r) {
+  if (!r) return;
+  if (r->d_table || r->d_in || r->d_out) {
+    (void)hipSetDevice(r->device);
+    (void)hipDeviceSynchronize();
+    (void)stream_collect_retired(r, true);
+    (void)hipFree(r->d_table);
+    (void)hipFree(r->d_plane[0]);
+    (void)hipFree(r->d_plane[1]);
+    (void)hipFree(r->d_pos);
+    (void)hipFree(r->d_in);
+    (void)hipFree(r->d_out);
+    for (int k = 0; k < af_stream_resampler::Stager::kSlots; ++k) {
+      if (r->stager.pinned[k]) (void)hipHostFree(r->stager.pinned[k]);
+      if (r->stager.done[k]) (void)hipEventDestroy(r->stager.done[k]);
+    }
+    if (r->ev0) (void)hipEventDestroy(r->ev0);
+    if (r->ev1) (void)hipEventDestroy(r->ev1);
+  }
+  delete r;
+}
+
+int af_stream_resampler_reset(af_stream_resampler *r) {
+  if (!r) return fail(AF_ERR_INVALID_ARGUMENT, "resampler is null");
+  r->last_index = r->plan.initial_index();
+  r->pending = r->chunks = r->frames_in = r->frames_out = 0;
+  r->fresh = true;  // the plane is zeroed in stream order in front of the next push
+  return AF_OK;
+}
+
+int af_stream_resampler_clear_pending(af_stream_resampler *r) {  // dsp_loop.rs:941-944: resample_input.clear()
+  if (!r) return fail(AF_ERR_INVALID_ARGUMENT, "resampler is null");
+  r->pending = 0;
+  return AF_OK;
+}
+
+int64_t af_stream_resampler_output_frames(const af_stream_resampler *r, int64_t n_in) {
+  if (!r || n_in < 0) return 0;
+  return stream_replay(r, n_in, nullptr).n_out;
+}
+int64_t af_stream_resampler_pending_input(const af_stream_resampler *r) { return r ? r->pending : 0; }
+int af_stream_resampler_output_delay(const af_stream_resampler *r) { return r ? r->plan.output_delay() : 0; }
+int64_t af_stream_resampler_frames_in(const af_stream_resampler *r) { return r ? r->frames_in : 0; }
+int64_t af_stream_resampler_frames_out(const af_stream_resampler *r) { return r ? r->frames_out : 0; }
+
+int af_stream_resampler_push_device(af_stream_resampler *r, const float *d_in, int64_t n_in, int64_t in_stride, float *d_out,
+                                    int64_t out_capacity, int64_t out_stride, int64_t *n_out, void *hip_stream) {
+  if (n_out) *n_out = 0;
+  StreamReplay p{};
+  if (int rc = stream_push_check(r, d_in, n_in, in_stride, d_out, out_capacity, out_stride, &p)) return rc;
+  if (int rc = stream_push_enqueue(r, p, d_in, n_in, in_stride, d_out, out_stride, static_cast<hipStream_t>(hip_stream))) return rc;
+  if (n_out) *n_out = p.n_out;
+  return AF_OK;
+}
+
+int af_stream_resampler_push_host(af_stream_resampler *r, const float *in, int64_t n_in, int64_t in_stride, float *out,
+                                  int64_t out_capacity, int64_t out_stride, int64_t *n_out) {
+  if (n_out) *n_out = 0;
+  StreamReplay p{};
+  if (int rc = stream_push_check(r, in, n_in, in_stride, out, out_capacity, out_stride, &p)) return rc;
+  for (int64_t s = 0; s < r->n_streams; ++s)
+    for (int64_t i = 0; i < n_in; ++i)
+      if (!std::isfinite(in[s * in_stride + i])) return fail(AF_ERR_NON_FINITE, "samples must be finite");
+  AF_HIP(hipSetDevice(r->device));
+  const int64_t B = r->n_streams, need_in = std::max<int64_t>(1, B * n_in), need_out = std::max<int64_t>(1, B * p.n_out);
+  if (need_in > r->in_capacity) {  // (the host entry point synchronises before it returns: nothing reads the old buffer)
+    if (r->d_in) AF_HIP(hipFree(r->d_in));
+    r->d_in = nullptr;
+    r->in_capacity = 0;
+    AF_HIP(hipMalloc(&r->d_in, sizeof(float) * need_in));
+    r->in_capacity = need_in;
+  }
+  if (need_out > r->out_capacity) {
+    if (r->d_out) AF_HIP(hipFree(r->d_out));
+    r->d_out = nullptr;
+    r->out_capacity = 0;
+    AF_HIP(hipMalloc(&r->d_out, sizeof(float) * need_out));
+    r->out_capacity = need_out;
+  }
+  const size_t f4 = sizeof(float);
+  if (n_in > 0) AF_HIP(hipMemcpy2D(r->d_in, f4 * n_in, in, f4 * in_stride, f4 * n_in, B, hipMemcpyHostToDevice));
+  if (int rc = stream_push_enqueue(r, p, r->d_in, n_in, std::max<int64_t>(n_in, 1), r->d_out, std::max<int64_t>(p.n_out, 1), nullptr)) return rc;
+  AF_HIP(hipStreamSynchronize(nullptr));
+  if (p.n_out > 0) AF_HIP(hipMemcpy2D(out, f4 * out_stride, r->d_out, f4 * p.n_out, f4 * p.n_out, B, hipMemcpyDeviceToHost));
+  if (n_out) *n_out = p.n_out;
+  return AF_OK;
+}
+
+int af_stream_resampler_last_kernel_ms(af_stream_resampler *r, double *ms) {
   if (!r || !ms) return fail(AF_ERR_INVALID_ARGUMENT, "null argument");
   *ms = 0.0;
   if (!r->timed) return AF_OK;

@@ -110,43 +110,53 @@ struct ResamplePlan {
     return (int64_t)std::round(((double)n_in * (double)output_rate) / (double)input_rate);
   }
 
+  // One call of rubato's SincFixedIn::process_into_buffer on a whole chunk: advances `last_index` by the crate's repeated
+  // addition and returns the frames the chunk produces.  With `pos`, appends where every produced frame reads its input;
+  // `origin` is the index of the chunk's first frame on the caller's input axis.
+  int64_t chunk_positions(double &last_index, int64_t origin, std::vector<ResamplePos> *pos) const {
+    const double t_ratio = 1.0 / ratio;
+    const long end_idx = (long)chunk - ((long)sinc_len + 1) - (long)std::ceil(t_ratio);
+    double idx = last_index;
+    int64_t made = 0;
+    while (idx < (double)end_idx) {
+      idx += t_ratio;
+      ++made;
+      if (!pos) continue;
+      long index = (long)std::floor(idx);
+      long sub = (long)std::floor((idx - std::floor(idx)) * (double)kResampleOversampling);
+      long pi_[4], ps[4];
+      pi_[0] = index; ps[0] = sub - 1;
+      if (ps[0] < 0) { ps[0] += kResampleOversampling; pi_[0] -= 1; }
+      pi_[1] = index; ps[1] = sub;
+      for (int k = 2; k < 4; ++k) {
+        sub += 1;
+        if (sub >= kResampleOversampling) { sub -= kResampleOversampling; index += 1; }
+        pi_[k] = index; ps[k] = sub;
+      }
+      const double scaled = idx * (double)kResampleOversampling;
+      ResamplePos r{};
+      r.base = origin + pi_[0];
+      r.frac = scaled - std::floor(scaled);
+      for (int k = 0; k < 4; ++k) {
+        r.sub[k] = (uint16_t)ps[k];
+        r.off[k] = (uint8_t)(pi_[k] - pi_[0]);
+      }
+      pos->push_back(r);
+    }
+    last_index = idx - (double)chunk;
+    return made;
+  }
+  double initial_index() const { return -(double)(sinc_len / 2); }
+
   // Replays the reference's driver loop (full chunks, one zero-padded partial chunk, silent flush chunks until
   // expected + delay frames exist) and records where every produced frame reads its input.
   int64_t positions(int64_t n_in, std::vector<ResamplePos> &pos, int64_t *blocks) const {
     pos.clear();
-    const double t_ratio = 1.0 / ratio;
-    const long end_idx = (long)chunk - ((long)sinc_len + 1) - (long)std::ceil(t_ratio);
     const int64_t target = expected_frames(n_in) + output_delay();
-    double last_index = -(double)(sinc_len / 2);
+    double last_index = initial_index();
     int64_t nblocks = 0, chunk_index = 0;
     auto run_chunk = [&]() {
-      double idx = last_index;
-      int64_t made = 0;
-      while (idx < (double)end_idx) {
-        idx += t_ratio;
-        long index = (long)std::floor(idx);
-        long sub = (long)std::floor((idx - std::floor(idx)) * (double)kResampleOversampling);
-        long pi_[4], ps[4];
-        pi_[0] = index; ps[0] = sub - 1;
-        if (ps[0] < 0) { ps[0] += kResampleOversampling; pi_[0] -= 1; }
-        pi_[1] = index; ps[1] = sub;
-        for (int k = 2; k < 4; ++k) {
-          sub += 1;
-          if (sub >= kResampleOversampling) { sub -= kResampleOversampling; index += 1; }
-          pi_[k] = index; ps[k] = sub;
-        }
-        const double scaled = idx * (double)kResampleOversampling;
-        ResamplePos r{};
-        r.base = chunk_index * chunk + pi_[0];
-        r.frac = scaled - std::floor(scaled);
-        for (int k = 0; k < 4; ++k) {
-          r.sub[k] = (uint16_t)ps[k];
-          r.off[k] = (uint8_t)(pi_[k] - pi_[0]);
-        }
-        pos.push_back(r);
-        ++made;
-      }
-      last_index = idx - (double)chunk;
+      const int64_t made = chunk_positions(last_index, chunk_index * chunk, &pos);
       ++chunk_index;
       ++nblocks;
       return made;

@@ -199,6 +199,23 @@ SIGNATURES = {
     "af_resampler_process_device": (C.c_int, [_vp, _vp, _vp, _i64, _i32, _i64, _i64, _vp]),
     "af_resampler_process_host": (C.c_int, [_vp, _dp, _dp, _i64, _i32, _i64, _i64]),
     "af_resampler_last_kernel_ms": (C.c_int, [_vp, _dp]),
+    # streaming product resampler + the engine's device-rate I/O
+    "af_stream_resampler_create": (C.c_int, [C.c_uint32, C.c_uint32, _i64, _i32, _i32, _i32, _i32, C.POINTER(_vp)]),
+    "af_stream_resampler_destroy": (None, [_vp]),
+    "af_stream_resampler_push_host": (C.c_int, [_vp, _fp, _i64, _i64, _fp, _i64, _i64, C.POINTER(_i64)]),
+    "af_stream_resampler_push_device": (C.c_int, [_vp, _vp, _i64, _i64, _vp, _i64, _i64, C.POINTER(_i64), _vp]),
+    "af_stream_resampler_output_frames": (_i64, [_vp, _i64]),
+    "af_stream_resampler_pending_input": (_i64, [_vp]),
+    "af_stream_resampler_output_delay": (C.c_int, [_vp]),
+    "af_stream_resampler_frames_in": (_i64, [_vp]),
+    "af_stream_resampler_frames_out": (_i64, [_vp]),
+    "af_stream_resampler_reset": (C.c_int, [_vp]),
+    "af_stream_resampler_clear_pending": (C.c_int, [_vp]),
+    "af_stream_resampler_last_kernel_ms": (C.c_int, [_vp, _dp]),
+    "af_engine_set_io_sample_rates": (C.c_int, [_vp, C.c_uint32, C.c_uint32]),
+    "af_engine_stream_plan": (C.c_int, [_vp, _i64, C.POINTER(_i64), C.POINTER(_i64), C.POINTER(_i64)]),
+    "af_engine_io_resampler_delay": (C.c_int, [_vp, C.POINTER(_i32), C.POINTER(_i32)]),
+    "af_engine_io_resampler_pending": (C.c_int, [_vp, C.POINTER(_i64), C.POINTER(_i64)]),
     "af_gate_process_host": (C.c_int, [_fp, _fp, _i64, _i32, _i64, _d, _d, _d, _d, _i32, _i32, _fp, C.POINTER(C.c_uint64), _i32]),
     "af_measure_integrated_loudness_device": (C.c_int, [_vp, _i64, _i32, _i64, C.c_uint32, _i32, _dp, C.POINTER(_i32)]),
     "af_measure_integrated_loudness_host": (C.c_int, [_fp, _i64, _i32, _i64, C.c_uint32, _i32, _dp, C.POINTER(_i32)]),
@@ -220,6 +237,8 @@ VALUE_FUNCTIONS = {
     "af_noise_suppressor_backend_error",
     "af_resampler_destroy", "af_resampler_output_delay", "af_resampler_expected_frames", "af_resampler_sinc_len",
     "af_gate_threshold_db", "af_engine_gate_enabled",
+    "af_stream_resampler_destroy", "af_stream_resampler_output_frames", "af_stream_resampler_pending_input",
+    "af_stream_resampler_output_delay", "af_stream_resampler_frames_in", "af_stream_resampler_frames_out",
 }
 
 _lib = None

@@ -140,6 +140,41 @@ class Engine:
         _lib.check(self._lib.af_engine_process_host(self._h, a.ctypes.data_as(fp), out.ctypes.data_as(fp), int(n), layout))
         return out
 
+    def stream_plan(self, n_in: int) -> tuple[int, int, int]:
+        """What the next ``stream`` call of n_in frames per stream will do, from the host alone: (frames the input resampler
+        hands the chain, frames the chain returns, frames that come out).  Size VAD / activity evidence from the first two."""
+        a, b, c = C.c_int64(0), C.c_int64(0), C.c_int64(0)
+        _lib.check(self._lib.af_engine_stream_plan(self._h, int(n_in), C.byref(a), C.byref(b), C.byref(c)))
+        return a.value, b.value, c.value
+
+    def stream(self, x: np.ndarray) -> np.ndarray:
+        """One wake-up over af_engine_stream_host: float32 [n_streams, n] at the input rate -> [n_streams, m] at the output
+        rate (``set_io_sample_rates``; without it the engine's own rate on both sides)."""
+        a = np.ascontiguousarray(x, dtype=np.float32)
+        if a.ndim == 1:
+            a = a.reshape(1, -1)
+        if a.shape[0] != self.n_streams:
+            raise ValueError(f"expected {self.n_streams} streams, got {a.shape[0]}")
+        n = a.shape[1]
+        stride = max(self.stream_plan(n)[2], 1)
+        out = np.empty((self.n_streams, stride), dtype=np.float32)
+        fp = C.POINTER(C.c_float)
+        n_out = C.c_int64(0)
+        _lib.check(self._lib.af_engine_stream_host(self._h, a.ctypes.data_as(fp), n, out.ctypes.data_as(fp), stride, C.byref(n_out)))
+        return np.ascontiguousarray(out[:, : n_out.value])
+
+    def io_resampler_delay(self) -> tuple[int, int]:
+        """(input side, output side) ``output_delay()`` in frames, 0 for a side that does not resample."""
+        a, b = C.c_int32(0), C.c_int32(0)
+        _lib.check(self._lib.af_engine_io_resampler_delay(self._h, C.byref(a), C.byref(b)))
+        return a.value, b.value
+
+    def io_resampler_pending(self) -> tuple[int, int]:
+        """(input side, output side) frames queued in the I/O resamplers, 0 for a side that does not resample."""
+        a, b = C.c_int64(0), C.c_int64(0)
+        _lib.check(self._lib.af_engine_io_resampler_pending(self._h, C.byref(a), C.byref(b)))
+        return a.value, b.value
+
     def suppressor_trace(self) -> np.ndarray:
         """[frames, n_streams, 2] int32: (silence flag, pitch index) of every frame of the last process call
         (needs ``suppressor_set_trace_enabled(1)`` before the call)."""
@@ -1038,6 +1073,96 @@ class Resampler:
     def last_kernel_ms(self) -> float:
         ms = C.c_double(0.0)
         _lib.check(self._lib.af_resampler_last_kernel_ms(self._h, C.byref(ms)))
+        return ms.value
+
+
+class StreamResampler:
+    """The product resampler as the realtime loop drives it (dsp_loop.rs:963-1011): `n_streams` streams in lock step, state
+    carried across pushes, float32 in and out.  A push returns the frames of the chunks it completed (possibly none)."""
+
+    def __init__(self, input_rate: int, output_rate: int, n_streams: int = 1, chunk_size: int = RESAMPLER_CHUNK_SIZE,
+                 sinc_len: int | None = None, window: str | None = None, device: int = 0):
+        sinc_len = PRODUCT_RESAMPLER_SINC_LEN if sinc_len is None else int(sinc_len)
+        name = PRODUCT_RESAMPLER_WINDOW_NAME if window is None else window
+        # (the library checks the rest of the contract of resampling.rs:187-214, in its order; window names live here)
+        window_id = RESAMPLER_WINDOW_IDS.get(name, -1)
+        if int(input_rate) < 0 or int(output_rate) < 0:
+            raise ValueError("sample rates must be positive")
+        self._lib = _lib.load()
+        handle = C.c_void_p()
+        rc = self._lib.af_stream_resampler_create(int(input_rate), int(output_rate), int(chunk_size), sinc_len, window_id,
+                                                  int(n_streams), int(device), C.byref(handle))
+        if rc == _lib.AF_ERR_INVALID_ARGUMENT and window_id < 0 and "window" in _lib.last_error():
+            raise ValueError(f"unsupported resampler window {name!r}")
+        _lib.check(rc)
+        self._h = handle
+        self.input_rate, self.output_rate, self.n_streams = int(input_rate), int(output_rate), int(n_streams)
+
+    def close(self) -> None:
+        if getattr(self, "_h", None):
+            self._lib.af_stream_resampler_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def output_frames(self, n_in: int) -> int:
+        """Frames per stream the next push of n_in frames would produce (host replay, changes nothing)."""
+        return int(self._lib.af_stream_resampler_output_frames(self._h, int(n_in)))
+
+    @property
+    def pending_input(self) -> int:
+        return int(self._lib.af_stream_resampler_pending_input(self._h))
+
+    @property
+    def output_delay(self) -> int:
+        return int(self._lib.af_stream_resampler_output_delay(self._h))
+
+    @property
+    def frames_in(self) -> int:
+        return int(self._lib.af_stream_resampler_frames_in(self._h))
+
+    @property
+    def frames_out(self) -> int:
+        return int(self._lib.af_stream_resampler_frames_out(self._h))
+
+    def reset(self) -> None:
+        _lib.check(self._lib.af_stream_resampler_reset(self._h))
+
+    def clear_pending(self) -> None:
+        _lib.check(self._lib.af_stream_resampler_clear_pending(self._h))
+
+    def push(self, x: np.ndarray, out_capacity: int | None = None) -> np.ndarray:
+        """float32 [n_streams, n] (or [n] for one stream) -> float32 [n_streams, m]."""
+        a = np.ascontiguousarray(x, dtype=np.float32)
+        if a.ndim == 1:
+            a = a.reshape(1, -1)
+        if a.shape[0] != self.n_streams:
+            raise ValueError(f"expected {self.n_streams} streams, got {a.shape[0]}")
+        n = a.shape[1]
+        cap = self.output_frames(n) if out_capacity is None else int(out_capacity)
+        out = np.empty((self.n_streams, max(cap, 1)), dtype=np.float32)
+        fp = C.POINTER(C.c_float)
+        n_out = C.c_int64(0)
+        _lib.check(self._lib.af_stream_resampler_push_host(self._h, a.ctypes.data_as(fp), n, max(n, 1), out.ctypes.data_as(fp), cap,
+                                                           out.shape[1], C.byref(n_out)))
+        return np.ascontiguousarray(out[:, : n_out.value])
+
+    def push_device(self, in_ptr: int, n_in: int, in_stride: int, out_ptr: int, out_capacity: int, out_stride: int,
+                    hip_stream: int = 0) -> int:
+        """Device pointers, asynchronous on ``hip_stream``; returns the frames per stream the push produces.  The input
+        must be finite: nothing on the device checks it."""
+        n_out = C.c_int64(0)
+        _lib.check(self._lib.af_stream_resampler_push_device(self._h, C.c_void_p(in_ptr), int(n_in), int(in_stride), C.c_void_p(out_ptr),
+                                                             int(out_capacity), int(out_stride), C.byref(n_out), C.c_void_p(hip_stream)))
+        return n_out.value
+
+    def last_kernel_ms(self) -> float:
+        ms = C.c_double(0.0)
+        _lib.check(self._lib.af_stream_resampler_last_kernel_ms(self._h, C.byref(ms)))
         return ms.value
 
 

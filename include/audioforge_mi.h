@@ -366,6 +366,81 @@ int af_resampler_process_host(af_resampler *r, const double *in, double *out, in
 /* HIP-event time of the last launch */
 int af_resampler_last_kernel_ms(af_resampler *r, double *ms);
 
+/* ---- streaming product resampler -----------------------------------------------------------------
+ * The same SincFixedIn as the realtime loop drives it (rust-core/src/audio/processor/dsp_loop.rs:274-317 builds one per
+ * side whose device rate differs from the processing rate; :963-1011 input side, :843-895 output side): every wake-up
+ * pushes its new f32 samples `as f64` into a queue, runs process_into_buffer while a whole chunk (input_frames_next() ==
+ * chunk_size) is queued, takes the produced frames back `as f32`, and leaves the rest for the next wake-up.  An
+ * af_stream_resampler is that object for `n_streams` streams advancing in lock step: positions, the queue length and the
+ * chunk counter are host scalars, the audio state (2 * sinc_len frames of history + the queued remainder, f32) lives on
+ * the device.  Audio is f32, stream-major, strides in frames.  No partial chunk, no flush: what af_resampler_* add for
+ * whole clips is the offline driver's (resampling.rs:179-261), not the loop's. */
+typedef struct af_stream_resampler af_stream_resampler;
+/* build_sinc_resampler_with_quality (resampling.rs:140-156) with the argument contract and messages of
+ * af_resampler_create (resampling.rs:187-214; AF_ERR_UNSUPPORTED beyond sinc_len 256 or below ratio 0.2: the LDS tile).
+ * Every argument is validated before any HIP call; no GPU work happens until the first push. */
+int af_stream_resampler_create(uint32_t input_rate, uint32_t output_rate, int64_t chunk_size, int32_t sinc_len,
+                               int32_t window, int32_t n_streams, int32_t device, af_stream_resampler **out);
+void af_stream_resampler_destroy(af_stream_resampler *r);
+/* One wake-up (dsp_loop.rs:963-1011): appends n_in frames per stream (in[s * in_stride + t]), runs every chunk that is
+ * complete, writes the frames they produce (rounded to f32, nearest even) to out[s * out_stride + t] and keeps the
+ * remainder (< chunk_size frames).  *n_out = frames produced per stream, possibly 0.  Validated before anything is
+ * touched: AF_ERR_INVALID_ARGUMENT when out_capacity (frames per stream `out` can take) or out_stride is below what the
+ * call produces (af_stream_resampler_output_frames), AF_ERR_NON_FINITE "samples must be finite" (resampling.rs:206-210);
+ * a refused call leaves the queue, the history and the position as they were.  Host pointers; synchronises. */
+int af_stream_resampler_push_host(af_stream_resampler *r, const float *in, int64_t n_in, int64_t in_stride, float *out,
+                                  int64_t out_capacity, int64_t out_stride, int64_t *n_out);
+/* The same with device pointers, asynchronous on `hip_stream` (a hipStream_t, NULL = default stream): enqueues and returns,
+ * never waits on the host (the per-call position table goes through pinned staging slots).  Successive pushes must be
+ * ordered by the caller (one stream, or events).  FINITE INPUT IS THE CALLER'S CONTRACT here: nothing on the device
+ * checks it.  Unlike the crate, whose dot products span exactly sinc_len frames, the kernels run every sinc row with
+ * zero pad taps either side, and NaN * 0 = NaN: a non-finite frame would also reach the outputs whose windows merely
+ * neighbour it. */
+int af_stream_resampler_push_device(af_stream_resampler *r, const float *d_in, int64_t n_in, int64_t in_stride,
+                                    float *d_out, int64_t out_capacity, int64_t out_stride, int64_t *n_out,
+                                    void *hip_stream);
+/* frames per stream the next push of n_in frames would produce: a host replay of process_into_buffer's position loop,
+ * changes no state; VALUE */
+int64_t af_stream_resampler_output_frames(const af_stream_resampler *r, int64_t n_in);
+/* resample_input.len() after the last push (dsp_loop.rs:984); VALUE */
+int64_t af_stream_resampler_pending_input(const af_stream_resampler *r);
+/* Resampler::output_delay (resampling.rs:216); VALUE */
+int af_stream_resampler_output_delay(const af_stream_resampler *r);
+/* frames per stream pushed / produced since create or reset; VALUES */
+int64_t af_stream_resampler_frames_in(const af_stream_resampler *r);
+int64_t af_stream_resampler_frames_out(const af_stream_resampler *r);
+/* a fresh resampler (what dsp_loop.rs:274-317 builds at start): zero history, position -sinc_len / 2, nothing queued */
+int af_stream_resampler_reset(af_stream_resampler *r);
+/* the input backlog drop, dsp_loop.rs:941-944 (resample_input.clear()): the queue is emptied, history and position stay */
+int af_stream_resampler_clear_pending(af_stream_resampler *r);
+/* HIP-event time of the last push's kernels */
+int af_stream_resampler_last_kernel_ms(af_stream_resampler *r, double *ms);
+
+/* ---- device-rate I/O of an engine: dsp_loop.rs:274-317 ---------------------------------------------------------
+ * af_engine_set_io_sample_rates: a configuration setter (AF_ERR_STATE after streaming started).  A rate of 0, or equal to
+ *   the engine's, means no resampler on that side (dsp_loop.rs:274, 292); with both sides off every call behaves as
+ *   without this setter.  Otherwise that side gets build_sinc_resampler's product configuration (resampling.rs:140-156).
+ * With a rate set, af_engine_stream_host takes `in` at the input rate and returns `out` at the output rate: input
+ *   resampler (dsp_loop.rs:963-1011) -> the chain on the frames it produced (not called when no chunk completed) -> output
+ *   resampler (dsp_loop.rs:843-895; not called when the chain returned nothing).  *n_out is what af_engine_stream_plan
+ *   said; out_stride below it refuses the call with everything untouched.  af_engine_process_host / _device return
+ *   AF_ERR_UNSUPPORTED.  af_engine_reset restarts both resamplers.  Block statistics, af_engine_samples_processed,
+ *   af_engine_pending_input and the evidence setters stay in engine-rate samples: size evidence from
+ *   af_engine_stream_plan's engine_frames_*.
+ *   DEVIATION: a non-finite host sample refuses the call (AF_ERR_NON_FINITE, nothing touched).  The reference resamples
+ *   first and scrubs afterwards (routing.rs:802-823), which smears one NaN over the 2 * sinc_len frames around it and
+ *   then zeroes them all.
+ * af_engine_stream_plan: exact host replay, changes no state: the frames the input resampler will hand the chain, the
+ *   frames the chain will return (the suppressor's 480-frame rule included) and the frames that will come out.
+ * af_engine_io_resampler_delay: output_delay() of each side, 0 when off; the loop adds the output side's to its
+ *   reported latency (dsp_loop.rs:310-313).
+ * af_engine_io_resampler_pending: frames queued in each side's resampler (af_stream_resampler_pending_input), 0 when off. */
+int af_engine_set_io_sample_rates(af_engine *e, uint32_t input_rate, uint32_t output_rate);
+int af_engine_stream_plan(const af_engine *e, int64_t n_in, int64_t *engine_frames_in, int64_t *engine_frames_out,
+                          int64_t *n_out);
+int af_engine_io_resampler_delay(const af_engine *e, int32_t *input_frames, int32_t *output_frames);
+int af_engine_io_resampler_pending(const af_engine *e, int64_t *input_frames, int64_t *output_frames);
+
 /* ---- noise gate -------------------------------------------------------------------------------
  * NoiseGate (rust-core/src/dsp/gate.rs) on the path `simulate_gate_suppressor_order` exercises
  * (python_api.rs:312-319 builds the gate without a VadAutoGate, so process_block_inplace runs the per-sample
