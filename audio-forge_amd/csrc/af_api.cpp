@@ -3331,6 +3331,16 @@ int af_resampler_process_host(af_resampler *r, const double *in, double *out, in
   return AF_OK;
 }
 
+// host only: the kernel af_resampler_process_* launches for this plan (af::resample_pick_form, the launcher's own choice)
+int af_resampler_launch_form(const af_resampler *r, int32_t *form, int32_t *segment_outputs, int32_t *streams_per_workgroup) {
+  if (!r) return fail(AF_ERR_INVALID_ARGUMENT, "resampler is null");
+  const af::ResampleForm f = af::resample_pick_form(r->plan.ratio, r->plan.sinc_len, r->variant);
+  if (form) *form = f.form;
+  if (segment_outputs) *segment_outputs = f.segment_outputs;
+  if (streams_per_workgroup) *streams_per_workgroup = f.streams_per_workgroup;
+  return AF_OK;
+}
+
 int af_resampler_last_kernel_ms(af_resampler *r, double *ms) {
   if (!r || !ms) return fail(AF_ERR_INVALID_ARGUMENT, "null argument");
   *ms = 0.0;
@@ -3608,6 +3618,16 @@ int af_stream_resampler_push_host(af_stream_resampler *r, const float *in, int64
   AF_HIP(hipStreamSynchronize(nullptr));
   if (p.n_out > 0) AF_HIP(hipMemcpy2D(out, f4 * out_stride, r->d_out, f4 * p.n_out, f4 * p.n_out, B, hipMemcpyDeviceToHost));
   if (n_out) *n_out = p.n_out;
+  return AF_OK;
+}
+
+int af_stream_resampler_launch_form(const af_stream_resampler *r, int32_t *form, int32_t *segment_outputs,
+                                    int32_t *streams_per_workgroup) {  // as af_resampler_launch_form
+  if (!r) return fail(AF_ERR_INVALID_ARGUMENT, "resampler is null");
+  const af::ResampleForm f = af::resample_pick_form(r->plan.ratio, r->plan.sinc_len, r->variant);
+  if (form) *form = f.form;
+  if (segment_outputs) *segment_outputs = f.segment_outputs;
+  if (streams_per_workgroup) *streams_per_workgroup = f.streams_per_workgroup;
   return AF_OK;
 }
 

@@ -81,10 +81,6 @@ static hipError_t launch_resample_mfma_variant(const ResampleArgs &a, hipStream_
   hipLaunchKernelGGL(resample_mfma_kernel<kGroups>, grid, dim3(kGroups * 4 * kResLanes), dyn, stream, a);
   return hipGetLastError();
 }
-static hipError_t launch_resample_mfma(const ResampleArgs &a, int variant, hipStream_t stream) {
-  return variant == 2 ? launch_resample_mfma_variant<2>(a, stream) : launch_resample_mfma_variant<4>(a, stream);
-}
-
 // the matrix-core tile needs: 128 outputs' span + the tap round-up inside 288 rows, and a tile's four windows
 // starting within 8 frames of each other (row padding 16)
 bool resample_mfma_ok(double ratio, int sinc_len) {
@@ -118,13 +114,19 @@ int resample_segment_outputs(double ratio, int sinc_len) {
   return 0;
 }
 
+ResampleForm resample_pick_form(double ratio, int sinc_len, int variant) {
+  if (variant != 1 && resample_mfma_ok(ratio, sinc_len)) return ResampleForm{1, kMfSeg, variant == 2 ? 32 : 64};
+  return ResampleForm{0, resample_segment_outputs(ratio, sinc_len), kResLanes};
+}
+
 hipError_t launch_resample(const double *in, double *out, const ResamplePos *pos, const double *table, int64_t n_in,
                            int64_t n_out, int64_t in_stride, int64_t out_stride, int32_t n_streams, int32_t sinc_len,
                            double ratio, int variant, hipStream_t stream) {
   ResampleArgs a{in, out, pos, table, n_in, n_out, in_stride, out_stride, n_streams, sinc_len, kResMaxRows};
   if (n_out <= 0 || n_streams <= 0) return hipSuccess;
-  if (variant != 1 && resample_mfma_ok(ratio, sinc_len)) return launch_resample_mfma(a, variant, stream);
-  switch (resample_segment_outputs(ratio, sinc_len)) {
+  const ResampleForm f = resample_pick_form(ratio, sinc_len, variant);
+  if (f.form == 1) return f.streams_per_workgroup == 32 ? launch_resample_mfma_variant<2>(a, stream) : launch_resample_mfma_variant<4>(a, stream);
+  switch (f.segment_outputs) {
     case 128: return launch_resample_variant<16, 8>(a, stream);
     case 64: return launch_resample_variant<16, 4>(a, stream);
     case 32: return launch_resample_variant<16, 2>(a, stream);

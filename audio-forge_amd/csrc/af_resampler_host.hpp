@@ -31,6 +31,17 @@ struct ResamplePos {
 };
 static_assert(sizeof(ResamplePos) == 32, "position record");
 
+// Which kernel a job runs (af_resampler.hip): the body, the outputs one workgroup takes along time and the streams it takes.
+// segment_outputs == 0: no form holds the shape (the job is refused).
+struct ResampleForm {
+  int form;  // 0: vector body, 1: matrix-core body
+  int segment_outputs, streams_per_workgroup;
+};
+// `variant`: 0 matrix-core body with 64 streams per workgroup where the shape allows, 1 always the vector body, 2 the
+// matrix-core body with 32 streams per workgroup.  The one place the choice is made: both launchers and the read-outs
+// of the C ABI call it.
+ResampleForm resample_pick_form(double ratio, int sinc_len, int variant);
+
 // rubato::calculate_cutoff as identified from the reference's published measurements
 // (tools/fit_resampler_cutoff.py; the three measured configurations are exact f32 values).
 inline float resample_calculate_cutoff(int sinc_len, int window) {

@@ -127,8 +127,9 @@ hipError_t launch_resample_stream(const float *plane, const float *in, float *ou
   if (split < 0 || split > plane_stride || n_in < 0) return hipErrorInvalidValue;
   ResampleStreamArgs a{plane, in, out, pos, table, split, split + n_in, n_out, in_stride, out_stride, plane_stride, n_streams,
                        sinc_len, kResMaxRows};
-  if (variant != 1 && resample_mfma_ok(ratio, sinc_len)) return variant == 2 ? launch_stream_mfma<2>(a, stream) : launch_stream_mfma<4>(a, stream);
-  switch (resample_segment_outputs(ratio, sinc_len)) {
+  const ResampleForm f = resample_pick_form(ratio, sinc_len, variant);
+  if (f.form == 1) return f.streams_per_workgroup == 32 ? launch_stream_mfma<2>(a, stream) : launch_stream_mfma<4>(a, stream);
+  switch (f.segment_outputs) {
     case 128: return launch_stream_valu<16, 8>(a, stream);
     case 64: return launch_stream_valu<16, 4>(a, stream);
     case 32: return launch_stream_valu<16, 2>(a, stream);

@@ -199,6 +199,7 @@ SIGNATURES = {
     "af_resampler_process_device": (C.c_int, [_vp, _vp, _vp, _i64, _i32, _i64, _i64, _vp]),
     "af_resampler_process_host": (C.c_int, [_vp, _dp, _dp, _i64, _i32, _i64, _i64]),
     "af_resampler_last_kernel_ms": (C.c_int, [_vp, _dp]),
+    "af_resampler_launch_form": (C.c_int, [_vp, C.POINTER(_i32), C.POINTER(_i32), C.POINTER(_i32)]),
     # streaming product resampler + the engine's device-rate I/O
     "af_stream_resampler_create": (C.c_int, [C.c_uint32, C.c_uint32, _i64, _i32, _i32, _i32, _i32, C.POINTER(_vp)]),
     "af_stream_resampler_destroy": (None, [_vp]),
@@ -212,6 +213,7 @@ SIGNATURES = {
     "af_stream_resampler_reset": (C.c_int, [_vp]),
     "af_stream_resampler_clear_pending": (C.c_int, [_vp]),
     "af_stream_resampler_last_kernel_ms": (C.c_int, [_vp, _dp]),
+    "af_stream_resampler_launch_form": (C.c_int, [_vp, C.POINTER(_i32), C.POINTER(_i32), C.POINTER(_i32)]),
     "af_engine_set_io_sample_rates": (C.c_int, [_vp, C.c_uint32, C.c_uint32]),
     "af_engine_stream_plan": (C.c_int, [_vp, _i64, C.POINTER(_i64), C.POINTER(_i64), C.POINTER(_i64)]),
     "af_engine_io_resampler_delay": (C.c_int, [_vp, C.POINTER(_i32), C.POINTER(_i32)]),

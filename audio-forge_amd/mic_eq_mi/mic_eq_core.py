@@ -1075,6 +1075,14 @@ class Resampler:
         _lib.check(self._lib.af_resampler_last_kernel_ms(self._h, C.byref(ms)))
         return ms.value
 
+    @property
+    def launch_form(self) -> tuple[int, int, int]:
+        """(form, segment_outputs, streams_per_workgroup) of the kernel ``process`` launches: form 0 is the vector body,
+        1 the matrix-core body.  Host only; the launcher's own choice (ratio, sinc length, AF_RESAMPLER_VARIANT at create)."""
+        form, seg, streams = C.c_int32(0), C.c_int32(0), C.c_int32(0)
+        _lib.check(self._lib.af_resampler_launch_form(self._h, C.byref(form), C.byref(seg), C.byref(streams)))
+        return form.value, seg.value, streams.value
+
 
 class StreamResampler:
     """The product resampler as the realtime loop drives it (dsp_loop.rs:963-1011): `n_streams` streams in lock step, state
@@ -1164,6 +1172,13 @@ class StreamResampler:
         ms = C.c_double(0.0)
         _lib.check(self._lib.af_stream_resampler_last_kernel_ms(self._h, C.byref(ms)))
         return ms.value
+
+    @property
+    def launch_form(self) -> tuple[int, int, int]:
+        """As ``Resampler.launch_form``, for the kernel a push launches."""
+        form, seg, streams = C.c_int32(0), C.c_int32(0), C.c_int32(0)
+        _lib.check(self._lib.af_stream_resampler_launch_form(self._h, C.byref(form), C.byref(seg), C.byref(streams)))
+        return form.value, seg.value, streams.value
 
 
 def simulate_product_resampler_batch(samples: np.ndarray, input_rate: int, output_rate: int,

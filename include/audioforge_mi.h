@@ -365,6 +365,12 @@ int af_resampler_process_host(af_resampler *r, const double *in, double *out, in
                               int64_t in_stride, int64_t out_stride);
 /* HIP-event time of the last launch */
 int af_resampler_last_kernel_ms(af_resampler *r, double *ms);
+/* host only, touches no device: the kernel af_resampler_process_* launches for this resampler, chosen by the launcher's own
+ * rule from the ratio, the sinc length and AF_RESAMPLER_VARIANT as read at create.  *form: 0 the vector body, 1 the
+ * matrix-core body; *segment_outputs: output frames one workgroup takes (128, 64, 32, 16 or 8; always 128 for the
+ * matrix-core body); *streams_per_workgroup: 64, or 32 for AF_RESAMPLER_VARIANT=mfma32.  Any pointer may be NULL. */
+int af_resampler_launch_form(const af_resampler *r, int32_t *form, int32_t *segment_outputs,
+                             int32_t *streams_per_workgroup);
 
 /* ---- streaming product resampler -----------------------------------------------------------------
  * The same SincFixedIn as the realtime loop drives it (rust-core/src/audio/processor/dsp_loop.rs:274-317 builds one per
@@ -415,6 +421,9 @@ int af_stream_resampler_reset(af_stream_resampler *r);
 int af_stream_resampler_clear_pending(af_stream_resampler *r);
 /* HIP-event time of the last push's kernels */
 int af_stream_resampler_last_kernel_ms(af_stream_resampler *r, double *ms);
+/* as af_resampler_launch_form, for the kernel a push launches */
+int af_stream_resampler_launch_form(const af_stream_resampler *r, int32_t *form, int32_t *segment_outputs,
+                                    int32_t *streams_per_workgroup);
 
 /* ---- device-rate I/O of an engine: dsp_loop.rs:274-317 ---------------------------------------------------------
  * af_engine_set_io_sample_rates: a configuration setter (AF_ERR_STATE after streaming started).  A rate of 0, or equal to

@@ -6,10 +6,12 @@ cubic, on the same host-built coefficient table and positions: outputs must be B
 """
 import json
 import pathlib
+from concurrent.futures import ThreadPoolExecutor
 
 import numpy as np
 import pytest
 
+import resampler_forms as F
 import resampler_stimuli as R
 
 pytestmark = pytest.mark.gpu
@@ -27,8 +29,9 @@ def mi():
 
 @pytest.mark.parametrize("fi,fo", [(44_100, 48_000), (48_000, 44_100), (32_000, 48_000), (96_000, 48_000), (48_000, 16_000)])
 def test_bit_exact_against_oracle(mi, oracle, fi, fo):
-    """Ragged batch (67 streams), length that is not a multiple of the chunk, several ratios incl. the
-    segment sizes 128 / 64 / 32 of the kernel."""
+    """Ragged batch (67 streams), length that is not a multiple of the chunk, five ratios at sinc length 128: the matrix-core
+    kernel (three of them) and the vector kernel with segments of 64 and 32 outputs, six streams of stream groups 0 and 3
+    compared.  Every form, every stream and the tails: test_every_form_is_bit_exact_on_every_stream below."""
     from mic_eq_mi import mic_eq_core as core
 
     rng = np.random.default_rng(fi ^ fo)
@@ -42,6 +45,104 @@ def test_bit_exact_against_oracle(mi, oracle, fi, fo):
         assert (delay, expected, blocks) == (d, e, b)
         assert out.shape[1] == want.size
         assert np.array_equal(out[s], want), (s, float(np.max(np.abs(out[s] - want))))
+
+
+SILENT, IMPULSE_MID, IMPULSE_FIRST, IMPULSE_LAST, CONSTANT, SUBNORMAL, HUGE = 3, 5, 17, 34, 45, 51, 66
+
+
+def _form_batch(n, seed):
+    """67 streams of noise at 0.25, with the special rows spread over all four stream groups of a matrix-core workgroup
+    (16 streams each) and the last, partly filled workgroup: silence, an impulse in the middle, at frame 0 and at the last
+    frame, a constant 1.0, noise at 1e-308 (f64 subnormal samples and products) and at 1e300."""
+    rng = np.random.default_rng(seed)
+    x = rng.standard_normal((F.N_STREAMS, n)) * 0.25
+    x[SILENT] = 0.0
+    x[CONSTANT] = 1.0
+    x[SUBNORMAL] *= 4e-308
+    x[HUGE] *= 4e300
+    for s in (IMPULSE_MID, IMPULSE_FIRST, IMPULSE_LAST):
+        x[s] = 0.0
+    if n:
+        x[IMPULSE_MID, min(1000, n - 1)] = 1.0
+        x[IMPULSE_FIRST, 0] = 1.0
+        x[IMPULSE_LAST, n - 1] = 1.0
+    return x
+
+
+def _bits64(a):
+    return np.ascontiguousarray(a, dtype=np.float64).view(np.uint64)
+
+
+def _oracle_batch(oracle, x, row):
+    """[n_streams, n_out] f64 from the oracle, stream by stream on a thread pool, and its (delay, expected, blocks)"""
+    oracle.simulate_product_resampler(x[0], row.fi, row.fo, row.chunk, row.sinc_len, row.window)  # binds the signature once
+    with ThreadPoolExecutor(max_workers=16) as pool:
+        per = list(pool.map(lambda s: oracle.simulate_product_resampler(x[s], row.fi, row.fo, row.chunk, row.sinc_len, row.window),
+                            range(x.shape[0])))
+    assert len({p[1:] for p in per}) == 1 and len({p[0].size for p in per}) == 1
+    return np.stack([p[0] for p in per]), per[0][1:]
+
+
+def _assert_all_streams_equal(got, want, what):
+    assert got.shape == want.shape, (what, got.shape, want.shape)
+    differ = _bits64(got) != _bits64(want)
+    if differ.any():
+        streams = np.flatnonzero(differ.any(axis=1))
+        first = int(np.flatnonzero(differ.any(axis=0))[0])
+        raise AssertionError(f"{what}: {streams.size} streams differ from the oracle: {streams.tolist()}, first differing output {first}")
+
+
+@pytest.mark.parametrize("row", F.ROWS, ids=lambda r: r.id)
+def test_every_form_is_bit_exact_on_every_stream(mi, oracle, row):
+    """Every launch form of the one-shot kernels (tests/resampler_forms.py), 67 streams, all of them compared as bit patterns:
+    the tile geometry edges, two or three input lengths per row for the tails (partial last tile, odd last output, a last
+    segment of one output, a whole job shorter than a segment, a pure flush), impulses at both ends, a constant, subnormal
+    and very large samples."""
+    from mic_eq_mi import mic_eq_core as core
+
+    r = F.make_resampler(core, row)
+    assert r.launch_form == row.form
+    for n in row.lengths:
+        x = _form_batch(n, row.fi ^ row.fo ^ n)
+        want, (delay, expected, blocks) = _oracle_batch(oracle, x, row)
+        n_out, b = r.plan(n)
+        assert (n_out, b, r.output_delay, r.expected_frames(n)) == (want.shape[1], blocks, delay, expected), (row.id, n)
+        got = r.process(x)
+        _assert_all_streams_equal(got, want, (row.id, n))
+        if n > 1 and n_out > 2 * row.sinc_len:
+            assert np.any(want[SUBNORMAL] != 0.0) and np.all(np.abs(want[SUBNORMAL]) < 1e-306)
+            assert np.all(np.isfinite(want[HUGE])) and np.max(np.abs(want[HUGE])) > 1e299
+    r.close()
+
+
+@pytest.mark.parametrize("row_id", ["44100-48000-sinc128", "48000-40000-sinc128"])
+def test_strided_device_entry_point(mi, oracle, row_id):
+    """af_resampler_process_device with in_stride > n_in and out_stride > n_out, one matrix-core and one vector row: NaN behind
+    every input row must not be read, the cells behind every output row must not be written."""
+    import torch
+
+    from mic_eq_mi import mic_eq_core as core
+
+    row = next(r for r in F.ROWS if r.id == row_id)
+    n = 1024
+    x = _form_batch(n, 1234)
+    want, _ = _oracle_batch(oracle, x, row)
+    r = F.make_resampler(core, row)
+    assert r.launch_form == row.form
+    n_out, _ = r.plan(n)
+    assert n_out == want.shape[1]
+    padded = np.full((F.N_STREAMS, n + 3), np.nan)
+    padded[:, :n] = x
+    d_in = torch.from_numpy(padded).cuda()
+    d_out = torch.full((F.N_STREAMS, n_out + 5), 7.0, dtype=torch.float64, device="cuda")
+    torch.cuda.synchronize()
+    r.process_device(d_in.data_ptr(), d_out.data_ptr(), n, F.N_STREAMS, n + 3, n_out + 5)
+    torch.cuda.synchronize()
+    y = d_out.cpu().numpy()
+    assert not np.isnan(y).any(), "a kernel read past n_in"
+    assert (y[:, n_out:] == 7.0).all(), "the resampler wrote past a row's frames"
+    _assert_all_streams_equal(y[:, :n_out], want, row_id)
+    r.close()
 
 
 def test_operator_surface_matches_reference(mi, oracle):

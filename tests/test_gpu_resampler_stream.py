@@ -12,14 +12,15 @@ import numpy as np
 import pytest
 
 import chain_oracle as CO
+import resampler_forms as F
 import resampler_stream_oracle as RS
 import signals as S
 
 pytestmark = pytest.mark.gpu
 
-N_STREAMS = 67
-CALLS = [100, 441, 3000, 1, 1023, 1024, 1025, 479, 2000, 7, 1100]  # zero-output calls and a 3000-frame call among them
-OTHER_PARTITION = [3000, 1024, 1, 1, 2500, 441, 441, 441, 441, sum(CALLS) - (3000 + 1024 + 2 + 2500 + 4 * 441)]
+N_STREAMS = F.N_STREAMS
+CALLS = F.CALLS  # zero-output calls and a 3000-frame call among them
+OTHER_PARTITION = F.OTHER_PARTITION
 RATIOS = [(44_100, 48_000), (48_000, 44_100), (32_000, 48_000), (96_000, 48_000), (48_000, 16_000)]  # test_bit_exact_against_oracle's
 
 
@@ -89,6 +90,43 @@ def test_every_call_is_bit_exact(core, fi, fo):
     # the same input under another partition: identical bytes
     r.reset()
     again = np.concatenate(_push_all(r, x, OTHER_PARTITION), axis=1)
+    assert np.array_equal(_bits(again), _bits(np.concatenate(got, axis=1)))
+    r.close()
+    o.close()
+
+
+@pytest.mark.parametrize("row", [r for r in F.ROWS if r.calls], ids=lambda r: r.id)
+def test_every_form_streams_bit_exact(core, row):
+    """The launch forms the ratios above do not reach (tests/resampler_forms.py): the 32-stream matrix-core kernel, the vector
+    kernels with segments of 128 and 8 outputs, the geometry edges of both tiles, and chunks of 40 and 160 frames, where
+    the split between the carried plane and the call's input moves through a tile from call to call.  Every call, all 67
+    streams, bit for bit; then the same frames under a second partition."""
+    calls, other = list(row.calls), list(row.other)
+    kw = dict(chunk_size=row.chunk, sinc_len=row.sinc_len, window=row.window)
+    x = _batch(N_STREAMS, sum(calls), row.fi ^ row.fo ^ row.sinc_len)
+    want = _oracle_calls(x, calls, row.fi, row.fo, **kw)
+    assert any(w.shape[1] == 0 for w in want) and any(w.shape[1] > 0 for w in want)
+    r = F.make_stream_resampler(core, row, N_STREAMS)
+    assert r.launch_form == row.form
+    o = RS.StreamOracle(row.fi, row.fo, **kw)
+    at = 0
+    got = []
+    for n, w in zip(calls, want):
+        assert r.output_frames(n) == w.shape[1], n
+        y = r.push(x[:, at : at + n])
+        o.push(x[0, at : at + n])
+        at += n
+        assert y.shape == w.shape, (n, y.shape, w.shape)
+        differ = _bits(y) != _bits(w)
+        if differ.any():
+            streams = np.flatnonzero(differ.any(axis=1)).tolist()
+            raise AssertionError(f"{row.id}, call of {n} frames at {at - n}: streams {streams} differ, first differing output "
+                                 f"{int(np.flatnonzero(differ.any(axis=0))[0])} of {w.shape[1]}")
+        assert r.pending_input == o.pending_input
+        got.append(y)
+    assert r.frames_in == sum(calls) and r.frames_out == sum(w.shape[1] for w in want)
+    r.reset()
+    again = np.concatenate(_push_all(r, x, other), axis=1)
     assert np.array_equal(_bits(again), _bits(np.concatenate(got, axis=1)))
     r.close()
     o.close()
