@@ -1,11 +1,13 @@
 // af_api.cpp -- the C ABI of include/audioforge_mi.h on top of the host mirror and the kernels.
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cmath>
 #include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <limits>
 #include <memory>
 #include <string>
 #include <utility>
@@ -14,6 +16,7 @@
 #include "../../include/audioforge_mi.h"
 #include "af_device.h"
 #include "af_host.hpp"
+#include "af_mixdown_host.hpp"
 #include "af_resampler_host.hpp"
 #include "af_stages.h"
 #include "af_suppressor_host.hpp"
@@ -261,6 +264,9 @@ struct af_engine {
   af_stream_resampler *rs_in = nullptr, *rs_out = nullptr;
   float *d_rs_in = nullptr, *d_rs_mid = nullptr, *d_rs_out = nullptr;  // af_engine_stream_host: device-rate input | engine-rate audio | device-rate output
   int64_t rs_in_capacity = 0, rs_mid_capacity = 0, rs_out_capacity = 0;  // bytes
+  af_mixdown *mix = nullptr;     // af_engine_set_input_channels with more than one channel: the mixdown in front of everything
+  float *d_mix_in = nullptr;     // af_engine_stream_host: the interleaved device frames
+  int64_t mix_in_capacity = 0;   // bytes
 
   af_engine(double fs, int n, int dev) : proto(fs), n_streams(n), device(dev), sample_rate(fs) {}
 };
@@ -1517,8 +1523,10 @@ void af_engine_destroy(af_engine *e) {
   }
   af_stream_resampler_destroy(e->rs_in);
   af_stream_resampler_destroy(e->rs_out);
-  if (e->d_rs_in || e->d_rs_mid || e->d_rs_out) {
+  af_mixdown_destroy(e->mix);
+  if (e->d_rs_in || e->d_rs_mid || e->d_rs_out || e->d_mix_in) {
     (void)hipSetDevice(e->device);
+    (void)hipFree(e->d_mix_in);
     (void)hipFree(e->d_rs_in);
     (void)hipFree(e->d_rs_mid);
     (void)hipFree(e->d_rs_out);
@@ -1555,6 +1563,7 @@ int af_engine_reset(af_engine *e) {
   e->vad_dec_blocks = 0;
   if (e->rs_in) (void)af_stream_resampler_reset(e->rs_in);    // fresh resamplers on both sides: zero history, nothing queued
   if (e->rs_out) (void)af_stream_resampler_reset(e->rs_out);
+  if (e->mix) (void)af_mixdown_reset(e->mix);  // a fresh PhaseSafeMonoState and fresh diagnostics (a new input stream)
   return AF_OK;
 }
 
@@ -1995,6 +2004,10 @@ static int check_evidence_blocks(const af_engine *e, int64_t n_run) {
 }
 
 static bool io_resampled(const af_engine *e) { return e->rs_in || e->rs_out; }
+static const char *const kStreamOnlyMessage =
+    "this engine resamples its input or output (af_engine_set_io_sample_rates): use af_engine_stream_host";
+static const char *const kChannelsStreamOnlyMessage =
+    "this engine takes multichannel input (af_engine_set_input_channels): use af_engine_stream_host";
 
 static int process_device_impl(af_engine *e, const float *in, float *out, int64_t n_samples, int64_t stream_stride, int32_t layout,
                                void *hip_stream) {
@@ -2832,8 +2845,8 @@ static int process_device_impl(af_engine *e, const float *in, float *out, int64_
 
 int af_engine_process_device(af_engine *e, const float *in, float *out, int64_t n_samples, int64_t stream_stride,
                              int32_t layout, void *hip_stream) {
-  if (e && io_resampled(e))
-    return fail(AF_ERR_UNSUPPORTED, "this engine resamples its input or output (af_engine_set_io_sample_rates): use af_engine_stream_host");
+  if (e && io_resampled(e)) return fail(AF_ERR_UNSUPPORTED, "%s", kStreamOnlyMessage);
+  if (e && e->mix) return fail(AF_ERR_UNSUPPORTED, "%s", kChannelsStreamOnlyMessage);
   return process_device_impl(e, in, out, n_samples, stream_stride, layout, hip_stream);
 }
 
@@ -2917,6 +2930,42 @@ int af_engine_io_resampler_pending(const af_engine *e, int64_t *input_frames, in
   return AF_OK;
 }
 
+// ---- multichannel input: the capture callback's mixdown (input.rs:785-843) in front of the input resampler / the chain
+int af_engine_set_input_channels(af_engine *e, int32_t n_channels, int32_t mode) {
+  if (int rc = require_config(e)) return rc;
+  af_mixdown *m = nullptr;
+  if (int rc = af_mixdown_create(n_channels, mode, e->n_streams, e->device, &m)) return rc;
+  af_mixdown_destroy(e->mix);
+  e->mix = nullptr;
+  if (n_channels > 1) e->mix = m;  // one channel: the feature is off, every call is as without this setter
+  else af_mixdown_destroy(m);
+  return AF_OK;
+}
+
+int af_engine_set_input_channel_mode(af_engine *e, int32_t mode) {  // live: the callback loads the mode per chunk (input.rs:814-816)
+  if (!e) return fail(AF_ERR_INVALID_ARGUMENT, "engine is null");
+  if (!e->mix) {
+    if (mode < 0 || mode > 4) return fail(AF_ERR_INVALID_ARGUMENT, "unknown input channel mode %d", mode);
+    return AF_OK;  // mono input: nothing to mix
+  }
+  return af_mixdown_set_mode(e->mix, mode);
+}
+
+int af_engine_read_input_phase(af_engine *e, float *stereo_correlation, uint64_t *phase_warning_count, int32_t *strategy,
+                               float *estimated_delay, int32_t *polarity_flipped, int32_t n_streams) {
+  if (!e) return fail(AF_ERR_INVALID_ARGUMENT, "engine is null");
+  if (n_streams != e->n_streams) return fail(AF_ERR_INVALID_ARGUMENT, "n_streams must be the engine's %d", e->n_streams);
+  if (e->mix) return af_mixdown_read_diagnostics(e->mix, stereo_correlation, phase_warning_count, strategy, estimated_delay, polarity_flipped, n_streams);
+  for (int32_t s = 0; s < n_streams; ++s) {  // mono input, input.rs:789-793: none / 0 / false, no correlation
+    if (stereo_correlation) stereo_correlation[s] = std::numeric_limits<float>::quiet_NaN();
+    if (phase_warning_count) phase_warning_count[s] = 0;
+    if (strategy) strategy[s] = 0;
+    if (estimated_delay) estimated_delay[s] = 0.0f;
+    if (polarity_flipped) polarity_flipped[s] = 0;
+  }
+  return AF_OK;
+}
+
 // host arithmetic only: what the next af_engine_stream_host call of n_in frames will do
 int af_engine_stream_plan(const af_engine *e, int64_t n_in, int64_t *engine_frames_in, int64_t *engine_frames_out, int64_t *n_out) {
   if (!e) return fail(AF_ERR_INVALID_ARGUMENT, "engine is null");
@@ -2946,7 +2995,8 @@ static int stream_host_resampled(af_engine *e, const float *in, int64_t n_in, fl
     return fail(AF_ERR_INVALID_ARGUMENT, "this call produces %lld frames per stream (af_engine_stream_plan) but out_stride is %lld",
                 (long long)m3, (long long)out_stride);
   const int64_t B = e->n_streams;
-  for (int64_t i = 0; i < B * n_in; ++i)
+  const int64_t C = e->mix ? af_mixdown_channels(e->mix) : 1;  // in[(s * n_in + t) * C + c]
+  for (int64_t i = 0; i < B * n_in * C; ++i)
     if (!std::isfinite(in[i])) return fail(AF_ERR_NON_FINITE, "samples must be finite");
   if (int rc = ensure_started(e)) return rc;
   if (int rc = check_evidence_blocks(e, m2)) return rc;
@@ -2957,7 +3007,16 @@ static int stream_host_resampled(af_engine *e, const float *in, int64_t n_in, fl
   if (int rc = grow_device(e, reinterpret_cast<void **>(&e->d_rs_mid), &e->rs_mid_capacity, f4 * B * mid_stride, nullptr)) return rc;
   if (int rc = grow_device(e, reinterpret_cast<void **>(&e->d_rs_out), &e->rs_out_capacity, f4 * B * std::max<int64_t>(m3, 1), nullptr)) return rc;
   int64_t got = 0;
-  if (e->rs_in) {
+  if (e->mix) {  // the capture callback's mixdown first (input.rs:785-843): mono into what the mono path would have uploaded
+    if (int rc = grow_device(e, reinterpret_cast<void **>(&e->d_mix_in), &e->mix_in_capacity, f4 * B * C * std::max<int64_t>(n_in, 1), nullptr)) return rc;
+    if (n_in > 0) {
+      AF_HIP(hipMemcpy(e->d_mix_in, in, f4 * B * n_in * C, hipMemcpyHostToDevice));
+      if (int rc = af_mixdown_push_device(e->mix, e->d_mix_in, n_in, n_in, e->rs_in ? e->d_rs_in : e->d_rs_mid,
+                                          e->rs_in ? n_in : mid_stride, nullptr)) return rc;
+    }
+    if (e->rs_in)
+      if (int rc = af_stream_resampler_push_device(e->rs_in, e->d_rs_in, n_in, std::max<int64_t>(n_in, 1), e->d_rs_mid, m1, mid_stride, &got, nullptr)) return rc;
+  } else if (e->rs_in) {
     if (n_in > 0) AF_HIP(hipMemcpy(e->d_rs_in, in, f4 * B * n_in, hipMemcpyHostToDevice));
     if (int rc = af_stream_resampler_push_device(e->rs_in, e->d_rs_in, n_in, std::max<int64_t>(n_in, 1), e->d_rs_mid, m1, mid_stride, &got, nullptr)) return rc;
   } else if (n_in > 0) {
@@ -2985,14 +3044,14 @@ static int stream_host_resampled(af_engine *e, const float *in, int64_t n_in, fl
 int af_engine_process_host(af_engine *e, const float *in, float *out, int64_t n_samples, int32_t layout) {
   if (layout != AF_LAYOUT_STREAM_MAJOR && layout != AF_LAYOUT_TIME_MAJOR)
     return fail(AF_ERR_INVALID_ARGUMENT, "unknown layout %d", layout);
-  if (e && io_resampled(e))
-    return fail(AF_ERR_UNSUPPORTED, "this engine resamples its input or output (af_engine_set_io_sample_rates): use af_engine_stream_host");
+  if (e && io_resampled(e)) return fail(AF_ERR_UNSUPPORTED, "%s", kStreamOnlyMessage);
+  if (e && e->mix) return fail(AF_ERR_UNSUPPORTED, "%s", kChannelsStreamOnlyMessage);
   return process_host_impl(e, in, n_samples, out, layout == AF_LAYOUT_STREAM_MAJOR ? n_samples : (e ? e->n_streams : 0), layout, nullptr);
 }
 
 int af_engine_stream_host(af_engine *e, const float *in, int64_t n_in, float *out, int64_t out_stride, int64_t *n_out) {
   if (n_out) *n_out = 0;
-  if (e && io_resampled(e)) return stream_host_resampled(e, in, n_in, out, out_stride, n_out);
+  if (e && (io_resampled(e) || e->mix)) return stream_host_resampled(e, in, n_in, out, out_stride, n_out);
   return process_host_impl(e, in, n_in, out, out_stride, AF_LAYOUT_STREAM_MAJOR, n_out);
 }
 
@@ -3639,6 +3698,215 @@ int af_stream_resampler_last_kernel_ms(af_stream_resampler *r, double *ms) {
   float t = 0.0f;
   AF_HIP(hipEventElapsedTime(&t, r->ev0, r->ev1));
   *ms = t;
+  return AF_OK;
+}
+
+}  // extern "C"
+
+// ------------------------------------------------------------------------------------------
+// The capture callback's mixdown (input.rs:383-736, 785-843): interleaved device frames -> mono.  Kernels, passes and the
+// state plane: af_mixdown.hip / af_mixdown_host.hpp.
+struct af_mixdown {
+  int device = 0, n_streams = 0, channels = 1;
+  int mode = 0;               // live: read at each push, per chunk (input.rs:814-816)
+  bool fresh = true;          // the plane is (re)initialised in stream order in front of the next push
+  uint32_t *d_plane = nullptr;
+  float *d_in = nullptr, *d_out = nullptr;  // staging of the host entry point
+  int64_t in_capacity = 0, out_capacity = 0;  // floats
+  std::vector<hipEvent_t> events;  // three per chunk of the last push: before the decision pass | between | after the mix
+  int timed_chunks = 0;
+};
+
+namespace {
+
+int mixdown_check_mode(int32_t mode) {
+  if (mode < 0 || mode > 4)
+    return fail(AF_ERR_INVALID_ARGUMENT, "unknown input channel mode %d (0 average, 1 left, 2 right, 3 max_rms, 4 phase_safe_mono)", mode);
+  return AF_OK;
+}
+
+int mixdown_push_check(af_mixdown *m, const float *in, int64_t n_frames, int64_t in_stride, const float *out, int64_t out_stride) {
+  if (!m) return fail(AF_ERR_INVALID_ARGUMENT, "mixdown is null");
+  if (n_frames < 0 || in_stride < n_frames) return fail(AF_ERR_INVALID_ARGUMENT, "in_stride must cover n_frames frames");
+  if (out_stride < n_frames) return fail(AF_ERR_INVALID_ARGUMENT, "out_stride must cover n_frames frames");
+  if ((!in || !out) && n_frames > 0) return fail(AF_ERR_INVALID_ARGUMENT, "null buffer");
+  return AF_OK;
+}
+
+// one callback (input.rs:807-842): chunks of at most 8192 frames, one decision per chunk, all enqueued on `stream`
+int mixdown_enqueue(af_mixdown *m, const float *d_in, int64_t n_frames, int64_t in_stride, float *d_out, int64_t out_stride,
+                    hipStream_t stream) {
+  AF_HIP(hipSetDevice(m->device));
+  if (!m->d_plane) {
+    AF_HIP(hipMalloc(&m->d_plane, sizeof(uint32_t) * af::kMfCount * (size_t)m->n_streams));
+    m->fresh = true;
+  }
+  if (m->fresh) {
+    AF_HIP(af::launch_mixdown_init(m->d_plane, m->n_streams, stream));
+    m->fresh = false;
+  }
+  const int C = m->channels, mode = m->mode, B = m->n_streams;
+  const int64_t chunks = (n_frames + af::kMixChunk - 1) / af::kMixChunk;
+  while ((int64_t)m->events.size() < 3 * chunks) {
+    hipEvent_t ev;
+    AF_HIP(hipEventCreate(&ev));
+    m->events.push_back(ev);
+  }
+  m->timed_chunks = 0;
+  for (int64_t j = 0; j < chunks; ++j) {
+    const int64_t at = j * af::kMixChunk;
+    const int32_t n = (int32_t)std::min<int64_t>(af::kMixChunk, n_frames - at);
+    const float *src = d_in + at * C;
+    float *dst = d_out + at;
+    int host_kind = -1, host_channel = 0;
+    AF_HIP(hipEventRecord(m->events[3 * j], stream));
+    if (C == 2) {  // stereo always gets its correlation and warning count (input.rs:675-677, 833-838)
+      AF_HIP(af::launch_mixdown_decide(src, in_stride, n, m->d_plane, B, mode, stream));
+    } else if (C > 2 && mode == af::kMixMaxRms) {
+      AF_HIP(af::launch_mixdown_energy(src, in_stride, n, C, m->d_plane, B, stream));
+    } else if (C == 1) {  // the one-channel copy, input.rs:789-805
+      host_kind = af::kMixKindSelect;
+    } else if (mode == af::kMixLeft || mode == af::kMixRight) {
+      host_kind = af::kMixKindSelect;
+      host_channel = mode == af::kMixRight ? 1 : 0;
+    } else {  // Average, and PhaseSafeMono off stereo (input.rs:719)
+      host_kind = af::kMixKindAverage;
+    }
+    AF_HIP(hipEventRecord(m->events[3 * j + 1], stream));
+    AF_HIP(af::launch_mixdown_mix(src, in_stride, n, C, dst, out_stride, m->d_plane, B, host_kind, host_channel, stream));
+    AF_HIP(hipEventRecord(m->events[3 * j + 2], stream));
+  }
+  m->timed_chunks = (int)chunks;
+  return AF_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int af_mixdown_create(int32_t n_channels, int32_t mode, int32_t n_streams, int32_t device, af_mixdown **out) {
+  if (!out) return fail(AF_ERR_INVALID_ARGUMENT, "out is null");
+  *out = nullptr;
+  if (n_channels < 1) return fail(AF_ERR_INVALID_ARGUMENT, "n_channels must be >= 1");
+  if (n_channels > af::kMixMaxChannels)
+    return fail(AF_ERR_UNSUPPORTED, "%d input channels: the mixdown is built for at most %d", n_channels, af::kMixMaxChannels);
+  if (int rc = mixdown_check_mode(mode)) return rc;
+  if (n_streams <= 0) return fail(AF_ERR_INVALID_ARGUMENT, "n_streams must be positive");
+  if (device < 0) return fail(AF_ERR_INVALID_ARGUMENT, "device must be >= 0");
+  af_mixdown *m = new af_mixdown();
+  m->device = device;
+  m->n_streams = n_streams;
+  m->channels = n_channels;
+  m->mode = mode;
+  *out = m;
+  return AF_OK;
+}
+
+void af_mixdown_destroy(af_mixdown *m) {
+  if (!m) return;
+  if (m->d_plane || m->d_in || m->d_out || !m->events.empty()) {
+    (void)hipSetDevice(m->device);
+    (void)hipDeviceSynchronize();
+    (void)hipFree(m->d_plane);
+    (void)hipFree(m->d_in);
+    (void)hipFree(m->d_out);
+    for (hipEvent_t ev : m->events) (void)hipEventDestroy(ev);
+  }
+  delete m;
+}
+
+int af_mixdown_set_mode(af_mixdown *m, int32_t mode) {
+  if (!m) return fail(AF_ERR_INVALID_ARGUMENT, "mixdown is null");
+  if (int rc = mixdown_check_mode(mode)) return rc;
+  m->mode = mode;
+  return AF_OK;
+}
+
+int32_t af_mixdown_mode(const af_mixdown *m) { return m ? m->mode : 0; }
+int32_t af_mixdown_channels(const af_mixdown *m) { return m ? m->channels : 0; }
+
+int af_mixdown_reset(af_mixdown *m) {
+  if (!m) return fail(AF_ERR_INVALID_ARGUMENT, "mixdown is null");
+  m->fresh = true;  // the plane is rewritten in stream order in front of the next push
+  return AF_OK;
+}
+
+int af_mixdown_push_device(af_mixdown *m, const float *d_in, int64_t n_frames, int64_t in_stride_frames, float *d_out,
+                           int64_t out_stride, void *hip_stream) {
+  if (int rc = mixdown_push_check(m, d_in, n_frames, in_stride_frames, d_out, out_stride)) return rc;
+  if (n_frames == 0) return AF_OK;
+  return mixdown_enqueue(m, d_in, n_frames, in_stride_frames, d_out, out_stride, static_cast<hipStream_t>(hip_stream));
+}
+
+int af_mixdown_push_host(af_mixdown *m, const float *in, int64_t n_frames, int64_t in_stride_frames, float *out, int64_t out_stride) {
+  if (int rc = mixdown_push_check(m, in, n_frames, in_stride_frames, out, out_stride)) return rc;
+  const int64_t B = m->n_streams, C = m->channels;
+  for (int64_t s = 0; s < B; ++s)
+    for (int64_t i = 0; i < n_frames * C; ++i)
+      if (!std::isfinite(in[s * in_stride_frames * C + i])) return fail(AF_ERR_NON_FINITE, "samples must be finite");
+  if (n_frames == 0) return AF_OK;
+  AF_HIP(hipSetDevice(m->device));
+  const int64_t need_in = B * n_frames * C, need_out = B * n_frames;
+  if (need_in > m->in_capacity) {  // (the host entry point synchronises before it returns: nothing reads the old buffer)
+    if (m->d_in) AF_HIP(hipFree(m->d_in));
+    m->d_in = nullptr;
+    m->in_capacity = 0;
+    AF_HIP(hipMalloc(&m->d_in, sizeof(float) * need_in));
+    m->in_capacity = need_in;
+  }
+  if (need_out > m->out_capacity) {
+    if (m->d_out) AF_HIP(hipFree(m->d_out));
+    m->d_out = nullptr;
+    m->out_capacity = 0;
+    AF_HIP(hipMalloc(&m->d_out, sizeof(float) * need_out));
+    m->out_capacity = need_out;
+  }
+  const size_t f4 = sizeof(float);
+  AF_HIP(hipMemcpy2D(m->d_in, f4 * n_frames * C, in, f4 * in_stride_frames * C, f4 * n_frames * C, B, hipMemcpyHostToDevice));
+  if (int rc = mixdown_enqueue(m, m->d_in, n_frames, n_frames, m->d_out, n_frames, nullptr)) return rc;
+  AF_HIP(hipStreamSynchronize(nullptr));
+  AF_HIP(hipMemcpy2D(out, f4 * out_stride, m->d_out, f4 * n_frames, f4 * n_frames, B, hipMemcpyDeviceToHost));
+  return AF_OK;
+}
+
+int af_mixdown_read_diagnostics(af_mixdown *m, float *stereo_correlation, uint64_t *phase_warning_count, int32_t *strategy,
+                                float *estimated_delay, int32_t *polarity_flipped, int32_t n_streams) {
+  if (!m) return fail(AF_ERR_INVALID_ARGUMENT, "mixdown is null");
+  if (n_streams != m->n_streams) return fail(AF_ERR_INVALID_ARGUMENT, "n_streams must be the mixdown's %d", m->n_streams);
+  const size_t B = (size_t)n_streams;
+  std::vector<uint32_t> rows(6 * B, 0u);
+  if (m->d_plane && !m->fresh) {
+    AF_HIP(hipSetDevice(m->device));
+    AF_HIP(hipDeviceSynchronize());  // pushes may be queued on any stream
+    AF_HIP(hipMemcpy(rows.data(), m->d_plane + (size_t)af::kMfDiagCorrelation * B, sizeof(uint32_t) * 6 * B, hipMemcpyDeviceToHost));
+  } else {
+    for (size_t s = 0; s < B; ++s) rows[s] = 0x7fc00000u;  // no Some yet
+  }
+  static_assert(af::kMfDiagFlipped == af::kMfDiagCorrelation + 5, "the six diagnostic fields are consecutive");
+  for (size_t s = 0; s < B; ++s) {
+    if (stereo_correlation) std::memcpy(&stereo_correlation[s], &rows[s], 4);
+    if (phase_warning_count) phase_warning_count[s] = (uint64_t)rows[B + s] | ((uint64_t)rows[2 * B + s] << 32);
+    if (strategy) strategy[s] = (int32_t)rows[3 * B + s];
+    if (estimated_delay) std::memcpy(&estimated_delay[s], &rows[4 * B + s], 4);
+    if (polarity_flipped) polarity_flipped[s] = (int32_t)rows[5 * B + s];
+  }
+  return AF_OK;
+}
+
+int af_mixdown_last_kernel_ms(af_mixdown *m, double *decision_ms, double *mix_ms) {
+  if (!m) return fail(AF_ERR_INVALID_ARGUMENT, "mixdown is null");
+  if (decision_ms) *decision_ms = 0.0;
+  if (mix_ms) *mix_ms = 0.0;
+  if (m->timed_chunks == 0) return AF_OK;
+  AF_HIP(hipSetDevice(m->device));
+  AF_HIP(hipEventSynchronize(m->events[3 * (m->timed_chunks - 1) + 2]));
+  for (int j = 0; j < m->timed_chunks; ++j) {
+    float a = 0.0f, b = 0.0f;
+    AF_HIP(hipEventElapsedTime(&a, m->events[3 * j], m->events[3 * j + 1]));
+    AF_HIP(hipEventElapsedTime(&b, m->events[3 * j + 1], m->events[3 * j + 2]));
+    if (decision_ms) *decision_ms += a;
+    if (mix_ms) *mix_ms += b;
+  }
   return AF_OK;
 }
 

@@ -48,8 +48,9 @@ Engine = getattr(_core_module, "Engine", None) if _core_module is not None else 
 NoiseSuppressor = getattr(_core_module, "NoiseSuppressor", None) if _core_module is not None else None
 NoiseModel = getattr(_core_module, "NoiseModel", None) if _core_module is not None else None
 StreamResampler = getattr(_core_module, "StreamResampler", None) if _core_module is not None else None
+Mixdown = getattr(_core_module, "Mixdown", None) if _core_module is not None else None
 new_noise_suppression_engine = (getattr(_core_module, "new_noise_suppression_engine", _missing_core)
                                 if _core_module is not None else _missing_core)
 
-__all__ = ["CORE_AVAILABLE", "Engine", "NoiseSuppressor", "NoiseModel", "StreamResampler", "new_noise_suppression_engine", *_OPERATORS, "LAYOUT_STREAM_MAJOR", "LAYOUT_TIME_MAJOR", "KERNEL_AUTO",
+__all__ = ["CORE_AVAILABLE", "Engine", "NoiseSuppressor", "NoiseModel", "StreamResampler", "Mixdown", "new_noise_suppression_engine", *_OPERATORS, "LAYOUT_STREAM_MAJOR", "LAYOUT_TIME_MAJOR", "KERNEL_AUTO",
            "KERNEL_LANE_PER_STREAM", "KERNEL_PHASED", "KERNEL_QUAD", "KERNEL_STAGED"]

@@ -218,6 +218,19 @@ SIGNATURES = {
     "af_engine_stream_plan": (C.c_int, [_vp, _i64, C.POINTER(_i64), C.POINTER(_i64), C.POINTER(_i64)]),
     "af_engine_io_resampler_delay": (C.c_int, [_vp, C.POINTER(_i32), C.POINTER(_i32)]),
     "af_engine_io_resampler_pending": (C.c_int, [_vp, C.POINTER(_i64), C.POINTER(_i64)]),
+    "af_mixdown_create": (C.c_int, [_i32, _i32, _i32, _i32, C.POINTER(_vp)]),
+    "af_mixdown_destroy": (None, [_vp]),
+    "af_mixdown_set_mode": (C.c_int, [_vp, _i32]),
+    "af_mixdown_mode": (_i32, [_vp]),
+    "af_mixdown_channels": (_i32, [_vp]),
+    "af_mixdown_push_host": (C.c_int, [_vp, _fp, _i64, _i64, _fp, _i64]),
+    "af_mixdown_push_device": (C.c_int, [_vp, _vp, _i64, _i64, _vp, _i64, _vp]),
+    "af_mixdown_read_diagnostics": (C.c_int, [_vp, _fp, C.POINTER(C.c_uint64), C.POINTER(_i32), _fp, C.POINTER(_i32), _i32]),
+    "af_mixdown_reset": (C.c_int, [_vp]),
+    "af_mixdown_last_kernel_ms": (C.c_int, [_vp, _dp, _dp]),
+    "af_engine_set_input_channels": (C.c_int, [_vp, _i32, _i32]),
+    "af_engine_set_input_channel_mode": (C.c_int, [_vp, _i32]),
+    "af_engine_read_input_phase": (C.c_int, [_vp, _fp, C.POINTER(C.c_uint64), C.POINTER(_i32), _fp, C.POINTER(_i32), _i32]),
     "af_gate_process_host": (C.c_int, [_fp, _fp, _i64, _i32, _i64, _d, _d, _d, _d, _i32, _i32, _fp, C.POINTER(C.c_uint64), _i32]),
     "af_measure_integrated_loudness_device": (C.c_int, [_vp, _i64, _i32, _i64, C.c_uint32, _i32, _dp, C.POINTER(_i32)]),
     "af_measure_integrated_loudness_host": (C.c_int, [_fp, _i64, _i32, _i64, C.c_uint32, _i32, _dp, C.POINTER(_i32)]),
@@ -241,6 +254,7 @@ VALUE_FUNCTIONS = {
     "af_gate_threshold_db", "af_engine_gate_enabled",
     "af_stream_resampler_destroy", "af_stream_resampler_output_frames", "af_stream_resampler_pending_input",
     "af_stream_resampler_output_delay", "af_stream_resampler_frames_in", "af_stream_resampler_frames_out",
+    "af_mixdown_destroy", "af_mixdown_mode", "af_mixdown_channels",
 }
 
 _lib = None

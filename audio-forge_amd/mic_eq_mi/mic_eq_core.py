@@ -151,6 +151,14 @@ class Engine:
         """One wake-up over af_engine_stream_host: float32 [n_streams, n] at the input rate -> [n_streams, m] at the output
         rate (``set_io_sample_rates``; without it the engine's own rate on both sides)."""
         a = np.ascontiguousarray(x, dtype=np.float32)
+        channels = getattr(self, "_input_channels", 1)
+        if channels > 1:  # set_input_channels: interleaved frames, [n_streams, n, channels]
+            if a.ndim == 2 and self.n_streams == 1:
+                a = a.reshape(1, *a.shape)
+            if a.ndim != 3 or a.shape[2] != channels:
+                raise ValueError(f"expected [streams, frames, {channels}] interleaved frames, got shape {a.shape}")
+        elif a.ndim == 3:
+            raise ValueError("3-D input needs set_input_channels(n_channels > 1, mode) first")
         if a.ndim == 1:
             a = a.reshape(1, -1)
         if a.shape[0] != self.n_streams:
@@ -162,6 +170,21 @@ class Engine:
         n_out = C.c_int64(0)
         _lib.check(self._lib.af_engine_stream_host(self._h, a.ctypes.data_as(fp), n, out.ctypes.data_as(fp), stride, C.byref(n_out)))
         return np.ascontiguousarray(out[:, : n_out.value])
+
+    def set_input_channels(self, n_channels: int, mode="average") -> None:
+        """Multichannel input (a configuration setter): ``stream`` then takes [n_streams, n, n_channels] and the capture
+        callback's mixdown (input.rs:785-843) runs first on the device.  One channel: off.  ``mode``: an id of
+        input.rs:158-180 ("average", "left", "right", "max_rms", "phase_safe_mono") or its number."""
+        _lib.check(self._lib.af_engine_set_input_channels(self._h, int(n_channels), input_channel_mode(mode)))
+        self._input_channels = int(n_channels)
+
+    def set_input_channel_mode(self, mode) -> None:
+        """Live: takes effect with the next ``stream`` call and keeps the phase-safe history."""
+        _lib.check(self._lib.af_engine_set_input_channel_mode(self._h, input_channel_mode(mode)))
+
+    def input_phase(self) -> dict:
+        """The capture callback's phase diagnostics, arrays per stream: as ``Mixdown.diagnostics``."""
+        return _read_phase(self._lib.af_engine_read_input_phase, self._h, self.n_streams)
 
     def io_resampler_delay(self) -> tuple[int, int]:
         """(input side, output side) ``output_delay()`` in frames, 0 for a side that does not resample."""
@@ -1179,6 +1202,97 @@ class StreamResampler:
         form, seg, streams = C.c_int32(0), C.c_int32(0), C.c_int32(0)
         _lib.check(self._lib.af_stream_resampler_launch_form(self._h, C.byref(form), C.byref(seg), C.byref(streams)))
         return form.value, seg.value, streams.value
+
+
+INPUT_CHANNEL_MODE_IDS = {"average": 0, "left": 1, "right": 2, "max_rms": 3, "phase_safe_mono": 4}  # input.rs:158-180
+PHASE_RESCUE_STRATEGY_NAMES = ("none", "polarity_flip", "fractional_delay", "max_rms_fallback")  # input.rs:49-56
+
+
+def input_channel_mode(mode) -> int:
+    """An InputChannelMode id (input.rs:158-180) or number -> the number; anything else is a ValueError."""
+    if isinstance(mode, str):
+        if mode not in INPUT_CHANNEL_MODE_IDS:
+            raise ValueError(f"unknown input channel mode {mode!r}; expected one of {sorted(INPUT_CHANNEL_MODE_IDS)}")
+        return INPUT_CHANNEL_MODE_IDS[mode]
+    if isinstance(mode, (bool, float)) or not isinstance(mode, (int, np.integer)):
+        raise ValueError(f"unknown input channel mode {mode!r}")
+    return int(mode)
+
+
+def _read_phase(fn, handle, n_streams: int) -> dict:
+    corr = np.empty(n_streams, dtype=np.float32)
+    warn = np.empty(n_streams, dtype=np.uint64)
+    strategy = np.empty(n_streams, dtype=np.int32)
+    delay = np.empty(n_streams, dtype=np.float32)
+    flipped = np.empty(n_streams, dtype=np.int32)
+    fp, ip = C.POINTER(C.c_float), C.POINTER(C.c_int32)
+    _lib.check(fn(handle, corr.ctypes.data_as(fp), warn.ctypes.data_as(C.POINTER(C.c_uint64)), strategy.ctypes.data_as(ip),
+                  delay.ctypes.data_as(fp), flipped.ctypes.data_as(ip), int(n_streams)))
+    return dict(stereo_correlation=corr, phase_warning_count=warn, strategy=strategy, estimated_delay=delay,
+                polarity_flipped=flipped.astype(bool))
+
+
+class Mixdown:
+    """The capture callback's mixdown (input.rs:383-736, 785-843) for `n_streams` streams: interleaved frames of
+    `n_channels` channels -> mono, bit-exact with the reference's f32 arithmetic.  A push is one callback; the mode is live."""
+
+    def __init__(self, n_channels: int, mode="average", n_streams: int = 1, device: int = 0):
+        self._lib = _lib.load()
+        handle = C.c_void_p()
+        _lib.check(self._lib.af_mixdown_create(int(n_channels), input_channel_mode(mode), int(n_streams), int(device), C.byref(handle)))
+        self._h = handle
+        self.n_channels, self.n_streams = int(n_channels), int(n_streams)
+
+    def close(self) -> None:
+        if getattr(self, "_h", None):
+            self._lib.af_mixdown_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def set_mode(self, mode) -> None:
+        _lib.check(self._lib.af_mixdown_set_mode(self._h, input_channel_mode(mode)))
+
+    @property
+    def mode(self) -> int:
+        return int(self._lib.af_mixdown_mode(self._h))
+
+    def push(self, x: np.ndarray) -> np.ndarray:
+        """float32 [n_streams, n, n_channels] (or [n, n_channels] for one stream) -> float32 [n_streams, n]."""
+        a = np.ascontiguousarray(x, dtype=np.float32)
+        if a.ndim == 2 and self.n_streams == 1:
+            a = a.reshape(1, *a.shape)
+        if a.ndim != 3 or a.shape[0] != self.n_streams or a.shape[2] != self.n_channels:
+            raise ValueError(f"expected [{self.n_streams}, frames, {self.n_channels}] interleaved frames, got shape {a.shape}")
+        n = a.shape[1]
+        out = np.empty((self.n_streams, max(n, 1)), dtype=np.float32)
+        fp = C.POINTER(C.c_float)
+        _lib.check(self._lib.af_mixdown_push_host(self._h, a.ctypes.data_as(fp), n, n, out.ctypes.data_as(fp), out.shape[1]))
+        return np.ascontiguousarray(out[:, :n])
+
+    def push_device(self, in_ptr: int, n_frames: int, in_stride_frames: int, out_ptr: int, out_stride: int, hip_stream: int = 0) -> None:
+        """Device pointers, asynchronous on ``hip_stream``: in[(s * in_stride_frames + t) * n_channels + c] ->
+        out[s * out_stride + t].  The input must be finite: nothing on the device checks it."""
+        _lib.check(self._lib.af_mixdown_push_device(self._h, C.c_void_p(in_ptr), int(n_frames), int(in_stride_frames),
+                                                    C.c_void_p(out_ptr), int(out_stride), C.c_void_p(hip_stream)))
+
+    def diagnostics(self) -> dict:
+        """Arrays per stream: stereo_correlation (NaN until a first one), phase_warning_count, strategy
+        (PHASE_RESCUE_STRATEGY_NAMES), estimated_delay, polarity_flipped."""
+        return _read_phase(self._lib.af_mixdown_read_diagnostics, self._h, self.n_streams)
+
+    def reset(self) -> None:
+        _lib.check(self._lib.af_mixdown_reset(self._h))
+
+    def last_kernel_ms(self) -> tuple[float, float]:
+        """(decision passes, mix passes) of the last push, from HIP events."""
+        a, b = C.c_double(0.0), C.c_double(0.0)
+        _lib.check(self._lib.af_mixdown_last_kernel_ms(self._h, C.byref(a), C.byref(b)))
+        return a.value, b.value
 
 
 def simulate_product_resampler_batch(samples: np.ndarray, input_rate: int, output_rate: int,

@@ -450,6 +450,62 @@ int af_engine_stream_plan(const af_engine *e, int64_t n_in, int64_t *engine_fram
 int af_engine_io_resampler_delay(const af_engine *e, int32_t *input_frames, int32_t *output_frames);
 int af_engine_io_resampler_pending(const af_engine *e, int64_t *input_frames, int64_t *output_frames);
 
+/* ---- input mixdown: multichannel device frames -> mono ----------------------------------------------------------
+ * What the reference's capture callback does before a frame reaches the input ring (rust-core/src/audio/input.rs:785-843
+ * over :383-736): interleaved frames of `n_channels` channels become mono under one of five InputChannelModes
+ * (input.rs:137-144): 0 average, 1 left, 2 right, 3 max_rms (the channel with the largest energy of the chunk,
+ * input.rs:383-407), 4 phase_safe_mono.  For stereo, phase_safe_mono measures the channel correlation (input.rs:409-435),
+ * searches 17 lags x 2 polarities for a better alignment and refines the lag with a parabola (input.rs:477-537), then mixes
+ * by a polarity flip, a 4-point Lagrange fractional delay (input.rs:121-134), the strongest channel or a plain average, with
+ * a hysteresis on the decision and a 16-frame history across callbacks (input.rs:539-636).  Off stereo it is the average
+ * (input.rs:719).  One channel is a copy (input.rs:789-805).  A call is one callback: it is cut into chunks of at most 8192
+ * frames with one decision each (input.rs:807-842).  An af_mixdown is that for `n_streams` independent streams; the result
+ * is bit-exact with the reference's f32 arithmetic.  f32 frames only: the reference converts i16 / u16 device formats
+ * through cpal first.  Audio layout: in[(s * in_stride_frames + t) * n_channels + c], out[s * out_stride + t]. */
+typedef struct af_mixdown af_mixdown;
+/* Everything is validated before any HIP call: n_channels >= 1 (AF_ERR_UNSUPPORTED above 8), mode 0..4 (an unknown value
+ * is refused: the reference's unwrap_or(Average), input.rs:815-816, guards a corrupted atomic, not an API), n_streams > 0.
+ * No GPU work happens until the first push. */
+int af_mixdown_create(int32_t n_channels, int32_t mode, int32_t n_streams, int32_t device, af_mixdown **out);
+void af_mixdown_destroy(af_mixdown *m);
+/* The mode is live: the callback loads it per chunk (input.rs:814-816), so a set takes effect with the next push and keeps
+ * the history and last_candidate (input.rs:780 builds the state once per stream).  af_mixdown_mode / _channels: VALUES */
+int af_mixdown_set_mode(af_mixdown *m, int32_t mode);
+int32_t af_mixdown_mode(const af_mixdown *m);
+int32_t af_mixdown_channels(const af_mixdown *m);
+/* One callback of n_frames frames per stream, host pointers; synchronises.  DEVIATION: a non-finite sample refuses the call
+ * with nothing touched (AF_ERR_NON_FINITE "samples must be finite"), as af_stream_resampler_push_host does; the reference
+ * mixes whatever the device delivers (input.rs:785-843) and scrubs later (routing.rs:802-823). */
+int af_mixdown_push_host(af_mixdown *m, const float *in, int64_t n_frames, int64_t in_stride_frames, float *out,
+                         int64_t out_stride);
+/* The same with device pointers, asynchronous on `hip_stream` (a hipStream_t, NULL = default stream): two launches per
+ * chunk, no host wait.  Successive pushes must be ordered by the caller.  Finite input is the caller's contract. */
+int af_mixdown_push_device(af_mixdown *m, const float *d_in, int64_t n_frames, int64_t in_stride_frames, float *d_out,
+                           int64_t out_stride, void *hip_stream);
+/* InputStreamOptions' atomics as the callback leaves them (input.rs:181-186, 825-838), one entry per stream, any pointer
+ * may be null: the last Some stereo correlation (NaN until a first one), the count of chunks whose correlation was below
+ * -0.75 (input.rs:24), and the last chunk's PhaseRescueStrategy (input.rs:31-37: 0 none, 1 polarity_flip,
+ * 2 fractional_delay, 3 max_rms_fallback), estimated delay in frames and polarity-flipped flag.  Waits for the device. */
+int af_mixdown_read_diagnostics(af_mixdown *m, float *stereo_correlation, uint64_t *phase_warning_count, int32_t *strategy,
+                                float *estimated_delay, int32_t *polarity_flipped, int32_t n_streams);
+/* a fresh PhaseSafeMonoState (input.rs:96-105) and fresh diagnostics: what a new input stream starts from (input.rs:780) */
+int af_mixdown_reset(af_mixdown *m);
+/* HIP-event times of the last push, summed over its chunks: the decision passes and the mix passes */
+int af_mixdown_last_kernel_ms(af_mixdown *m, double *decision_ms, double *mix_ms);
+
+/* ---- multichannel input of an engine: input.rs:785-843 ----------------------------------------------------------
+ * af_engine_set_input_channels: a configuration setter (AF_ERR_STATE after streaming started), arguments as
+ *   af_mixdown_create.  One channel means the feature is off and every call behaves as without this setter.  With more,
+ *   af_engine_stream_host takes in[(s * n_in + t) * n_channels + c]; the mixdown runs first on the device and feeds the
+ *   input resampler if one is set (dsp_loop.rs:963-1011), otherwise the chain.  af_engine_stream_plan keeps counting
+ *   frames.  af_engine_process_host / _device return AF_ERR_UNSUPPORTED.  af_engine_reset resets the mixdown.
+ * af_engine_set_input_channel_mode: live, as af_mixdown_set_mode (input.rs:814-816).
+ * af_engine_read_input_phase: as af_mixdown_read_diagnostics; with one channel NaN / 0 / none / 0 / false (input.rs:789-793). */
+int af_engine_set_input_channels(af_engine *e, int32_t n_channels, int32_t mode);
+int af_engine_set_input_channel_mode(af_engine *e, int32_t mode);
+int af_engine_read_input_phase(af_engine *e, float *stereo_correlation, uint64_t *phase_warning_count, int32_t *strategy,
+                               float *estimated_delay, int32_t *polarity_flipped, int32_t n_streams);
+
 /* ---- noise gate -------------------------------------------------------------------------------
  * NoiseGate (rust-core/src/dsp/gate.rs) on the path `simulate_gate_suppressor_order` exercises
  * (python_api.rs:312-319 builds the gate without a VadAutoGate, so process_block_inplace runs the per-sample
