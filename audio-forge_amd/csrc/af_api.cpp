@@ -17,6 +17,7 @@
 #include "af_device.h"
 #include "af_host.hpp"
 #include "af_mixdown_host.hpp"
+#include "af_output_writer_host.hpp"
 #include "af_resampler_host.hpp"
 #include "af_stages.h"
 #include "af_suppressor_host.hpp"
@@ -267,6 +268,17 @@ struct af_engine {
   af_mixdown *mix = nullptr;     // af_engine_set_input_channels with more than one channel: the mixdown in front of everything
   float *d_mix_in = nullptr;     // af_engine_stream_host: the interleaved device frames
   int64_t mix_in_capacity = 0;   // bytes
+  // af_engine_set_output_writer: the output writer (output_writer.rs:62-343) behind the chain / the output resampler, at the
+  // I/O output rate if one is set, otherwise at the engine's.  Null = off, every call is as without the setter.
+  af_output_writer *ow = nullptr;
+  uint32_t io_output_rate = 0;        // af_engine_set_io_sample_rates' output rate while it differs from the engine's
+  std::vector<int64_t> ow_fill;       // af_engine_set_output_queue_fill; empty = the target centre (no error)
+  std::vector<int64_t> ow_written;    // of the last af_engine_stream_host
+  int64_t *d_ow_fill = nullptr, *d_ow_written = nullptr;
+  float *d_ow_out = nullptr;
+  int64_t ow_out_capacity = 0;        // bytes
+  int64_t ow_target_center = 0, ow_capacity = 0;
+  bool ow_fill_dirty = true;          // the device copy of ow_fill is stale
 
   af_engine(double fs, int n, int dev) : proto(fs), n_streams(n), device(dev), sample_rate(fs) {}
 };
@@ -1524,6 +1536,13 @@ void af_engine_destroy(af_engine *e) {
   af_stream_resampler_destroy(e->rs_in);
   af_stream_resampler_destroy(e->rs_out);
   af_mixdown_destroy(e->mix);
+  af_output_writer_destroy(e->ow);
+  if (e->d_ow_fill || e->d_ow_out) {
+    (void)hipSetDevice(e->device);
+    (void)hipFree(e->d_ow_fill);
+    (void)hipFree(e->d_ow_written);
+    (void)hipFree(e->d_ow_out);
+  }
   if (e->d_rs_in || e->d_rs_mid || e->d_rs_out || e->d_mix_in) {
     (void)hipSetDevice(e->device);
     (void)hipFree(e->d_mix_in);
@@ -1564,6 +1583,10 @@ int af_engine_reset(af_engine *e) {
   if (e->rs_in) (void)af_stream_resampler_reset(e->rs_in);    // fresh resamplers on both sides: zero history, nothing queued
   if (e->rs_out) (void)af_stream_resampler_reset(e->rs_out);
   if (e->mix) (void)af_mixdown_reset(e->mix);  // a fresh PhaseSafeMonoState and fresh diagnostics (a new input stream)
+  if (e->ow) (void)af_output_writer_reset(e->ow);  // dsp_loop.rs:796-802; the fill evidence is dropped with it
+  e->ow_fill.clear();
+  e->ow_fill_dirty = true;
+  std::fill(e->ow_written.begin(), e->ow_written.end(), 0);
   return AF_OK;
 }
 
@@ -2006,6 +2029,8 @@ static int check_evidence_blocks(const af_engine *e, int64_t n_run) {
 static bool io_resampled(const af_engine *e) { return e->rs_in || e->rs_out; }
 static const char *const kStreamOnlyMessage =
     "this engine resamples its input or output (af_engine_set_io_sample_rates): use af_engine_stream_host";
+static const char *const kWriterStreamOnlyMessage =
+    "this engine runs the output writer (af_engine_set_output_writer): use af_engine_stream_host";
 static const char *const kChannelsStreamOnlyMessage =
     "this engine takes multichannel input (af_engine_set_input_channels): use af_engine_stream_host";
 
@@ -2847,6 +2872,7 @@ int af_engine_process_device(af_engine *e, const float *in, float *out, int64_t 
                              int32_t layout, void *hip_stream) {
   if (e && io_resampled(e)) return fail(AF_ERR_UNSUPPORTED, "%s", kStreamOnlyMessage);
   if (e && e->mix) return fail(AF_ERR_UNSUPPORTED, "%s", kChannelsStreamOnlyMessage);
+  if (e && e->ow) return fail(AF_ERR_UNSUPPORTED, "%s", kWriterStreamOnlyMessage);
   return process_device_impl(e, in, out, n_samples, stream_stride, layout, hip_stream);
 }
 
@@ -2892,6 +2918,26 @@ static int process_host_impl(af_engine *e, const float *in, int64_t n_in, float 
   return check_device_status(e);
 }
 
+// the engine's output writer at the rate its output side runs at, with the limits dsp_loop.rs:781-795 derives from it
+static int engine_build_writer(af_engine *e) {
+  const double r = e->io_output_rate ? (double)e->io_output_rate : e->sample_rate;
+  if (r != std::floor(r) || r <= 0 || r > INT32_MAX)
+    return fail(AF_ERR_INVALID_ARGUMENT, "the output writer needs an integer output sample rate");
+  const int32_t rate = (int32_t)r;
+  af_output_writer_config cfg;
+  if (int rc = af_output_writer_default_config(rate, &cfg)) return rc;
+  af_output_writer *w = nullptr;
+  if (int rc = af_output_writer_create(&cfg, e->n_streams, e->device, &w)) return rc;
+  af_output_writer_destroy(e->ow);
+  e->ow = w;
+  e->ow_target_center = cfg.target_center;
+  e->ow_capacity = cfg.queue_capacity;
+  e->ow_fill.clear();
+  e->ow_fill_dirty = true;
+  e->ow_written.assign((size_t)e->n_streams, 0);
+  return AF_OK;
+}
+
 // ---- device-rate I/O: dsp_loop.rs:274-317 (the two resamplers), 963-1011 (input side), 843-895 (output side)
 int af_engine_set_io_sample_rates(af_engine *e, uint32_t input_rate, uint32_t output_rate) {
   if (int rc = require_config(e)) return rc;
@@ -2913,6 +2959,8 @@ int af_engine_set_io_sample_rates(af_engine *e, uint32_t input_rate, uint32_t ou
   af_stream_resampler_destroy(e->rs_out);
   e->rs_in = rin;
   e->rs_out = rout;
+  e->io_output_rate = want_out ? output_rate : 0;
+  if (e->ow) return engine_build_writer(e);  // the writer runs at the output side's rate
   return AF_OK;
 }
 
@@ -2966,8 +3014,66 @@ int af_engine_read_input_phase(af_engine *e, float *stereo_correlation, uint64_t
   return AF_OK;
 }
 
-// host arithmetic only: what the next af_engine_stream_host call of n_in frames will do
+// ---- the output writer behind the chain / the output resampler (output_writer.rs:62-343)
+int af_engine_set_output_writer(af_engine *e, int32_t enabled) {
+  if (int rc = require_config(e)) return rc;
+  if (!enabled) {  // off: every call takes the branch it took before
+    af_output_writer_destroy(e->ow);
+    e->ow = nullptr;
+    e->ow_fill.clear();
+    e->ow_fill_dirty = true;
+    e->ow_written.clear();
+    return AF_OK;
+  }
+  return engine_build_writer(e);
+}
+
+int af_engine_set_output_queue_fill(af_engine *e, const int64_t *fill, int32_t n_streams) {
+  if (!e) return fail(AF_ERR_INVALID_ARGUMENT, "engine is null");
+  if (!e->ow) return fail(AF_ERR_STATE, "the output writer is off (af_engine_set_output_writer)");
+  if (n_streams != e->n_streams) return fail(AF_ERR_INVALID_ARGUMENT, "n_streams must be the engine's %d", e->n_streams);
+  if (!fill) return fail(AF_ERR_INVALID_ARGUMENT, "fill is null");
+  for (int32_t s = 0; s < n_streams; ++s)
+    if (fill[s] < 0 || fill[s] > e->ow_capacity)
+      return fail(AF_ERR_INVALID_ARGUMENT, "fill[%d] = %lld is outside the queue's 0 .. %lld", s, (long long)fill[s], (long long)e->ow_capacity);
+  e->ow_fill.assign(fill, fill + n_streams);
+  e->ow_fill_dirty = true;
+  return AF_OK;
+}
+
+int af_engine_read_output_written(af_engine *e, int64_t *written, int32_t n_streams) {
+  if (!e || !written) return fail(AF_ERR_INVALID_ARGUMENT, "null argument");
+  if (!e->ow) return fail(AF_ERR_STATE, "the output writer is off (af_engine_set_output_writer)");
+  if (n_streams != e->n_streams) return fail(AF_ERR_INVALID_ARGUMENT, "n_streams must be the engine's %d", e->n_streams);
+  for (int32_t s = 0; s < n_streams; ++s) written[s] = e->ow_written[(size_t)s];
+  return AF_OK;
+}
+
+int af_engine_read_output_counters(af_engine *e, uint64_t *jitter_dropped, uint64_t *retime_adjustments, uint64_t *recovery_events,
+                                   uint64_t *short_write_dropped, uint64_t *clip_events, uint64_t *true_peak_events, int32_t n_streams) {
+  if (!e) return fail(AF_ERR_INVALID_ARGUMENT, "engine is null");
+  if (!e->ow) return fail(AF_ERR_STATE, "the output writer is off (af_engine_set_output_writer)");
+  return af_output_writer_read_counters(e->ow, jitter_dropped, retime_adjustments, recovery_events, short_write_dropped, clip_events,
+                                        true_peak_events, n_streams);
+}
+
+int af_engine_read_output_meters(af_engine *e, float *db, float *linear, float *ratio, float *drift_ema, int64_t *out_len,
+                                 int64_t *fade_remaining, int64_t *fill_after, int32_t n_streams) {
+  if (!e) return fail(AF_ERR_INVALID_ARGUMENT, "engine is null");
+  if (!e->ow) return fail(AF_ERR_STATE, "the output writer is off (af_engine_set_output_writer)");
+  return af_output_writer_read_meters(e->ow, db, linear, ratio, drift_ema, out_len, fade_remaining, fill_after, n_streams);
+}
+
+// host arithmetic only: what the next af_engine_stream_host call of n_in frames will do (m3: frames into the output writer)
+static int stream_frames(const af_engine *e, int64_t n_in, int64_t *engine_frames_in, int64_t *engine_frames_out, int64_t *n_out);
 int af_engine_stream_plan(const af_engine *e, int64_t n_in, int64_t *engine_frames_in, int64_t *engine_frames_out, int64_t *n_out) {
+  int64_t m3 = 0;
+  if (int rc = stream_frames(e, n_in, engine_frames_in, engine_frames_out, &m3)) return rc;
+  if (e->ow && m3 > 0) m3 = af_output_writer_max_output_frames(e->ow, m3);  // the longest row the writer can yield
+  if (n_out) *n_out = m3;
+  return AF_OK;
+}
+static int stream_frames(const af_engine *e, int64_t n_in, int64_t *engine_frames_in, int64_t *engine_frames_out, int64_t *n_out) {
   if (!e) return fail(AF_ERR_INVALID_ARGUMENT, "engine is null");
   if (n_in < 0) return fail(AF_ERR_INVALID_ARGUMENT, "n_samples must be >= 0");
   const int64_t m1 = e->rs_in ? af_stream_resampler_output_frames(e->rs_in, n_in) : n_in;
@@ -2989,11 +3095,15 @@ static int stream_host_resampled(af_engine *e, const float *in, int64_t n_in, fl
   if (n_in < 0) return fail(AF_ERR_INVALID_ARGUMENT, "n_samples must be >= 0");
   if (n_in > 0 && !in) return fail(AF_ERR_INVALID_ARGUMENT, "audio pointers are null");
   int64_t m1 = 0, m2 = 0, m3 = 0;
-  if (int rc = af_engine_stream_plan(e, n_in, &m1, &m2, &m3)) return rc;
+  if (int rc = stream_frames(e, n_in, &m1, &m2, &m3)) return rc;
   if (m3 > 0 && !out) return fail(AF_ERR_INVALID_ARGUMENT, "audio pointers are null");
-  if (out_stride < m3)
+  if (e->ow && m3 > af::kOwMaxBlock)
+    return fail(AF_ERR_INVALID_ARGUMENT, "this call hands the output writer %lld frames per stream; it takes at most %d",
+                (long long)m3, af::kOwMaxBlock);
+  const int64_t ow_width = (e->ow && m3 > 0) ? af_output_writer_max_output_frames(e->ow, m3) : 0;
+  if (out_stride < std::max(m3, ow_width))
     return fail(AF_ERR_INVALID_ARGUMENT, "this call produces %lld frames per stream (af_engine_stream_plan) but out_stride is %lld",
-                (long long)m3, (long long)out_stride);
+                (long long)std::max(m3, ow_width), (long long)out_stride);
   const int64_t B = e->n_streams;
   const int64_t C = e->mix ? af_mixdown_channels(e->mix) : 1;  // in[(s * n_in + t) * C + c]
   for (int64_t i = 0; i < B * n_in * C; ++i)
@@ -3035,6 +3145,39 @@ static int stream_host_resampled(af_engine *e, const float *in, int64_t n_in, fl
     res = e->d_rs_out;
     res_stride = std::max<int64_t>(m3, 1);
   }
+  if (e->ow) {  // write_chunk on what the chain / the output resampler produced (dsp_loop.rs:843-895)
+    std::fill(e->ow_written.begin(), e->ow_written.end(), 0);
+    if (m3 == 0) {  // nothing to write: the reference's write_chunk returns false on an empty block
+      AF_HIP(hipStreamSynchronize(nullptr));
+      return check_device_status(e);
+    }
+    if (!e->d_ow_fill) {
+      AF_HIP(hipMalloc(&e->d_ow_fill, sizeof(int64_t) * (size_t)B));
+      AF_HIP(hipMalloc(&e->d_ow_written, sizeof(int64_t) * (size_t)B));
+    }
+    if (int rc = grow_device(e, reinterpret_cast<void **>(&e->d_ow_out), &e->ow_out_capacity, f4 * B * ow_width, nullptr)) return rc;
+    if (e->ow_fill_dirty) {  // uploaded when af_engine_set_output_queue_fill (or a reset) changed it, not per call
+      if (e->ow_fill.empty()) e->ow_fill.assign((size_t)B, e->ow_target_center);  // no evidence yet: no error
+      AF_HIP(hipMemcpy(e->d_ow_fill, e->ow_fill.data(), sizeof(int64_t) * (size_t)B, hipMemcpyHostToDevice));
+      e->ow_fill_dirty = false;
+    }
+    // limiter_enabled and the ceiling as the loop takes them from the limiter (dsp_loop.rs:535, output_writer.rs:208-215)
+    if (int rc = af_output_writer_set_limiter(e->ow, e->proto.limiter_enabled ? 1 : 0,
+                                              std::pow(10.0f, (float)e->proto.limiter.ceiling_db / 20.0f))) return rc;
+    if (int rc = af_output_writer_push_device(e->ow, res, m3, res_stride, e->d_ow_fill, 0, e->d_ow_out, ow_width, ow_width,
+                                              e->d_ow_written, nullptr)) return rc;
+    AF_HIP(hipStreamSynchronize(nullptr));
+    AF_HIP(hipMemcpy(e->ow_written.data(), e->d_ow_written, sizeof(int64_t) * (size_t)B, hipMemcpyDeviceToHost));
+    int64_t longest = 0;
+    for (int64_t v : e->ow_written) longest = std::max(longest, v);
+    if (longest > 0) {
+      AF_HIP(hipMemcpy2D(out, f4 * out_stride, e->d_ow_out, f4 * ow_width, f4 * longest, B, hipMemcpyDeviceToHost));
+      for (int64_t s = 0; s < B; ++s)  // rows are zero beyond their own length
+        std::fill(out + s * out_stride + e->ow_written[(size_t)s], out + s * out_stride + longest, 0.0f);
+    }
+    if (n_out) *n_out = longest;
+    return check_device_status(e);
+  }
   AF_HIP(hipStreamSynchronize(nullptr));
   if (m3 > 0) AF_HIP(hipMemcpy2D(out, f4 * out_stride, res, f4 * res_stride, f4 * m3, B, hipMemcpyDeviceToHost));
   if (n_out) *n_out = m3;
@@ -3046,12 +3189,13 @@ int af_engine_process_host(af_engine *e, const float *in, float *out, int64_t n_
     return fail(AF_ERR_INVALID_ARGUMENT, "unknown layout %d", layout);
   if (e && io_resampled(e)) return fail(AF_ERR_UNSUPPORTED, "%s", kStreamOnlyMessage);
   if (e && e->mix) return fail(AF_ERR_UNSUPPORTED, "%s", kChannelsStreamOnlyMessage);
+  if (e && e->ow) return fail(AF_ERR_UNSUPPORTED, "%s", kWriterStreamOnlyMessage);
   return process_host_impl(e, in, n_samples, out, layout == AF_LAYOUT_STREAM_MAJOR ? n_samples : (e ? e->n_streams : 0), layout, nullptr);
 }
 
 int af_engine_stream_host(af_engine *e, const float *in, int64_t n_in, float *out, int64_t out_stride, int64_t *n_out) {
   if (n_out) *n_out = 0;
-  if (e && (io_resampled(e) || e->mix)) return stream_host_resampled(e, in, n_in, out, out_stride, n_out);
+  if (e && (io_resampled(e) || e->mix || e->ow)) return stream_host_resampled(e, in, n_in, out, out_stride, n_out);
   return process_host_impl(e, in, n_in, out, out_stride, AF_LAYOUT_STREAM_MAJOR, n_out);
 }
 
@@ -4268,5 +4412,360 @@ int32_t af_noise_suppressor_latency_samples(const af_noise_suppressor *) { retur
 int32_t af_noise_suppressor_backend_available(const af_noise_suppressor *s) { return s ? 1 : 0; }   // rnnoise.rs:317-319
 int32_t af_noise_suppressor_backend_failed(const af_noise_suppressor *) { return 0; }               // rnnoise.rs:325-327
 const char *af_noise_suppressor_backend_error(const af_noise_suppressor *) { return nullptr; }      // rnnoise.rs:321-323
+
+}  // extern "C"
+
+// ------------------------------------------------------------------------------------------
+// The output writer (output_writer.rs:62-343): drift retime, discontinuity fade, safety, queue accounting.  Kernels, passes
+// and the state plane: af_output_writer.hip / af_output_writer_host.hpp.
+struct af_output_writer {
+  int device = 0, n_streams = 0;
+  af_output_writer_config cfg{};
+  bool limiter_enabled = true;   // live, output_writer.rs:208, 214
+  float ceiling_linear = 1.0f;   // live, :209
+  float release_coeff = 0.0f;    // TruePeakLimiter::default_settings(rate): 80 ms, true_peak.rs:285-287, 308-313
+  bool fresh = true;             // the plane is (re)initialised in stream order in front of the next push
+  uint32_t *d_plane = nullptr;
+  float *d_x = nullptr, *d_tg = nullptr;  // scratch rows of the passes
+  int64_t scratch_frames = 0;             // frames per stream they hold
+  float *d_in = nullptr, *d_out = nullptr;  // staging of the host entry point
+  int64_t *d_fill = nullptr, *d_written = nullptr;
+  int64_t in_capacity = 0, out_capacity = 0;  // floats
+  std::vector<float> host_rows;               // ... and its copy-back rows, kept between calls
+  hipEvent_t ev[6] = {};  // before the plan pass, then behind each of the five passes
+  bool timed = false;
+};
+
+namespace {
+
+int64_t ow_duration_samples(int64_t rate, int64_t ms) {  // resampling.rs:1-3
+  return std::max<int64_t>((rate * ms + 500) / 1000, 1);
+}
+
+int64_t ow_max_output_frames(const af_output_writer *w, int64_t n_in) {
+  // resampling.rs:92-94 at the smallest ratio; the clean path and a pass-through yield n_in
+  const int64_t desired = (int64_t)std::fmax(std::round((float)n_in / af::kOwMinRatio), 1.0f);
+  const int64_t retimed = std::min<int64_t>({desired, std::max<int64_t>(w->cfg.queue_capacity, 1), (int64_t)af::kOwScratch});
+  return std::max(n_in, retimed);
+}
+
+int ow_push_check(af_output_writer *w, const float *in, int64_t n_in, int64_t in_stride, const int64_t *fill, const float *out,
+                  int64_t out_capacity, int64_t out_stride, const int64_t *written) {
+  if (!w) return fail(AF_ERR_INVALID_ARGUMENT, "output writer is null");
+  if (n_in < 0) return fail(AF_ERR_INVALID_ARGUMENT, "n_in must be >= 0");
+  if (n_in > af::kOwMaxBlock)
+    return fail(AF_ERR_INVALID_ARGUMENT, "n_in %lld: a push takes at most %d frames", (long long)n_in, af::kOwMaxBlock);
+  if (!written) return fail(AF_ERR_INVALID_ARGUMENT, "written is null");
+  if (n_in == 0) return AF_OK;
+  if (!in || !out || !fill) return fail(AF_ERR_INVALID_ARGUMENT, "null buffer");
+  if (in_stride < n_in) return fail(AF_ERR_INVALID_ARGUMENT, "in_stride must cover n_in frames");
+  const int64_t need = ow_max_output_frames(w, n_in);
+  if (out_capacity < need || out_stride < need)
+    return fail(AF_ERR_INVALID_ARGUMENT, "out_capacity and out_stride must cover the %lld frames a push of %lld can yield",
+                (long long)need, (long long)n_in);
+  return AF_OK;
+}
+
+// one write_chunk per stream, all enqueued on `stream`
+int ow_enqueue(af_output_writer *w, const float *d_in, int64_t n_in, int64_t in_stride, const int64_t *d_fill, int clean_path,
+               float *d_out, int64_t out_stride, int64_t *d_written, hipStream_t stream) {
+  AF_HIP(hipSetDevice(w->device));
+  const int B = w->n_streams;
+  if (!w->d_plane) {
+    AF_HIP(hipMalloc(&w->d_plane, sizeof(uint32_t) * af::kOwCount * (size_t)B));
+    for (hipEvent_t &ev : w->ev) AF_HIP(hipEventCreate(&ev));
+    w->fresh = true;
+  }
+  const int64_t max_out = ow_max_output_frames(w, n_in);
+  if (!w->d_x) {  // once, for the longest block a push may bring: no later push allocates or waits
+    const int64_t longest = ow_max_output_frames(w, af::kOwMaxBlock);
+    AF_HIP(hipMalloc(&w->d_x, sizeof(float) * (size_t)longest * B));
+    AF_HIP(hipMalloc(&w->d_tg, sizeof(float) * (size_t)longest * B));
+    w->scratch_frames = longest;
+  }
+  if (w->fresh) {
+    AF_HIP(af::launch_output_writer_init(w->d_plane, B, stream));
+    w->fresh = false;
+  }
+  af::OwPush p{};
+  p.in = d_in;
+  p.in_stride = in_stride;
+  p.n = (int32_t)n_in;
+  p.fill = d_fill;
+  p.clean_path = clean_path ? 1 : 0;
+  p.out = d_out;
+  p.out_stride = out_stride;
+  p.written = d_written;
+  p.plane = w->d_plane;
+  p.n_streams = B;
+  p.x = w->d_x;
+  p.tg = w->d_tg;
+  p.max_out = (int32_t)max_out;
+  p.limiter_on = w->limiter_enabled ? 1 : 0;
+  p.ceiling = w->limiter_enabled ? w->ceiling_linear : 1.0f;                  // output_writer.rs:208-212
+  p.limiter_ceiling = std::min(std::max(p.ceiling, 0.000001f), 1.0f);         // true_peak.rs:304-306
+  p.clamp_ceiling = std::min(std::max(p.ceiling, 0.0f), 1.0f);                // routing.rs:774
+  p.release_coeff = w->release_coeff;
+  p.capacity = w->cfg.queue_capacity;
+  p.center = w->cfg.target_center;
+  p.hard = w->cfg.hard_backlog;
+  p.fade = w->cfg.fade_frames;
+  AF_HIP(hipEventRecord(w->ev[0], stream));
+  AF_HIP(af::launch_output_writer_plan(p, stream));
+  AF_HIP(hipEventRecord(w->ev[1], stream));
+  AF_HIP(af::launch_output_writer_shape(p, stream));
+  AF_HIP(hipEventRecord(w->ev[2], stream));
+  if (p.limiter_on) AF_HIP(af::launch_output_writer_gain(p, stream));
+  AF_HIP(hipEventRecord(w->ev[3], stream));
+  AF_HIP(af::launch_output_writer_out(p, stream));
+  AF_HIP(hipEventRecord(w->ev[4], stream));
+  AF_HIP(af::launch_output_writer_finish(p, stream));
+  AF_HIP(hipEventRecord(w->ev[5], stream));
+  w->timed = true;
+  return AF_OK;
+}
+
+// rows [first, first + count) of the plane, or the fresh plane's values before a first push
+int ow_read_rows(af_output_writer *w, int first, int count, std::vector<uint32_t> &rows) {
+  const size_t B = (size_t)w->n_streams;
+  rows.assign((size_t)count * B, 0u);
+  if (w->d_plane && !w->fresh) {
+    AF_HIP(hipSetDevice(w->device));
+    AF_HIP(hipDeviceSynchronize());  // pushes may be queued on any stream
+    AF_HIP(hipMemcpy(rows.data(), w->d_plane + (size_t)first * B, sizeof(uint32_t) * (size_t)count * B, hipMemcpyDeviceToHost));
+    return AF_OK;
+  }
+  auto bits = [](float v) { uint32_t u; std::memcpy(&u, &v, 4); return u; };
+  for (int f = first; f < first + count; ++f) {
+    float v = 0.0f;
+    if (f == af::kOwGain || f == af::kOwMinGain || f == af::kOwRecRatio) v = 1.0f;
+    if (f == af::kOwDbClipPeak || f == af::kOwDbTruePeak || f == af::kOwDbTruePeakInput) v = -120.0f;
+    if (f == af::kOwDbHeadroom) v = 120.0f;
+    for (size_t s = 0; s < B; ++s) rows[(size_t)(f - first) * B + s] = bits(v);
+  }
+  return AF_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int af_output_writer_default_config(int32_t output_rate, af_output_writer_config *cfg) {
+  if (!cfg) return fail(AF_ERR_INVALID_ARGUMENT, "cfg is null");
+  if (output_rate <= 0) return fail(AF_ERR_INVALID_ARGUMENT, "output_rate must be positive");
+  const int64_t low = ow_duration_samples(output_rate, 30), high = ow_duration_samples(output_rate, 40);  // processor.rs:66-67
+  cfg->output_rate = output_rate;
+  cfg->queue_capacity = 2 * (int64_t)output_rate;                          // dsp_loop.rs:204
+  cfg->target_center = (low + high + 1) / 2;                               // dsp_loop.rs:786-787
+  cfg->hard_backlog = ow_duration_samples(output_rate, 60);                // dsp_loop.rs:788-789, processor.rs:68
+  cfg->fade_frames = std::max<int64_t>(ow_duration_samples(output_rate, 6), 1);  // dsp_loop.rs:794-795
+  return AF_OK;
+}
+
+int af_output_writer_create(const af_output_writer_config *cfg, int32_t n_streams, int32_t device, af_output_writer **out) {
+  if (!out) return fail(AF_ERR_INVALID_ARGUMENT, "out is null");
+  *out = nullptr;
+  if (!cfg) return fail(AF_ERR_INVALID_ARGUMENT, "cfg is null");
+  constexpr int64_t kLim = INT32_MAX;
+  if (cfg->output_rate <= 0) return fail(AF_ERR_INVALID_ARGUMENT, "output_rate must be positive");
+  if (cfg->queue_capacity < 1 || cfg->queue_capacity > kLim) return fail(AF_ERR_INVALID_ARGUMENT, "queue_capacity must be 1 .. 2^31 - 1");
+  if (cfg->target_center < 0 || cfg->target_center > kLim) return fail(AF_ERR_INVALID_ARGUMENT, "target_center must be 0 .. 2^31 - 1");
+  if (cfg->hard_backlog < 0 || cfg->hard_backlog > kLim) return fail(AF_ERR_INVALID_ARGUMENT, "hard_backlog must be 0 .. 2^31 - 1");
+  if (cfg->fade_frames < 1 || cfg->fade_frames > kLim) return fail(AF_ERR_INVALID_ARGUMENT, "fade_frames must be 1 .. 2^31 - 1");
+  if (n_streams <= 0 || n_streams > 65535) return fail(AF_ERR_INVALID_ARGUMENT, "n_streams must be 1 .. 65535");
+  if (device < 0) return fail(AF_ERR_INVALID_ARGUMENT, "device must be >= 0");
+  af_output_writer *w = new af_output_writer();
+  w->device = device;
+  w->n_streams = n_streams;
+  w->cfg = *cfg;
+  const float rate = std::max((float)cfg->output_rate, 1.0f);  // true_peak.rs:279
+  w->release_coeff = (float)af::time_constant_to_coeff((double)std::min(std::max(80.0f, 5.0f), 500.0f), (double)rate);
+  *out = w;
+  return AF_OK;
+}
+
+void af_output_writer_destroy(af_output_writer *w) {
+  if (!w) return;
+  if (w->d_plane || w->d_in || w->d_out || w->d_x) {
+    (void)hipSetDevice(w->device);
+    (void)hipDeviceSynchronize();
+    (void)hipFree(w->d_plane);
+    (void)hipFree(w->d_x);
+    (void)hipFree(w->d_tg);
+    (void)hipFree(w->d_in);
+    (void)hipFree(w->d_out);
+    (void)hipFree(w->d_fill);
+    (void)hipFree(w->d_written);
+    for (hipEvent_t ev : w->ev)
+      if (ev) (void)hipEventDestroy(ev);
+  }
+  delete w;
+}
+
+int af_output_writer_set_limiter(af_output_writer *w, int32_t enabled, float ceiling_linear) {
+  if (!w) return fail(AF_ERR_INVALID_ARGUMENT, "output writer is null");
+  if (!std::isfinite(ceiling_linear)) return fail(AF_ERR_INVALID_ARGUMENT, "ceiling_linear must be finite");
+  w->limiter_enabled = enabled != 0;
+  w->ceiling_linear = ceiling_linear;
+  return AF_OK;
+}
+
+int af_output_writer_reset(af_output_writer *w) {
+  if (!w) return fail(AF_ERR_INVALID_ARGUMENT, "output writer is null");
+  w->fresh = true;  // the plane is rewritten in stream order in front of the next push
+  return AF_OK;
+}
+
+int64_t af_output_writer_max_output_frames(const af_output_writer *w, int64_t n_in) {
+  if (!w || n_in < 1) return 0;
+  return ow_max_output_frames(w, n_in);
+}
+
+int af_output_writer_push_device(af_output_writer *w, const float *d_in, int64_t n_in, int64_t in_stride, const int64_t *d_fill,
+                                 int32_t clean_path, float *d_out, int64_t out_capacity, int64_t out_stride, int64_t *d_written,
+                                 void *hip_stream) {
+  if (int rc = ow_push_check(w, d_in, n_in, in_stride, d_fill, d_out, out_capacity, out_stride, d_written)) return rc;
+  hipStream_t stream = static_cast<hipStream_t>(hip_stream);
+  if (n_in == 0) {
+    AF_HIP(hipSetDevice(w->device));
+    AF_HIP(hipMemsetAsync(d_written, 0, sizeof(int64_t) * (size_t)w->n_streams, stream));
+    return AF_OK;
+  }
+  return ow_enqueue(w, d_in, n_in, in_stride, d_fill, clean_path, d_out, out_stride, d_written, stream);
+}
+
+int af_output_writer_push_host(af_output_writer *w, const float *in, int64_t n_in, int64_t in_stride, const int64_t *fill,
+                               int32_t clean_path, float *out, int64_t out_capacity, int64_t out_stride, int64_t *written) {
+  if (int rc = ow_push_check(w, in, n_in, in_stride, fill, out, out_capacity, out_stride, written)) return rc;
+  const int64_t B = w->n_streams;
+  if (n_in == 0) {
+    for (int64_t s = 0; s < B; ++s) written[s] = 0;
+    return AF_OK;
+  }
+  for (int64_t s = 0; s < B; ++s)
+    if (fill[s] < 0 || fill[s] > w->cfg.queue_capacity)
+      return fail(AF_ERR_INVALID_ARGUMENT, "fill[%lld] = %lld is outside the queue's 0 .. %lld", (long long)s, (long long)fill[s],
+                  (long long)w->cfg.queue_capacity);
+  AF_HIP(hipSetDevice(w->device));
+  const int64_t max_out = ow_max_output_frames(w, n_in);
+  const int64_t need_in = B * n_in, need_out = B * max_out;
+  if (!w->d_fill) {
+    AF_HIP(hipMalloc(&w->d_fill, sizeof(int64_t) * (size_t)B));
+    AF_HIP(hipMalloc(&w->d_written, sizeof(int64_t) * (size_t)B));
+  }
+  if (need_in > w->in_capacity) {  // (the host entry point synchronises before it returns: nothing reads the old buffer)
+    if (w->d_in) AF_HIP(hipFree(w->d_in));
+    w->d_in = nullptr;
+    w->in_capacity = 0;
+    AF_HIP(hipMalloc(&w->d_in, sizeof(float) * need_in));
+    w->in_capacity = need_in;
+  }
+  if (need_out > w->out_capacity) {
+    if (w->d_out) AF_HIP(hipFree(w->d_out));
+    w->d_out = nullptr;
+    w->out_capacity = 0;
+    AF_HIP(hipMalloc(&w->d_out, sizeof(float) * need_out));
+    w->out_capacity = need_out;
+  }
+  const size_t f4 = sizeof(float);
+  AF_HIP(hipMemcpy2D(w->d_in, f4 * n_in, in, f4 * in_stride, f4 * n_in, B, hipMemcpyHostToDevice));
+  AF_HIP(hipMemcpy(w->d_fill, fill, sizeof(int64_t) * (size_t)B, hipMemcpyHostToDevice));
+  if (int rc = ow_enqueue(w, w->d_in, n_in, n_in, w->d_fill, clean_path, w->d_out, max_out, w->d_written, nullptr)) return rc;
+  AF_HIP(hipStreamSynchronize(nullptr));
+  AF_HIP(hipMemcpy(written, w->d_written, sizeof(int64_t) * (size_t)B, hipMemcpyDeviceToHost));
+  int64_t longest = 0;
+  for (int64_t s = 0; s < B; ++s) longest = std::max(longest, std::min(std::max<int64_t>(written[s], 0), max_out));
+  if ((int64_t)w->host_rows.size() < B * longest) w->host_rows.resize((size_t)(B * longest));
+  if (longest > 0)
+    AF_HIP(hipMemcpy2D(w->host_rows.data(), f4 * longest, w->d_out, f4 * max_out, f4 * longest, B, hipMemcpyDeviceToHost));
+  for (int64_t s = 0; s < B; ++s)  // the rest of a row stays as the caller left it
+    std::memcpy(out + s * out_stride, w->host_rows.data() + s * longest, f4 * (size_t)std::min(std::max<int64_t>(written[s], 0), max_out));
+  return AF_OK;
+}
+
+int af_output_writer_read_counters(af_output_writer *w, uint64_t *jitter_dropped, uint64_t *retime_adjustments,
+                                   uint64_t *recovery_events, uint64_t *short_write_dropped, uint64_t *clip_events,
+                                   uint64_t *true_peak_events, int32_t n_streams) {
+  if (!w) return fail(AF_ERR_INVALID_ARGUMENT, "output writer is null");
+  if (n_streams != w->n_streams) return fail(AF_ERR_INVALID_ARGUMENT, "n_streams must be the output writer's %d", w->n_streams);
+  std::vector<uint32_t> rows;
+  if (int rc = ow_read_rows(w, af::kOwCntJitterDropped, 12, rows)) return rc;
+  static_assert(af::kOwCntTruePeak == af::kOwCntJitterDropped + 10, "the six counters are consecutive word pairs");
+  const size_t B = (size_t)n_streams;
+  uint64_t *dst[6] = {jitter_dropped, retime_adjustments, recovery_events, short_write_dropped, clip_events, true_peak_events};
+  for (int c = 0; c < 6; ++c)
+    if (dst[c])
+      for (size_t s = 0; s < B; ++s) dst[c][s] = (uint64_t)rows[(2 * c) * B + s] | ((uint64_t)rows[(2 * c + 1) * B + s] << 32);
+  return AF_OK;
+}
+
+int af_output_writer_read_meters(af_output_writer *w, float *db, float *linear, float *ratio, float *drift_ema, int64_t *out_len,
+                                 int64_t *fade_remaining, int64_t *fill_after, int32_t n_streams) {
+  if (!w) return fail(AF_ERR_INVALID_ARGUMENT, "output writer is null");
+  if (n_streams != w->n_streams) return fail(AF_ERR_INVALID_ARGUMENT, "n_streams must be the output writer's %d", w->n_streams);
+  std::vector<uint32_t> rows;
+  if (int rc = ow_read_rows(w, 0, af::kOwCount, rows)) return rc;
+  const size_t B = (size_t)n_streams;
+  static_assert(af::kOwDbHeadroom == af::kOwDbClipPeak + 5 && af::kOwClipMax == af::kOwInTp + 4, "consecutive fields");
+  if (db) std::memcpy(db, &rows[(size_t)af::kOwDbClipPeak * B], 4 * 6 * B);
+  if (linear) std::memcpy(linear, &rows[(size_t)af::kOwInTp * B], 4 * 5 * B);
+  if (ratio) std::memcpy(ratio, &rows[(size_t)af::kOwRecRatio * B], 4 * B);
+  if (drift_ema) std::memcpy(drift_ema, &rows[(size_t)af::kOwEma * B], 4 * B);
+  for (size_t s = 0; s < B; ++s) {
+    if (out_len) out_len[s] = rows[(size_t)af::kOwRecOutLen * B + s];
+    if (fade_remaining) fade_remaining[s] = rows[(size_t)af::kOwFadeRemaining * B + s];
+    if (fill_after) fill_after[s] = rows[(size_t)af::kOwRecFillAfter * B + s];
+  }
+  return AF_OK;
+}
+
+int af_output_writer_read_state(af_output_writer *w, float *gain, float *delay, int32_t *write_idx, float *histories,
+                                int32_t n_streams) {
+  if (!w) return fail(AF_ERR_INVALID_ARGUMENT, "output writer is null");
+  if (n_streams != w->n_streams) return fail(AF_ERR_INVALID_ARGUMENT, "n_streams must be the output writer's %d", w->n_streams);
+  std::vector<uint32_t> rows;
+  if (int rc = ow_read_rows(w, 0, af::kOwCount, rows)) return rc;
+  const size_t B = (size_t)n_streams;
+  auto at = [&](int f, size_t s) { float v; std::memcpy(&v, &rows[(size_t)f * B + s], 4); return v; };
+  for (size_t s = 0; s < B; ++s) {
+    const int sel = (int)(rows[(size_t)af::kOwSel * B + s] & 1u);
+    const int base = af::kOwHist + sel * 3 * af::kOwTaps;
+    const int widx = (int)rows[(size_t)af::kOwWriteIdx * B + s];
+    if (gain) gain[s] = at(af::kOwGain, s);
+    if (write_idx) write_idx[s] = widx;
+    if (histories)
+      for (int k = 0; k < 3 * af::kOwTaps; ++k) histories[s * 3 * af::kOwTaps + k] = at(base + k, s);
+    if (delay)  // the frame k + 1 steps back sits k + 1 slots behind the write index (true_peak.rs:343-345)
+      for (int k = 0; k < af::kOwLookahead; ++k)
+        delay[s * af::kOwLookahead + (size_t)((widx - 1 - k + 2 * af::kOwLookahead) % af::kOwLookahead)] = at(base + k, s);
+  }
+  return AF_OK;
+}
+
+int af_output_writer_last_kernel_ms(af_output_writer *w, double *ms) {
+  if (!w) return fail(AF_ERR_INVALID_ARGUMENT, "output writer is null");
+  if (ms) *ms = 0.0;
+  if (!w->timed) return AF_OK;
+  AF_HIP(hipSetDevice(w->device));
+  AF_HIP(hipEventSynchronize(w->ev[5]));
+  float t = 0.0f;
+  AF_HIP(hipEventElapsedTime(&t, w->ev[0], w->ev[5]));
+  if (ms) *ms = t;
+  return AF_OK;
+}
+
+int af_output_writer_last_pass_ms(af_output_writer *w, double *pass_ms) {
+  if (!w || !pass_ms) return fail(AF_ERR_INVALID_ARGUMENT, "null argument");
+  for (int k = 0; k < 5; ++k) pass_ms[k] = 0.0;
+  if (!w->timed) return AF_OK;
+  AF_HIP(hipSetDevice(w->device));
+  AF_HIP(hipEventSynchronize(w->ev[5]));
+  for (int k = 0; k < 5; ++k) {
+    float t = 0.0f;
+    AF_HIP(hipEventElapsedTime(&t, w->ev[k], w->ev[k + 1]));
+    pass_ms[k] = t;
+  }
+  return AF_OK;
+}
 
 }  // extern "C"

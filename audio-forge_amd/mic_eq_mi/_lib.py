@@ -228,6 +228,24 @@ SIGNATURES = {
     "af_mixdown_read_diagnostics": (C.c_int, [_vp, _fp, C.POINTER(C.c_uint64), C.POINTER(_i32), _fp, C.POINTER(_i32), _i32]),
     "af_mixdown_reset": (C.c_int, [_vp]),
     "af_mixdown_last_kernel_ms": (C.c_int, [_vp, _dp, _dp]),
+    "af_output_writer_default_config": (C.c_int, [_i32, _vp]),
+    "af_output_writer_create": (C.c_int, [_vp, _i32, _i32, C.POINTER(_vp)]),
+    "af_output_writer_destroy": (None, [_vp]),
+    "af_output_writer_set_limiter": (C.c_int, [_vp, _i32, C.c_float]),
+    "af_output_writer_reset": (C.c_int, [_vp]),
+    "af_output_writer_max_output_frames": (_i64, [_vp, _i64]),
+    "af_output_writer_push_host": (C.c_int, [_vp, _fp, _i64, _i64, C.POINTER(_i64), _i32, _fp, _i64, _i64, C.POINTER(_i64)]),
+    "af_output_writer_push_device": (C.c_int, [_vp, _vp, _i64, _i64, _vp, _i32, _vp, _i64, _i64, _vp, _vp]),
+    "af_output_writer_read_counters": (C.c_int, [_vp] + [C.POINTER(C.c_uint64)] * 6 + [_i32]),
+    "af_output_writer_read_meters": (C.c_int, [_vp, _fp, _fp, _fp, _fp, C.POINTER(_i64), C.POINTER(_i64), C.POINTER(_i64), _i32]),
+    "af_output_writer_read_state": (C.c_int, [_vp, _fp, _fp, C.POINTER(_i32), _fp, _i32]),
+    "af_output_writer_last_kernel_ms": (C.c_int, [_vp, _dp]),
+    "af_output_writer_last_pass_ms": (C.c_int, [_vp, _dp]),
+    "af_engine_set_output_writer": (C.c_int, [_vp, _i32]),
+    "af_engine_set_output_queue_fill": (C.c_int, [_vp, C.POINTER(_i64), _i32]),
+    "af_engine_read_output_written": (C.c_int, [_vp, C.POINTER(_i64), _i32]),
+    "af_engine_read_output_counters": (C.c_int, [_vp] + [C.POINTER(C.c_uint64)] * 6 + [_i32]),
+    "af_engine_read_output_meters": (C.c_int, [_vp, _fp, _fp, _fp, _fp, C.POINTER(_i64), C.POINTER(_i64), C.POINTER(_i64), _i32]),
     "af_engine_set_input_channels": (C.c_int, [_vp, _i32, _i32]),
     "af_engine_set_input_channel_mode": (C.c_int, [_vp, _i32]),
     "af_engine_read_input_phase": (C.c_int, [_vp, _fp, C.POINTER(C.c_uint64), C.POINTER(_i32), _fp, C.POINTER(_i32), _i32]),
@@ -255,6 +273,7 @@ VALUE_FUNCTIONS = {
     "af_stream_resampler_destroy", "af_stream_resampler_output_frames", "af_stream_resampler_pending_input",
     "af_stream_resampler_output_delay", "af_stream_resampler_frames_in", "af_stream_resampler_frames_out",
     "af_mixdown_destroy", "af_mixdown_mode", "af_mixdown_channels",
+    "af_output_writer_destroy", "af_output_writer_max_output_frames",
 }
 
 _lib = None

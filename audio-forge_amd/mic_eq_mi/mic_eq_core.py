@@ -186,6 +186,33 @@ class Engine:
         """The capture callback's phase diagnostics, arrays per stream: as ``Mixdown.diagnostics``."""
         return _read_phase(self._lib.af_engine_read_input_phase, self._h, self.n_streams)
 
+    def set_output_writer(self, enabled: bool) -> None:
+        """The output writer behind the chain / output resampler (a configuration setter): every ``stream`` call then ends
+        with one write_chunk per stream (output_writer.rs:62-110) and returns ragged rows, zero beyond ``output_written()``."""
+        _lib.check(self._lib.af_engine_set_output_writer(self._h, int(bool(enabled))))
+
+    def set_output_queue_fill(self, fill) -> None:
+        """Frames in each stream's playback queue, used from the next ``stream`` call on (until then: the target centre)."""
+        f = np.asarray(fill)
+        if f.shape != (self.n_streams,) or not np.issubdtype(f.dtype, np.integer):
+            raise ValueError(f"fill must be {self.n_streams} integers (frames in each stream's queue)")
+        f = np.ascontiguousarray(f, dtype=np.int64)
+        _lib.check(self._lib.af_engine_set_output_queue_fill(self._h, f.ctypes.data_as(C.POINTER(C.c_int64)), self.n_streams))
+
+    def output_written(self) -> np.ndarray:
+        """Frames of each row of the last ``stream`` call that reached the queue."""
+        w = np.zeros(self.n_streams, dtype=np.int64)
+        _lib.check(self._lib.af_engine_read_output_written(self._h, w.ctypes.data_as(C.POINTER(C.c_int64)), self.n_streams))
+        return w
+
+    def output_counters(self) -> dict:
+        """As ``OutputWriter.counters``."""
+        return _read_writer_counters(self._lib.af_engine_read_output_counters, self._h, self.n_streams)
+
+    def output_meters(self) -> dict:
+        """As ``OutputWriter.meters``."""
+        return _read_writer_meters(self._lib.af_engine_read_output_meters, self._h, self.n_streams)
+
     def io_resampler_delay(self) -> tuple[int, int]:
         """(input side, output side) ``output_delay()`` in frames, 0 for a side that does not resample."""
         a, b = C.c_int32(0), C.c_int32(0)
@@ -1293,6 +1320,151 @@ class Mixdown:
         a, b = C.c_double(0.0), C.c_double(0.0)
         _lib.check(self._lib.af_mixdown_last_kernel_ms(self._h, C.byref(a), C.byref(b)))
         return a.value, b.value
+
+
+class OutputWriterConfig(C.Structure):
+    """af_output_writer_config: the limits of output_writer.rs:20-27 and the queue's capacity."""
+    _fields_ = [("output_rate", C.c_int32), ("queue_capacity", C.c_int64), ("target_center", C.c_int64),
+                ("hard_backlog", C.c_int64), ("fade_frames", C.c_int64)]
+
+
+OUTPUT_WRITER_COUNTERS = ("jitter_dropped", "retime_adjustments", "recovery_events", "short_write_dropped", "clip_events",
+                          "true_peak_events")  # output_writer.rs:2-5, 10, 12
+OUTPUT_WRITER_DB = ("clip_peak_db", "true_peak_db", "true_peak_input_db", "gain_reduction_db", "gain_reduction_history_db",
+                    "headroom_db")  # output_writer.rs:11-17
+OUTPUT_WRITER_LINEAR = ("input_true_peak", "limiter_output_true_peak", "detector_true_peak", "min_gain", "max_clipped")
+
+
+def _read_writer_counters(fn, handle, n: int) -> dict:
+    rows = np.zeros((6, n), dtype=np.uint64)
+    up = C.POINTER(C.c_uint64)
+    _lib.check(fn(handle, *[rows[k].ctypes.data_as(up) for k in range(6)], n))
+    return dict(zip(OUTPUT_WRITER_COUNTERS, rows))
+
+
+def _read_writer_meters(fn, handle, n: int) -> dict:
+    db, lin = np.zeros((6, n), dtype=np.float32), np.zeros((5, n), dtype=np.float32)
+    ratio, ema = np.zeros(n, dtype=np.float32), np.zeros(n, dtype=np.float32)
+    out_len, fade, fill = (np.zeros(n, dtype=np.int64) for _ in range(3))
+    fp, lp = C.POINTER(C.c_float), C.POINTER(C.c_int64)
+    _lib.check(fn(handle, db.ctypes.data_as(fp), lin.ctypes.data_as(fp), ratio.ctypes.data_as(fp), ema.ctypes.data_as(fp),
+                  out_len.ctypes.data_as(lp), fade.ctypes.data_as(lp), fill.ctypes.data_as(lp), n))
+    m = dict(zip(OUTPUT_WRITER_DB, db))
+    m.update(zip(OUTPUT_WRITER_LINEAR, lin))
+    m.update(ratio=ratio, ema=ema, out_len=out_len, fade_remaining=fade, fill_after=fill)
+    return m
+
+
+def output_writer_default_config(output_rate: int) -> dict:
+    """The limits dsp_loop.rs:781-795 derives from the output rate, and the queue capacity of :204."""
+    cfg = OutputWriterConfig()
+    _lib.check(_lib.load().af_output_writer_default_config(int(output_rate), C.byref(cfg)))
+    return {name: int(getattr(cfg, name)) for name, _ in OutputWriterConfig._fields_}
+
+
+class OutputWriter:
+    """The output writer (output_writer.rs:62-343) for `n_streams` streams: drift retime, discontinuity fade, safety
+    limiter and the queue write's accounting, bit-exact with the reference's f32 arithmetic.  A push is one write_chunk
+    per stream; the caller reports each stream's queue fill and gets ragged rows back."""
+
+    def __init__(self, output_rate: int = 48_000, n_streams: int = 1, device: int = 0, queue_capacity: int | None = None,
+                 target_center: int | None = None, hard_backlog: int | None = None, fade_frames: int | None = None):
+        self._lib = _lib.load()
+        cfg = OutputWriterConfig()
+        _lib.check(self._lib.af_output_writer_default_config(int(output_rate), C.byref(cfg)))
+        for name, value in (("queue_capacity", queue_capacity), ("target_center", target_center), ("hard_backlog", hard_backlog),
+                            ("fade_frames", fade_frames)):
+            if value is not None:
+                setattr(cfg, name, int(value))
+        handle = C.c_void_p()
+        _lib.check(self._lib.af_output_writer_create(C.byref(cfg), int(n_streams), int(device), C.byref(handle)))
+        self._h = handle
+        self.n_streams = int(n_streams)
+        self.config = {name: int(getattr(cfg, name)) for name, _ in OutputWriterConfig._fields_}
+
+    def close(self) -> None:
+        if getattr(self, "_h", None):
+            self._lib.af_output_writer_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def set_limiter(self, enabled: bool, ceiling_linear: float = 1.0) -> None:
+        """Live, read at each push (output_writer.rs:208-215)."""
+        _lib.check(self._lib.af_output_writer_set_limiter(self._h, int(bool(enabled)), float(ceiling_linear)))
+
+    def reset(self) -> None:
+        _lib.check(self._lib.af_output_writer_reset(self._h))
+
+    def max_output_frames(self, n_in: int) -> int:
+        return int(self._lib.af_output_writer_max_output_frames(self._h, int(n_in)))
+
+    def _fill(self, fill) -> np.ndarray:
+        f = np.ascontiguousarray(np.broadcast_to(np.asarray(fill), (self.n_streams,)) if np.ndim(fill) == 0 else fill)
+        if f.shape != (self.n_streams,) or not np.issubdtype(f.dtype, np.integer):
+            raise ValueError(f"fill must be {self.n_streams} integers (frames in each stream's queue)")
+        return np.ascontiguousarray(f, dtype=np.int64)
+
+    def push(self, x: np.ndarray, fill, clean_path: bool = False) -> tuple[np.ndarray, np.ndarray]:
+        """float32 [n_streams, n] (or [n] for one stream) and fill[n_streams] -> (rows [n_streams, max_output_frames(n)],
+        written[n_streams]): row s holds written[s] frames and zeros behind them."""
+        a = np.ascontiguousarray(x, dtype=np.float32)
+        if a.ndim == 1 and self.n_streams == 1:
+            a = a.reshape(1, -1)
+        if a.ndim != 2 or a.shape[0] != self.n_streams:
+            raise ValueError(f"expected [{self.n_streams}, frames] samples, got shape {a.shape}")
+        f = self._fill(fill)
+        n = a.shape[1]
+        width = max(self.max_output_frames(n), 1)
+        out = np.zeros((self.n_streams, width), dtype=np.float32)
+        written = np.zeros(self.n_streams, dtype=np.int64)
+        fp, lp = C.POINTER(C.c_float), C.POINTER(C.c_int64)
+        _lib.check(self._lib.af_output_writer_push_host(self._h, a.ctypes.data_as(fp), n, n, f.ctypes.data_as(lp),
+                                                        int(bool(clean_path)), out.ctypes.data_as(fp), width, width,
+                                                        written.ctypes.data_as(lp)))
+        return out, written
+
+    def push_device(self, in_ptr: int, n_in: int, in_stride: int, fill_ptr: int, clean_path: bool, out_ptr: int,
+                    out_capacity: int, out_stride: int, written_ptr: int, hip_stream: int = 0) -> None:
+        """Device pointers (fill and written are int64 arrays), asynchronous on ``hip_stream``."""
+        _lib.check(self._lib.af_output_writer_push_device(self._h, C.c_void_p(in_ptr), int(n_in), int(in_stride), C.c_void_p(fill_ptr),
+                                                          int(bool(clean_path)), C.c_void_p(out_ptr), int(out_capacity),
+                                                          int(out_stride), C.c_void_p(written_ptr), C.c_void_p(hip_stream)))
+
+    def counters(self) -> dict:
+        """Arrays per stream of the running counts (OUTPUT_WRITER_COUNTERS)."""
+        return _read_writer_counters(self._lib.af_output_writer_read_counters, self._h, self.n_streams)
+
+    def meters(self) -> dict:
+        """Arrays per stream: the dB fields (OUTPUT_WRITER_DB), the last push's linear statistics (OUTPUT_WRITER_LINEAR), its
+        ratio, the drift EMA, out_len, fade_remaining and the modelled fill after the write."""
+        return _read_writer_meters(self._lib.af_output_writer_read_meters, self._h, self.n_streams)
+
+    def state(self) -> dict:
+        """Test read-out: the limiter's gain [n], delay line [n, 20] and write index [n], the histories [n, 3, 32]."""
+        n = self.n_streams
+        gain, delay = np.zeros(n, dtype=np.float32), np.zeros((n, 20), dtype=np.float32)
+        widx, hist = np.zeros(n, dtype=np.int32), np.zeros((n, 3, 32), dtype=np.float32)
+        fp = C.POINTER(C.c_float)
+        _lib.check(self._lib.af_output_writer_read_state(self._h, gain.ctypes.data_as(fp), delay.ctypes.data_as(fp),
+                                                         widx.ctypes.data_as(C.POINTER(C.c_int32)), hist.ctypes.data_as(fp), n))
+        return dict(gain=gain, delay=delay, write_idx=widx, histories=hist)
+
+    def last_kernel_ms(self) -> float:
+        """All passes of the last push, from HIP events."""
+        ms = C.c_double(0.0)
+        _lib.check(self._lib.af_output_writer_last_kernel_ms(self._h, C.byref(ms)))
+        return ms.value
+
+    def last_pass_ms(self) -> list[float]:
+        """(plan, shape, gain, out, finish) of the last push, from HIP events; gain is 0 with the limiter off."""
+        ms = (C.c_double * 5)()
+        _lib.check(self._lib.af_output_writer_last_pass_ms(self._h, ms))
+        return list(ms)
 
 
 def simulate_product_resampler_batch(samples: np.ndarray, input_rate: int, output_rate: int,

@@ -493,6 +493,102 @@ int af_mixdown_reset(af_mixdown *m);
 /* HIP-event times of the last push, summed over its chunks: the decision passes and the mix passes */
 int af_mixdown_last_kernel_ms(af_mixdown *m, double *decision_ms, double *mix_ms);
 
+/* ---- output writer: drift retime, discontinuity fade, safety limiter, queue accounting per stream ------------------
+ * What the reference does to every block between the chain / output resampler and the playback queue
+ * (rust-core/src/audio/processor/output_writer.rs:62-110, OutputWriteContext::write_chunk): the jitter-buffer retime
+ * (:112-159 over resampling.rs:81-120), the fade after a short write (:161-192), scrub + a second TruePeakLimiter at the
+ * device rate + ceiling clamp with clip metrics + a TruePeakDetector (:194-288, routing.rs:651-655, 697-703, 768-799) and
+ * the queue write's accounting (:290-343).  An af_output_writer is that for `n_streams` independent streams.  The queue
+ * itself is the caller's: each push is told how many frames every stream's queue holds (`fill`, capacity - free_len at
+ * :67-69) and answers with how many frames of the row reach it (`written`, min(pending, free)).  The output is ragged:
+ * stream s yields written[s] frames.  Audio, decisions, counters and linear statistics are bit-exact with the reference's
+ * f32 arithmetic; the dB fields are 20 log10f of such values.  Layout: in[s * in_stride + t], out[s * out_stride + t]. */
+typedef struct af_output_writer af_output_writer;
+typedef struct af_output_writer_config {
+  int32_t output_rate;      /* the limiter's rate: TruePeakLimiter::default_settings(output_rate), dsp_loop.rs:798-799 */
+  int64_t queue_capacity;   /* frames the queue holds, dsp_loop.rs:204 */
+  int64_t target_center;    /* OutputWriteLimits::output_target_center_samples, output_writer.rs:22 */
+  int64_t hard_backlog;     /* ... output_hard_backlog_samples, :23 */
+  int64_t fade_frames;      /* ... discontinuity_fade_samples, :24 */
+} af_output_writer_config;
+/* dsp_loop.rs:781-795 from the output rate: capacity 2 * rate (:204), centre div_ceil(30 ms + 40 ms, 2), hard backlog
+ * 60 ms, fade max(6 ms, 1), each through duration_samples (resampling.rs:1-3).  The ratios are the reference's constants
+ * (1.03 and 1.06, dsp_loop.rs:790-791; 0.008 and 0.96, processor.rs:69-70). */
+int af_output_writer_default_config(int32_t output_rate, af_output_writer_config *cfg);
+/* Everything is validated before any HIP call: rate > 0, capacity >= 1 and below 2^31, centre / backlog >= 0 and below
+ * 2^31, fade 1 .. 2^31 - 1, 0 < n_streams <= 65535.  The limiter starts enabled with ceiling 1.0.  No GPU work happens
+ * until the first push. */
+int af_output_writer_create(const af_output_writer_config *cfg, int32_t n_streams, int32_t device, af_output_writer **out);
+void af_output_writer_destroy(af_output_writer *w);
+/* limiter_enabled and output_ceiling_linear are live: read at each push (output_writer.rs:208-215).  Disabled, the ceiling
+ * is 1.0, the limiter is reset by every push, the gain-reduction field is 0 and its history decays by 0.15 (:219-227). */
+int af_output_writer_set_limiter(af_output_writer *w, int32_t enabled, float ceiling_linear);
+/* fresh EMA, fade, limiter, detector, counters and dB fields, as the loop builds them (dsp_loop.rs:796-802) */
+int af_output_writer_reset(af_output_writer *w);
+/* the longest row a push of n_in frames can yield: n_in on the clean path, round(n_in / 0.96) capped by the queue capacity
+ * and the reference's 8672-frame scratch on the retimed one (resampling.rs:92-94).  VALUE; 0 for a null writer or n_in < 1 */
+int64_t af_output_writer_max_output_frames(const af_output_writer *w, int64_t n_in);
+/* One write_chunk per stream on host pointers; synchronises.  fill[s]: frames in stream s's queue at the call.  Row s of
+ * `out` gets written[s] frames; the rest of the row is left untouched.  clean_path (the raw-monitor route,
+ * routing.rs:691-694) skips the retime and the fade, not the safety step.  Validated before anything is touched: n_in == 0
+ * is a no-op (the reference returns false, :63-65) that zeroes `written`; n_in > 8192, out_capacity or out_stride below
+ * af_output_writer_max_output_frames(w, n_in), in_stride < n_in, or any fill[s] outside 0 .. capacity is
+ * AF_ERR_INVALID_ARGUMENT.  DEVIATION: the reference's 8672-frame scratches truncate a longer block and raise
+ * FixedBufferOverflow (:174-177, 204-207); here such a call is refused with nothing touched.  Non-finite input is
+ * accepted: scrubbing it is this stage's job (:213). */
+int af_output_writer_push_host(af_output_writer *w, const float *in, int64_t n_in, int64_t in_stride, const int64_t *fill,
+                               int32_t clean_path, float *out, int64_t out_capacity, int64_t out_stride, int64_t *written);
+/* The same with device pointers (fill and written too), asynchronous on `hip_stream` (a hipStream_t, NULL = default
+ * stream): four or five launches whatever the data, no host wait.  Successive pushes must be ordered by the caller.  A
+ * fill outside 0 .. capacity cannot be seen from the host: it is clamped on the device.  The first push allocates the writer's
+ * scratch rows for the longest block (8192 frames in); no later push allocates or waits. */
+int af_output_writer_push_device(af_output_writer *w, const float *d_in, int64_t n_in, int64_t in_stride, const int64_t *d_fill,
+                                 int32_t clean_path, float *d_out, int64_t out_capacity, int64_t out_stride, int64_t *d_written,
+                                 void *hip_stream);
+/* OutputWriteCounters' running counts (output_writer.rs:2-5, 10, 12), one entry per stream, any pointer may be null.
+ * Waits for the device. */
+int af_output_writer_read_counters(af_output_writer *w, uint64_t *jitter_dropped, uint64_t *retime_adjustments,
+                                   uint64_t *recovery_events, uint64_t *short_write_dropped, uint64_t *clip_events,
+                                   uint64_t *true_peak_events, int32_t n_streams);
+/* db: [6][n_streams], the atomics of output_writer.rs:11-17 in that order (clip peak, true peak, true-peak input, gain
+ * reduction, gain-reduction history, headroom).  linear: [5][n_streams], the last push's input true peak, limiter output
+ * true peak, detector true peak, minimum gain and maximum clipped amplitude.  Then the last push's ratio, the drift EMA,
+ * out_len, the fade frames remaining and the modelled fill after the write (:333-343).  Any pointer may be null. */
+int af_output_writer_read_meters(af_output_writer *w, float *db, float *linear, float *ratio, float *drift_ema, int64_t *out_len,
+                                 int64_t *fade_remaining, int64_t *fill_after, int32_t n_streams);
+/* test read-out of the limiter and detector state (true_peak.rs:250-263, 190-193): gain [n], the delay line [n][20] as the
+ * reference indexes it, its write index [n], and the histories [n][3][32] (limiter input, limiter output, detector) */
+int af_output_writer_read_state(af_output_writer *w, float *gain, float *delay, int32_t *write_idx, float *histories,
+                                int32_t n_streams);
+/* HIP-event time of the last push, all passes */
+int af_output_writer_last_kernel_ms(af_output_writer *w, double *ms);
+/* ... and of each pass: pass_ms[5] = plan, shape, gain (0 with the limiter off), out, finish */
+int af_output_writer_last_pass_ms(af_output_writer *w, double *pass_ms);
+
+/* ---- the output writer of an engine: dsp_loop.rs:781-895 ---------------------------------------------------------------
+ * af_engine_set_output_writer: a configuration setter (AF_ERR_STATE after streaming started).  Enabled, every
+ *   af_engine_stream_host call ends with one write_chunk per stream (output_writer.rs:62-110) on the device, behind the output
+ *   resampler if one is set (then at the I/O output rate, otherwise at the engine's; limits as af_output_writer_default_config).
+ *   limiter_enabled and the ceiling are the engine's limiter's, 10^(ceiling_db / 20) in f32 (dsp_loop.rs:535,
+ *   output_writer.rs:208-215).  *n_out is the largest written[s]; rows are zero beyond their own length;
+ *   af_engine_stream_plan's n_out becomes af_output_writer_max_output_frames of what it reported before, and out_stride must
+ *   cover it.  A call whose output side exceeds 8192 frames is refused with everything untouched.  af_engine_process_host /
+ *   _device return AF_ERR_UNSUPPORTED.  af_engine_reset resets the writer and drops the fill.  Disabled (the default), every
+ *   call takes the branch it took before.
+ * af_engine_set_output_queue_fill: fill[s] frames are in stream s's playback queue (capacity - free_len, output_writer.rs:67-69);
+ *   used by every af_engine_stream_host from the next one until it is set again.  Until it is first set the fill is the target
+ *   centre (no error, ratio 1).  0 .. capacity, AF_ERR_STATE with the writer off.
+ * af_engine_read_output_written: written[s] of the last af_engine_stream_host.
+ * af_engine_read_output_counters / _meters: as af_output_writer_read_counters / _meters. */
+int af_engine_set_output_writer(af_engine *e, int32_t enabled);
+int af_engine_set_output_queue_fill(af_engine *e, const int64_t *fill, int32_t n_streams);
+int af_engine_read_output_written(af_engine *e, int64_t *written, int32_t n_streams);
+int af_engine_read_output_counters(af_engine *e, uint64_t *jitter_dropped, uint64_t *retime_adjustments, uint64_t *recovery_events,
+                                   uint64_t *short_write_dropped, uint64_t *clip_events, uint64_t *true_peak_events,
+                                   int32_t n_streams);
+int af_engine_read_output_meters(af_engine *e, float *db, float *linear, float *ratio, float *drift_ema, int64_t *out_len,
+                                 int64_t *fade_remaining, int64_t *fill_after, int32_t n_streams);
+
 /* ---- multichannel input of an engine: input.rs:785-843 ----------------------------------------------------------
  * af_engine_set_input_channels: a configuration setter (AF_ERR_STATE after streaming started), arguments as
  *   af_mixdown_create.  One channel means the feature is off and every call behaves as without this setter.  With more,
