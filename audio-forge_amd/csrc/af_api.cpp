@@ -19,6 +19,7 @@
 #include "af_mixdown_host.hpp"
 #include "af_output_writer_host.hpp"
 #include "af_resampler_host.hpp"
+#include "af_retune.h"
 #include "af_stages.h"
 #include "af_suppressor_host.hpp"
 
@@ -279,6 +280,19 @@ struct af_engine {
   int64_t ow_out_capacity = 0;        // bytes
   int64_t ow_target_center = 0, ow_capacity = 0;
   bool ow_fill_dirty = true;          // the device copy of ow_fill is stale
+  // Live control (af_engine_set_live_control): with the switch on the chain setters are accepted after streaming started.  A
+  // setter then edits the prototype and this preset's parameter block (the next call uploads what changed, as it does while a
+  // crossfade advances) and records what the reference setter does to the running object's STATE as edits of state-plane rows;
+  // the next call that runs the chain applies the list with one launch of retune_state_kernel ahead of everything else.
+  bool live_control = false;
+  std::vector<af::RetuneOp> retune_ops;
+  std::vector<char> live_retuned;     // per preset: a live setter was accepted since the last reset (the prototype follows the device)
+  std::vector<char> live_cuts;        // per preset: ... one that moved the de-esser's cut frequencies (DeEsserParams::dyn_pending_row is in force)
+  int dyn_pending_row = 0;            // first of the 15 plane rows behind every kernel's own (allocated with live control on), or 0
+  af::ChainParams *d_retune = nullptr;  // the op list on the device, in parameter-block units (it travels through stage_upload)
+  int64_t retune_capacity = 0;        // bytes
+  hipEvent_t ev_retune0 = nullptr, ev_retune1 = nullptr;
+  bool retune_timed = false;          // the last call launched the retune kernel between the two events
 
   af_engine(double fs, int n, int dev) : proto(fs), n_streams(n), device(dev), sample_rate(fs) {}
 };
@@ -287,8 +301,12 @@ namespace {
 
 int require_config(af_engine *e) {
   if (!e) return fail(AF_ERR_INVALID_ARGUMENT, "engine is null");
-  if (e->started)
+  if (e->started) {
+    if (e->live_control)
+      return fail(AF_ERR_STATE, "configuration setter called after streaming started: it changes which kernels, stages or buffers are "
+                                "resident and is out of scope of live control; call af_engine_reset first");
     return fail(AF_ERR_STATE, "setter called after streaming started; call af_engine_reset first");
+  }
   e->params_dirty = true;
   return AF_OK;
 }
@@ -416,6 +434,13 @@ int upload_initial_state(af_engine *e) {
     const int meter_slots = (p.compressor_enabled && p.compressor.auto_makeup_enabled) ? hp.comp.meter_slots : 0;
     n64 = std::max(n64, af::f64_field_count(hp.n_eq_sections, meter_slots));
     n32 = std::max(n32, af::f32_field_count(p.limiter.lookahead_samples));
+  }
+  // live control: 3 x 5 more rows for each stream's pending dynamic-EQ coefficients (af_device.h, dyn_pending_row), behind
+  // every row a kernel addresses by itself
+  e->dyn_pending_row = 0;
+  if (e->live_control) {
+    e->dyn_pending_row = n64;
+    n64 += 15;
   }
   if (e->d_st64 && (n64 != e->n_f64 || n32 != e->n_f32)) {
     AF_HIP(hipFree(e->d_st64));
@@ -588,6 +613,145 @@ void advance_crossfades(af_engine *e, int64_t n) {
     }
   }
  }
+}
+
+// ---- live control ---------------------------------------------------------------------------------------------------
+// Which mode a LIVE setter runs in: configuration (as require_config), live, or refused exactly as before the switch existed.
+int setter_mode(af_engine *e, bool *live) {
+  *live = false;
+  if (!e) return fail(AF_ERR_INVALID_ARGUMENT, "engine is null");
+  if (e->started) {
+    if (!e->live_control) return fail(AF_ERR_STATE, "setter called after streaming started; call af_engine_reset first");
+    *live = true;
+    return AF_OK;
+  }
+  e->params_dirty = true;
+  return AF_OK;
+}
+
+// The prototype of the selected preset takes over what moved on the device side since the start: the sections' active /
+// pending coefficients and crossfade counters (advance_crossfades keeps them in the parameter block).  A reference setter
+// applied to it afterwards then acts on the running filter: schedule() keeps `active` and restarts the counter.
+void live_sync_proto(af_engine *e) {
+  const int k = e->current_preset;
+  e->live_retuned.resize(1 + e->extra_presets.size(), 0);
+  e->live_retuned[(size_t)k] = 1;
+  af::ChainProto &p = cur(e);
+  const af::ChainParams &o = preset_params(e, k);
+  auto take = [](af::BiquadProto &b, const af::SectionParams &sp) {
+    b.active = sp.active;
+    b.pending = sp.pending;
+    b.xf_total = sp.xf_total;
+    b.xf_remaining = sp.xf_remaining;
+  };
+  int n = 0;
+  for (int b = 0; b < af::kNumBands; ++b)
+    for (int sct = 0; sct < p.eq.bands[b].processing_sections; ++sct) take(p.eq.bands[b].sections[sct], o.eq[n++]);
+  for (int i = 0; i < 3; ++i) {
+    take(p.deesser.bands[i].detector_hp, o.deesser.bands[i].detector_hp);
+    take(p.deesser.bands[i].detector_lp, o.deesser.bands[i].detector_lp);
+    take(p.deesser.bands[i].dynamic_eq, o.deesser.bands[i].dynamic_eq);
+  }
+}
+
+// Record one state edit for the selected preset.  An earlier edit of the same row that nothing read since is superseded, so
+// the list stays as short as the set of rows the setters touch however often they are called between two calls.
+void live_op(af_engine *e, int32_t kind, int dst, int src, double value, double value2 = 0.0) {
+  const int32_t preset = e->current_preset;
+  auto &ops = e->retune_ops;
+  for (size_t i = ops.size(); i-- > 0;) {
+    if (ops[i].preset != preset) continue;
+    if (ops[i].kind != af::kRetuneSet && ops[i].src == dst) break;  // read since: everything before it stays
+    if (ops[i].dst == dst) {
+      ops.erase(ops.begin() + (std::ptrdiff_t)i);
+      break;
+    }
+  }
+  ops.push_back(af::RetuneOp{kind, preset, dst, kind == af::kRetuneSet ? 0 : src, value, value2});
+}
+void live_set(af_engine *e, int row, double v) { live_op(e, af::kRetuneSet, row, 0, v); }
+void live_copy(af_engine *e, int dst, int src) { live_op(e, af::kRetuneCopy, dst, src, 0.0); }
+// Biquad::schedule_coefficients_crossfade, biquad.rs:256-257: the pending path starts from the live memories (rows z1 z2 pz1 pz2)
+void live_restart_section(af_engine *e, int z_row) {
+  live_copy(e, z_row + 2, z_row);
+  live_copy(e, z_row + 3, z_row + 1);
+}
+// Compressor::reset_adaptive_release_state, compressor.rs:288-291
+void live_reset_release_envelopes(af_engine *e) {
+  live_copy(e, af::kCompFastEnv, af::kCompGr);
+  live_set(e, af::kCompSlowEnv, 0.0);
+}
+// current_release_ms / target_release_ms / release_coeff as a setter leaves them with adaptive release off (compressor.rs:238-242)
+void live_set_release(af_engine *e, const af::CompressorProto &c) {
+  live_set(e, af::kCompCurReleaseMs, c.current_release_ms);
+  live_set(e, af::kCompTargetReleaseMs, c.target_release_ms);
+  live_set(e, af::kCompReleaseCoeff, c.release_coeff);
+}
+
+// the selected preset's parameter block follows its prototype (the next call uploads it if it changed)
+int live_commit(af_engine *e) {
+  af::ChainParams &o = preset_params(e, e->current_preset);
+  const int n_before = o.n_eq_sections;
+  export_params(e, cur(e), o);
+  if ((size_t)e->current_preset < e->live_cuts.size() && e->live_cuts[(size_t)e->current_preset]) o.deesser.dyn_pending_row = e->dyn_pending_row;
+  if (o.n_eq_sections != n_before) return fail(AF_ERR_BACKEND, "internal: a live setter changed the EQ's section count");
+  return AF_OK;
+}
+
+// A live change of one EQ band (eq.rs:279-298 on the running band): checked first, then the prototype, the parameter block
+// and the edit list.  `c` is the band's whole new configuration.
+int live_eq_set_band(af_engine *e, int band, const af::EqBandConfig &c) {
+  if (c.filter_type < 0 || c.filter_type > 5)
+    return fail(AF_ERR_INVALID_ARGUMENT, "band %d has unsupported EQ filter type id: %d", band, c.filter_type);
+  const std::string msg = af::eq_validate(c, band, cur(e).sample_rate);
+  if (!msg.empty()) return fail(AF_ERR_INVALID_ARGUMENT, "%s", msg.c_str());
+  const af::EqProto &eq = cur(e).eq;
+  if (af::EqBandProto::required_sections(c) > eq.bands[band].processing_sections)
+    return fail(AF_ERR_UNSUPPORTED, "band %d would need %d biquad sections and holds %d: the per-stream state planes are sized when "
+                                    "streaming starts; call af_engine_reset first",
+                band, af::EqBandProto::required_sections(c), eq.bands[band].processing_sections);
+  live_sync_proto(e);
+  int first = 0;
+  for (int b = 0; b < band; ++b) first += eq.bands[b].processing_sections;
+  cur(e).eq.set_band_config(band, c);
+  for (int sct = 0; sct < eq.bands[band].processing_sections; ++sct) live_restart_section(e, af::kEqBase + 4 * (first + sct));
+  return live_commit(e);
+}
+
+// The edits recorded since the last call, in one launch on the call's stream: behind the previous call's work, ahead of this
+// call's first parameter upload and kernel.  Nothing pending: nothing launched.
+int launch_pending_retune(af_engine *e, hipStream_t stream) {
+  e->retune_timed = false;
+  if (e->retune_ops.empty()) return AF_OK;
+  const size_t bytes = e->retune_ops.size() * sizeof(af::RetuneOp);
+  const size_t blocks = (bytes + sizeof(af::ChainParams) - 1) / sizeof(af::ChainParams);
+  if (int rc = grow_device(e, reinterpret_cast<void **>(&e->d_retune), &e->retune_capacity, (int64_t)(blocks * sizeof(af::ChainParams)), stream))
+    return rc;
+  std::vector<af::ChainParams> carrier(blocks);  // (the pinned stager moves parameter blocks: the list rides in as many as it fills)
+  std::memcpy(carrier.data(), e->retune_ops.data(), bytes);
+  if (int rc = stage_upload(e, e->d_retune, carrier.data(), blocks, stream)) return rc;
+  af::RetuneArgs ra{};
+  ra.ops = reinterpret_cast<const af::RetuneOp *>(e->d_retune);
+  ra.group_preset = e->extra_presets.empty() ? nullptr : e->d_group_preset;
+  ra.st64 = e->d_st64;
+  ra.n_ops = (int32_t)e->retune_ops.size();
+  ra.n_streams = e->n_streams;
+  ra.n_fields = e->n_f64;
+  if (e->timing) {
+    if (!e->ev_retune0) {
+      AF_HIP(hipEventCreate(&e->ev_retune0));
+      AF_HIP(hipEventCreate(&e->ev_retune1));
+    }
+    AF_HIP(hipEventRecord(e->ev_retune0, stream));
+  }
+  AF_HIP(af::launch_retune_state(ra, stream));
+  if (e->timing) {
+    AF_HIP(hipEventRecord(e->ev_retune1, stream));
+    e->retune_timed = true;
+  }
+  e->last_launches += 1;
+  e->retune_ops.clear();
+  return AF_OK;
 }
 
 // The gate's parameters and state pointer on a pre-pass launch (gate.rs:158-225 for the derived constants).
@@ -1485,6 +1649,9 @@ void af_engine_destroy(af_engine *e) {
     (void)hipFree(e->d_asm);
     (void)hipFree(e->d_trace);
     (void)hipFree(e->d_block_power);
+    (void)hipFree(e->d_retune);
+    if (e->ev_retune0) (void)hipEventDestroy(e->ev_retune0);
+    if (e->ev_retune1) (void)hipEventDestroy(e->ev_retune1);
     if (e->ev_start) (void)hipEventDestroy(e->ev_start);
     if (e->ev_stop) (void)hipEventDestroy(e->ev_stop);
     if (e->ev_mid) (void)hipEventDestroy(e->ev_mid);
@@ -1569,6 +1736,22 @@ int af_engine_reset(af_engine *e) {
   e->pending = 0;
   e->last_output_samples = 0;
   e->trace_frames = 0;
+  // live control: what is pending is dropped; a preset that was retuned live restarts like the reference's reset() -- every
+  // filter from its configured target (Biquad::reset, biquad.rs:341-347), not from wherever a crossfade stood
+  e->retune_ops.clear();
+  e->retune_timed = false;
+  for (size_t k = 0; k < e->live_retuned.size() && k <= e->extra_presets.size(); ++k) {
+    if (!e->live_retuned[k]) continue;
+    af::ChainProto &p = k == 0 ? e->proto : e->extra_presets[k - 1].proto;
+    p.eq.reset();
+    for (auto &b : p.deesser.bands) {
+      b.detector_hp.reset();
+      b.detector_lp.reset();
+      b.dynamic_eq.reset();
+    }
+  }
+  e->live_retuned.clear();
+  e->live_cuts.clear();
   if (e->d_gate) {  // NoiseGate::reset, gate.rs:759-785: every state field back to its initial value
     AF_HIP(hipSetDevice(e->device));
     AF_HIP(hipMemset(e->d_gate, 0, sizeof(int64_t) * af::kGateFields * e->n_streams));
@@ -1591,6 +1774,28 @@ int af_engine_reset(af_engine *e) {
 }
 
 int32_t af_engine_n_streams(const af_engine *e) { return e ? e->n_streams : 0; }
+
+int af_engine_set_live_control(af_engine *e, int32_t enabled) {
+  if (int rc = require_config(e)) return rc;
+  e->live_control = enabled != 0;
+  return AF_OK;
+}
+int af_engine_live_control_pending(const af_engine *e, int32_t *ops) {
+  if (!e) return fail(AF_ERR_INVALID_ARGUMENT, "engine is null");
+  if (ops) *ops = (int32_t)e->retune_ops.size();
+  return AF_OK;
+}
+int af_engine_last_retune_ms(af_engine *e, double *ms) {
+  if (!e || !ms) return fail(AF_ERR_INVALID_ARGUMENT, "null argument");
+  *ms = 0.0;
+  if (!e->timing || !e->retune_timed) return AF_OK;
+  AF_HIP(hipSetDevice(e->device));
+  AF_HIP(hipEventSynchronize(e->ev_retune1));
+  float t = 0.0f;
+  AF_HIP(hipEventElapsedTime(&t, e->ev_retune0, e->ev_retune1));
+  *ms = (double)t;
+  return AF_OK;
+}
 
 #define AF_SETTER(expr)              \
   do {                               \
@@ -1621,22 +1826,51 @@ int af_engine_set_control_block_samples(af_engine *e, int32_t n) {
   AF_SETTER(AF_ALL_PRESETS(p.control_block = n));
 }
 
-int af_eq_set_band_frequency(af_engine *e, int32_t band, double hz) {
-  if (int rc = check_band(band)) return rc;
-  AF_SETTER(cur(e).eq.set_band_frequency(band, hz));
-}
-int af_eq_set_band_gain(af_engine *e, int32_t band, double db) {
-  if (int rc = check_band(band)) return rc;
-  AF_SETTER(cur(e).eq.set_band_gain(band, db));
-}
-int af_eq_set_band_q(af_engine *e, int32_t band, double q) {
-  if (int rc = check_band(band)) return rc;
-  AF_SETTER(cur(e).eq.set_band_q(band, q));
-}
+// A live setter: in configuration mode exactly AF_SETTER; after streaming started with live control on, `apply` acts on the
+// prototype once it has caught up with the device (live_sync_proto), `record` lists the state edits, and the preset's
+// parameter block is re-exported.  `check`: what must hold for the live form, tested before anything is touched.
+#define AF_LIVE_SETTER(check, apply, record)             \
+  do {                                                   \
+    bool live__ = false;                                 \
+    if (int rc__ = setter_mode(e, &live__)) return rc__; \
+    if (live__) {                                        \
+      check;                                             \
+      live_sync_proto(e);                                \
+    }                                                    \
+    apply;                                               \
+    if (live__) {                                        \
+      record;                                            \
+      return live_commit(e);                             \
+    }                                                    \
+    return AF_OK;                                        \
+  } while (0)
+#define AF_LIVE_PARAM_SETTER(apply) AF_LIVE_SETTER((void)0, apply, (void)0)
+
+// the EQ's legacy setters change one field of the band's configuration (eq.rs:406-438)
+#define AF_EQ_LIVE_FIELD(field, value, config_call)                      \
+  do {                                                                   \
+    if (int rc__ = check_band(band)) return rc__;                        \
+    bool live__ = false;                                                 \
+    if (int rc__ = setter_mode(e, &live__)) return rc__;                 \
+    if (live__) {                                                        \
+      af::EqBandConfig c__ = cur(e).eq.bands[band].config;               \
+      c__.field = (value);                                               \
+      return live_eq_set_band(e, band, c__);                             \
+    }                                                                    \
+    config_call;                                                         \
+    return AF_OK;                                                        \
+  } while (0)
+int af_eq_set_band_frequency(af_engine *e, int32_t band, double hz) { AF_EQ_LIVE_FIELD(frequency_hz, hz, cur(e).eq.set_band_frequency(band, hz)); }
+int af_eq_set_band_gain(af_engine *e, int32_t band, double db) { AF_EQ_LIVE_FIELD(gain_db, db, cur(e).eq.set_band_gain(band, db)); }
+int af_eq_set_band_q(af_engine *e, int32_t band, double q) { AF_EQ_LIVE_FIELD(q, q, cur(e).eq.set_band_q(band, q)); }
 int af_eq_set_band_config(af_engine *e, int32_t band, const af_eq_band_config *c) {
   if (int rc = check_band(band)) return rc;
   if (!c) return fail(AF_ERR_INVALID_ARGUMENT, "config is null");
-  AF_SETTER(cur(e).eq.set_band_config(band, to_cfg(*c)));
+  bool live = false;
+  if (int rc = setter_mode(e, &live)) return rc;
+  if (live) return live_eq_set_band(e, band, to_cfg(*c));
+  cur(e).eq.set_band_config(band, to_cfg(*c));
+  return AF_OK;
 }
 int af_eq_reset(af_engine *e) { AF_SETTER(cur(e).eq.reset()); }
 int af_eq_band_config_validate(const af_eq_band_config *c, int32_t index, double sample_rate) {
@@ -1648,18 +1882,50 @@ int af_eq_band_config_validate(const af_eq_band_config *c, int32_t index, double
   return AF_OK;
 }
 
-int af_compressor_set_threshold(af_engine *e, double v) { AF_SETTER(cur(e).compressor.set_threshold(v)); }
-int af_compressor_set_ratio(af_engine *e, double v) { AF_SETTER(cur(e).compressor.set_ratio(v)); }
-int af_compressor_set_attack_time(af_engine *e, double v) { AF_SETTER(cur(e).compressor.set_attack_time(v)); }
-int af_compressor_set_release_time(af_engine *e, double v) { AF_SETTER(cur(e).compressor.set_release_time(v)); }
-int af_compressor_set_makeup_gain(af_engine *e, double v) { AF_SETTER(cur(e).compressor.set_makeup_gain(v)); }
-int af_compressor_set_adaptive_release(af_engine *e, int32_t on) { AF_SETTER(cur(e).compressor.set_adaptive_release(on != 0)); }
-int af_compressor_set_base_release_time(af_engine *e, double v) { AF_SETTER(cur(e).compressor.set_base_release_time(v)); }
+// Live (compressor.rs:210-371 on the running compressor): what each setter edits beyond its parameters is recorded as state edits.
+int af_compressor_set_threshold(af_engine *e, double v) {
+  AF_LIVE_SETTER((void)0, cur(e).compressor.set_threshold(v), live_reset_release_envelopes(e));
+}
+int af_compressor_set_ratio(af_engine *e, double v) { AF_LIVE_PARAM_SETTER(cur(e).compressor.set_ratio(v)); }
+int af_compressor_set_attack_time(af_engine *e, double v) { AF_LIVE_PARAM_SETTER(cur(e).compressor.set_attack_time(v)); }
+int af_compressor_set_release_time(af_engine *e, double v) {
+  AF_LIVE_SETTER((void)0, cur(e).compressor.set_release_time(v),
+                 if (!cur(e).compressor.adaptive_release) live_set_release(e, cur(e).compressor));
+}
+int af_compressor_set_makeup_gain(af_engine *e, double v) {
+  AF_LIVE_SETTER((void)0, cur(e).compressor.set_makeup_gain(v),
+                 if (!cur(e).compressor.auto_makeup_enabled) live_set(e, af::kCompSmoothedMakeup, v));
+}
+// the stage pipeline runs every preset's stages as roles of the same dispatches: its presets take the same code paths
+#define AF_LIVE_SAME_PATHS_CHECK(what)                                                                                            \
+  if (e->pipe.active && !e->extra_presets.empty())                                                                                \
+    return fail(AF_ERR_UNSUPPORTED, what " cannot change live on a multi-preset engine that runs the stage pipeline: every preset " \
+                                         "must take the same code paths; call af_engine_reset first")
+int af_compressor_set_adaptive_release(af_engine *e, int32_t on) {
+  AF_LIVE_SETTER(AF_LIVE_SAME_PATHS_CHECK("adaptive release"), cur(e).compressor.set_adaptive_release(on != 0), {
+    if (!on) live_set_release(e, cur(e).compressor);
+    live_reset_release_envelopes(e);
+  });
+}
+int af_compressor_set_base_release_time(af_engine *e, double v) {
+  AF_LIVE_SETTER((void)0, cur(e).compressor.set_base_release_time(v),
+                 if (!cur(e).compressor.adaptive_release) live_set_release(e, cur(e).compressor));
+}
+// a configuration setter: the token-ring kernel and the stage plan are built per value, and the loudness meter's rows exist only
+// when it was on at the start
 int af_compressor_set_auto_makeup_enabled(af_engine *e, int32_t on) { AF_SETTER(cur(e).compressor.set_auto_makeup_enabled(on != 0)); }
-int af_compressor_set_target_lufs(af_engine *e, double v) { AF_SETTER(cur(e).compressor.set_target_lufs(v)); }
-int af_compressor_set_sidechain_highpass_enabled(af_engine *e, int32_t on) { AF_SETTER(cur(e).compressor.set_sidechain_highpass_enabled(on != 0)); }
+int af_compressor_set_target_lufs(af_engine *e, double v) { AF_LIVE_PARAM_SETTER(cur(e).compressor.set_target_lufs(v)); }
+int af_compressor_set_sidechain_highpass_enabled(af_engine *e, int32_t on) {
+  const bool changes = e && cur(e).compressor.sidechain_highpass_enabled != (on != 0);
+  AF_LIVE_SETTER(if (changes) AF_LIVE_SAME_PATHS_CHECK("the side-chain high-pass"),
+                 cur(e).compressor.set_sidechain_highpass_enabled(on != 0), {
+    if (changes)  // reset_sidechain_highpass_state, compressor.rs:397-404
+      for (int row : {af::kCompScPrevIn, af::kCompScPrevOut, af::kCompLowEnv, af::kCompVoicedEnv, af::kCompPresenceEnv, af::kCompPlosive})
+        live_set(e, row, 0.0);
+  });
+}
 
-int af_compressor_set_noise_reference_reliability(af_engine *e, double v) { AF_SETTER(cur(e).compressor.set_noise_reference_reliability(v)); }
+int af_compressor_set_noise_reference_reliability(af_engine *e, double v) { AF_LIVE_PARAM_SETTER(cur(e).compressor.set_noise_reference_reliability(v)); }
 
 int af_compressor_set_activity_evidence(af_engine *e, const double *vad_probabilities, int64_t n_blocks, int32_t per_stream,
                                         double vad_reliability, double noise_floor_db, double live_noise_reliability) {
@@ -1696,23 +1962,40 @@ int af_compressor_set_activity_evidence(af_engine *e, const double *vad_probabil
   return AF_OK;
 }
 
-int af_limiter_set_ceiling(af_engine *e, double v) { AF_SETTER(cur(e).limiter.set_ceiling(v)); }
-int af_limiter_set_release_time(af_engine *e, double v) { AF_SETTER(cur(e).limiter.set_release_time(v)); }
+int af_limiter_set_ceiling(af_engine *e, double v) { AF_LIVE_PARAM_SETTER(cur(e).limiter.set_ceiling(v)); }  // (limiter.rs:139-152: parameters only)
+int af_limiter_set_release_time(af_engine *e, double v) { AF_LIVE_PARAM_SETTER(cur(e).limiter.set_release_time(v)); }
 int af_limiter_set_lookahead_ms(af_engine *e, double v) { AF_SETTER(cur(e).limiter.set_lookahead_ms(v)); }
 double af_limiter_ceiling_db(const af_engine *e) { return e ? cur(e).limiter.ceiling_db : 0.0; }
 int32_t af_limiter_lookahead_samples(const af_engine *e) { return e ? cur(e).limiter.lookahead_samples : 0; }
 
-int af_true_peak_limiter_set_release_ms(af_engine *e, float ms) { AF_SETTER(cur(e).tp_limiter.set_release_ms(ms)); }
+int af_true_peak_limiter_set_release_ms(af_engine *e, float ms) { AF_LIVE_PARAM_SETTER(cur(e).tp_limiter.set_release_ms(ms)); }
 
-int af_deesser_set_auto_enabled(af_engine *e, int32_t on) { AF_SETTER(cur(e).deesser.auto_enabled = on != 0); }
-int af_deesser_set_auto_amount(af_engine *e, double v) { AF_SETTER(cur(e).deesser.set_auto_amount(v)); }
-int af_deesser_set_low_cut_hz(af_engine *e, double v) { AF_SETTER(cur(e).deesser.set_low_cut_hz(v)); }
-int af_deesser_set_high_cut_hz(af_engine *e, double v) { AF_SETTER(cur(e).deesser.set_high_cut_hz(v)); }
-int af_deesser_set_threshold_db(af_engine *e, double v) { AF_SETTER(cur(e).deesser.set_threshold_db(v)); }
-int af_deesser_set_ratio(af_engine *e, double v) { AF_SETTER(cur(e).deesser.set_ratio(v)); }
-int af_deesser_set_attack_ms(af_engine *e, double v) { AF_SETTER(cur(e).deesser.set_attack_ms(v)); }
-int af_deesser_set_release_ms(af_engine *e, double v) { AF_SETTER(cur(e).deesser.set_release_ms(v)); }
-int af_deesser_set_max_reduction_db(af_engine *e, double v) { AF_SETTER(cur(e).deesser.set_max_reduction_db(v)); }
+// Live: the de-esser's scalar settings are parameters only (deesser.rs:294-353).  Its cut frequencies move nine filters
+// (set_bounds, deesser.rs:64-73): each detector filter and each dynamic EQ gets a crossfade from its live memories, and the
+// dynamic EQ's crossfade runs from the stream's live coefficients to the new centre / Q at the stream's momentary gain --
+// per-stream values, computed on the device into the rows at dyn_pending_row.
+static void live_deesser_bounds(af_engine *e) {
+  e->live_cuts.resize(1 + e->extra_presets.size(), 0);
+  e->live_cuts[(size_t)e->current_preset] = 1;
+  const af::DeEsserParams dp = cur(e).deesser.params();
+  for (int i = 0; i < 3; ++i) {
+    const int base = af::kDeBand0 + i * af::kDeBandStride;
+    for (int z_row : {base + 11, base + 15, base + 19}) live_restart_section(e, z_row);  // detector_hp, detector_lp, dynamic_eq
+    live_set(e, base + 5, 0.0);  // a newly scheduled crossfade is not cancelled
+    live_op(e, af::kRetunePeaking, e->dyn_pending_row + 5 * i, base + 4, dp.bands[i].dyn_cos_omega, dp.bands[i].dyn_alpha);
+  }
+}
+#define AF_DEESSER_CUT_LIVE_CHECK                                                                                              \
+  if (e->dyn_pending_row == 0) return fail(AF_ERR_BACKEND, "internal: live control is on but the pending-coefficient rows are missing")
+int af_deesser_set_auto_enabled(af_engine *e, int32_t on) { AF_LIVE_PARAM_SETTER(cur(e).deesser.auto_enabled = on != 0); }
+int af_deesser_set_auto_amount(af_engine *e, double v) { AF_LIVE_PARAM_SETTER(cur(e).deesser.set_auto_amount(v)); }
+int af_deesser_set_low_cut_hz(af_engine *e, double v) { AF_LIVE_SETTER(AF_DEESSER_CUT_LIVE_CHECK, cur(e).deesser.set_low_cut_hz(v), live_deesser_bounds(e)); }
+int af_deesser_set_high_cut_hz(af_engine *e, double v) { AF_LIVE_SETTER(AF_DEESSER_CUT_LIVE_CHECK, cur(e).deesser.set_high_cut_hz(v), live_deesser_bounds(e)); }
+int af_deesser_set_threshold_db(af_engine *e, double v) { AF_LIVE_PARAM_SETTER(cur(e).deesser.set_threshold_db(v)); }
+int af_deesser_set_ratio(af_engine *e, double v) { AF_LIVE_PARAM_SETTER(cur(e).deesser.set_ratio(v)); }
+int af_deesser_set_attack_ms(af_engine *e, double v) { AF_LIVE_PARAM_SETTER(cur(e).deesser.set_attack_ms(v)); }
+int af_deesser_set_release_ms(af_engine *e, double v) { AF_LIVE_PARAM_SETTER(cur(e).deesser.set_release_ms(v)); }
+int af_deesser_set_max_reduction_db(af_engine *e, double v) { AF_LIVE_PARAM_SETTER(cur(e).deesser.set_max_reduction_db(v)); }
 
 // ---- RNNoise suppressor (rust-core/src/dsp/rnnoise.rs) ----
 int af_engine_set_suppressor_enabled(af_engine *e, int32_t on) { AF_SETTER(e->supp.enabled = on != 0); }
@@ -2154,6 +2437,9 @@ static int process_device_impl(af_engine *e, const float *in, float *out, int64_
   }
   for (auto &pr : e->chain_ms_events) { (void)hipEventDestroy(pr.first); (void)hipEventDestroy(pr.second); }
   e->chain_ms_events.clear();
+  // live control: the state edits of the setters called since the last call that ran the chain (this call's first sample is
+  // the chain's next one); the parameter blocks they changed are uploaded below like any other change
+  if (int rc = launch_pending_retune(e, stream)) return rc;
 
   // ---- The noise gate without the suppressor: the front end and the gate run as the pre-pass (`in` -> `out`, on this stream),
   // and the chain then runs on `out` in place with the front end's flags stripped, as it does behind the suppressor.

@@ -203,8 +203,17 @@ __global__ __launch_bounds__(kLanes) void deesser_lane_kernel(DeEsserArgs a) {
           }
           const int rem = bp.dynamic_eq.xf_remaining > n ? (int)(bp.dynamic_eq.xf_remaining - n) : 0;
           if (rem > 0 && B[i].cancelled == 0.0) {
-            processed = section_sample(bp.dynamic_eq, rem, processed, B[i].eq);
-            if (rem == 1) B[i].dyn = bp.dynamic_eq.pending;
+            if (D.dyn_pending_row != 0) {  // scheduled on the running filter: from the stream's live coefficients to its own target
+              SectionParams sp = bp.dynamic_eq;
+              const double *pc = &a.st64[(int64_t)(D.dyn_pending_row + 5 * i) * NS + sc];
+              sp.active = B[i].dyn;
+              sp.pending = BiquadCoef{pc[0], pc[NS], pc[2 * NS], pc[3 * NS], pc[4 * NS]};
+              processed = section_sample(sp, rem, processed, B[i].eq);
+              if (rem == 1) B[i].dyn = sp.pending;
+            } else {
+              processed = section_sample(bp.dynamic_eq, rem, processed, B[i].eq);
+              if (rem == 1) B[i].dyn = bp.dynamic_eq.pending;
+            }
           } else {
             processed = (float)direct(B[i].dyn, (double)processed, B[i].eq.z1, B[i].eq.z2);
           }

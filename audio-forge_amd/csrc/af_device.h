@@ -82,7 +82,12 @@ struct DeEsserParams {
   double attack_coeff, release_coeff, detector_attack_coeff, detector_release_coeff;
   double max_reduction_db, threshold_db, ratio, auto_amount;
   double baseline_fall, baseline_rise, baseline_inactive;  // tc(13.88 / 34.72 / 20.82 ms), deesser.rs:274-287
-  int32_t auto_enabled, pad;
+  int32_t auto_enabled;
+  // 0, or the first of 15 f64 state-plane rows ([band][b0 b1 b2 a1 a2]) that hold each stream's PENDING dynamic-EQ
+  // coefficients: a crossfade scheduled on a running de-esser targets coefficients that carry the stream's momentary gain
+  // (biquad.rs:350-374 with deesser.rs:536-538), and starts from the stream's live ones.  0: the crossfade was scheduled
+  // before the first sample, every stream's gain is 0 dB and the uniform `dynamic_eq` block is exact.
+  int32_t dyn_pending_row;
   DeEsserBandParams bands[3];
 };
 

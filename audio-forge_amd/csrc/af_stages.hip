@@ -1065,7 +1065,10 @@ __device__ __forceinline__ void stage_f5_body(const StageArgs &a, const float *x
       const int i = wave + 4 * k;
       const int64_t n = abs0 - kTpTaps + i;
       const float o = (float)dclamp((double)delayed[k] * gain[k], -ceil_lin, ceil_lin);
-      const float v = finite_f32(o) ? o : 0.0f;  // TruePeakLimiter input scrub, true_peak.rs:342
+      float v = finite_f32(o) ? o : 0.0f;  // TruePeakLimiter input scrub, true_peak.rs:342
+      // A sample of an earlier window is what that window wrote: the same value while the ceiling stands, and the one clamped
+      // to the ceiling of ITS time when a live setter has moved the ceiling since.
+      if (n < n0) v = a.r.xl[gb32 + eoff(n, w.lane, R32)];
       xl_t[i][w.lane] = v;
       if (n >= n0 && n < n_end && i >= kTpTaps) a.r.xl[gb32 + eoff(n, w.lane, R32)] = v;
     }
@@ -1725,6 +1728,7 @@ template <int kBand>
 __device__ __forceinline__ void stage_de6_body(const StageArgs &a, const ChainParams &PW, int bx) {
   const Who w = who(a, bx);
   const SectionParams sec = PW.deesser.bands[kBand].dynamic_eq;  // the window's own block (crossfade counters as of its first sample)
+  const int pending_row = PW.deesser.dyn_pending_row;
   __builtin_amdgcn_s_setprio(3);
   const int R = a.r.rows_f64, R32 = a.r.rows_f32;
   const int64_t n0 = a.n0, n_end = a.n0 + a.n;
@@ -1772,8 +1776,17 @@ __device__ __forceinline__ void stage_de6_body(const StageArgs &a, const ChainPa
       const int64_t k = na - n0;
       const int rem = sec.xf_remaining > k ? (int)(sec.xf_remaining - k) : 0;
       if (rem > 0 && cancelled == 0.0) {
-        y[j] = section_sample(sec, rem, cur.x.v[j], eq);
-        if (rem == 1) dyn = sec.pending;
+        if (pending_row != 0) {  // scheduled on the running filter: from the stream's live coefficients to its own target
+          SectionParams sp = sec;
+          const double *pc = &a.st64[(int64_t)(pending_row + 5 * kBand) * w.NS + w.sc];
+          sp.active = dyn;
+          sp.pending = BiquadCoef{pc[0], pc[w.NS], pc[2 * w.NS], pc[3 * w.NS], pc[4 * w.NS]};
+          y[j] = section_sample(sp, rem, cur.x.v[j], eq);
+          if (rem == 1) dyn = sp.pending;
+        } else {
+          y[j] = section_sample(sec, rem, cur.x.v[j], eq);
+          if (rem == 1) dyn = sec.pending;
+        }
       } else {
         y[j] = (float)direct(dyn, (double)cur.x.v[j], eq.z1, eq.z2);
       }

@@ -70,6 +70,9 @@ SIGNATURES = {
     "af_engine_destroy": (None, [_vp]),
     "af_engine_reset": (C.c_int, [_vp]),
     "af_engine_n_streams": (_i32, [_vp]),
+    "af_engine_set_live_control": (C.c_int, [_vp, _i32]),
+    "af_engine_live_control_pending": (C.c_int, [_vp, C.POINTER(_i32)]),
+    "af_engine_last_retune_ms": (C.c_int, [_vp, _dp]),
     "af_engine_set_deesser_enabled": (C.c_int, [_vp, _i32]),
     "af_engine_set_eq_enabled": (C.c_int, [_vp, _i32]),
     "af_engine_set_compressor_enabled": (C.c_int, [_vp, _i32]),

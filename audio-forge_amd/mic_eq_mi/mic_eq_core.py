@@ -117,6 +117,25 @@ class Engine:
         c = EqBandConfig(EQ_TYPE_IDS[name], float(freq), float(gain), float(q), int(slope), int(bool(enabled)))
         _lib.check(self._lib.af_eq_set_band_config(self._h, band, C.byref(c)))
 
+    def set_live_control(self, enabled: bool) -> None:
+        """Accept the chain setters (``eq_set_band_*``, ``compressor_set_*``, ``limiter_set_ceiling`` / ``_release_time``,
+        ``true_peak_limiter_set_release_ms``, ``deesser_set_*``) after ``process`` / ``stream`` has started: they then act on
+        the running streams, like the reference's realtime control plane, from the first sample of the next call.  A
+        configuration setter (RuntimeError after the first call); off by default."""
+        _lib.check(self._lib.af_engine_set_live_control(self._h, int(bool(enabled))))
+
+    def live_control_pending(self) -> int:
+        """State edits recorded by live setters that the next call will apply."""
+        ops = C.c_int32(0)
+        _lib.check(self._lib.af_engine_live_control_pending(self._h, C.byref(ops)))
+        return ops.value
+
+    def last_retune_ms(self) -> float:
+        """Device time of the last call's state-retune launch (timing enabled), 0.0 when it launched none."""
+        ms = C.c_double(0.0)
+        _lib.check(self._lib.af_engine_last_retune_ms(self._h, C.byref(ms)))
+        return ms.value
+
     # -- processing ---------------------------------------------------------------
     def process(self, audio: np.ndarray, layout: int = _lib.LAYOUT_STREAM_MAJOR) -> np.ndarray:
         """Host arrays: [n_streams, n] (stream-major) or [n, n_streams] (time-major) float32."""

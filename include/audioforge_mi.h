@@ -29,7 +29,8 @@ typedef enum af_status {
   AF_ERR_INVALID_ARGUMENT = -1, /* PyValueError in the reference binding            */
   AF_ERR_BACKEND = -2,          /* PyRuntimeError: HIP failure / no device          */
   AF_ERR_NON_FINITE = -3,       /* "audio must contain only finite samples"         */
-  AF_ERR_STATE = -4,            /* setter used after streaming started (see below)  */
+  AF_ERR_STATE = -4,            /* configuration setter used after streaming started, or
+                                   any chain setter then with live control off (below) */
   AF_ERR_UNSUPPORTED = -5
 } af_status;
 
@@ -95,10 +96,38 @@ void af_engine_destroy(af_engine *engine);
 int af_engine_reset(af_engine *engine);
 int32_t af_engine_n_streams(const af_engine *engine);
 
-/* Setters mirror the reference structs and may be called until the first
- * af_engine_process_* call; afterwards they return AF_ERR_STATE (live retuning of
- * resident streams is out of scope -- the reference does it through its realtime
- * control plane, audio/processor/control.rs). */
+/* Setters mirror the reference structs.  Until the first af_engine_process_* / af_engine_stream_* call every setter is
+ * accepted (configuration mode); af_engine_reset returns the engine to that mode.
+ *
+ * After streaming started a CONFIGURATION setter returns AF_ERR_STATE: the stage enables and af_engine_set_eq_before_deesser
+ * (they change which kernels and stages are resident), af_limiter_set_lookahead_ms (ring and LDS sizes),
+ * af_compressor_set_auto_makeup_enabled (the kernel form and the state planes' size are chosen per value), af_eq_reset,
+ * af_engine_set_control_block_samples, the scrub / clamp / pre-filter switches, preset count and assignment, kernel selection,
+ * af_engine_set_live_control, and every setter documented below as a configuration setter.
+ *
+ * The other chain setters (af_eq_set_band_*, af_compressor_set_*, af_limiter_set_ceiling / _release_time,
+ * af_true_peak_limiter_set_release_ms, af_deesser_set_*) are LIVE setters.  With live control off (the default) they too
+ * return AF_ERR_STATE after streaming started.  With af_engine_set_live_control(e, 1) they are accepted between calls and
+ * act like the reference's realtime control plane (audio/processor/control.rs:844-919 applied at the top of a wake-up,
+ * dsp_loop.rs:604-637): the reference setter's effect on the RUNNING object -- a coefficient crossfade that starts from the
+ * live filter memories (biquad.rs:249-260), the compressor's release fields and release envelopes (compressor.rs:210-275),
+ * the side-chain reset on a toggle (compressor.rs:366-371) -- lands at the first sample the chain processes in the next
+ * call, for every stream of the selected preset, in the order the setters were called.  Per-stream state is edited on the
+ * device by one extra kernel launch in front of that call; a call with nothing pending launches nothing extra.
+ * Arguments are checked first: a live EQ setter validates the band it would produce with EqBandConfig::validate
+ * (af_eq_band_config_validate: AF_ERR_INVALID_ARGUMENT and the same message), and a refused setter leaves nothing pending.
+ * Refused live with AF_ERR_UNSUPPORTED, nothing pending: an EQ band change that needs more biquad sections than the band
+ * holds (the state planes are sized at start);
+ * af_compressor_set_adaptive_release / _sidechain_highpass_enabled on a multi-preset engine that runs the stage pipeline
+ * (its presets must take the same code paths).
+ * af_engine_reset keeps the switch, drops what is pending, and re-arms a preset that was retuned live like the reference's
+ * reset(): every filter starts from its configured target (Biquad::reset, biquad.rs:341-347).
+ * Setters and process calls of one engine are single-threaded, as everywhere in this header. */
+int af_engine_set_live_control(af_engine *e, int32_t enabled);  /* a configuration setter; off by default */
+/* state edits recorded since the last call that ran the chain (0 with nothing pending); `ops` may be null */
+int af_engine_live_control_pending(const af_engine *e, int32_t *ops);
+/* with af_engine_set_timing_enabled: device time of the last call's state-retune launch, 0 when it launched none (synchronises) */
+int af_engine_last_retune_ms(af_engine *e, double *ms);
 
 /* ---- chain switches: block_processor.rs:62-84 ----------------------------------- */
 int af_engine_set_deesser_enabled(af_engine *e, int32_t enabled);
