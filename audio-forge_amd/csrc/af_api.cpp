@@ -3,7 +3,6 @@
 
 #include <algorithm>
 #include <cmath>
-#include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -13,7 +12,7 @@
 #include <utility>
 #include <vector>
 
-#include "../../include/audioforge_mi.h"
+#include "af_api_internal.hpp"
 #include "af_device.h"
 #include "af_host.hpp"
 #include "af_mixdown_host.hpp"
@@ -39,20 +38,6 @@ hipError_t launch_chain_quad(const LaunchArgs &args, int n_sections, int lookahe
 size_t quad_kernel_dynamic_lds(int n_sections, int lookahead_samples, bool crossfade);
 hipError_t launch_merge_side_stats(BlockStats *rows, const BlockStats *input_rows, const BlockStats *deesser_rows,
                                    int64_t n, hipStream_t stream);
-hipError_t launch_resample(const double *in, double *out, const ResamplePos *pos, const double *table, int64_t n_in,
-                           int64_t n_out, int64_t in_stride, int64_t out_stride, int32_t n_streams, int32_t sinc_len,
-                           double ratio, int variant, hipStream_t stream);
-int resample_segment_outputs(double ratio, int sinc_len);
-hipError_t launch_resample_stream(const float *plane, const float *in, float *out, const ResamplePos *pos, const double *table,
-                                  int64_t split, int64_t n_in, int64_t n_out, int64_t in_stride, int64_t out_stride,
-                                  int32_t plane_stride, int32_t n_streams, int32_t sinc_len, double ratio, int variant,
-                                  hipStream_t stream);
-hipError_t launch_resample_stream_advance(const float *plane, float *next, const float *in, int64_t split, int64_t n_in,
-                                          int64_t shift, int64_t in_stride, int32_t count, int32_t plane_stride, int32_t n_streams,
-                                          hipStream_t stream);
-hipError_t launch_kweight_energy(const float *audio, double *partial, int32_t *non_finite, const double b[5],
-                                 const double a5[5], int64_t n_samples, int64_t stride, int64_t n100, int32_t n_streams,
-                                 int32_t s100, hipStream_t stream);
 hipError_t launch_deesser(const ChainParams *d_params, double *st64, float *st32, const float *in, float *out,
                           BlockStats *rows, int64_t n_samples, int64_t stream_stride, int32_t n_streams,
                           int32_t layout, bool front_end, bool write_out_power, hipStream_t stream);
@@ -77,28 +62,7 @@ constexpr int kEqParamSlots = 16;  // parameter blocks the EQ / de-esser stages 
 static_assert(sizeof(af_block_stats) == sizeof(af::BlockStats), "stats row layout");
 static_assert(sizeof(af_block_stats) == 72, "stats row size");
 
-namespace {
-
-thread_local std::string g_last_error;
-
-int fail(int code, const char *fmt, ...) {
-  char buf[512];
-  va_list ap;
-  va_start(ap, fmt);
-  std::vsnprintf(buf, sizeof buf, fmt, ap);
-  va_end(ap);
-  g_last_error = buf;
-  return code;
-}
-
-#define AF_HIP(expr)                                                                              \
-  do {                                                                                            \
-    hipError_t err__ = (expr);                                                                    \
-    if (err__ != hipSuccess)                                                                      \
-      return fail(AF_ERR_BACKEND, "%s failed: %s", #expr, hipGetErrorString(err__));              \
-  } while (0)
-
-}  // namespace
+thread_local std::string af_last_error_text;
 
 // one more chain preset of an engine (preset 0 is af_engine::proto / host_params)
 struct af_preset {
@@ -115,15 +79,16 @@ struct af_engine {
   std::vector<af_preset> extra_presets;
   int current_preset = 0;
   std::vector<int32_t> group_preset;         // [ceil(n_streams / 64)], empty = every group runs preset 0
-  int32_t *d_group_preset = nullptr;
-  af::ChainParams *d_params_multi = nullptr;  // [1 + extra_presets.size()]
-  af::ChainParams *d_params_eq = nullptr;     // [1 + extra_presets.size()]: what the systolic EQ kernel reads (af_eq_systolic.hip)
+  af::DeviceBuffer<int32_t> d_group_preset;
+  af::DeviceBuffer<af::ChainParams> d_params_multi;  // [1 + extra_presets.size()]
+  af::DeviceBuffer<af::ChainParams> d_params_eq;  // [1 + extra_presets.size()]: what the systolic EQ kernel reads (af_eq_systolic.hip)
   std::vector<af::ChainParams> uploaded_eq;
   int eq_params_presets = 0;
   uint64_t eq_slot_cursor = 0;               // stage pipeline with the de-esser: the next window's parameter slot
   std::vector<af::ChainParams> uploaded_multi;
   int n_streams;
   int device;
+  bool touched_device = false;  // use_device() succeeded once: there may be allocations, and the destructor has a device to wait for
   bool started = false;
   bool params_dirty = true;
   int kernel = AF_KERNEL_AUTO;
@@ -138,83 +103,70 @@ struct af_engine {
   af::ChainParams host_params{};
   af::ChainParams uploaded{};   // what d_params currently holds
   bool uploaded_valid = false;
-  af::ChainParams *d_params = nullptr;
-  double *d_st64 = nullptr;
-  float *d_st32 = nullptr;
+  af::DeviceBuffer<af::ChainParams> d_params;
+  af::DeviceBuffer<double> d_st64;
+  af::DeviceBuffer<float> d_st32;
   int n_f64 = 0, n_f32 = 0;
-  af::BlockStats *d_stats = nullptr;
-  af::BlockStats *d_stats_pre = nullptr;   // rows of the pre-pass launch (auto-makeup)
-  int64_t stats_pre_capacity = 0;
-  af::ChainParams *d_params_pre = nullptr;
+  af::DeviceBuffer<af::BlockStats> d_stats;
+  af::DeviceBuffer<af::BlockStats> d_stats_pre;  // rows of the pre-pass launch (auto-makeup)
+  af::DeviceBuffer<af::ChainParams> d_params_pre;
   af::ChainParams uploaded_pre{};          // what d_params_pre currently holds
   bool uploaded_pre_valid = false;
-  double *d_block_power = nullptr;         // [blocks][streams] of the current call: compressor-input block power written by the systolic EQ
-  int64_t block_power_capacity = 0;        // doubles
+  af::DeviceBuffer<double> d_block_power;  // [blocks][streams] of the current call: compressor-input block power written by the systolic EQ
   // Parameter uploads go through engine-owned pinned staging slots (stage_upload): the host never waits for a stream, and
   // a slot is only reused once the copy that read it has run.
-  struct ParamStager {
-    static constexpr int kSlots = 32;      // (the stage pipeline with the de-esser uploads one block per window: the host may run this many windows ahead)
-    af::ChainParams *pinned = nullptr;     // [kSlots][blocks_per_slot]
-    size_t blocks_per_slot = 0;
-    hipEvent_t done[kSlots] = {};
-    bool used[kSlots] = {};
-    int next = 0;
-  } stager;
+  af::PinnedSlots<32> stager;  // (the stage pipeline with the de-esser uploads one block per window: the host may run this many windows ahead)
   // Device buffers that had to grow while earlier work may still read them: kept until that work has ended (an event on the
   // stream the call was made on), freed by a later call, a reset or the destructor -- growing never synchronises the device.
-  struct Retired { void *p; hipEvent_t ev; };
-  std::vector<Retired> retired;
+  af::RetireList retired;
   hipStream_t syn_stream = nullptr;        // CU partition: pitch spectra + network + resynthesis (else the caller's stream)
   hipStream_t fin_stream = nullptr;        // resynthesis + overlap-add of window w beside pitch spectra + network of w+1
   hipStream_t rnn_stream = nullptr;        // the network of window w beside the pitch spectra of w+1 (AF_RNN_STREAM=0: on syn_stream)
   hipStream_t lim_stream = nullptr;        // AF_ROLES=2: the limiter half of the chain (af_roles.hip) on CUs of its own
   hipStream_t eq_stream = nullptr;         // the window's systolic EQ (af_eq_systolic.hip), behind its overlap-add, beside the next window's synthesis
   int partition_chain_cus = 0;             // CUs reserved for the chain stream (0 = the streams are not masked)
-  af::BlockStats *d_stats_de = nullptr;    // rows of the de-esser pass
-  af::ChainParams *d_params_de = nullptr;  // the de-esser pass reads the unedited parameter block
+  af::DeviceBuffer<af::BlockStats> d_stats_de;    // rows of the de-esser pass
+  af::DeviceBuffer<af::ChainParams> d_params_de;  // the de-esser pass reads the unedited parameter block
   af::ChainParams uploaded_de{};
   bool uploaded_de_valid = false;
-  double *d_vad = nullptr;                 // [blocks][streams] speech posteriors for the next call
-  int64_t vad_capacity = 0, vad_blocks = 0;
+  af::DeviceBuffer<double> d_vad;          // [blocks][streams] speech posteriors for the next call
+  int64_t vad_blocks = 0;
   double vad_reliability = 0.0, noise_floor_db = 0.0, live_noise_reliability = 0.0;
   bool has_evidence = false;
-  int32_t *d_status = nullptr;
+  af::DeviceBuffer<int32_t> d_status;
   bool eq_params_on_es = false;              // the EQ parameter block's last upload ran on the EQ stream (two-part EQ: who must wait for it)
-  int64_t *d_ready = nullptr;                // samples of the running call the suppressor's side has finished (LaunchArgs::ready)
-  int64_t stats_capacity = 0;  // rows
-  float *d_io = nullptr;       // staging for the host entry point
-  int64_t io_capacity = 0;     // floats
+  af::DeviceBuffer<int64_t> d_ready;         // samples of the running call the suppressor's side has finished (LaunchArgs::ready)
+  af::DeviceBuffer<float> d_io;  // staging for the host entry point
   hipStream_t last_stream = nullptr;
   af::SuppressorHost supp;
   bool borrowed_streams = false;                         // AF_SERIAL_STREAMS: the side streams alias the caller's
   hipStream_t aux_stream = nullptr;                      // chain launches while the suppressor fills the chip
   hipStream_t pre_stream = nullptr;                      // the suppressor's sample-serial pre-pass, two windows ahead
   hipStream_t ana_stream = nullptr;                      // spectra + pitch, one window ahead
-  std::vector<hipEvent_t> sync_events;
+  std::vector<af::Event> sync_events;
   size_t ev_cursor = 0;                                  // next free entry of sync_events within the current call
-  std::vector<std::pair<hipEvent_t, hipEvent_t>> chain_ms_events;  // timing brackets of the chain launches of the last call
+  std::vector<af::TimedSpan> chain_ms_events;  // timing brackets of the chain launches of the last call
   // rnnoise.rs:114-164: the samples of a call that do not fill a 480-sample frame wait here for the next call
-  float *d_pending = nullptr;   // [streams][480]
+  af::DeviceBuffer<float> d_pending;  // [streams][480]
   int pending = 0;              // samples per stream waiting in d_pending (all streams advance in lock step)
-  float *d_asm = nullptr;       // [streams][asm_stride]: pending samples + this call's, when the two have to be joined
-  int64_t asm_capacity = 0;     // floats
+  af::DeviceBuffer<float> d_asm;  // [streams][asm_stride]: pending samples + this call's, when the two have to be joined
   int64_t last_output_samples = 0;  // samples per stream the last process call produced
-  int32_t *d_trace = nullptr;   // [frames][streams][2]: (silence, pitch index) of every frame of the last call
-  int64_t trace_capacity = 0, trace_frames = 0;
+  af::DeviceBuffer<int32_t> d_trace;  // [frames][streams][2]: (silence, pitch index) of every frame of the last call
+  int64_t trace_frames = 0;
   bool trace = false;
   // the stage-pipeline form of the chain (af_stages.hip): rings, one stream and a ring of events per stage
   struct StagePipe {
     bool decided = false, active = false;  // chosen at the first call after a reset, then kept (the rings ARE the histories)
     af::StageRings rings{};
-    std::vector<void *> allocs;
+    std::vector<af::DeviceBuffer<>> allocs;
     int64_t tw_max = 0;                    // longest window the rings were sized for
     hipStream_t stream = nullptr;          // where the launch steps go when the suppressor's pipeline feeds the chain
     int64_t windows = 0;                   // windows launched since the rings were last cleared
     static constexpr int kMkSets = 4;
-    double *d_mk = nullptr;
+    af::DeviceBuffer<double> d_mk;
     int64_t mk_rows = 0;                   // rows (blocks x streams) per set
     static constexpr int kBpSets = 16;
-    double *d_bp = nullptr;                // auto-makeup: block powers, written seven launch steps before they are read
+    af::DeviceBuffer<double> d_bp;         // auto-makeup: block powers, written seven launch steps before they are read
     int64_t call_stride = 0;               // stream stride of the call being scheduled
     const af::ChainParams *d_chain = nullptr;  // the parameter block(s) the stages read (an array with several presets)
     bool with_deesser = false;             // the rings include the de-esser stages'
@@ -225,14 +177,14 @@ struct af_engine {
   // 254, 16 -> 259, 50 -> 260.  End of round 3 (one chain launch per call: a window costs the chain nothing any more):
   // 12 -> 165.2, 14 -> 166.1, 16 -> 163.2, 18 -> 164.5, 20 -> 165.0, 24 -> 166.7, 32 -> 169.2
   int supp_window_frames = 16;
-  hipEvent_t ev_start = nullptr, ev_stop = nullptr, ev_mid = nullptr;  // start | suppressor done | chain done
+  af::Event ev_start, ev_stop, ev_mid;  // start | suppressor done | chain done
   // the noise gate stage (realtime stage 1, dsp_loop.rs:1371-1435): engine-wide parameters, live between calls; per-stream
   // state in `d_gate` ([af::kGateFields][stream], zero = NoiseGate's initial state), allocated at the first gated call and
   // touched only by the pre-pass that gates
   bool gate_enabled = false;
   double gate_threshold_db = -40.0, gate_attack_ms = 10.0, gate_release_ms = 100.0;  // NoiseGate::new(-40, 10, 100, fs)
   int gate_mode = 0;                 // 0 ThresholdOnly, 1 VadAssisted, 2 VadOnly
-  int64_t *d_gate = nullptr;
+  af::DeviceBuffer<int64_t> d_gate;
   // the VAD-fused modes (gate.rs:652-741): a VadAutoGate::without_backend attached to the gate.  Its settings are engine-wide
   // and kept across a detach; its state and the fused gate's own fields live in `d_gate_vad` ([af::kVadFields][stream],
   // allocated at the first fused call).  `vad_ctl_fresh` / `vad_fused_fresh`: that part of the plane has to be (re)initialised
@@ -241,43 +193,31 @@ struct af_engine {
   float vad_threshold = 0.48f;       // ControlState's default, processor/control.rs:89
   float vad_hold_ms = 200.0f, vad_margin_db = 10.0f;  // vad.rs:667, 675
   bool vad_auto_threshold = true;
-  uint32_t *d_gate_vad = nullptr;
-  uint32_t *d_vad_dec = nullptr;     // [block][af::kVadDecWords][stream] decision rows of the running call
-  int64_t vad_dec_capacity = 0;      // bytes
+  af::DeviceBuffer<uint32_t> d_gate_vad;
+  af::DeviceBuffer<uint32_t> d_vad_dec;  // [block][af::kVadDecWords][stream] decision rows of the running call
   int64_t vad_dec_blocks = 0;        // rows the last fused call wrote (af_engine_read_gate_vad_decisions)
   // evidence for the next fused call: one probability and one availability flag per control block, shared or per stream
   std::vector<float> vad_ev_prob;
   std::vector<uint8_t> vad_ev_avail;
   int64_t vad_ev_blocks = 0;
   bool vad_ev_per_stream = false;
-  uint8_t *d_vad_ev = nullptr;       // [probabilities f32 | flags u8] of the running call
-  int64_t vad_ev_capacity = 0;       // bytes
-  struct EvidenceStager {            // pinned slots, as ParamStager: the host never waits for a stream
-    static constexpr int kSlots = 8;
-    uint8_t *pinned[kSlots] = {};
-    size_t bytes[kSlots] = {};
-    hipEvent_t done[kSlots] = {};
-    bool used[kSlots] = {};
-    int next = 0;
-  } ev_stager;
+  af::DeviceBuffer<uint8_t> d_vad_ev;  // [probabilities f32 | flags u8] of the running call
+  af::PinnedSlots<8> ev_stager;      // it travels through pinned slots, as the parameter blocks do
   double sample_rate;
   // Device-rate I/O (dsp_loop.rs:274-317): a streaming product resampler in front of and / or behind the chain, built by
   // af_engine_set_io_sample_rates.  Null = that side runs at the engine's rate; both null = the engine as it always was.
   af_stream_resampler *rs_in = nullptr, *rs_out = nullptr;
-  float *d_rs_in = nullptr, *d_rs_mid = nullptr, *d_rs_out = nullptr;  // af_engine_stream_host: device-rate input | engine-rate audio | device-rate output
-  int64_t rs_in_capacity = 0, rs_mid_capacity = 0, rs_out_capacity = 0;  // bytes
+  af::DeviceBuffer<float> d_rs_in, d_rs_mid, d_rs_out;  // af_engine_stream_host: device-rate input | engine-rate audio | device-rate output
   af_mixdown *mix = nullptr;     // af_engine_set_input_channels with more than one channel: the mixdown in front of everything
-  float *d_mix_in = nullptr;     // af_engine_stream_host: the interleaved device frames
-  int64_t mix_in_capacity = 0;   // bytes
+  af::DeviceBuffer<float> d_mix_in;  // af_engine_stream_host: the interleaved device frames
   // af_engine_set_output_writer: the output writer (output_writer.rs:62-343) behind the chain / the output resampler, at the
   // I/O output rate if one is set, otherwise at the engine's.  Null = off, every call is as without the setter.
   af_output_writer *ow = nullptr;
   uint32_t io_output_rate = 0;        // af_engine_set_io_sample_rates' output rate while it differs from the engine's
   std::vector<int64_t> ow_fill;       // af_engine_set_output_queue_fill; empty = the target centre (no error)
   std::vector<int64_t> ow_written;    // of the last af_engine_stream_host
-  int64_t *d_ow_fill = nullptr, *d_ow_written = nullptr;
-  float *d_ow_out = nullptr;
-  int64_t ow_out_capacity = 0;        // bytes
+  af::DeviceBuffer<int64_t> d_ow_fill, d_ow_written;
+  af::DeviceBuffer<float> d_ow_out;
   int64_t ow_target_center = 0, ow_capacity = 0;
   bool ow_fill_dirty = true;          // the device copy of ow_fill is stale
   // Live control (af_engine_set_live_control): with the switch on the chain setters are accepted after streaming started.  A
@@ -289,13 +229,34 @@ struct af_engine {
   std::vector<char> live_retuned;     // per preset: a live setter was accepted since the last reset (the prototype follows the device)
   std::vector<char> live_cuts;        // per preset: ... one that moved the de-esser's cut frequencies (DeEsserParams::dyn_pending_row is in force)
   int dyn_pending_row = 0;            // first of the 15 plane rows behind every kernel's own (allocated with live control on), or 0
-  af::ChainParams *d_retune = nullptr;  // the op list on the device, in parameter-block units (it travels through stage_upload)
-  int64_t retune_capacity = 0;        // bytes
-  hipEvent_t ev_retune0 = nullptr, ev_retune1 = nullptr;
-  bool retune_timed = false;          // the last call launched the retune kernel between the two events
+  af::DeviceBuffer<af::ChainParams> d_retune;  // the op list on the device, in parameter-block units (it travels through stage_upload)
+  af::TimedSpan retune_span;          // around the last call's launch of the retune kernel, if it made one with timing on
 
   af_engine(double fs, int n, int dev) : proto(fs), n_streams(n), device(dev), sample_rate(fs) {}
+  ~af_engine();
+  hipError_t use_device() {
+    const hipError_t err = hipSetDevice(device);
+    touched_device |= err == hipSuccess;
+    return err;
+  }
 };
+
+// The device comes to rest first; the streams, the suppressor's buffers and the sub-objects go with the engine's device current;
+// then the members release themselves.  An engine that never used its device makes no HIP call here (nor do its sub-objects).
+af_engine::~af_engine() {
+  if (touched_device) {
+    (void)hipSetDevice(device);
+    (void)hipDeviceSynchronize();
+    if (borrowed_streams) aux_stream = pre_stream = ana_stream = fin_stream = eq_stream = nullptr;
+    for (hipStream_t st : {pipe.stream, lim_stream, fin_stream, rnn_stream, eq_stream, syn_stream, aux_stream, pre_stream, ana_stream})
+      if (st) (void)hipStreamDestroy(st);
+    supp.release_all();
+  }
+  af_stream_resampler_destroy(rs_in);
+  af_stream_resampler_destroy(rs_out);
+  af_mixdown_destroy(mix);
+  af_output_writer_destroy(ow);
+}
 
 namespace {
 
@@ -313,59 +274,7 @@ int require_config(af_engine *e) {
 
 // Copy `count` parameter blocks to the device behind everything already queued on `stream`, from a pinned engine-owned slot.
 int stage_upload(af_engine *e, af::ChainParams *dst, const af::ChainParams *src, size_t count, hipStream_t stream) {
-  auto &st = e->stager;
-  if (count > st.blocks_per_slot) {
-    for (int k = 0; k < af_engine::ParamStager::kSlots; ++k)
-      if (st.used[k]) { AF_HIP(hipEventSynchronize(st.done[k])); st.used[k] = false; }
-    if (st.pinned) AF_HIP(hipHostFree(st.pinned));
-    st.pinned = nullptr;
-    AF_HIP(hipHostMalloc(reinterpret_cast<void **>(&st.pinned), sizeof(af::ChainParams) * count * af_engine::ParamStager::kSlots, hipHostMallocDefault));
-    st.blocks_per_slot = count;
-  }
-  const int slot = st.next;
-  st.next = (st.next + 1) % af_engine::ParamStager::kSlots;
-  if (!st.done[slot]) AF_HIP(hipEventCreateWithFlags(&st.done[slot], hipEventDisableTiming));
-  if (st.used[slot]) AF_HIP(hipEventSynchronize(st.done[slot]));  // kSlots uploads ago: normally long done
-  af::ChainParams *host = st.pinned + (size_t)slot * st.blocks_per_slot;
-  std::memcpy(host, src, sizeof(af::ChainParams) * count);
-  AF_HIP(hipMemcpyAsync(dst, host, sizeof(af::ChainParams) * count, hipMemcpyHostToDevice, stream));
-  AF_HIP(hipEventRecord(st.done[slot], stream));
-  st.used[slot] = true;
-  return AF_OK;
-}
-
-// free the retired buffers whose last reader has ended (`all`: wait for them)
-int collect_retired(af_engine *e, bool all) {
-  size_t kept = 0;
-  for (auto &r : e->retired) {
-    hipError_t q = all ? hipEventSynchronize(r.ev) : hipEventQuery(r.ev);
-    if (q == hipSuccess) {
-      (void)hipFree(r.p);
-      (void)hipEventDestroy(r.ev);
-    } else {
-      if (q != hipErrorNotReady) (void)hipGetLastError();
-      e->retired[kept++] = r;
-    }
-  }
-  e->retired.resize(kept);
-  return AF_OK;
-}
-
-// Make `*p` hold at least `need` bytes.  Growth is geometric; the old buffer (its contents are per-call scratch, never
-// carried over) is retired behind an event on `stream` instead of being freed under the feet of queued kernels.
-int grow_device(af_engine *e, void **p, int64_t *capacity_bytes, int64_t need, hipStream_t stream) {
-  if (need <= *capacity_bytes) return AF_OK;
-  const int64_t cap = std::max<int64_t>(need, *capacity_bytes + *capacity_bytes / 2);
-  void *fresh = nullptr;
-  AF_HIP(hipMalloc(&fresh, (size_t)cap));
-  if (*p) {
-    hipEvent_t ev;
-    AF_HIP(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
-    AF_HIP(hipEventRecord(ev, stream));
-    e->retired.push_back({*p, ev});
-  }
-  *p = fresh;
-  *capacity_bytes = cap;
+  AF_HIP(e->stager.upload(dst, src, sizeof(af::ChainParams) * count, stream));
   return AF_OK;
 }
 
@@ -442,18 +351,14 @@ int upload_initial_state(af_engine *e) {
     e->dyn_pending_row = n64;
     n64 += 15;
   }
-  if (e->d_st64 && (n64 != e->n_f64 || n32 != e->n_f32)) {
-    AF_HIP(hipFree(e->d_st64));
-    AF_HIP(hipFree(e->d_st32));
-    e->d_st64 = nullptr;
-    e->d_st32 = nullptr;
+  if (n64 != e->n_f64 || n32 != e->n_f32) {
+    e->d_st64.release();
+    e->d_st32.release();
   }
-  if (!e->d_st64) {
-    AF_HIP(hipMalloc(&e->d_st64, sizeof(double) * n64 * B));
-    AF_HIP(hipMalloc(&e->d_st32, sizeof(float) * n32 * B));
-    e->n_f64 = n64;
-    e->n_f32 = n32;
-  }
+  AF_HIP(e->d_st64.reserve_exact(sizeof(double) * n64 * B));
+  AF_HIP(e->d_st32.reserve_exact(sizeof(float) * n32 * B));
+  e->n_f64 = n64;
+  e->n_f32 = n32;
   // every stream starts from its preset's prototype
   std::vector<std::vector<double>> v64s(n_presets, std::vector<double>(n64, 0.0));
   std::vector<std::vector<float>> v32s(n_presets, std::vector<float>(n32, 0.0f));
@@ -492,7 +397,7 @@ int upload_initial_state(af_engine *e) {
 }
 
 int ensure_started(af_engine *e) {
-  AF_HIP(hipSetDevice(e->device));
+  AF_HIP(e->use_device());
   if (!e->started) {
     export_params(e);
     // the limiter's delay ring and suffix maxima live in LDS: kernel 3 (16 streams per workgroup) holds ~1000 samples
@@ -520,21 +425,19 @@ int ensure_started(af_engine *e) {
         return fail(AF_ERR_UNSUPPORTED, "multi-preset engines run the token-ring kernel or the stage pipeline");
       const size_t n_groups = (size_t)(e->n_streams + 63) / 64;
       if (e->group_preset.size() != n_groups) e->group_preset.assign(n_groups, 0);
-      if (e->d_group_preset) AF_HIP(hipFree(e->d_group_preset));
-      if (e->d_params_multi) AF_HIP(hipFree(e->d_params_multi));
-      e->d_group_preset = nullptr;
-      e->d_params_multi = nullptr;
-      AF_HIP(hipMalloc(&e->d_group_preset, sizeof(int32_t) * n_groups));
+      e->d_group_preset.release();
+      e->d_params_multi.release();
+      AF_HIP(e->d_group_preset.reserve_exact(sizeof(int32_t) * n_groups));
       AF_HIP(hipMemcpy(e->d_group_preset, e->group_preset.data(), sizeof(int32_t) * n_groups, hipMemcpyHostToDevice));
-      AF_HIP(hipMalloc(&e->d_params_multi, sizeof(af::ChainParams) * (1 + e->extra_presets.size())));
+      AF_HIP(e->d_params_multi.reserve_exact(sizeof(af::ChainParams) * (1 + e->extra_presets.size())));
       e->uploaded_multi.clear();
     }
-    if (!e->d_params) AF_HIP(hipMalloc(&e->d_params, sizeof(af::ChainParams)));
-    if (!e->d_params_pre) AF_HIP(hipMalloc(&e->d_params_pre, sizeof(af::ChainParams)));
-    if (!e->d_params_de) AF_HIP(hipMalloc(&e->d_params_de, sizeof(af::ChainParams)));
+    AF_HIP(e->d_params.reserve_exact(sizeof(af::ChainParams)));
+    AF_HIP(e->d_params_pre.reserve_exact(sizeof(af::ChainParams)));
+    AF_HIP(e->d_params_de.reserve_exact(sizeof(af::ChainParams)));
     if (!e->d_status) {
-      AF_HIP(hipMalloc(&e->d_status, sizeof(int32_t)));
-      AF_HIP(hipMemset(e->d_status, 0, sizeof(int32_t)));
+      AF_HIP(e->d_status.reserve_exact(sizeof(int32_t)));
+      AF_HIP(e->d_status.keep_if(hipMemset(e->d_status, 0, sizeof(int32_t))));
     }
     int rc = upload_initial_state(e);
     if (rc) return rc;
@@ -721,34 +624,24 @@ int live_eq_set_band(af_engine *e, int band, const af::EqBandConfig &c) {
 // The edits recorded since the last call, in one launch on the call's stream: behind the previous call's work, ahead of this
 // call's first parameter upload and kernel.  Nothing pending: nothing launched.
 int launch_pending_retune(af_engine *e, hipStream_t stream) {
-  e->retune_timed = false;
+  e->retune_span.clear();
   if (e->retune_ops.empty()) return AF_OK;
   const size_t bytes = e->retune_ops.size() * sizeof(af::RetuneOp);
   const size_t blocks = (bytes + sizeof(af::ChainParams) - 1) / sizeof(af::ChainParams);
-  if (int rc = grow_device(e, reinterpret_cast<void **>(&e->d_retune), &e->retune_capacity, (int64_t)(blocks * sizeof(af::ChainParams)), stream))
-    return rc;
+  AF_HIP(e->d_retune.reserve_retiring(blocks * sizeof(af::ChainParams), e->retired, stream));
   std::vector<af::ChainParams> carrier(blocks);  // (the pinned stager moves parameter blocks: the list rides in as many as it fills)
   std::memcpy(carrier.data(), e->retune_ops.data(), bytes);
   if (int rc = stage_upload(e, e->d_retune, carrier.data(), blocks, stream)) return rc;
   af::RetuneArgs ra{};
-  ra.ops = reinterpret_cast<const af::RetuneOp *>(e->d_retune);
+  ra.ops = reinterpret_cast<const af::RetuneOp *>(e->d_retune.get());
   ra.group_preset = e->extra_presets.empty() ? nullptr : e->d_group_preset;
   ra.st64 = e->d_st64;
   ra.n_ops = (int32_t)e->retune_ops.size();
   ra.n_streams = e->n_streams;
   ra.n_fields = e->n_f64;
-  if (e->timing) {
-    if (!e->ev_retune0) {
-      AF_HIP(hipEventCreate(&e->ev_retune0));
-      AF_HIP(hipEventCreate(&e->ev_retune1));
-    }
-    AF_HIP(hipEventRecord(e->ev_retune0, stream));
-  }
+  if (e->timing) AF_HIP(e->retune_span.begin(stream));
   AF_HIP(af::launch_retune_state(ra, stream));
-  if (e->timing) {
-    AF_HIP(hipEventRecord(e->ev_retune1, stream));
-    e->retune_timed = true;
-  }
+  if (e->timing) AF_HIP(e->retune_span.end(stream));
   e->last_launches += 1;
   e->retune_ops.clear();
   return AF_OK;
@@ -810,7 +703,7 @@ void vad_gate_args(const af_engine *e, af::VadGateArgs &va) {
 int vad_gate_prepare(af_engine *e, int64_t blocks, hipStream_t stream, af::VadGateArgs &va) {
   const int64_t NS = e->n_streams;
   if (!e->d_gate_vad) {
-    AF_HIP(hipMalloc(&e->d_gate_vad, sizeof(uint32_t) * af::kVadFields * NS));
+    AF_HIP(e->d_gate_vad.reserve_exact(sizeof(uint32_t) * af::kVadFields * NS));
     e->vad_ctl_fresh = e->vad_fused_fresh = true;
   }
   if (e->vad_ctl_fresh || e->vad_fused_fresh) {
@@ -818,32 +711,16 @@ int vad_gate_prepare(af_engine *e, int64_t blocks, hipStream_t stream, af::VadGa
                                      e->vad_fused_fresh, stream));
     e->vad_ctl_fresh = e->vad_fused_fresh = false;
   }
-  if (int rc = grow_device(e, reinterpret_cast<void **>(&e->d_vad_dec), &e->vad_dec_capacity,
-                           blocks * af::kVadDecWords * NS * (int64_t)sizeof(uint32_t), stream)) return rc;
+  AF_HIP(e->d_vad_dec.reserve_retiring((size_t)(blocks * af::kVadDecWords * NS) * sizeof(uint32_t), e->retired, stream));
   vad_gate_args(e, va);
   va.prob = nullptr;
   va.avail = nullptr;
   va.ev_stride = 0;
   if (e->vad_ev_blocks > 0) {
     const size_t count = e->vad_ev_prob.size(), bytes = count * (sizeof(float) + 1);
-    if (int rc = grow_device(e, reinterpret_cast<void **>(&e->d_vad_ev), &e->vad_ev_capacity, (int64_t)bytes, stream)) return rc;
-    auto &st = e->ev_stager;
-    const int slot = st.next;
-    st.next = (st.next + 1) % af_engine::EvidenceStager::kSlots;
-    if (!st.done[slot]) AF_HIP(hipEventCreateWithFlags(&st.done[slot], hipEventDisableTiming));
-    if (st.used[slot]) AF_HIP(hipEventSynchronize(st.done[slot]));  // kSlots calls ago: long done
-    if (st.bytes[slot] < bytes) {
-      if (st.pinned[slot]) AF_HIP(hipHostFree(st.pinned[slot]));
-      st.pinned[slot] = nullptr;
-      AF_HIP(hipHostMalloc(reinterpret_cast<void **>(&st.pinned[slot]), bytes, hipHostMallocDefault));
-      st.bytes[slot] = bytes;
-    }
-    std::memcpy(st.pinned[slot], e->vad_ev_prob.data(), count * sizeof(float));
-    std::memcpy(st.pinned[slot] + count * sizeof(float), e->vad_ev_avail.data(), count);
-    AF_HIP(hipMemcpyAsync(e->d_vad_ev, st.pinned[slot], bytes, hipMemcpyHostToDevice, stream));
-    AF_HIP(hipEventRecord(st.done[slot], stream));
-    st.used[slot] = true;
-    va.prob = reinterpret_cast<const float *>(e->d_vad_ev);
+    AF_HIP(e->d_vad_ev.reserve_retiring(bytes, e->retired, stream));
+    AF_HIP(e->ev_stager.upload(e->d_vad_ev, e->vad_ev_prob.data(), count * sizeof(float), e->vad_ev_avail.data(), count, stream));
+    va.prob = reinterpret_cast<const float *>(e->d_vad_ev.get());
     va.avail = e->d_vad_ev + count * sizeof(float);
     va.ev_stride = e->vad_ev_per_stream ? NS : 0;
     e->vad_ev_blocks = 0;  // consumed: evidence is for ONE call
@@ -909,18 +786,14 @@ int launch_chain_multi(af_engine *e, uint32_t strip, uint32_t add, const float *
   a.samples_before = samples_before;
   a.n_streams = e->n_streams;
   a.layout = layout;
-  hipEvent_t t0 = nullptr, t1 = nullptr;
-  if (e->timing) {
-    AF_HIP(hipEventCreate(&t0));
-    AF_HIP(hipEventCreate(&t1));
-    AF_HIP(hipEventRecord(t0, stream));
-  }
+  af::TimedSpan span;
+  if (e->timing) AF_HIP(span.begin(stream));
   if (!stats_cleared) AF_HIP(hipMemsetAsync(stats, 0, sizeof(af::BlockStats) * rows, stream));  // fields are written by their tokens
   AF_HIP(af::launch_chain_ring_lds(a, dyn, e->ring_variant, false, stream));
   e->last_launches += 1;
   if (e->timing) {
-    AF_HIP(hipEventRecord(t1, stream));
-    e->chain_ms_events.push_back({t0, t1});
+    AF_HIP(span.end(stream));
+    e->chain_ms_events.push_back(std::move(span));
   }
   advance_crossfades(e, n_samples);
   return AF_OK;
@@ -1005,12 +878,8 @@ int launch_chain_segment(af_engine *e, const af::ChainParams &run_in, bool run_m
         if (int rc = stage_upload(e, e->d_params, &e->uploaded, 1, stream)) return rc;
         e->uploaded_valid = true;
       }
-      hipEvent_t t0 = nullptr, t1 = nullptr;
-      if (e->timing) {
-        AF_HIP(hipEventCreate(&t0));
-        AF_HIP(hipEventCreate(&t1));
-        AF_HIP(hipEventRecord(t0, stream));
-      }
+      af::TimedSpan span;
+      if (e->timing) AF_HIP(span.begin(stream));
       if (!stats_cleared) AF_HIP(hipMemsetAsync(stats, 0, sizeof(af::BlockStats) * rows, stream));
       af::LaunchArgs ra{};
       ra.st64 = e->d_st64;
@@ -1047,8 +916,8 @@ int launch_chain_segment(af_engine *e, const af::ChainParams &run_in, bool run_m
         e->last_launches += 1;
       }
       if (e->timing) {  // (with the limiter on its own stream the bracket holds what the chain stream did)
-        AF_HIP(hipEventRecord(t1, stream));
-        e->chain_ms_events.push_back({t0, t1});
+        AF_HIP(span.end(stream));
+        e->chain_ms_events.push_back(std::move(span));
       }
       if (lim_stream != stream) {
         hipEvent_t comp_done;
@@ -1076,17 +945,11 @@ int launch_chain_segment(af_engine *e, const af::ChainParams &run_in, bool run_m
   a.samples_before = samples_before;
   a.n_streams = e->n_streams;
   a.layout = layout;
-  hipEvent_t t0 = nullptr, t1 = nullptr;
-  if (e->timing) {
-    AF_HIP(hipEventCreate(&t0));
-    AF_HIP(hipEventCreate(&t1));
-    AF_HIP(hipEventRecord(t0, stream));
-  }
-  if ((two_pass || deesser) && rows > e->stats_pre_capacity) {  // (per-call scratch: the old rows are retired, not freed)
-    int64_t cap_pre = e->stats_pre_capacity * (int64_t)sizeof(af::BlockStats), cap_de = cap_pre;
-    if (int rc = grow_device(e, reinterpret_cast<void **>(&e->d_stats_pre), &cap_pre, rows * (int64_t)sizeof(af::BlockStats), stream)) return rc;
-    if (int rc = grow_device(e, reinterpret_cast<void **>(&e->d_stats_de), &cap_de, rows * (int64_t)sizeof(af::BlockStats), stream)) return rc;
-    e->stats_pre_capacity = std::min(cap_pre, cap_de) / (int64_t)sizeof(af::BlockStats);
+  af::TimedSpan span;
+  if (e->timing) AF_HIP(span.begin(stream));
+  if (two_pass || deesser) {  // (per-call scratch: the old rows are retired, not freed)
+    AF_HIP(e->d_stats_pre.reserve_retiring(sizeof(af::BlockStats) * rows, e->retired, stream));
+    AF_HIP(e->d_stats_de.reserve_retiring(sizeof(af::BlockStats) * rows, e->retired, stream));
   }
   const af::BlockStats *input_rows = nullptr;  // where the block input statistics end up when a side pass saw the input
   if (deesser) {
@@ -1184,8 +1047,8 @@ int launch_chain_segment(af_engine *e, const af::ChainParams &run_in, bool run_m
     e->last_launches += 1;
   }
   if (e->timing) {
-    AF_HIP(hipEventRecord(t1, stream));
-    e->chain_ms_events.push_back({t0, t1});
+    AF_HIP(span.end(stream));
+    e->chain_ms_events.push_back(std::move(span));
   }
   if (!followed_counter) advance_crossfades(e, n_samples);  // (a one-launch call: the caller moves the counters window by window)
   return AF_OK;
@@ -1195,11 +1058,11 @@ int launch_chain_segment(af_engine *e, const af::ChainParams &run_in, bool run_m
 // an event of the engine's pool, valid until the end of the current process call
 int engine_event(af_engine *e, hipEvent_t *out_ev) {
   if (e->ev_cursor == e->sync_events.size()) {
-    hipEvent_t ev;
-    AF_HIP(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
-    e->sync_events.push_back(ev);
+    af::Event ev;
+    AF_HIP(ev.create(hipEventDisableTiming));
+    e->sync_events.push_back(std::move(ev));
   }
-  *out_ev = e->sync_events[e->ev_cursor++];
+  *out_ev = e->sync_events[e->ev_cursor++].get();
   return AF_OK;
 }
 
@@ -1246,11 +1109,9 @@ int stage_pipe_prepare(af_engine *e, int64_t tw_max) {
     const int64_t rows = ((std::max(tw_max, sp.tw_max) + cb - 1) / cb + 1) * e->n_streams;
     if (rows > sp.mk_rows) {
       if (sp.d_mk || sp.d_bp) AF_HIP(hipDeviceSynchronize());
-      if (sp.d_mk) (void)hipFree(sp.d_mk);
-      if (sp.d_bp) (void)hipFree(sp.d_bp);
-      sp.d_mk = sp.d_bp = nullptr;
-      AF_HIP(hipMalloc(&sp.d_mk, sizeof(double) * rows * af_engine::StagePipe::kMkSets));
-      AF_HIP(hipMalloc(&sp.d_bp, sizeof(double) * rows * af_engine::StagePipe::kBpSets));
+      sp.mk_rows = 0;
+      AF_HIP(sp.d_mk.reserve_exact(sizeof(double) * rows * af_engine::StagePipe::kMkSets));
+      AF_HIP(sp.d_bp.reserve_exact(sizeof(double) * rows * af_engine::StagePipe::kBpSets));
       sp.mk_rows = rows;
     }
   }
@@ -1260,7 +1121,6 @@ int stage_pipe_prepare(af_engine *e, int64_t tw_max) {
       return fail(AF_ERR_UNSUPPORTED, "a call of %lld samples per window after smaller ones: the stage pipeline's rings were sized for %lld",
                   (long long)tw_max, (long long)sp.tw_max);
     AF_HIP(hipDeviceSynchronize());
-    for (void *p : sp.allocs) (void)hipFree(p);
     sp.allocs.clear();
     sp.rings = af::StageRings{};
   }
@@ -1274,18 +1134,15 @@ int stage_pipe_prepare(af_engine *e, int64_t tw_max) {
   const size_t r64 = pow2_at_least((deesser ? 6 : 4) * tw_max + hist), r32 = pow2_at_least(10 * tw_max + hist);
   sp.rings.rows_f64 = (int32_t)r64;
   sp.rings.rows_f32 = (int32_t)r32;
-  auto ring32 = [&](float **p) -> hipError_t {
-    hipError_t err = hipMalloc(p, sizeof(float) * r32 * 64 * groups);
-    if (err != hipSuccess) return err;
-    sp.allocs.push_back(*p);
-    return hipMemset(*p, 0, sizeof(float) * r32 * 64 * groups);
+  auto ring = [&](void **p, size_t bytes) -> hipError_t {
+    af::DeviceBuffer<> buf;
+    if (hipError_t err = buf.reserve_exact(bytes); err != hipSuccess) return err;
+    *p = buf.get();
+    sp.allocs.push_back(std::move(buf));
+    return hipMemset(*p, 0, bytes);
   };
-  auto ring64 = [&](double **p) -> hipError_t {
-    hipError_t err = hipMalloc(p, sizeof(double) * r64 * 64 * groups);
-    if (err != hipSuccess) return err;
-    sp.allocs.push_back(*p);
-    return hipMemset(*p, 0, sizeof(double) * r64 * 64 * groups);
-  };
+  auto ring32 = [&](float **p) { return ring(reinterpret_cast<void **>(p), sizeof(float) * r32 * 64 * groups); };
+  auto ring64 = [&](double **p) { return ring(reinterpret_cast<void **>(p), sizeof(double) * r64 * 64 * groups); };
   af::StageRings &r = sp.rings;
   for (float **p : {&r.xi, &r.xe, &r.xc, &r.sfx, &r.xl, &r.itp, &r.tgt, &r.gt, &r.od}) AF_HIP(ring32(p));
   for (double **p : {&r.d, &r.pr, &r.low_e, &r.voiced_e, &r.pres_e, &r.rms_e, &r.ipk_db, &r.rms_db, &r.w_db, &r.peak_db, &r.target, &r.gr, &r.glin, &r.fast_r, &r.slow_r, &r.tgt_ms, &r.tg, &r.g})
@@ -1460,16 +1317,13 @@ int stage_diag_step(af_engine *e, const af::ChainParams &run, const StagePlan &p
       blocks += role.gx * gy;
     }
     if (d.n_roles == 0) continue;
-    hipEvent_t t0 = nullptr, t1 = nullptr;
-    if (e->timing && pass == 0) {  // the serial stages' dispatch is what a step lasts: what af_engine_last_chain_launch_ms reports
-      AF_HIP(hipEventCreate(&t0));
-      AF_HIP(hipEventCreate(&t1));
-      AF_HIP(hipEventRecord(t0, stream));
-    }
+    const bool timed = e->timing && pass == 0;  // the serial stages' dispatch is what a step lasts: what af_engine_last_chain_launch_ms reports
+    af::TimedSpan span;
+    if (timed) AF_HIP(span.begin(stream));
     AF_HIP(af::launch_stage_diag(d, blocks, pass, stream));
-    if (t0) {
-      AF_HIP(hipEventRecord(t1, stream));
-      e->chain_ms_events.push_back({t0, t1});
+    if (timed) {
+      AF_HIP(span.end(stream));
+      e->chain_ms_events.push_back(std::move(span));
     }
     e->last_launches += 1;
   }
@@ -1579,9 +1433,8 @@ int stage_diag_eq_params(af_engine *e, hipStream_t stream, bool *crossfade, int3
   // stages read their filters' crossfade counters as of the window's first sample up to eight launch steps after it entered.
   constexpr int kSlots = kEqParamSlots;
   if (!e->d_params_eq || e->eq_params_presets != n_presets) {
-    if (e->d_params_eq) AF_HIP(hipFree(e->d_params_eq));
-    e->d_params_eq = nullptr;
-    AF_HIP(hipMalloc(&e->d_params_eq, sizeof(af::ChainParams) * n_presets * kSlots));
+    e->d_params_eq.release();
+    AF_HIP(e->d_params_eq.reserve_exact(sizeof(af::ChainParams) * n_presets * kSlots));
     e->eq_params_presets = n_presets;
     e->uploaded_eq.clear();
   }
@@ -1605,7 +1458,7 @@ int stage_diag_eq_params(af_engine *e, hipStream_t stream, bool *crossfade, int3
 extern "C" {
 
 int af_version(void) { return 100; }
-const char *af_last_error(void) { return g_last_error.c_str(); }
+const char *af_last_error(void) { return af_last_error_text.c_str(); }
 
 int af_device_count(void) {
   int n = 0;
@@ -1625,107 +1478,14 @@ int af_engine_create(double sample_rate, int32_t n_streams, int32_t device, af_e
   return AF_OK;
 }
 
-void af_engine_destroy(af_engine *e) {
-  if (!e) return;
-  if (e->d_params || e->d_st64 || e->d_stats || e->d_io || e->d_pending || e->d_asm || e->d_trace || e->d_group_preset || e->d_params_multi) {
-    (void)hipSetDevice(e->device);
-    (void)hipDeviceSynchronize();
-    (void)hipFree(e->d_params);
-    (void)hipFree(e->d_st64);
-    (void)hipFree(e->d_st32);
-    (void)hipFree(e->d_stats);
-    (void)hipFree(e->d_stats_pre);
-    (void)hipFree(e->d_params_pre);
-    (void)hipFree(e->d_params_de);
-    (void)hipFree(e->d_stats_de);
-    (void)hipFree(e->d_vad);
-    (void)hipFree(e->d_status);
-    (void)hipFree(e->d_ready);
-    (void)hipFree(e->d_io);
-    (void)hipFree(e->d_pending);
-    (void)hipFree(e->d_group_preset);
-    (void)hipFree(e->d_params_eq);
-    (void)hipFree(e->d_params_multi);
-    (void)hipFree(e->d_asm);
-    (void)hipFree(e->d_trace);
-    (void)hipFree(e->d_block_power);
-    (void)hipFree(e->d_retune);
-    if (e->ev_retune0) (void)hipEventDestroy(e->ev_retune0);
-    if (e->ev_retune1) (void)hipEventDestroy(e->ev_retune1);
-    if (e->ev_start) (void)hipEventDestroy(e->ev_start);
-    if (e->ev_stop) (void)hipEventDestroy(e->ev_stop);
-    if (e->ev_mid) (void)hipEventDestroy(e->ev_mid);
-  }
-  if (e->pipe.rings.xe || e->pipe.d_mk) {
-    (void)hipSetDevice(e->device);
-    (void)hipDeviceSynchronize();
-    for (void *p : e->pipe.allocs) (void)hipFree(p);
-    (void)hipFree(e->pipe.d_mk);
-    (void)hipFree(e->pipe.d_bp);
-  }
-  if (!e->retired.empty() || e->stager.pinned) {
-    (void)hipSetDevice(e->device);
-    (void)collect_retired(e, true);
-    for (hipEvent_t ev : e->stager.done)
-      if (ev) { (void)hipEventSynchronize(ev); (void)hipEventDestroy(ev); }
-    if (e->stager.pinned) (void)hipHostFree(e->stager.pinned);
-  }
-  if (e->pipe.stream) (void)hipStreamDestroy(e->pipe.stream);
-  for (hipEvent_t ev : e->sync_events) (void)hipEventDestroy(ev);
-  for (auto &pr : e->chain_ms_events) { (void)hipEventDestroy(pr.first); (void)hipEventDestroy(pr.second); }
-  if (e->borrowed_streams) e->aux_stream = e->pre_stream = e->ana_stream = e->fin_stream = e->eq_stream = nullptr;
-  if (e->lim_stream) (void)hipStreamDestroy(e->lim_stream);
-  if (e->fin_stream) (void)hipStreamDestroy(e->fin_stream);
-  if (e->rnn_stream) (void)hipStreamDestroy(e->rnn_stream);
-  if (e->eq_stream) (void)hipStreamDestroy(e->eq_stream);
-  if (e->syn_stream) (void)hipStreamDestroy(e->syn_stream);
-  if (e->aux_stream) (void)hipStreamDestroy(e->aux_stream);
-  if (e->pre_stream) (void)hipStreamDestroy(e->pre_stream);
-  if (e->ana_stream) (void)hipStreamDestroy(e->ana_stream);
-  if (e->supp.d_blob || e->supp.d_state || e->supp.d_xh) {
-    (void)hipSetDevice(e->device);
-    e->supp.release_all();
-  }
-  if (e->d_gate) {
-    (void)hipSetDevice(e->device);
-    (void)hipFree(e->d_gate);
-  }
-  if (e->d_gate_vad || e->d_vad_dec || e->d_vad_ev) {
-    (void)hipSetDevice(e->device);
-    (void)hipFree(e->d_gate_vad);
-    (void)hipFree(e->d_vad_dec);
-    (void)hipFree(e->d_vad_ev);
-  }
-  for (int k = 0; k < af_engine::EvidenceStager::kSlots; ++k) {
-    if (e->ev_stager.pinned[k]) (void)hipHostFree(e->ev_stager.pinned[k]);
-    if (e->ev_stager.done[k]) (void)hipEventDestroy(e->ev_stager.done[k]);
-  }
-  af_stream_resampler_destroy(e->rs_in);
-  af_stream_resampler_destroy(e->rs_out);
-  af_mixdown_destroy(e->mix);
-  af_output_writer_destroy(e->ow);
-  if (e->d_ow_fill || e->d_ow_out) {
-    (void)hipSetDevice(e->device);
-    (void)hipFree(e->d_ow_fill);
-    (void)hipFree(e->d_ow_written);
-    (void)hipFree(e->d_ow_out);
-  }
-  if (e->d_rs_in || e->d_rs_mid || e->d_rs_out || e->d_mix_in) {
-    (void)hipSetDevice(e->device);
-    (void)hipFree(e->d_mix_in);
-    (void)hipFree(e->d_rs_in);
-    (void)hipFree(e->d_rs_mid);
-    (void)hipFree(e->d_rs_out);
-  }
-  delete e;
-}
+void af_engine_destroy(af_engine *e) { delete e; }
 
 int af_engine_reset(af_engine *e) {
   if (!e) return fail(AF_ERR_INVALID_ARGUMENT, "engine is null");
   if (e->started) {
-    AF_HIP(hipSetDevice(e->device));
+    AF_HIP(e->use_device());
     AF_HIP(hipDeviceSynchronize());
-    (void)collect_retired(e, true);
+    e->retired.collect(true);
   }
   e->started = false;
   e->uploaded_valid = e->uploaded_pre_valid = e->uploaded_de_valid = false;
@@ -1739,7 +1499,7 @@ int af_engine_reset(af_engine *e) {
   // live control: what is pending is dropped; a preset that was retuned live restarts like the reference's reset() -- every
   // filter from its configured target (Biquad::reset, biquad.rs:341-347), not from wherever a crossfade stood
   e->retune_ops.clear();
-  e->retune_timed = false;
+  e->retune_span.clear();
   for (size_t k = 0; k < e->live_retuned.size() && k <= e->extra_presets.size(); ++k) {
     if (!e->live_retuned[k]) continue;
     af::ChainProto &p = k == 0 ? e->proto : e->extra_presets[k - 1].proto;
@@ -1753,7 +1513,7 @@ int af_engine_reset(af_engine *e) {
   e->live_retuned.clear();
   e->live_cuts.clear();
   if (e->d_gate) {  // NoiseGate::reset, gate.rs:759-785: every state field back to its initial value
-    AF_HIP(hipSetDevice(e->device));
+    AF_HIP(e->use_device());
     AF_HIP(hipMemset(e->d_gate, 0, sizeof(int64_t) * af::kGateFields * e->n_streams));
   }
   // ... + VadAutoGate::reset (vad.rs:1017-1031): the plane is rewritten in front of the next fused pass; pending evidence is
@@ -1788,12 +1548,9 @@ int af_engine_live_control_pending(const af_engine *e, int32_t *ops) {
 int af_engine_last_retune_ms(af_engine *e, double *ms) {
   if (!e || !ms) return fail(AF_ERR_INVALID_ARGUMENT, "null argument");
   *ms = 0.0;
-  if (!e->timing || !e->retune_timed) return AF_OK;
-  AF_HIP(hipSetDevice(e->device));
-  AF_HIP(hipEventSynchronize(e->ev_retune1));
-  float t = 0.0f;
-  AF_HIP(hipEventElapsedTime(&t, e->ev_retune0, e->ev_retune1));
-  *ms = (double)t;
+  if (!e->timing || !e->retune_span.used()) return AF_OK;
+  AF_HIP(e->use_device());
+  AF_HIP(e->retune_span.elapsed_ms(ms));
   return AF_OK;
 }
 
@@ -1945,13 +1702,9 @@ int af_compressor_set_activity_evidence(af_engine *e, const double *vad_probabil
     e->host_params.comp.has_evidence = e->has_evidence ? 1 : 0;
   }
   if (n_blocks == 0) return AF_OK;
-  AF_HIP(hipSetDevice(e->device));
+  AF_HIP(e->use_device());
   const int64_t total = n_blocks * e->n_streams;
-  if (total > e->vad_capacity) {
-    if (e->d_vad) AF_HIP(hipFree(e->d_vad));
-    AF_HIP(hipMalloc(&e->d_vad, sizeof(double) * total));
-    e->vad_capacity = total;
-  }
+  AF_HIP(e->d_vad.reserve_exact(sizeof(double) * total));
   if (per_stream) {
     AF_HIP(hipMemcpy(e->d_vad, vad_probabilities, sizeof(double) * total, hipMemcpyHostToDevice));
   } else {
@@ -2039,7 +1792,7 @@ int af_gate_set_mode(af_engine *e, int32_t mode) {  // gate_controls.rs:75-81; g
   e->gate_mode = mode;
   if (mode == 0) drop_vad_evidence(e);  // (as on a detach: no fused call can follow until the mode changes again)
   if (mode == 0 && e->d_gate) {  // set_gate_mode(ThresholdOnly) clears the auto-relax counter at once
-    AF_HIP(hipSetDevice(e->device));
+    AF_HIP(e->use_device());
     AF_HIP(hipDeviceSynchronize());
     AF_HIP(hipMemset(e->d_gate + (int64_t)af::kGateRelax * e->n_streams, 0, sizeof(int64_t) * e->n_streams));
     // ... and puts gate_state back to Closed (gate.rs:814-815)
@@ -2113,7 +1866,7 @@ int af_engine_read_gate_vad_decisions(af_engine *e, float *probability, float *n
   if (n_blocks == 0) return AF_OK;
   const int64_t NS = e->n_streams;
   std::vector<uint32_t> rows((size_t)(n_blocks * af::kVadDecWords * NS));
-  AF_HIP(hipSetDevice(e->device));
+  AF_HIP(e->use_device());
   AF_HIP(hipDeviceSynchronize());
   AF_HIP(hipMemcpy(rows.data(), e->d_vad_dec, sizeof(uint32_t) * rows.size(), hipMemcpyDeviceToHost));
   for (int64_t b = 0; b < n_blocks; ++b)
@@ -2135,7 +1888,7 @@ int af_engine_read_gate_vad_state(af_engine *e, float *noise_floor_db, float *no
   const bool ctl_live = e->d_gate_vad && !e->vad_ctl_fresh, fused_live = e->d_gate_vad && !e->vad_fused_fresh;
   if (ctl_live || fused_live) {
     rows.resize((size_t)(af::kVadFields * NS));
-    AF_HIP(hipSetDevice(e->device));
+    AF_HIP(e->use_device());
     AF_HIP(hipDeviceSynchronize());
     AF_HIP(hipMemcpy(rows.data(), e->d_gate_vad, sizeof(uint32_t) * rows.size(), hipMemcpyDeviceToHost));
   }
@@ -2191,7 +1944,7 @@ int af_engine_read_gate_state(af_engine *e, float *current_gain, uint64_t *chatt
   std::vector<int64_t> rows;
   if (e->d_gate) {
     rows.resize((size_t)(af::kGateFields * NS));
-    AF_HIP(hipSetDevice(e->device));
+    AF_HIP(e->use_device());
     AF_HIP(hipDeviceSynchronize());
     AF_HIP(hipMemcpy(rows.data(), e->d_gate, sizeof(int64_t) * rows.size(), hipMemcpyDeviceToHost));
   }
@@ -2227,7 +1980,7 @@ int af_suppressor_debug_read(af_engine *e, int32_t frame, int32_t stream, float 
   if (!e || !e->supp.d_rec) return fail(AF_ERR_STATE, "no suppressor window has run");
   if (frame < 0 || frame >= e->supp.ws_frames || stream < 0 || stream >= e->n_streams)
     return fail(AF_ERR_INVALID_ARGUMENT, "frame/stream out of range");
-  AF_HIP(hipSetDevice(e->device));
+  AF_HIP(e->use_device());
   AF_HIP(hipDeviceSynchronize());
   const size_t cell = (size_t)frame * e->n_streams + stream;
   AF_HIP(hipMemcpy(rec_out, e->supp.d_rec + cell, sizeof(af::SuppFrameRec), hipMemcpyDeviceToHost));
@@ -2377,11 +2130,11 @@ static int process_device_impl(af_engine *e, const float *in, float *out, int64_
     return fail(AF_ERR_UNSUPPORTED, "this engine runs its front end in the noise gate's pre-pass, which needs stream-major audio");
   // ---- accepted: from here on the call only fails on a backend error
   if (e->gate_enabled && !e->d_gate) {
-    AF_HIP(hipMalloc(&e->d_gate, sizeof(int64_t) * af::kGateFields * e->n_streams));
-    AF_HIP(hipMemset(e->d_gate, 0, sizeof(int64_t) * af::kGateFields * e->n_streams));
+    AF_HIP(e->d_gate.reserve_exact(sizeof(int64_t) * af::kGateFields * e->n_streams));
+    AF_HIP(e->d_gate.keep_if(hipMemset(e->d_gate, 0, sizeof(int64_t) * af::kGateFields * e->n_streams)));
   }
   e->last_stream = stream;
-  (void)collect_retired(e, false);
+  e->retired.collect(false);
   const bool fused_gate = n_run > 0 && gate_vad_fused(e);
   af::VadGateArgs vad_args{};
   if (fused_gate)
@@ -2389,12 +2142,10 @@ static int process_device_impl(af_engine *e, const float *in, float *out, int64_
   if (e->supp.enabled) {
     const int64_t B = e->n_streams;
     if (e->pending > 0 || rem > 0) {
-      if (!e->d_pending) AF_HIP(hipMalloc(&e->d_pending, sizeof(float) * af::kRnnFrame * B));
+      AF_HIP(e->d_pending.reserve_exact(sizeof(float) * af::kRnnFrame * B));
       const size_t f4 = sizeof(float);
       if (n_run > 0) {
-        int64_t cap = e->asm_capacity * (int64_t)f4;  // (scratch of one call: grown geometrically, the old buffer retired)
-        if (int rc = grow_device(e, reinterpret_cast<void **>(&e->d_asm), &cap, B * n_run * (int64_t)f4, stream)) return rc;
-        e->asm_capacity = cap / (int64_t)f4;
+        AF_HIP(e->d_asm.reserve_retiring(f4 * B * n_run, e->retired, stream));  // (scratch of one call: grown geometrically, the old buffer retired)
         // [pending | head of this call] -> whole frames; the tail of this call waits (copied before anything writes `out`,
         // which may alias `in`)
         if (e->pending > 0)
@@ -2422,20 +2173,11 @@ static int process_device_impl(af_engine *e, const float *in, float *out, int64_
   e->last_launches = 0;
   if (n_samples == 0) return AF_OK;
   const int64_t rows = blocks * e->n_streams;
-  {
-    int64_t cap = e->stats_capacity * (int64_t)sizeof(af::BlockStats);
-    if (int rc = grow_device(e, reinterpret_cast<void **>(&e->d_stats), &cap, rows * (int64_t)sizeof(af::BlockStats), stream)) return rc;
-    e->stats_capacity = cap / (int64_t)sizeof(af::BlockStats);
-  }
+  AF_HIP(e->d_stats.reserve_retiring(sizeof(af::BlockStats) * rows, e->retired, stream));
   if (e->timing) {
-    if (!e->ev_start) {
-      AF_HIP(hipEventCreate(&e->ev_start));
-      AF_HIP(hipEventCreate(&e->ev_stop));
-      AF_HIP(hipEventCreate(&e->ev_mid));
-    }
-    AF_HIP(hipEventRecord(e->ev_start, stream));
+    for (af::Event *ev : {&e->ev_start, &e->ev_stop, &e->ev_mid}) AF_HIP(ev->create());
+    AF_HIP(hipEventRecord(e->ev_start.get(), stream));
   }
-  for (auto &pr : e->chain_ms_events) { (void)hipEventDestroy(pr.first); (void)hipEventDestroy(pr.second); }
   e->chain_ms_events.clear();
   // live control: the state edits of the setters called since the last call that ran the chain (this call's first sample is
   // the chain's next one); the parameter blocks they changed are uploaded below like any other change
@@ -2473,7 +2215,7 @@ static int process_device_impl(af_engine *e, const float *in, float *out, int64_
       AF_HIP(af::launch_gate_prepass(sa, stream));
     }
     e->last_launches += 1;
-    if (e->timing) AF_HIP(hipEventRecord(e->ev_mid, stream));  // the pre-pass counts as suppressor-side time
+    if (e->timing) AF_HIP(hipEventRecord(e->ev_mid.get(), stream));  // the pre-pass counts as suppressor-side time
     chain_in = out;
   }
   if (!e->supp.enabled && e->pipe.active) {
@@ -2519,8 +2261,8 @@ static int process_device_impl(af_engine *e, const float *in, float *out, int64_
       }
       e->pipe.windows += (int64_t)wins.size();
       if (e->timing) {
-        if (!gate_strip) AF_HIP(hipEventRecord(e->ev_mid, stream));
-        AF_HIP(hipEventRecord(e->ev_stop, stream));
+        if (!gate_strip) AF_HIP(hipEventRecord(e->ev_mid.get(), stream));
+        AF_HIP(hipEventRecord(e->ev_stop.get(), stream));
       }
       e->samples_processed += n_samples;
       return AF_OK;
@@ -2556,12 +2298,10 @@ static int process_device_impl(af_engine *e, const float *in, float *out, int64_
       }
       if (offload) {
         if (auto_mk) {
-          int64_t cap = e->block_power_capacity * (int64_t)sizeof(double);
-          if (int rc = grow_device(e, reinterpret_cast<void **>(&e->d_block_power), &cap, rows * (int64_t)sizeof(double), stream)) return rc;
-          e->block_power_capacity = cap / (int64_t)sizeof(double);
+          AF_HIP(e->d_block_power.reserve_retiring(sizeof(double) * rows, e->retired, stream));
         }
         AF_HIP(hipMemsetAsync(e->d_stats, 0, sizeof(af::BlockStats) * rows, stream));
-        if (!e->d_ready) AF_HIP(hipMalloc(&e->d_ready, sizeof(int64_t)));
+        AF_HIP(e->d_ready.reserve_exact(sizeof(int64_t)));
         AF_HIP(hipMemsetAsync(e->d_ready, 0, sizeof(int64_t), stream));
         hipEvent_t ev;
         if (int rc = engine_event(e, &ev)) return rc;
@@ -2575,9 +2315,8 @@ static int process_device_impl(af_engine *e, const float *in, float *out, int64_
                                           auto_mk ? e->d_block_power : nullptr, e->d_ready))
           return rc;
         if (!e->d_params_eq || e->eq_params_presets != 1) {
-          if (e->d_params_eq) AF_HIP(hipFree(e->d_params_eq));
-          e->d_params_eq = nullptr;
-          AF_HIP(hipMalloc(&e->d_params_eq, sizeof(af::ChainParams) * kEqParamSlots));
+          e->d_params_eq.release();
+          AF_HIP(e->d_params_eq.reserve_exact(sizeof(af::ChainParams) * kEqParamSlots));
           e->eq_params_presets = 1;
           e->uploaded_eq.clear();
         }
@@ -2606,8 +2345,8 @@ static int process_device_impl(af_engine *e, const float *in, float *out, int64_
           AF_HIP(hipStreamWaitEvent(stream, ev, 0));
         }
         if (e->timing) {
-          if (!gate_strip) AF_HIP(hipEventRecord(e->ev_mid, stream));
-          AF_HIP(hipEventRecord(e->ev_stop, stream));
+          if (!gate_strip) AF_HIP(hipEventRecord(e->ev_mid.get(), stream));
+          AF_HIP(hipEventRecord(e->ev_stop.get(), stream));
         }
         e->samples_processed += n_samples;
         return AF_OK;
@@ -2625,8 +2364,8 @@ static int process_device_impl(af_engine *e, const float *in, float *out, int64_
     }
     if (rc) return rc;
     if (e->timing) {
-      if (!gate_strip) AF_HIP(hipEventRecord(e->ev_mid, stream));  // no suppressor: everything is chain time
-      AF_HIP(hipEventRecord(e->ev_stop, stream));
+      if (!gate_strip) AF_HIP(hipEventRecord(e->ev_mid.get(), stream));  // no suppressor: everything is chain time
+      AF_HIP(hipEventRecord(e->ev_stop.get(), stream));
     }
     e->samples_processed += n_samples;
     return AF_OK;
@@ -2723,12 +2462,9 @@ static int process_device_impl(af_engine *e, const float *in, float *out, int64_
     AF_HIP(e->supp.ensure_workspace(e->n_streams, (int)longest));
   }
   if (e->trace) {
-    if (frames * e->n_streams > e->trace_capacity) {
+    if (sizeof(int32_t) * 2 * frames * e->n_streams > e->d_trace.bytes()) {
       AF_HIP(hipDeviceSynchronize());
-      if (e->d_trace) AF_HIP(hipFree(e->d_trace));
-      e->d_trace = nullptr;
-      AF_HIP(hipMalloc(&e->d_trace, sizeof(int32_t) * 2 * frames * e->n_streams));
-      e->trace_capacity = frames * e->n_streams;
+      AF_HIP(e->d_trace.reserve_exact(sizeof(int32_t) * 2 * frames * e->n_streams));
     }
     e->trace_frames = frames;
   }
@@ -2770,9 +2506,7 @@ static int process_device_impl(af_engine *e, const float *in, float *out, int64_
   const bool auto_makeup_call = (run.flags & af::kFlagCompressor) && run.comp.auto_makeup_enabled;
   if (eq_offload && auto_makeup_call && !e->pipe.active) {
     // the systolic EQ kernel is then also the pre-pass of every window (it leaves the compressor-input block powers here)
-    int64_t cap = e->block_power_capacity * (int64_t)sizeof(double);
-    if (int rc = grow_device(e, reinterpret_cast<void **>(&e->d_block_power), &cap, rows * (int64_t)sizeof(double), stream)) return rc;
-    e->block_power_capacity = cap / (int64_t)sizeof(double);
+    AF_HIP(e->d_block_power.reserve_retiring(sizeof(double) * rows, e->retired, stream));
   }
   auto next_event = [&](hipEvent_t *out_ev) -> int { return engine_event(e, out_ev); };
   // The call's statistics rows are cleared ONCE, here (their fields are written by the kernels that own them).  Round 2 cleared
@@ -2798,7 +2532,7 @@ static int process_device_impl(af_engine *e, const float *in, float *out, int64_
                     af::ring_kernel_dynamic_lds(run.n_eq_sections, run.lim.lookahead_samples, false) <= af::kMaxLdsBytes &&
                     (!auto_makeup_call || e->d_block_power != nullptr) && win_f0.size() >= 2;
   if (persistent) {
-    if (!e->d_ready) AF_HIP(hipMalloc(&e->d_ready, sizeof(int64_t)));
+    AF_HIP(e->d_ready.reserve_exact(sizeof(int64_t)));
     AF_HIP(hipMemsetAsync(e->d_ready, 0, sizeof(int64_t), stream));
   }
   {  // the side streams start after whatever the caller queued before this call
@@ -3019,9 +2753,8 @@ static int process_device_impl(af_engine *e, const float *in, float *out, int64_
         const hipStream_t es = (eq_on_fin && fin && fin != syn) ? fin : e->eq_stream;
         AF_HIP(hipStreamWaitEvent(es, syn_done[w], 0));
         if (!e->d_params_eq || e->eq_params_presets != n_presets) {
-          if (e->d_params_eq) AF_HIP(hipFree(e->d_params_eq));
-          e->d_params_eq = nullptr;
-          AF_HIP(hipMalloc(&e->d_params_eq, sizeof(af::ChainParams) * n_presets * kEqParamSlots));  // (sized as the stage pipeline sizes it)
+          e->d_params_eq.release();
+          AF_HIP(e->d_params_eq.reserve_exact(sizeof(af::ChainParams) * n_presets * kEqParamSlots));  // (sized as the stage pipeline sizes it)
           e->eq_params_presets = n_presets;
           e->uploaded_eq.clear();
         }
@@ -3126,7 +2859,7 @@ static int process_device_impl(af_engine *e, const float *in, float *out, int64_
     if (strip_front) run.flags &= ~(front | af::kFlagInputScrub);
     blocks_done += (seg_n + cb - 1) / cb;
   }
-  if (e->timing) AF_HIP(hipEventRecord(e->ev_mid, (fin && fin != syn) ? fin : syn));  // last suppressor kernel done
+  if (e->timing) AF_HIP(hipEventRecord(e->ev_mid.get(), (fin && fin != syn) ? fin : syn));  // last suppressor kernel done
   if (syn != stream && n_windows > 0) AF_HIP(hipStreamWaitEvent(stream, syn_done[n_windows - 1], 0));
   {
     hipEvent_t ev;
@@ -3149,7 +2882,7 @@ static int process_device_impl(af_engine *e, const float *in, float *out, int64_
     AF_HIP(hipEventRecord(ev, ds));
     AF_HIP(hipStreamWaitEvent(stream, ev, 0));
   }
-  if (e->timing) AF_HIP(hipEventRecord(e->ev_stop, stream));
+  if (e->timing) AF_HIP(hipEventRecord(e->ev_stop.get(), stream));
   e->samples_processed += n_samples;
   return AF_OK;
 }
@@ -3180,12 +2913,7 @@ static int process_host_impl(af_engine *e, const float *in, int64_t n_in, float 
                 "use af_engine_stream_host with a larger out_stride", (long long)produced, e->pending, (long long)out_stride);
   const int64_t io_stride = stream_major ? std::max<int64_t>(std::max(n_in, produced), 1) : B;
   const int64_t total = stream_major ? io_stride * B : n_in * B;
-  if (total > e->io_capacity) {
-    if (e->d_io) AF_HIP(hipFree(e->d_io));
-    e->d_io = nullptr;
-    AF_HIP(hipMalloc(&e->d_io, sizeof(float) * total));
-    e->io_capacity = total;
-  }
+  AF_HIP(e->d_io.reserve_exact(sizeof(float) * total));
   if (n_in > 0) {
     if (stream_major)
       AF_HIP(hipMemcpy2D(e->d_io, sizeof(float) * io_stride, in, sizeof(float) * n_in, sizeof(float) * n_in, B, hipMemcpyHostToDevice));
@@ -3392,19 +3120,18 @@ static int stream_host_resampled(af_engine *e, const float *in, int64_t n_in, fl
                 (long long)std::max(m3, ow_width), (long long)out_stride);
   const int64_t B = e->n_streams;
   const int64_t C = e->mix ? af_mixdown_channels(e->mix) : 1;  // in[(s * n_in + t) * C + c]
-  for (int64_t i = 0; i < B * n_in * C; ++i)
-    if (!std::isfinite(in[i])) return fail(AF_ERR_NON_FINITE, "samples must be finite");
+  if (!af::check_finite(in, 1, B * n_in * C, 0)) return fail(AF_ERR_NON_FINITE, "samples must be finite");
   if (int rc = ensure_started(e)) return rc;
   if (int rc = check_evidence_blocks(e, m2)) return rc;
   // ---- accepted
   const int64_t f4 = sizeof(float);
   const int64_t mid_stride = std::max<int64_t>(m1, 1) + af::kRnnFrame;  // the engine may return up to 479 frames more than it got
-  if (int rc = grow_device(e, reinterpret_cast<void **>(&e->d_rs_in), &e->rs_in_capacity, f4 * B * std::max<int64_t>(n_in, 1), nullptr)) return rc;
-  if (int rc = grow_device(e, reinterpret_cast<void **>(&e->d_rs_mid), &e->rs_mid_capacity, f4 * B * mid_stride, nullptr)) return rc;
-  if (int rc = grow_device(e, reinterpret_cast<void **>(&e->d_rs_out), &e->rs_out_capacity, f4 * B * std::max<int64_t>(m3, 1), nullptr)) return rc;
+  AF_HIP(e->d_rs_in.reserve_retiring(f4 * B * std::max<int64_t>(n_in, 1), e->retired, nullptr));
+  AF_HIP(e->d_rs_mid.reserve_retiring(f4 * B * mid_stride, e->retired, nullptr));
+  AF_HIP(e->d_rs_out.reserve_retiring(f4 * B * std::max<int64_t>(m3, 1), e->retired, nullptr));
   int64_t got = 0;
   if (e->mix) {  // the capture callback's mixdown first (input.rs:785-843): mono into what the mono path would have uploaded
-    if (int rc = grow_device(e, reinterpret_cast<void **>(&e->d_mix_in), &e->mix_in_capacity, f4 * B * C * std::max<int64_t>(n_in, 1), nullptr)) return rc;
+    AF_HIP(e->d_mix_in.reserve_retiring(f4 * B * C * std::max<int64_t>(n_in, 1), e->retired, nullptr));
     if (n_in > 0) {
       AF_HIP(hipMemcpy(e->d_mix_in, in, f4 * B * n_in * C, hipMemcpyHostToDevice));
       if (int rc = af_mixdown_push_device(e->mix, e->d_mix_in, n_in, n_in, e->rs_in ? e->d_rs_in : e->d_rs_mid,
@@ -3437,11 +3164,9 @@ static int stream_host_resampled(af_engine *e, const float *in, int64_t n_in, fl
       AF_HIP(hipStreamSynchronize(nullptr));
       return check_device_status(e);
     }
-    if (!e->d_ow_fill) {
-      AF_HIP(hipMalloc(&e->d_ow_fill, sizeof(int64_t) * (size_t)B));
-      AF_HIP(hipMalloc(&e->d_ow_written, sizeof(int64_t) * (size_t)B));
-    }
-    if (int rc = grow_device(e, reinterpret_cast<void **>(&e->d_ow_out), &e->ow_out_capacity, f4 * B * ow_width, nullptr)) return rc;
+    AF_HIP(e->d_ow_fill.reserve_exact(sizeof(int64_t) * (size_t)B));
+    AF_HIP(e->d_ow_written.reserve_exact(sizeof(int64_t) * (size_t)B));
+    AF_HIP(e->d_ow_out.reserve_retiring(f4 * B * ow_width, e->retired, nullptr));
     if (e->ow_fill_dirty) {  // uploaded when af_engine_set_output_queue_fill (or a reset) changed it, not per call
       if (e->ow_fill.empty()) e->ow_fill.assign((size_t)B, e->ow_target_center);  // no evidence yet: no error
       AF_HIP(hipMemcpy(e->d_ow_fill, e->ow_fill.data(), sizeof(int64_t) * (size_t)B, hipMemcpyHostToDevice));
@@ -3493,12 +3218,11 @@ int af_suppressor_debug_scale_for_model(const float *in, float *out, int64_t n, 
   if ((!in || !out) && n > 0) return fail(AF_ERR_INVALID_ARGUMENT, "null argument");
   if (n <= 0) return AF_OK;
   AF_HIP(hipSetDevice(device));
-  float *d = nullptr;
-  AF_HIP(hipMalloc(&d, sizeof(float) * n));
+  af::DeviceBuffer<float> d;
+  AF_HIP(d.reserve_exact(sizeof(float) * n));
   hipError_t err = hipMemcpy(d, in, sizeof(float) * n, hipMemcpyHostToDevice);
   if (err == hipSuccess) err = af::launch_scale_probe(d, d, n, nullptr);
   if (err == hipSuccess) err = hipMemcpy(out, d, sizeof(float) * n, hipMemcpyDeviceToHost);
-  (void)hipFree(d);
   if (err != hipSuccess) return fail(AF_ERR_BACKEND, "scale probe failed: %s", hipGetErrorString(err));
   return AF_OK;
 }
@@ -3514,7 +3238,7 @@ int af_suppressor_read_trace(af_engine *e, int32_t *out, int64_t capacity_frames
   if (capacity_frames < e->trace_frames)
     return fail(AF_ERR_INVALID_ARGUMENT, "capacity %lld < %lld frames", (long long)capacity_frames, (long long)e->trace_frames);
   if (e->trace_frames == 0) return AF_OK;
-  AF_HIP(hipSetDevice(e->device));
+  AF_HIP(e->use_device());
   AF_HIP(hipStreamSynchronize(e->last_stream));
   AF_HIP(hipMemcpy(out, e->d_trace, sizeof(int32_t) * 2 * e->trace_frames * e->n_streams, hipMemcpyDeviceToHost));
   return AF_OK;
@@ -3523,7 +3247,7 @@ int af_suppressor_read_trace(af_engine *e, int32_t *out, int64_t capacity_frames
 int af_engine_synchronize(af_engine *e) {
   if (!e) return fail(AF_ERR_INVALID_ARGUMENT, "engine is null");
   if (!e->started) return AF_OK;
-  AF_HIP(hipSetDevice(e->device));
+  AF_HIP(e->use_device());
   AF_HIP(hipStreamSynchronize(e->last_stream));
   return check_device_status(e);
 }
@@ -3536,7 +3260,7 @@ int af_engine_read_block_stats(af_engine *e, af_block_stats *out, int64_t capaci
   const int64_t rows = e->last_blocks * e->n_streams;
   if (capacity < rows) return fail(AF_ERR_INVALID_ARGUMENT, "capacity %lld < %lld rows", (long long)capacity, (long long)rows);
   if (rows == 0) return AF_OK;
-  AF_HIP(hipSetDevice(e->device));
+  AF_HIP(e->use_device());
   AF_HIP(hipStreamSynchronize(e->last_stream));
   AF_HIP(hipMemcpy(out, e->d_stats, sizeof(af::BlockStats) * rows, hipMemcpyDeviceToHost));
   return check_device_status(e);
@@ -3547,10 +3271,10 @@ int af_engine_last_kernel_ms(af_engine *e, double *ms, int32_t *launches) {
   *ms = 0.0;
   if (launches) *launches = e->last_launches;
   if (!e->timing || !e->ev_start || e->last_launches == 0) return AF_OK;
-  AF_HIP(hipSetDevice(e->device));
-  AF_HIP(hipEventSynchronize(e->ev_stop));
+  AF_HIP(e->use_device());
+  AF_HIP(hipEventSynchronize(e->ev_stop.get()));
   float t = 0.0f;
-  AF_HIP(hipEventElapsedTime(&t, e->ev_start, e->ev_stop));
+  AF_HIP(hipEventElapsedTime(&t, e->ev_start.get(), e->ev_stop.get()));
   *ms = (double)t;
   return AF_OK;
 }
@@ -3559,18 +3283,16 @@ int af_engine_last_stage_ms(af_engine *e, double *suppressor_ms, double *chain_m
   if (!e || !suppressor_ms || !chain_ms) return fail(AF_ERR_INVALID_ARGUMENT, "null argument");
   *suppressor_ms = *chain_ms = 0.0;
   if (!e->timing || !e->ev_start || e->last_launches == 0) return AF_OK;
-  AF_HIP(hipSetDevice(e->device));
-  AF_HIP(hipEventSynchronize(e->ev_stop));
+  AF_HIP(e->use_device());
+  AF_HIP(hipEventSynchronize(e->ev_stop.get()));
   float t = 0.0f;
-  AF_HIP(hipEventElapsedTime(&t, e->ev_start, e->ev_mid));
+  AF_HIP(hipEventElapsedTime(&t, e->ev_start.get(), e->ev_mid.get()));
   *suppressor_ms = (double)t;
-  double chain = 0.0;
-  for (auto &pr : e->chain_ms_events) {
-    AF_HIP(hipEventSynchronize(pr.second));
-    AF_HIP(hipEventElapsedTime(&t, pr.first, pr.second));
-    chain += (double)t;
+  for (const af::TimedSpan &span : e->chain_ms_events) {
+    double ms = 0.0;
+    AF_HIP(span.elapsed_ms(&ms));
+    *chain_ms += ms;  // summed over the chain launches of the call (they may overlap suppressor kernels)
   }
-  *chain_ms = chain;  // summed over the chain launches of the call (they may overlap suppressor kernels)
   return AF_OK;
 }
 
@@ -3579,12 +3301,11 @@ int af_engine_last_chain_launch_ms(af_engine *e, double *first_ms, double *tail_
   *first_ms = *tail_ms = 0.0;
   if (segments) *segments = (int32_t)e->chain_ms_events.size();
   if (!e->timing || !e->ev_start || e->last_launches == 0) return AF_OK;
-  AF_HIP(hipSetDevice(e->device));
-  float t = 0.0f;
-  for (auto &pr : e->chain_ms_events) {
-    AF_HIP(hipEventSynchronize(pr.second));
-    AF_HIP(hipEventElapsedTime(&t, pr.first, pr.second));
-    *first_ms += (double)t;
+  AF_HIP(e->use_device());
+  for (const af::TimedSpan &span : e->chain_ms_events) {
+    double ms = 0.0;
+    AF_HIP(span.elapsed_ms(&ms));
+    *first_ms += ms;
   }
   return AF_OK;
 }
@@ -3636,876 +3357,6 @@ int af_eq_magnitude_response_v2(const double *freqs, size_t n, const af_eq_band_
 int af_engine_eq_magnitude_response(const af_engine *e, const double *freqs, size_t n, double *out_db) {
   if (!e || (!freqs && n) || (!out_db && n)) return fail(AF_ERR_INVALID_ARGUMENT, "null argument");
   for (size_t i = 0; i < n; ++i) out_db[i] = cur(e).eq.magnitude_db(freqs[i]);
-  return AF_OK;
-}
-
-}  // extern "C"
-
-// ------------------------------------------------------------------------------------------
-// Product resampler (rust-core/src/audio/processor/resampling.rs:140-261)
-struct af_resampler {
-  af::ResamplePlan plan;
-  int device = 0;
-  std::vector<af::ResamplePos> pos;
-  int64_t planned_n_in = -1, planned_n_out = 0, planned_blocks = 0, uploaded_n_in = -1;
-  double *d_table = nullptr;
-  af::ResamplePos *d_pos = nullptr;
-  int64_t pos_capacity = 0;
-  double *d_in = nullptr, *d_out = nullptr;
-  int64_t in_capacity = 0, out_capacity = 0;
-  hipEvent_t ev0 = nullptr, ev1 = nullptr;
-  bool timed = false;
-  int variant = 0;  // 0: matrix-core kernel (64 streams per workgroup) when the shape allows; AF_RESAMPLER_VARIANT=valu -> 1: vector kernel, =mfma32 -> 2: matrix-core kernel with 32 streams per workgroup
-};
-
-namespace {
-// host only: replay the reference's chunk loop for n_in frames
-int resampler_plan(af_resampler *r, int64_t n_in) {
-  if (r->planned_n_in == n_in) return AF_OK;
-  r->planned_n_out = r->plan.positions(n_in, r->pos, &r->planned_blocks);
-  r->planned_n_in = n_in;
-  r->uploaded_n_in = -1;
-  return AF_OK;
-}
-// device side of the plan: coefficient table (once) and the position records of the current plan
-int resampler_upload(af_resampler *r) {
-  AF_HIP(hipSetDevice(r->device));
-  if (!r->d_table) {
-    AF_HIP(hipMalloc(&r->d_table, sizeof(double) * r->plan.table.size()));
-    AF_HIP(hipMemcpy(r->d_table, r->plan.table.data(), sizeof(double) * r->plan.table.size(), hipMemcpyHostToDevice));
-  }
-  if (r->uploaded_n_in == r->planned_n_in) return AF_OK;
-  if (r->planned_n_out > r->pos_capacity) {
-    if (r->d_pos) AF_HIP(hipFree(r->d_pos));
-    r->d_pos = nullptr;
-    AF_HIP(hipMalloc(&r->d_pos, sizeof(af::ResamplePos) * r->planned_n_out));
-    r->pos_capacity = r->planned_n_out;
-  }
-  if (r->planned_n_out > 0)
-    AF_HIP(hipMemcpy(r->d_pos, r->pos.data(), sizeof(af::ResamplePos) * r->planned_n_out, hipMemcpyHostToDevice));
-  r->uploaded_n_in = r->planned_n_in;
-  return AF_OK;
-}
-// the argument checks of simulate_product_resampler, resampling.rs:187-214, and what the kernels' LDS tiles hold; host only
-int resampler_check_arguments(uint32_t input_rate, uint32_t output_rate, int64_t chunk_size, int32_t sinc_len, int32_t window,
-                              int32_t device) {
-  if (input_rate == 0 || output_rate == 0) return fail(AF_ERR_INVALID_ARGUMENT, "sample rates must be positive");
-  if (chunk_size < 1 || chunk_size > 1024) return fail(AF_ERR_INVALID_ARGUMENT, "chunk_size must be between 1 and 1024");
-  if (sinc_len < 32 || sinc_len > 2048 || (sinc_len & (sinc_len - 1)) != 0)
-    return fail(AF_ERR_INVALID_ARGUMENT, "sinc_len must be a power of two between 32 and 2048");
-  if (window < 0 || window > af::kWinHann2) return fail(AF_ERR_INVALID_ARGUMENT, "unsupported resampler window %d", window);
-  if (device < 0) return fail(AF_ERR_INVALID_ARGUMENT, "device must be >= 0");
-  const double ratio = (double)output_rate / (double)input_rate;
-  if (chunk_size <= (int64_t)sinc_len + 1 + (int64_t)std::ceil(1.0 / ratio))
-    return fail(AF_ERR_UNSUPPORTED, "chunk_size %lld is too short for sinc_len %d: the reference's chunk loop would produce no frames",
-                (long long)chunk_size, sinc_len);
-  if (af::resample_segment_outputs(ratio, sinc_len) == 0)
-    return fail(AF_ERR_UNSUPPORTED, "sinc_len %d at ratio %.4f needs a longer input span than the LDS tile holds", sinc_len, ratio);
-  return AF_OK;
-}
-}  // namespace
-
-extern "C" {
-
-int af_resampler_calculate_cutoff(int32_t sinc_len, int32_t window, float *out) {
-  if (!out) return fail(AF_ERR_INVALID_ARGUMENT, "out is null");
-  if (window < 0 || window > af::kWinHann2) return fail(AF_ERR_INVALID_ARGUMENT, "unsupported resampler window %d", window);
-  *out = af::resample_calculate_cutoff(sinc_len, window);
-  return AF_OK;
-}
-
-int af_resampler_create(uint32_t input_rate, uint32_t output_rate, int64_t chunk_size, int32_t sinc_len, int32_t window,
-                        int32_t device, af_resampler **out) {
-  if (!out) return fail(AF_ERR_INVALID_ARGUMENT, "out is null");
-  *out = nullptr;
-  if (int rc = resampler_check_arguments(input_rate, output_rate, chunk_size, sinc_len, window, device)) return rc;
-  af_resampler *r = new af_resampler();
-  r->device = device;
-  r->plan.build(input_rate, output_rate, chunk_size, sinc_len, window);
-  if (const char *env = std::getenv("AF_RESAMPLER_VARIANT")) r->variant = std::strcmp(env, "valu") == 0 ? 1 : (std::strcmp(env, "mfma32") == 0 ? 2 : 0);
-  *out = r;
-  return AF_OK;
-}
-
-void af_resampler_destroy(af_resampler *r) {
-  if (!r) return;
-  if (r->d_table || r->d_pos || r->d_in || r->d_out) {
-    (void)hipSetDevice(r->device);
-    (void)hipDeviceSynchronize();
-    (void)hipFree(r->d_table);
-    (void)hipFree(r->d_pos);
-    (void)hipFree(r->d_in);
-    (void)hipFree(r->d_out);
-  }
-  if (r->ev0) (void)hipEventDestroy(r->ev0);
-  if (r->ev1) (void)hipEventDestroy(r->ev1);
-  delete r;
-}
-
-int af_resampler_output_delay(const af_resampler *r) { return r ? r->plan.output_delay() : 0; }
-int64_t af_resampler_expected_frames(const af_resampler *r, int64_t n_in) { return r ? r->plan.expected_frames(n_in) : 0; }
-int af_resampler_sinc_len(const af_resampler *r) { return r ? r->plan.sinc_len : 0; }
-
-int af_resampler_copy_sinc_table(const af_resampler *r, double *out) {
-  if (!r || !out) return fail(AF_ERR_INVALID_ARGUMENT, "null argument");
-  const int stride = r->plan.row_stride();
-  for (int row = 0; row < af::kResampleOversampling; ++row)
-    std::memcpy(out + (size_t)row * r->plan.sinc_len, r->plan.table.data() + (size_t)row * stride + af::kResampleTablePad,
-                sizeof(double) * r->plan.sinc_len);
-  return AF_OK;
-}
-
-int af_resampler_plan(af_resampler *r, int64_t n_in, int64_t *n_out, int64_t *blocks) {
-  if (!r) return fail(AF_ERR_INVALID_ARGUMENT, "resampler is null");
-  if (n_in < 0) return fail(AF_ERR_INVALID_ARGUMENT, "n_in must be >= 0");
-  if (int rc = resampler_plan(r, n_in)) return rc;
-  if (n_out) *n_out = r->planned_n_out;
-  if (blocks) *blocks = r->planned_blocks;
-  return AF_OK;
-}
-
-int af_resampler_process_device(af_resampler *r, const double *d_in, double *d_out, int64_t n_in, int32_t n_streams,
-                                int64_t in_stride, int64_t out_stride, void *stream) {
-  if (!r) return fail(AF_ERR_INVALID_ARGUMENT, "resampler is null");
-  if (n_streams <= 0) return fail(AF_ERR_INVALID_ARGUMENT, "n_streams must be positive");
-  if (n_in < 0 || in_stride < n_in) return fail(AF_ERR_INVALID_ARGUMENT, "in_stride must cover n_in frames");
-  if (int rc = resampler_plan(r, n_in)) return rc;
-  if (out_stride < r->planned_n_out) return fail(AF_ERR_INVALID_ARGUMENT, "out_stride must cover the %lld planned output frames", (long long)r->planned_n_out);
-  if ((!d_in && n_in > 0) || !d_out) return fail(AF_ERR_INVALID_ARGUMENT, "null device buffer");
-  if (int rc = resampler_upload(r)) return rc;
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  if (!r->ev0) {
-    AF_HIP(hipEventCreate(&r->ev0));
-    AF_HIP(hipEventCreate(&r->ev1));
-  }
-  AF_HIP(hipEventRecord(r->ev0, s));
-  AF_HIP(af::launch_resample(d_in, d_out, r->d_pos, r->d_table, n_in, r->planned_n_out, in_stride, out_stride, n_streams,
-                             r->plan.sinc_len, r->plan.ratio, r->variant, s));
-  AF_HIP(hipEventRecord(r->ev1, s));
-  r->timed = true;
-  return AF_OK;
-}
-
-int af_resampler_process_host(af_resampler *r, const double *in, double *out, int64_t n_in, int32_t n_streams,
-                              int64_t in_stride, int64_t out_stride) {
-  if (!r) return fail(AF_ERR_INVALID_ARGUMENT, "resampler is null");
-  if (n_streams <= 0) return fail(AF_ERR_INVALID_ARGUMENT, "n_streams must be positive");
-  if ((!in && n_in > 0) || !out) return fail(AF_ERR_INVALID_ARGUMENT, "null buffer");
-  if (n_in < 0 || in_stride < n_in) return fail(AF_ERR_INVALID_ARGUMENT, "in_stride must cover n_in frames");
-  for (int64_t s = 0; s < n_streams; ++s)
-    for (int64_t i = 0; i < n_in; ++i)
-      if (!std::isfinite(in[s * in_stride + i])) return fail(AF_ERR_NON_FINITE, "samples must be finite");
-  if (int rc = resampler_plan(r, n_in)) return rc;
-  const int64_t n_out = r->planned_n_out;
-  if (out_stride < n_out) return fail(AF_ERR_INVALID_ARGUMENT, "out_stride must cover the %lld planned output frames", (long long)n_out);
-  const int64_t need_in = std::max<int64_t>(1, (int64_t)n_streams * n_in), need_out = std::max<int64_t>(1, (int64_t)n_streams * n_out);
-  if (need_in > r->in_capacity) {
-    if (r->d_in) AF_HIP(hipFree(r->d_in));
-    r->d_in = nullptr;
-    AF_HIP(hipMalloc(&r->d_in, sizeof(double) * need_in));
-    r->in_capacity = need_in;
-  }
-  if (need_out > r->out_capacity) {
-    if (r->d_out) AF_HIP(hipFree(r->d_out));
-    r->d_out = nullptr;
-    AF_HIP(hipMalloc(&r->d_out, sizeof(double) * need_out));
-    r->out_capacity = need_out;
-  }
-  if (n_in > 0)
-    AF_HIP(hipMemcpy2D(r->d_in, sizeof(double) * n_in, in, sizeof(double) * in_stride, sizeof(double) * n_in, n_streams, hipMemcpyHostToDevice));
-  if (int rc = af_resampler_process_device(r, r->d_in, r->d_out, n_in, n_streams, n_in > 0 ? n_in : 1, n_out, nullptr)) return rc;
-  AF_HIP(hipStreamSynchronize(nullptr));
-  if (n_out > 0)
-    AF_HIP(hipMemcpy2D(out, sizeof(double) * out_stride, r->d_out, sizeof(double) * n_out, sizeof(double) * n_out, n_streams, hipMemcpyDeviceToHost));
-  return AF_OK;
-}
-
-// host only: the kernel af_resampler_process_* launches for this plan (af::resample_pick_form, the launcher's own choice)
-int af_resampler_launch_form(const af_resampler *r, int32_t *form, int32_t *segment_outputs, int32_t *streams_per_workgroup) {
-  if (!r) return fail(AF_ERR_INVALID_ARGUMENT, "resampler is null");
-  const af::ResampleForm f = af::resample_pick_form(r->plan.ratio, r->plan.sinc_len, r->variant);
-  if (form) *form = f.form;
-  if (segment_outputs) *segment_outputs = f.segment_outputs;
-  if (streams_per_workgroup) *streams_per_workgroup = f.streams_per_workgroup;
-  return AF_OK;
-}
-
-int af_resampler_last_kernel_ms(af_resampler *r, double *ms) {
-  if (!r || !ms) return fail(AF_ERR_INVALID_ARGUMENT, "null argument");
-  *ms = 0.0;
-  if (!r->timed) return AF_OK;
-  AF_HIP(hipEventSynchronize(r->ev1));
-  float t = 0.0f;
-  AF_HIP(hipEventElapsedTime(&t, r->ev0, r->ev1));
-  *ms = t;
-  return AF_OK;
-}
-
-}  // extern "C"
-
-// ------------------------------------------------------------------------------------------
-// The product resampler as a stream (dsp_loop.rs:274-317, 843-895, 963-1011): state carried across calls, f32 in and out.
-// Kernels and the layout of the carried plane: af_resampler_stream.hip.
-struct af_stream_resampler {
-  af::ResamplePlan plan;
-  int device = 0, n_streams = 0;
-  int variant = 0;             // as af_resampler::variant
-  int32_t plane_stride = 0;    // 2 * sinc_len + chunk - 1 frames per stream
-  // host state: all streams advance in lock step
-  double last_index = 0.0;     // SincFixedIn::last_index, advanced by the crate's repeated addition
-  int64_t pending = 0;         // frames queued behind the history that do not fill a chunk yet
-  int64_t chunks = 0, frames_in = 0, frames_out = 0;
-  bool fresh = true;           // the history has to be zeroed in front of the next launch (create, reset)
-  // device state
-  double *d_table = nullptr;
-  float *d_plane[2] = {nullptr, nullptr};  // ping-pong pair, [n_streams][plane_stride]
-  int cur = 0;
-  // per-call scratch: the position records of the chunks the call completes
-  std::vector<af::ResamplePos> pos;
-  af::ResamplePos *d_pos = nullptr;
-  int64_t pos_capacity = 0;    // bytes
-  struct Retired { void *p; hipEvent_t ev; };
-  std::vector<Retired> retired;
-  struct Stager {              // pinned slots, as af_engine::ParamStager: the host never waits for a stream
-    static constexpr int kSlots = 8;
-    void *pinned[kSlots] = {};
-    size_t bytes[kSlots] = {};
-    hipEvent_t done[kSlots] = {};
-    bool used[kSlots] = {};
-    int next = 0;
-  } stager;
-  float *d_in = nullptr, *d_out = nullptr;  // staging of the host entry point
-  int64_t in_capacity = 0, out_capacity = 0;
-  hipEvent_t ev0 = nullptr, ev1 = nullptr;
-  bool timed = false;
-};
-
-namespace {
-
-struct StreamReplay { int64_t chunks, n_out, rem; double last_index; };
-// What a push of n_in frames does, replayed on the host: changes nothing.  With `pos`, the position records of the frames
-// it produces, on the call's virtual axis (chunk j's buffer starts at axis frame j * chunk, its input 2 * sinc_len later).
-StreamReplay stream_replay(const af_stream_resampler *r, int64_t n_in, std::vector<af::ResamplePos> *pos) {
-  const int64_t total = r->pending + n_in, chunk = r->plan.chunk;
-  StreamReplay p{total / chunk, 0, total % chunk, r->last_index};
-  if (pos) pos->clear();
-  for (int64_t j = 0; j < p.chunks; ++j)
-    p.n_out += r->plan.chunk_positions(p.last_index, j * chunk + 2 * (int64_t)r->plan.sinc_len, pos);
-  return p;
-}
-
-int stream_collect_retired(af_stream_resampler *r, bool all) {
-  size_t kept = 0;
-  for (auto &x : r->retired) {
-    hipError_t q = all ? hipEventSynchronize(x.ev) : hipEventQuery(x.ev);
-    if (q == hipSuccess) {
-      (void)hipFree(x.p);
-      (void)hipEventDestroy(x.ev);
-    } else {
-      if (q != hipErrorNotReady) (void)hipGetLastError();
-      r->retired[kept++] = x;
-    }
-  }
-  r->retired.resize(kept);
-  return AF_OK;
-}
-
-// the call's position records -> d_pos behind everything queued on `stream`, through a pinned slot
-int stream_upload_positions(af_stream_resampler *r, hipStream_t stream) {
-  const int64_t need = (int64_t)(sizeof(af::ResamplePos) * r->pos.size());
-  if (need > r->pos_capacity) {  // per-call scratch: grown geometrically, the old buffer retired behind an event
-    const int64_t cap = std::max<int64_t>(need, r->pos_capacity + r->pos_capacity / 2);
-    void *fresh = nullptr;
-    AF_HIP(hipMalloc(&fresh, (size_t)cap));
-    if (r->d_pos) {
-      hipEvent_t ev;
-      AF_HIP(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
-      AF_HIP(hipEventRecord(ev, stream));
-      r->retired.push_back({r->d_pos, ev});
-    }
-    r->d_pos = static_cast<af::ResamplePos *>(fresh);
-    r->pos_capacity = cap;
-  }
-  auto &st = r->stager;
-  const int slot = st.next;
-  st.next = (st.next + 1) % af_stream_resampler::Stager::kSlots;
-  if (!st.done[slot]) AF_HIP(hipEventCreateWithFlags(&st.done[slot], hipEventDisableTiming));
-  if (st.used[slot]) AF_HIP(hipEventSynchronize(st.done[slot]));  // kSlots pushes ago: normally long done
-  if ((size_t)need > st.bytes[slot]) {
-    if (st.pinned[slot]) AF_HIP(hipHostFree(st.pinned[slot]));
-    st.pinned[slot] = nullptr;
-    const size_t cap = std::max<size_t>((size_t)need, st.bytes[slot] + st.bytes[slot] / 2);
-    st.bytes[slot] = 0;
-    AF_HIP(hipHostMalloc(&st.pinned[slot], cap, hipHostMallocDefault));
-    st.bytes[slot] = cap;
-  }
-  std::memcpy(st.pinned[slot], r->pos.data(), (size_t)need);
-  AF_HIP(hipMemcpyAsync(r->d_pos, st.pinned[slot], (size_t)need, hipMemcpyHostToDevice, stream));
-  AF_HIP(hipEventRecord(st.done[slot], stream));
-  st.used[slot] = true;
-  return AF_OK;
-}
-
-// The device half of a push whose replay `p` (with r->pos filled) has been accepted: enqueues on `stream`, commits the host state.
-int stream_push_enqueue(af_stream_resampler *r, const StreamReplay &p, const float *d_in, int64_t n_in, int64_t in_stride,
-                        float *d_out, int64_t out_stride, hipStream_t stream) {
-  AF_HIP(hipSetDevice(r->device));
-  (void)stream_collect_retired(r, false);
-  const size_t plane_bytes = sizeof(float) * (size_t)r->plane_stride * r->n_streams;
-  if (!r->d_table) {
-    AF_HIP(hipMalloc(&r->d_table, sizeof(double) * r->plan.table.size()));
-    AF_HIP(hipMemcpyAsync(r->d_table, r->plan.table.data(), sizeof(double) * r->plan.table.size(), hipMemcpyHostToDevice, stream));
-    AF_HIP(hipMalloc(&r->d_plane[0], plane_bytes));
-    AF_HIP(hipMalloc(&r->d_plane[1], plane_bytes));
-    AF_HIP(hipEventCreate(&r->ev0));
-    AF_HIP(hipEventCreate(&r->ev1));
-    r->fresh = true;
-  }
-  if (r->fresh) {  // SincFixedIn::new / reset: a history of zeros
-    AF_HIP(hipMemsetAsync(r->d_plane[r->cur], 0, plane_bytes, stream));
-    r->fresh = false;
-  }
-  const int64_t split = 2 * (int64_t)r->plan.sinc_len + r->pending;
-  if (p.n_out > 0)
-    if (int rc = stream_upload_positions(r, stream)) return rc;
-  AF_HIP(hipEventRecord(r->ev0, stream));
-  if (p.n_out > 0)
-    AF_HIP(af::launch_resample_stream(r->d_plane[r->cur], d_in, d_out, r->d_pos, r->d_table, split, n_in, p.n_out, in_stride,
-                                      out_stride, r->plane_stride, r->n_streams, r->plan.sinc_len, r->plan.ratio, r->variant, stream));
-  if (n_in > 0) {  // the plane of the next call: the last 2 * sinc_len frames consumed + the remainder, into the other plane
-    AF_HIP(af::launch_resample_stream_advance(r->d_plane[r->cur], r->d_plane[r->cur ^ 1], d_in, split, n_in, p.chunks * r->plan.chunk,
-                                              in_stride, (int32_t)(2 * r->plan.sinc_len + p.rem), r->plane_stride, r->n_streams, stream));
-    r->cur ^= 1;
-  }
-  AF_HIP(hipEventRecord(r->ev1, stream));
-  r->timed = true;
-  r->last_index = p.last_index;
-  r->pending = p.rem;
-  r->chunks += p.chunks;
-  r->frames_in += n_in;
-  r->frames_out += p.n_out;
-  return AF_OK;
-}
-
-// everything that can refuse a push, before anything is touched; fills r->pos
-int stream_push_check(af_stream_resampler *r, const float *in, int64_t n_in, int64_t in_stride, const float *out, int64_t out_capacity,
-                      int64_t out_stride, StreamReplay *p) {
-  if (!r) return fail(AF_ERR_INVALID_ARGUMENT, "resampler is null");
-  if (n_in < 0 || in_stride < n_in) return fail(AF_ERR_INVALID_ARGUMENT, "in_stride must cover n_in frames");
-  if (!in && n_in > 0) return fail(AF_ERR_INVALID_ARGUMENT, "null buffer");
-  *p = stream_replay(r, n_in, &r->pos);
-  if (out_capacity < p->n_out || out_stride < p->n_out)
-    return fail(AF_ERR_INVALID_ARGUMENT, "this push produces %lld frames per stream: out_capacity %lld / out_stride %lld is too small",
-                (long long)p->n_out, (long long)out_capacity, (long long)out_stride);
-  if (!out && p->n_out > 0) return fail(AF_ERR_INVALID_ARGUMENT, "null buffer");
-  return AF_OK;
-}
-
-}  // namespace
-
-extern "C" {
-
-int af_stream_resampler_create(uint32_t input_rate, uint32_t output_rate, int64_t chunk_size, int32_t sinc_len, int32_t window,
-                               int32_t n_streams, int32_t device, af_stream_resampler **out) {
-  if (!out) return fail(AF_ERR_INVALID_ARGUMENT, "out is null");
-  *out = nullptr;
-  if (int rc = resampler_check_arguments(input_rate, output_rate, chunk_size, sinc_len, window, device)) return rc;
-  if (n_streams <= 0) return fail(AF_ERR_INVALID_ARGUMENT, "n_streams must be positive");
-  af_stream_resampler *r = new af_stream_resampler();
-  r->device = device;
-  r->n_streams = n_streams;
-  r->plan.build(input_rate, output_rate, chunk_size, sinc_len, window);
-  r->plane_stride = (int32_t)(2 * r->plan.sinc_len + chunk_size - 1);
-  r->last_index = r->plan.initial_index();
-  if (const char *env = std::getenv("AF_RESAMPLER_VARIANT")) r->variant = std::strcmp(env, "valu") == 0 ? 1 : (std::strcmp(env, "mfma32") == 0 ? 2 : 0);
-  *out = r;
-  return AF_OK;
-}
-
-void af_stream_resampler_destroy(af_stream_resampler *r) {
-  if (!r) return;
-  if (r->d_table || r->d_in || r->d_out) {
-    (void)hipSetDevice(r->device);
-    (void)hipDeviceSynchronize();
-    (void)stream_collect_retired(r, true);
-    (void)hipFree(r->d_table);
-    (void)hipFree(r->d_plane[0]);
-    (void)hipFree(r->d_plane[1]);
-    (void)hipFree(r->d_pos);
-    (void)hipFree(r->d_in);
-    (void)hipFree(r->d_out);
-    for (int k = 0; k < af_stream_resampler::Stager::kSlots; ++k) {
-      if (r->stager.pinned[k]) (void)hipHostFree(r->stager.pinned[k]);
-      if (r->stager.done[k]) (void)hipEventDestroy(r->stager.done[k]);
-    }
-    if (r->ev0) (void)hipEventDestroy(r->ev0);
-    if (r->ev1) (void)hipEventDestroy(r->ev1);
-  }
-  delete r;
-}
-
-int af_stream_resampler_reset(af_stream_resampler *r) {
-  if (!r) return fail(AF_ERR_INVALID_ARGUMENT, "resampler is null");
-  r->last_index = r->plan.initial_index();
-  r->pending = r->chunks = r->frames_in = r->frames_out = 0;
-  r->fresh = true;  // the plane is zeroed in stream order in front of the next push
-  return AF_OK;
-}
-
-int af_stream_resampler_clear_pending(af_stream_resampler *r) {  // dsp_loop.rs:941-944: resample_input.clear()
-  if (!r) return fail(AF_ERR_INVALID_ARGUMENT, "resampler is null");
-  r->pending = 0;
-  return AF_OK;
-}
-
-int64_t af_stream_resampler_output_frames(const af_stream_resampler *r, int64_t n_in) {
-  if (!r || n_in < 0) return 0;
-  return stream_replay(r, n_in, nullptr).n_out;
-}
-int64_t af_stream_resampler_pending_input(const af_stream_resampler *r) { return r ? r->pending : 0; }
-int af_stream_resampler_output_delay(const af_stream_resampler *r) { return r ? r->plan.output_delay() : 0; }
-int64_t af_stream_resampler_frames_in(const af_stream_resampler *r) { return r ? r->frames_in : 0; }
-int64_t af_stream_resampler_frames_out(const af_stream_resampler *r) { return r ? r->frames_out : 0; }
-
-int af_stream_resampler_push_device(af_stream_resampler *r, const float *d_in, int64_t n_in, int64_t in_stride, float *d_out,
-                                    int64_t out_capacity, int64_t out_stride, int64_t *n_out, void *hip_stream) {
-  if (n_out) *n_out = 0;
-  StreamReplay p{};
-  if (int rc = stream_push_check(r, d_in, n_in, in_stride, d_out, out_capacity, out_stride, &p)) return rc;
-  if (int rc = stream_push_enqueue(r, p, d_in, n_in, in_stride, d_out, out_stride, static_cast<hipStream_t>(hip_stream))) return rc;
-  if (n_out) *n_out = p.n_out;
-  return AF_OK;
-}
-
-int af_stream_resampler_push_host(af_stream_resampler *r, const float *in, int64_t n_in, int64_t in_stride, float *out,
-                                  int64_t out_capacity, int64_t out_stride, int64_t *n_out) {
-  if (n_out) *n_out = 0;
-  StreamReplay p{};
-  if (int rc = stream_push_check(r, in, n_in, in_stride, out, out_capacity, out_stride, &p)) return rc;
-  for (int64_t s = 0; s < r->n_streams; ++s)
-    for (int64_t i = 0; i < n_in; ++i)
-      if (!std::isfinite(in[s * in_stride + i])) return fail(AF_ERR_NON_FINITE, "samples must be finite");
-  AF_HIP(hipSetDevice(r->device));
-  const int64_t B = r->n_streams, need_in = std::max<int64_t>(1, B * n_in), need_out = std::max<int64_t>(1, B * p.n_out);
-  if (need_in > r->in_capacity) {  // (the host entry point synchronises before it returns: nothing reads the old buffer)
-    if (r->d_in) AF_HIP(hipFree(r->d_in));
-    r->d_in = nullptr;
-    r->in_capacity = 0;
-    AF_HIP(hipMalloc(&r->d_in, sizeof(float) * need_in));
-    r->in_capacity = need_in;
-  }
-  if (need_out > r->out_capacity) {
-    if (r->d_out) AF_HIP(hipFree(r->d_out));
-    r->d_out = nullptr;
-    r->out_capacity = 0;
-    AF_HIP(hipMalloc(&r->d_out, sizeof(float) * need_out));
-    r->out_capacity = need_out;
-  }
-  const size_t f4 = sizeof(float);
-  if (n_in > 0) AF_HIP(hipMemcpy2D(r->d_in, f4 * n_in, in, f4 * in_stride, f4 * n_in, B, hipMemcpyHostToDevice));
-  if (int rc = stream_push_enqueue(r, p, r->d_in, n_in, std::max<int64_t>(n_in, 1), r->d_out, std::max<int64_t>(p.n_out, 1), nullptr)) return rc;
-  AF_HIP(hipStreamSynchronize(nullptr));
-  if (p.n_out > 0) AF_HIP(hipMemcpy2D(out, f4 * out_stride, r->d_out, f4 * p.n_out, f4 * p.n_out, B, hipMemcpyDeviceToHost));
-  if (n_out) *n_out = p.n_out;
-  return AF_OK;
-}
-
-int af_stream_resampler_launch_form(const af_stream_resampler *r, int32_t *form, int32_t *segment_outputs,
-                                    int32_t *streams_per_workgroup) {  // as af_resampler_launch_form
-  if (!r) return fail(AF_ERR_INVALID_ARGUMENT, "resampler is null");
-  const af::ResampleForm f = af::resample_pick_form(r->plan.ratio, r->plan.sinc_len, r->variant);
-  if (form) *form = f.form;
-  if (segment_outputs) *segment_outputs = f.segment_outputs;
-  if (streams_per_workgroup) *streams_per_workgroup = f.streams_per_workgroup;
-  return AF_OK;
-}
-
-int af_stream_resampler_last_kernel_ms(af_stream_resampler *r, double *ms) {
-  if (!r || !ms) return fail(AF_ERR_INVALID_ARGUMENT, "null argument");
-  *ms = 0.0;
-  if (!r->timed) return AF_OK;
-  AF_HIP(hipEventSynchronize(r->ev1));
-  float t = 0.0f;
-  AF_HIP(hipEventElapsedTime(&t, r->ev0, r->ev1));
-  *ms = t;
-  return AF_OK;
-}
-
-}  // extern "C"
-
-// ------------------------------------------------------------------------------------------
-// The capture callback's mixdown (input.rs:383-736, 785-843): interleaved device frames -> mono.  Kernels, passes and the
-// state plane: af_mixdown.hip / af_mixdown_host.hpp.
-struct af_mixdown {
-  int device = 0, n_streams = 0, channels = 1;
-  int mode = 0;               // live: read at each push, per chunk (input.rs:814-816)
-  bool fresh = true;          // the plane is (re)initialised in stream order in front of the next push
-  uint32_t *d_plane = nullptr;
-  float *d_in = nullptr, *d_out = nullptr;  // staging of the host entry point
-  int64_t in_capacity = 0, out_capacity = 0;  // floats
-  std::vector<hipEvent_t> events;  // three per chunk of the last push: before the decision pass | between | after the mix
-  int timed_chunks = 0;
-};
-
-namespace {
-
-int mixdown_check_mode(int32_t mode) {
-  if (mode < 0 || mode > 4)
-    return fail(AF_ERR_INVALID_ARGUMENT, "unknown input channel mode %d (0 average, 1 left, 2 right, 3 max_rms, 4 phase_safe_mono)", mode);
-  return AF_OK;
-}
-
-int mixdown_push_check(af_mixdown *m, const float *in, int64_t n_frames, int64_t in_stride, const float *out, int64_t out_stride) {
-  if (!m) return fail(AF_ERR_INVALID_ARGUMENT, "mixdown is null");
-  if (n_frames < 0 || in_stride < n_frames) return fail(AF_ERR_INVALID_ARGUMENT, "in_stride must cover n_frames frames");
-  if (out_stride < n_frames) return fail(AF_ERR_INVALID_ARGUMENT, "out_stride must cover n_frames frames");
-  if ((!in || !out) && n_frames > 0) return fail(AF_ERR_INVALID_ARGUMENT, "null buffer");
-  return AF_OK;
-}
-
-// one callback (input.rs:807-842): chunks of at most 8192 frames, one decision per chunk, all enqueued on `stream`
-int mixdown_enqueue(af_mixdown *m, const float *d_in, int64_t n_frames, int64_t in_stride, float *d_out, int64_t out_stride,
-                    hipStream_t stream) {
-  AF_HIP(hipSetDevice(m->device));
-  if (!m->d_plane) {
-    AF_HIP(hipMalloc(&m->d_plane, sizeof(uint32_t) * af::kMfCount * (size_t)m->n_streams));
-    m->fresh = true;
-  }
-  if (m->fresh) {
-    AF_HIP(af::launch_mixdown_init(m->d_plane, m->n_streams, stream));
-    m->fresh = false;
-  }
-  const int C = m->channels, mode = m->mode, B = m->n_streams;
-  const int64_t chunks = (n_frames + af::kMixChunk - 1) / af::kMixChunk;
-  while ((int64_t)m->events.size() < 3 * chunks) {
-    hipEvent_t ev;
-    AF_HIP(hipEventCreate(&ev));
-    m->events.push_back(ev);
-  }
-  m->timed_chunks = 0;
-  for (int64_t j = 0; j < chunks; ++j) {
-    const int64_t at = j * af::kMixChunk;
-    const int32_t n = (int32_t)std::min<int64_t>(af::kMixChunk, n_frames - at);
-    const float *src = d_in + at * C;
-    float *dst = d_out + at;
-    int host_kind = -1, host_channel = 0;
-    AF_HIP(hipEventRecord(m->events[3 * j], stream));
-    if (C == 2) {  // stereo always gets its correlation and warning count (input.rs:675-677, 833-838)
-      AF_HIP(af::launch_mixdown_decide(src, in_stride, n, m->d_plane, B, mode, stream));
-    } else if (C > 2 && mode == af::kMixMaxRms) {
-      AF_HIP(af::launch_mixdown_energy(src, in_stride, n, C, m->d_plane, B, stream));
-    } else if (C == 1) {  // the one-channel copy, input.rs:789-805
-      host_kind = af::kMixKindSelect;
-    } else if (mode == af::kMixLeft || mode == af::kMixRight) {
-      host_kind = af::kMixKindSelect;
-      host_channel = mode == af::kMixRight ? 1 : 0;
-    } else {  // Average, and PhaseSafeMono off stereo (input.rs:719)
-      host_kind = af::kMixKindAverage;
-    }
-    AF_HIP(hipEventRecord(m->events[3 * j + 1], stream));
-    AF_HIP(af::launch_mixdown_mix(src, in_stride, n, C, dst, out_stride, m->d_plane, B, host_kind, host_channel, stream));
-    AF_HIP(hipEventRecord(m->events[3 * j + 2], stream));
-  }
-  m->timed_chunks = (int)chunks;
-  return AF_OK;
-}
-
-}  // namespace
-
-extern "C" {
-
-int af_mixdown_create(int32_t n_channels, int32_t mode, int32_t n_streams, int32_t device, af_mixdown **out) {
-  if (!out) return fail(AF_ERR_INVALID_ARGUMENT, "out is null");
-  *out = nullptr;
-  if (n_channels < 1) return fail(AF_ERR_INVALID_ARGUMENT, "n_channels must be >= 1");
-  if (n_channels > af::kMixMaxChannels)
-    return fail(AF_ERR_UNSUPPORTED, "%d input channels: the mixdown is built for at most %d", n_channels, af::kMixMaxChannels);
-  if (int rc = mixdown_check_mode(mode)) return rc;
-  if (n_streams <= 0) return fail(AF_ERR_INVALID_ARGUMENT, "n_streams must be positive");
-  if (device < 0) return fail(AF_ERR_INVALID_ARGUMENT, "device must be >= 0");
-  af_mixdown *m = new af_mixdown();
-  m->device = device;
-  m->n_streams = n_streams;
-  m->channels = n_channels;
-  m->mode = mode;
-  *out = m;
-  return AF_OK;
-}
-
-void af_mixdown_destroy(af_mixdown *m) {
-  if (!m) return;
-  if (m->d_plane || m->d_in || m->d_out || !m->events.empty()) {
-    (void)hipSetDevice(m->device);
-    (void)hipDeviceSynchronize();
-    (void)hipFree(m->d_plane);
-    (void)hipFree(m->d_in);
-    (void)hipFree(m->d_out);
-    for (hipEvent_t ev : m->events) (void)hipEventDestroy(ev);
-  }
-  delete m;
-}
-
-int af_mixdown_set_mode(af_mixdown *m, int32_t mode) {
-  if (!m) return fail(AF_ERR_INVALID_ARGUMENT, "mixdown is null");
-  if (int rc = mixdown_check_mode(mode)) return rc;
-  m->mode = mode;
-  return AF_OK;
-}
-
-int32_t af_mixdown_mode(const af_mixdown *m) { return m ? m->mode : 0; }
-int32_t af_mixdown_channels(const af_mixdown *m) { return m ? m->channels : 0; }
-
-int af_mixdown_reset(af_mixdown *m) {
-  if (!m) return fail(AF_ERR_INVALID_ARGUMENT, "mixdown is null");
-  m->fresh = true;  // the plane is rewritten in stream order in front of the next push
-  return AF_OK;
-}
-
-int af_mixdown_push_device(af_mixdown *m, const float *d_in, int64_t n_frames, int64_t in_stride_frames, float *d_out,
-                           int64_t out_stride, void *hip_stream) {
-  if (int rc = mixdown_push_check(m, d_in, n_frames, in_stride_frames, d_out, out_stride)) return rc;
-  if (n_frames == 0) return AF_OK;
-  return mixdown_enqueue(m, d_in, n_frames, in_stride_frames, d_out, out_stride, static_cast<hipStream_t>(hip_stream));
-}
-
-int af_mixdown_push_host(af_mixdown *m, const float *in, int64_t n_frames, int64_t in_stride_frames, float *out, int64_t out_stride) {
-  if (int rc = mixdown_push_check(m, in, n_frames, in_stride_frames, out, out_stride)) return rc;
-  const int64_t B = m->n_streams, C = m->channels;
-  for (int64_t s = 0; s < B; ++s)
-    for (int64_t i = 0; i < n_frames * C; ++i)
-      if (!std::isfinite(in[s * in_stride_frames * C + i])) return fail(AF_ERR_NON_FINITE, "samples must be finite");
-  if (n_frames == 0) return AF_OK;
-  AF_HIP(hipSetDevice(m->device));
-  const int64_t need_in = B * n_frames * C, need_out = B * n_frames;
-  if (need_in > m->in_capacity) {  // (the host entry point synchronises before it returns: nothing reads the old buffer)
-    if (m->d_in) AF_HIP(hipFree(m->d_in));
-    m->d_in = nullptr;
-    m->in_capacity = 0;
-    AF_HIP(hipMalloc(&m->d_in, sizeof(float) * need_in));
-    m->in_capacity = need_in;
-  }
-  if (need_out > m->out_capacity) {
-    if (m->d_out) AF_HIP(hipFree(m->d_out));
-    m->d_out = nullptr;
-    m->out_capacity = 0;
-    AF_HIP(hipMalloc(&m->d_out, sizeof(float) * need_out));
-    m->out_capacity = need_out;
-  }
-  const size_t f4 = sizeof(float);
-  AF_HIP(hipMemcpy2D(m->d_in, f4 * n_frames * C, in, f4 * in_stride_frames * C, f4 * n_frames * C, B, hipMemcpyHostToDevice));
-  if (int rc = mixdown_enqueue(m, m->d_in, n_frames, n_frames, m->d_out, n_frames, nullptr)) return rc;
-  AF_HIP(hipStreamSynchronize(nullptr));
-  AF_HIP(hipMemcpy2D(out, f4 * out_stride, m->d_out, f4 * n_frames, f4 * n_frames, B, hipMemcpyDeviceToHost));
-  return AF_OK;
-}
-
-int af_mixdown_read_diagnostics(af_mixdown *m, float *stereo_correlation, uint64_t *phase_warning_count, int32_t *strategy,
-                                float *estimated_delay, int32_t *polarity_flipped, int32_t n_streams) {
-  if (!m) return fail(AF_ERR_INVALID_ARGUMENT, "mixdown is null");
-  if (n_streams != m->n_streams) return fail(AF_ERR_INVALID_ARGUMENT, "n_streams must be the mixdown's %d", m->n_streams);
-  const size_t B = (size_t)n_streams;
-  std::vector<uint32_t> rows(6 * B, 0u);
-  if (m->d_plane && !m->fresh) {
-    AF_HIP(hipSetDevice(m->device));
-    AF_HIP(hipDeviceSynchronize());  // pushes may be queued on any stream
-    AF_HIP(hipMemcpy(rows.data(), m->d_plane + (size_t)af::kMfDiagCorrelation * B, sizeof(uint32_t) * 6 * B, hipMemcpyDeviceToHost));
-  } else {
-    for (size_t s = 0; s < B; ++s) rows[s] = 0x7fc00000u;  // no Some yet
-  }
-  static_assert(af::kMfDiagFlipped == af::kMfDiagCorrelation + 5, "the six diagnostic fields are consecutive");
-  for (size_t s = 0; s < B; ++s) {
-    if (stereo_correlation) std::memcpy(&stereo_correlation[s], &rows[s], 4);
-    if (phase_warning_count) phase_warning_count[s] = (uint64_t)rows[B + s] | ((uint64_t)rows[2 * B + s] << 32);
-    if (strategy) strategy[s] = (int32_t)rows[3 * B + s];
-    if (estimated_delay) std::memcpy(&estimated_delay[s], &rows[4 * B + s], 4);
-    if (polarity_flipped) polarity_flipped[s] = (int32_t)rows[5 * B + s];
-  }
-  return AF_OK;
-}
-
-int af_mixdown_last_kernel_ms(af_mixdown *m, double *decision_ms, double *mix_ms) {
-  if (!m) return fail(AF_ERR_INVALID_ARGUMENT, "mixdown is null");
-  if (decision_ms) *decision_ms = 0.0;
-  if (mix_ms) *mix_ms = 0.0;
-  if (m->timed_chunks == 0) return AF_OK;
-  AF_HIP(hipSetDevice(m->device));
-  AF_HIP(hipEventSynchronize(m->events[3 * (m->timed_chunks - 1) + 2]));
-  for (int j = 0; j < m->timed_chunks; ++j) {
-    float a = 0.0f, b = 0.0f;
-    AF_HIP(hipEventElapsedTime(&a, m->events[3 * j], m->events[3 * j + 1]));
-    AF_HIP(hipEventElapsedTime(&b, m->events[3 * j + 1], m->events[3 * j + 2]));
-    if (decision_ms) *decision_ms += a;
-    if (mix_ms) *mix_ms += b;
-  }
-  return AF_OK;
-}
-
-}  // extern "C"
-
-// ------------------------------------------------------------------------------------------
-// measure_integrated_loudness (lib.rs:290-298 over dsp/loudness.rs:43-83)
-namespace {
-// ebur128 `Mode::HISTOGRAM`: 1000 bins of 0.1 LU from -70 LUFS; blocks are represented by their bin's centre
-double hist_energy(int i) { return std::pow(10.0, ((double)i / 10.0 - 69.95 + 0.691) / 10.0); }
-double hist_boundary(int i) { return std::pow(10.0, ((double)i / 10.0 - 70.0 + 0.691) / 10.0); }
-size_t find_histogram_index(double energy) {
-  size_t lo = 0, hi = 1000;
-  do {
-    const size_t mid = (lo + hi) / 2;
-    if (energy >= hist_boundary((int)mid)) lo = mid; else hi = mid;
-  } while (hi - lo != 1);
-  return lo;
-}
-// 400 ms blocks every 100 ms, absolute gate -70 LUFS, relative gate -10 LU; false when nothing passes the gates
-bool gated_loudness(const double *part, int64_t n100, int64_t s100, double *lufs) {
-  std::vector<uint64_t> counts(1000, 0);
-  const double frames = (double)(s100 * 4);
-  for (int64_t b = 0; b + 4 <= n100; ++b) {
-    const double energy = (((part[b] + part[b + 1]) + part[b + 2]) + part[b + 3]) / frames;
-    if (energy >= hist_boundary(0)) counts[find_histogram_index(energy)]++;
-  }
-  double rel = 0.0;
-  uint64_t above = 0;
-  for (int i = 0; i < 1000; ++i) { rel += (double)counts[i] * hist_energy(i); above += counts[i]; }
-  if (!above) return false;
-  rel /= (double)above;
-  rel *= std::pow(10.0, -10.0 / 10.0);
-  size_t start;
-  if (rel < hist_boundary(0)) start = 0;
-  else { start = find_histogram_index(rel); if (rel > hist_energy((int)start)) ++start; }
-  double gated = 0.0;
-  above = 0;
-  for (size_t i = start; i < 1000; ++i) { gated += (double)counts[i] * hist_energy((int)i); above += counts[i]; }
-  if (!above) return false;
-  gated /= (double)above;
-  *lufs = 10.0 * (std::log(gated) / std::log(10.0)) - 0.691;
-  return std::isfinite(*lufs);
-}
-}  // namespace
-
-extern "C" {
-
-int af_measure_integrated_loudness_device(const float *d_audio, int64_t n_samples, int32_t n_streams, int64_t stream_stride,
-                                          uint32_t sample_rate, int32_t device, double *lufs, int32_t *status) {
-  // validate_sample_rate, loudness.rs:36-41
-  static const uint32_t rates[] = {8000, 16000, 32000, 44100, 48000, 88200, 96000};
-  bool rate_ok = false;
-  for (uint32_t r : rates) rate_ok |= r == sample_rate;
-  if (!rate_ok) return fail(AF_ERR_INVALID_ARGUMENT, "Invalid sample rate: %u", sample_rate);
-  if (n_samples <= 0) return fail(AF_ERR_INVALID_ARGUMENT, "Invalid audio: at least one sample is required");
-  if (n_streams <= 0 || !d_audio || !lufs) return fail(AF_ERR_INVALID_ARGUMENT, "null or empty batch");
-  if (stream_stride < n_samples) return fail(AF_ERR_INVALID_ARGUMENT, "stream_stride must cover n_samples");
-  AF_HIP(hipSetDevice(device));
-  double b[5], a[5];
-  af::kweighting_design((double)sample_rate, b, a);
-  const int64_t s100 = ((int64_t)sample_rate + 5) / 10, n100 = n_samples / s100;
-  double *d_part = nullptr;
-  int32_t *d_bad = nullptr;
-  AF_HIP(hipMalloc(&d_part, sizeof(double) * std::max<int64_t>(1, n100) * n_streams));
-  AF_HIP(hipMalloc(&d_bad, sizeof(int32_t) * n_streams));
-  hipError_t err = af::launch_kweight_energy(d_audio, d_part, d_bad, b, a, n_samples, stream_stride, n100, n_streams, (int32_t)s100, nullptr);
-  std::vector<double> part((size_t)std::max<int64_t>(1, n100) * n_streams);
-  std::vector<int32_t> bad(n_streams);
-  if (err == hipSuccess) err = hipMemcpy(part.data(), d_part, sizeof(double) * part.size(), hipMemcpyDeviceToHost);
-  if (err == hipSuccess) err = hipMemcpy(bad.data(), d_bad, sizeof(int32_t) * n_streams, hipMemcpyDeviceToHost);
-  (void)hipFree(d_part);
-  (void)hipFree(d_bad);
-  if (err != hipSuccess) return fail(AF_ERR_BACKEND, "integrated loudness failed: %s", hipGetErrorString(err));
-  int worst = AF_OK;
-  for (int32_t s = 0; s < n_streams; ++s) {
-    int st = AF_OK;
-    double v = -HUGE_VAL;
-    if (bad[s]) st = AF_ERR_NON_FINITE;
-    else if (!gated_loudness(part.data() + (size_t)s * std::max<int64_t>(1, n100), n100, s100, &v)) st = AF_ERR_UNSUPPORTED;
-    lufs[s] = v;
-    if (status) status[s] = st;
-    if (st != AF_OK && worst == AF_OK) worst = st;
-  }
-  if (worst == AF_ERR_NON_FINITE) return fail(worst, "Invalid audio: samples must be finite");
-  if (worst == AF_ERR_UNSUPPORTED)
-    return fail(AF_ERR_INVALID_ARGUMENT, "Loudness measurement failed: audio did not produce a finite gated loudness");
-  return AF_OK;
-}
-
-int af_measure_integrated_loudness_host(const float *audio, int64_t n_samples, int32_t n_streams, int64_t stream_stride,
-                                        uint32_t sample_rate, int32_t device, double *lufs, int32_t *status) {
-  if (!audio && n_samples > 0) return fail(AF_ERR_INVALID_ARGUMENT, "audio is null");
-  if (n_samples <= 0) return fail(AF_ERR_INVALID_ARGUMENT, "Invalid audio: at least one sample is required");
-  if (n_streams <= 0) return fail(AF_ERR_INVALID_ARGUMENT, "n_streams must be positive");
-  AF_HIP(hipSetDevice(device));
-  float *d_audio = nullptr;
-  AF_HIP(hipMalloc(&d_audio, sizeof(float) * (size_t)n_samples * n_streams));
-  hipError_t err = hipMemcpy2D(d_audio, sizeof(float) * n_samples, audio, sizeof(float) * stream_stride, sizeof(float) * n_samples,
-                               n_streams, hipMemcpyHostToDevice);
-  int rc = AF_OK;
-  if (err != hipSuccess) rc = fail(AF_ERR_BACKEND, "hipMemcpy2D failed: %s", hipGetErrorString(err));
-  else rc = af_measure_integrated_loudness_device(d_audio, n_samples, n_streams, n_samples, sample_rate, device, lufs, status);
-  (void)hipFree(d_audio);
-  return rc;
-}
-
-}  // extern "C"
-
-// ------------------------------------------------------------------------------------------
-// Noise gate, expander path (dsp/gate.rs:626-637), as simulate_gate_suppressor_order drives it
-namespace af {
-struct GateArgs {
-  const float *in;
-  float *out;
-  float *gain_trace;
-  uint64_t *chatter;
-  double *state;
-  double threshold_db, attack_coeff, release_coeff, rms_coeff;
-  int64_t n_samples, stride;
-  int32_t n_streams, block, vad_mode;
-  int32_t hold_samples, window_samples, cooldown_samples, relax_samples;
-};
-hipError_t launch_gate(const GateArgs &a, hipStream_t stream);
-}  // namespace af
-
-extern "C" {
-
-int af_gate_process_host(const float *in, float *out, int64_t n_samples, int32_t n_streams, int64_t stream_stride,
-                         double threshold_db, double attack_ms, double release_ms, double sample_rate, int32_t vad_mode,
-                         int32_t trace_block, float *gain_trace, uint64_t *chatter_events, int32_t device) {
-  if (!in || !out) return fail(AF_ERR_INVALID_ARGUMENT, "audio pointers are null");
-  if (n_samples < 0 || n_streams <= 0 || stream_stride < n_samples) return fail(AF_ERR_INVALID_ARGUMENT, "bad batch shape");
-  if (!std::isfinite(sample_rate) || sample_rate <= 0.0) return fail(AF_ERR_INVALID_ARGUMENT, "sample_rate must be positive and finite");
-  if (trace_block <= 0) trace_block = 480;
-  AF_HIP(hipSetDevice(device));
-  const int64_t blocks = (n_samples + trace_block - 1) / trace_block;
-  float *d_in = nullptr, *d_trace = nullptr;
-  uint64_t *d_chatter = nullptr;
-  const size_t audio_bytes = sizeof(float) * (size_t)std::max<int64_t>(1, n_samples) * n_streams;
-  AF_HIP(hipMalloc(&d_in, audio_bytes));
-  AF_HIP(hipMalloc(&d_trace, sizeof(float) * (size_t)std::max<int64_t>(1, blocks) * n_streams));
-  AF_HIP(hipMalloc(&d_chatter, sizeof(uint64_t) * n_streams));
-  hipError_t err = hipSuccess;
-  if (n_samples > 0)
-    err = hipMemcpy2D(d_in, sizeof(float) * n_samples, in, sizeof(float) * stream_stride, sizeof(float) * n_samples, n_streams,
-                      hipMemcpyHostToDevice);
-  af::GateArgs g{};
-  g.in = d_in; g.out = d_in; g.gain_trace = d_trace; g.chatter = d_chatter; g.state = nullptr;
-  g.threshold_db = threshold_db;
-  g.attack_coeff = af::time_constant_to_coeff(attack_ms, sample_rate);    // gate.rs:160-162
-  g.release_coeff = af::time_constant_to_coeff(release_ms, sample_rate);
-  g.rms_coeff = af::time_constant_to_coeff(8.0, sample_rate);
-  g.n_samples = n_samples; g.stride = n_samples; g.n_streams = n_streams; g.block = trace_block; g.vad_mode = vad_mode ? 1 : 0;
-  g.hold_samples = (int32_t)std::llround(sample_rate * 50.0 / 1000.0);
-  g.window_samples = (int32_t)std::llround(sample_rate * 500.0 / 1000.0);
-  g.cooldown_samples = (int32_t)std::llround(sample_rate * 1000.0 / 1000.0);
-  g.relax_samples = (int32_t)std::llround(sample_rate * 700.0 / 1000.0);
-  if (err == hipSuccess) err = af::launch_gate(g, nullptr);
-  if (err == hipSuccess && n_samples > 0)
-    err = hipMemcpy2D(out, sizeof(float) * stream_stride, d_in, sizeof(float) * n_samples, sizeof(float) * n_samples, n_streams,
-                      hipMemcpyDeviceToHost);
-  if (err == hipSuccess && gain_trace && blocks > 0)
-    err = hipMemcpy(gain_trace, d_trace, sizeof(float) * blocks * n_streams, hipMemcpyDeviceToHost);
-  if (err == hipSuccess && chatter_events) err = hipMemcpy(chatter_events, d_chatter, sizeof(uint64_t) * n_streams, hipMemcpyDeviceToHost);
-  (void)hipFree(d_in);
-  (void)hipFree(d_trace);
-  (void)hipFree(d_chatter);
-  if (err != hipSuccess) return fail(AF_ERR_BACKEND, "gate failed: %s", hipGetErrorString(err));
   return AF_OK;
 }
 
@@ -4698,360 +3549,5 @@ int32_t af_noise_suppressor_latency_samples(const af_noise_suppressor *) { retur
 int32_t af_noise_suppressor_backend_available(const af_noise_suppressor *s) { return s ? 1 : 0; }   // rnnoise.rs:317-319
 int32_t af_noise_suppressor_backend_failed(const af_noise_suppressor *) { return 0; }               // rnnoise.rs:325-327
 const char *af_noise_suppressor_backend_error(const af_noise_suppressor *) { return nullptr; }      // rnnoise.rs:321-323
-
-}  // extern "C"
-
-// ------------------------------------------------------------------------------------------
-// The output writer (output_writer.rs:62-343): drift retime, discontinuity fade, safety, queue accounting.  Kernels, passes
-// and the state plane: af_output_writer.hip / af_output_writer_host.hpp.
-struct af_output_writer {
-  int device = 0, n_streams = 0;
-  af_output_writer_config cfg{};
-  bool limiter_enabled = true;   // live, output_writer.rs:208, 214
-  float ceiling_linear = 1.0f;   // live, :209
-  float release_coeff = 0.0f;    // TruePeakLimiter::default_settings(rate): 80 ms, true_peak.rs:285-287, 308-313
-  bool fresh = true;             // the plane is (re)initialised in stream order in front of the next push
-  uint32_t *d_plane = nullptr;
-  float *d_x = nullptr, *d_tg = nullptr;  // scratch rows of the passes
-  int64_t scratch_frames = 0;             // frames per stream they hold
-  float *d_in = nullptr, *d_out = nullptr;  // staging of the host entry point
-  int64_t *d_fill = nullptr, *d_written = nullptr;
-  int64_t in_capacity = 0, out_capacity = 0;  // floats
-  std::vector<float> host_rows;               // ... and its copy-back rows, kept between calls
-  hipEvent_t ev[6] = {};  // before the plan pass, then behind each of the five passes
-  bool timed = false;
-};
-
-namespace {
-
-int64_t ow_duration_samples(int64_t rate, int64_t ms) {  // resampling.rs:1-3
-  return std::max<int64_t>((rate * ms + 500) / 1000, 1);
-}
-
-int64_t ow_max_output_frames(const af_output_writer *w, int64_t n_in) {
-  // resampling.rs:92-94 at the smallest ratio; the clean path and a pass-through yield n_in
-  const int64_t desired = (int64_t)std::fmax(std::round((float)n_in / af::kOwMinRatio), 1.0f);
-  const int64_t retimed = std::min<int64_t>({desired, std::max<int64_t>(w->cfg.queue_capacity, 1), (int64_t)af::kOwScratch});
-  return std::max(n_in, retimed);
-}
-
-int ow_push_check(af_output_writer *w, const float *in, int64_t n_in, int64_t in_stride, const int64_t *fill, const float *out,
-                  int64_t out_capacity, int64_t out_stride, const int64_t *written) {
-  if (!w) return fail(AF_ERR_INVALID_ARGUMENT, "output writer is null");
-  if (n_in < 0) return fail(AF_ERR_INVALID_ARGUMENT, "n_in must be >= 0");
-  if (n_in > af::kOwMaxBlock)
-    return fail(AF_ERR_INVALID_ARGUMENT, "n_in %lld: a push takes at most %d frames", (long long)n_in, af::kOwMaxBlock);
-  if (!written) return fail(AF_ERR_INVALID_ARGUMENT, "written is null");
-  if (n_in == 0) return AF_OK;
-  if (!in || !out || !fill) return fail(AF_ERR_INVALID_ARGUMENT, "null buffer");
-  if (in_stride < n_in) return fail(AF_ERR_INVALID_ARGUMENT, "in_stride must cover n_in frames");
-  const int64_t need = ow_max_output_frames(w, n_in);
-  if (out_capacity < need || out_stride < need)
-    return fail(AF_ERR_INVALID_ARGUMENT, "out_capacity and out_stride must cover the %lld frames a push of %lld can yield",
-                (long long)need, (long long)n_in);
-  return AF_OK;
-}
-
-// one write_chunk per stream, all enqueued on `stream`
-int ow_enqueue(af_output_writer *w, const float *d_in, int64_t n_in, int64_t in_stride, const int64_t *d_fill, int clean_path,
-               float *d_out, int64_t out_stride, int64_t *d_written, hipStream_t stream) {
-  AF_HIP(hipSetDevice(w->device));
-  const int B = w->n_streams;
-  if (!w->d_plane) {
-    AF_HIP(hipMalloc(&w->d_plane, sizeof(uint32_t) * af::kOwCount * (size_t)B));
-    for (hipEvent_t &ev : w->ev) AF_HIP(hipEventCreate(&ev));
-    w->fresh = true;
-  }
-  const int64_t max_out = ow_max_output_frames(w, n_in);
-  if (!w->d_x) {  // once, for the longest block a push may bring: no later push allocates or waits
-    const int64_t longest = ow_max_output_frames(w, af::kOwMaxBlock);
-    AF_HIP(hipMalloc(&w->d_x, sizeof(float) * (size_t)longest * B));
-    AF_HIP(hipMalloc(&w->d_tg, sizeof(float) * (size_t)longest * B));
-    w->scratch_frames = longest;
-  }
-  if (w->fresh) {
-    AF_HIP(af::launch_output_writer_init(w->d_plane, B, stream));
-    w->fresh = false;
-  }
-  af::OwPush p{};
-  p.in = d_in;
-  p.in_stride = in_stride;
-  p.n = (int32_t)n_in;
-  p.fill = d_fill;
-  p.clean_path = clean_path ? 1 : 0;
-  p.out = d_out;
-  p.out_stride = out_stride;
-  p.written = d_written;
-  p.plane = w->d_plane;
-  p.n_streams = B;
-  p.x = w->d_x;
-  p.tg = w->d_tg;
-  p.max_out = (int32_t)max_out;
-  p.limiter_on = w->limiter_enabled ? 1 : 0;
-  p.ceiling = w->limiter_enabled ? w->ceiling_linear : 1.0f;                  // output_writer.rs:208-212
-  p.limiter_ceiling = std::min(std::max(p.ceiling, 0.000001f), 1.0f);         // true_peak.rs:304-306
-  p.clamp_ceiling = std::min(std::max(p.ceiling, 0.0f), 1.0f);                // routing.rs:774
-  p.release_coeff = w->release_coeff;
-  p.capacity = w->cfg.queue_capacity;
-  p.center = w->cfg.target_center;
-  p.hard = w->cfg.hard_backlog;
-  p.fade = w->cfg.fade_frames;
-  AF_HIP(hipEventRecord(w->ev[0], stream));
-  AF_HIP(af::launch_output_writer_plan(p, stream));
-  AF_HIP(hipEventRecord(w->ev[1], stream));
-  AF_HIP(af::launch_output_writer_shape(p, stream));
-  AF_HIP(hipEventRecord(w->ev[2], stream));
-  if (p.limiter_on) AF_HIP(af::launch_output_writer_gain(p, stream));
-  AF_HIP(hipEventRecord(w->ev[3], stream));
-  AF_HIP(af::launch_output_writer_out(p, stream));
-  AF_HIP(hipEventRecord(w->ev[4], stream));
-  AF_HIP(af::launch_output_writer_finish(p, stream));
-  AF_HIP(hipEventRecord(w->ev[5], stream));
-  w->timed = true;
-  return AF_OK;
-}
-
-// rows [first, first + count) of the plane, or the fresh plane's values before a first push
-int ow_read_rows(af_output_writer *w, int first, int count, std::vector<uint32_t> &rows) {
-  const size_t B = (size_t)w->n_streams;
-  rows.assign((size_t)count * B, 0u);
-  if (w->d_plane && !w->fresh) {
-    AF_HIP(hipSetDevice(w->device));
-    AF_HIP(hipDeviceSynchronize());  // pushes may be queued on any stream
-    AF_HIP(hipMemcpy(rows.data(), w->d_plane + (size_t)first * B, sizeof(uint32_t) * (size_t)count * B, hipMemcpyDeviceToHost));
-    return AF_OK;
-  }
-  auto bits = [](float v) { uint32_t u; std::memcpy(&u, &v, 4); return u; };
-  for (int f = first; f < first + count; ++f) {
-    float v = 0.0f;
-    if (f == af::kOwGain || f == af::kOwMinGain || f == af::kOwRecRatio) v = 1.0f;
-    if (f == af::kOwDbClipPeak || f == af::kOwDbTruePeak || f == af::kOwDbTruePeakInput) v = -120.0f;
-    if (f == af::kOwDbHeadroom) v = 120.0f;
-    for (size_t s = 0; s < B; ++s) rows[(size_t)(f - first) * B + s] = bits(v);
-  }
-  return AF_OK;
-}
-
-}  // namespace
-
-extern "C" {
-
-int af_output_writer_default_config(int32_t output_rate, af_output_writer_config *cfg) {
-  if (!cfg) return fail(AF_ERR_INVALID_ARGUMENT, "cfg is null");
-  if (output_rate <= 0) return fail(AF_ERR_INVALID_ARGUMENT, "output_rate must be positive");
-  const int64_t low = ow_duration_samples(output_rate, 30), high = ow_duration_samples(output_rate, 40);  // processor.rs:66-67
-  cfg->output_rate = output_rate;
-  cfg->queue_capacity = 2 * (int64_t)output_rate;                          // dsp_loop.rs:204
-  cfg->target_center = (low + high + 1) / 2;                               // dsp_loop.rs:786-787
-  cfg->hard_backlog = ow_duration_samples(output_rate, 60);                // dsp_loop.rs:788-789, processor.rs:68
-  cfg->fade_frames = std::max<int64_t>(ow_duration_samples(output_rate, 6), 1);  // dsp_loop.rs:794-795
-  return AF_OK;
-}
-
-int af_output_writer_create(const af_output_writer_config *cfg, int32_t n_streams, int32_t device, af_output_writer **out) {
-  if (!out) return fail(AF_ERR_INVALID_ARGUMENT, "out is null");
-  *out = nullptr;
-  if (!cfg) return fail(AF_ERR_INVALID_ARGUMENT, "cfg is null");
-  constexpr int64_t kLim = INT32_MAX;
-  if (cfg->output_rate <= 0) return fail(AF_ERR_INVALID_ARGUMENT, "output_rate must be positive");
-  if (cfg->queue_capacity < 1 || cfg->queue_capacity > kLim) return fail(AF_ERR_INVALID_ARGUMENT, "queue_capacity must be 1 .. 2^31 - 1");
-  if (cfg->target_center < 0 || cfg->target_center > kLim) return fail(AF_ERR_INVALID_ARGUMENT, "target_center must be 0 .. 2^31 - 1");
-  if (cfg->hard_backlog < 0 || cfg->hard_backlog > kLim) return fail(AF_ERR_INVALID_ARGUMENT, "hard_backlog must be 0 .. 2^31 - 1");
-  if (cfg->fade_frames < 1 || cfg->fade_frames > kLim) return fail(AF_ERR_INVALID_ARGUMENT, "fade_frames must be 1 .. 2^31 - 1");
-  if (n_streams <= 0 || n_streams > 65535) return fail(AF_ERR_INVALID_ARGUMENT, "n_streams must be 1 .. 65535");
-  if (device < 0) return fail(AF_ERR_INVALID_ARGUMENT, "device must be >= 0");
-  af_output_writer *w = new af_output_writer();
-  w->device = device;
-  w->n_streams = n_streams;
-  w->cfg = *cfg;
-  const float rate = std::max((float)cfg->output_rate, 1.0f);  // true_peak.rs:279
-  w->release_coeff = (float)af::time_constant_to_coeff((double)std::min(std::max(80.0f, 5.0f), 500.0f), (double)rate);
-  *out = w;
-  return AF_OK;
-}
-
-void af_output_writer_destroy(af_output_writer *w) {
-  if (!w) return;
-  if (w->d_plane || w->d_in || w->d_out || w->d_x) {
-    (void)hipSetDevice(w->device);
-    (void)hipDeviceSynchronize();
-    (void)hipFree(w->d_plane);
-    (void)hipFree(w->d_x);
-    (void)hipFree(w->d_tg);
-    (void)hipFree(w->d_in);
-    (void)hipFree(w->d_out);
-    (void)hipFree(w->d_fill);
-    (void)hipFree(w->d_written);
-    for (hipEvent_t ev : w->ev)
-      if (ev) (void)hipEventDestroy(ev);
-  }
-  delete w;
-}
-
-int af_output_writer_set_limiter(af_output_writer *w, int32_t enabled, float ceiling_linear) {
-  if (!w) return fail(AF_ERR_INVALID_ARGUMENT, "output writer is null");
-  if (!std::isfinite(ceiling_linear)) return fail(AF_ERR_INVALID_ARGUMENT, "ceiling_linear must be finite");
-  w->limiter_enabled = enabled != 0;
-  w->ceiling_linear = ceiling_linear;
-  return AF_OK;
-}
-
-int af_output_writer_reset(af_output_writer *w) {
-  if (!w) return fail(AF_ERR_INVALID_ARGUMENT, "output writer is null");
-  w->fresh = true;  // the plane is rewritten in stream order in front of the next push
-  return AF_OK;
-}
-
-int64_t af_output_writer_max_output_frames(const af_output_writer *w, int64_t n_in) {
-  if (!w || n_in < 1) return 0;
-  return ow_max_output_frames(w, n_in);
-}
-
-int af_output_writer_push_device(af_output_writer *w, const float *d_in, int64_t n_in, int64_t in_stride, const int64_t *d_fill,
-                                 int32_t clean_path, float *d_out, int64_t out_capacity, int64_t out_stride, int64_t *d_written,
-                                 void *hip_stream) {
-  if (int rc = ow_push_check(w, d_in, n_in, in_stride, d_fill, d_out, out_capacity, out_stride, d_written)) return rc;
-  hipStream_t stream = static_cast<hipStream_t>(hip_stream);
-  if (n_in == 0) {
-    AF_HIP(hipSetDevice(w->device));
-    AF_HIP(hipMemsetAsync(d_written, 0, sizeof(int64_t) * (size_t)w->n_streams, stream));
-    return AF_OK;
-  }
-  return ow_enqueue(w, d_in, n_in, in_stride, d_fill, clean_path, d_out, out_stride, d_written, stream);
-}
-
-int af_output_writer_push_host(af_output_writer *w, const float *in, int64_t n_in, int64_t in_stride, const int64_t *fill,
-                               int32_t clean_path, float *out, int64_t out_capacity, int64_t out_stride, int64_t *written) {
-  if (int rc = ow_push_check(w, in, n_in, in_stride, fill, out, out_capacity, out_stride, written)) return rc;
-  const int64_t B = w->n_streams;
-  if (n_in == 0) {
-    for (int64_t s = 0; s < B; ++s) written[s] = 0;
-    return AF_OK;
-  }
-  for (int64_t s = 0; s < B; ++s)
-    if (fill[s] < 0 || fill[s] > w->cfg.queue_capacity)
-      return fail(AF_ERR_INVALID_ARGUMENT, "fill[%lld] = %lld is outside the queue's 0 .. %lld", (long long)s, (long long)fill[s],
-                  (long long)w->cfg.queue_capacity);
-  AF_HIP(hipSetDevice(w->device));
-  const int64_t max_out = ow_max_output_frames(w, n_in);
-  const int64_t need_in = B * n_in, need_out = B * max_out;
-  if (!w->d_fill) {
-    AF_HIP(hipMalloc(&w->d_fill, sizeof(int64_t) * (size_t)B));
-    AF_HIP(hipMalloc(&w->d_written, sizeof(int64_t) * (size_t)B));
-  }
-  if (need_in > w->in_capacity) {  // (the host entry point synchronises before it returns: nothing reads the old buffer)
-    if (w->d_in) AF_HIP(hipFree(w->d_in));
-    w->d_in = nullptr;
-    w->in_capacity = 0;
-    AF_HIP(hipMalloc(&w->d_in, sizeof(float) * need_in));
-    w->in_capacity = need_in;
-  }
-  if (need_out > w->out_capacity) {
-    if (w->d_out) AF_HIP(hipFree(w->d_out));
-    w->d_out = nullptr;
-    w->out_capacity = 0;
-    AF_HIP(hipMalloc(&w->d_out, sizeof(float) * need_out));
-    w->out_capacity = need_out;
-  }
-  const size_t f4 = sizeof(float);
-  AF_HIP(hipMemcpy2D(w->d_in, f4 * n_in, in, f4 * in_stride, f4 * n_in, B, hipMemcpyHostToDevice));
-  AF_HIP(hipMemcpy(w->d_fill, fill, sizeof(int64_t) * (size_t)B, hipMemcpyHostToDevice));
-  if (int rc = ow_enqueue(w, w->d_in, n_in, n_in, w->d_fill, clean_path, w->d_out, max_out, w->d_written, nullptr)) return rc;
-  AF_HIP(hipStreamSynchronize(nullptr));
-  AF_HIP(hipMemcpy(written, w->d_written, sizeof(int64_t) * (size_t)B, hipMemcpyDeviceToHost));
-  int64_t longest = 0;
-  for (int64_t s = 0; s < B; ++s) longest = std::max(longest, std::min(std::max<int64_t>(written[s], 0), max_out));
-  if ((int64_t)w->host_rows.size() < B * longest) w->host_rows.resize((size_t)(B * longest));
-  if (longest > 0)
-    AF_HIP(hipMemcpy2D(w->host_rows.data(), f4 * longest, w->d_out, f4 * max_out, f4 * longest, B, hipMemcpyDeviceToHost));
-  for (int64_t s = 0; s < B; ++s)  // the rest of a row stays as the caller left it
-    std::memcpy(out + s * out_stride, w->host_rows.data() + s * longest, f4 * (size_t)std::min(std::max<int64_t>(written[s], 0), max_out));
-  return AF_OK;
-}
-
-int af_output_writer_read_counters(af_output_writer *w, uint64_t *jitter_dropped, uint64_t *retime_adjustments,
-                                   uint64_t *recovery_events, uint64_t *short_write_dropped, uint64_t *clip_events,
-                                   uint64_t *true_peak_events, int32_t n_streams) {
-  if (!w) return fail(AF_ERR_INVALID_ARGUMENT, "output writer is null");
-  if (n_streams != w->n_streams) return fail(AF_ERR_INVALID_ARGUMENT, "n_streams must be the output writer's %d", w->n_streams);
-  std::vector<uint32_t> rows;
-  if (int rc = ow_read_rows(w, af::kOwCntJitterDropped, 12, rows)) return rc;
-  static_assert(af::kOwCntTruePeak == af::kOwCntJitterDropped + 10, "the six counters are consecutive word pairs");
-  const size_t B = (size_t)n_streams;
-  uint64_t *dst[6] = {jitter_dropped, retime_adjustments, recovery_events, short_write_dropped, clip_events, true_peak_events};
-  for (int c = 0; c < 6; ++c)
-    if (dst[c])
-      for (size_t s = 0; s < B; ++s) dst[c][s] = (uint64_t)rows[(2 * c) * B + s] | ((uint64_t)rows[(2 * c + 1) * B + s] << 32);
-  return AF_OK;
-}
-
-int af_output_writer_read_meters(af_output_writer *w, float *db, float *linear, float *ratio, float *drift_ema, int64_t *out_len,
-                                 int64_t *fade_remaining, int64_t *fill_after, int32_t n_streams) {
-  if (!w) return fail(AF_ERR_INVALID_ARGUMENT, "output writer is null");
-  if (n_streams != w->n_streams) return fail(AF_ERR_INVALID_ARGUMENT, "n_streams must be the output writer's %d", w->n_streams);
-  std::vector<uint32_t> rows;
-  if (int rc = ow_read_rows(w, 0, af::kOwCount, rows)) return rc;
-  const size_t B = (size_t)n_streams;
-  static_assert(af::kOwDbHeadroom == af::kOwDbClipPeak + 5 && af::kOwClipMax == af::kOwInTp + 4, "consecutive fields");
-  if (db) std::memcpy(db, &rows[(size_t)af::kOwDbClipPeak * B], 4 * 6 * B);
-  if (linear) std::memcpy(linear, &rows[(size_t)af::kOwInTp * B], 4 * 5 * B);
-  if (ratio) std::memcpy(ratio, &rows[(size_t)af::kOwRecRatio * B], 4 * B);
-  if (drift_ema) std::memcpy(drift_ema, &rows[(size_t)af::kOwEma * B], 4 * B);
-  for (size_t s = 0; s < B; ++s) {
-    if (out_len) out_len[s] = rows[(size_t)af::kOwRecOutLen * B + s];
-    if (fade_remaining) fade_remaining[s] = rows[(size_t)af::kOwFadeRemaining * B + s];
-    if (fill_after) fill_after[s] = rows[(size_t)af::kOwRecFillAfter * B + s];
-  }
-  return AF_OK;
-}
-
-int af_output_writer_read_state(af_output_writer *w, float *gain, float *delay, int32_t *write_idx, float *histories,
-                                int32_t n_streams) {
-  if (!w) return fail(AF_ERR_INVALID_ARGUMENT, "output writer is null");
-  if (n_streams != w->n_streams) return fail(AF_ERR_INVALID_ARGUMENT, "n_streams must be the output writer's %d", w->n_streams);
-  std::vector<uint32_t> rows;
-  if (int rc = ow_read_rows(w, 0, af::kOwCount, rows)) return rc;
-  const size_t B = (size_t)n_streams;
-  auto at = [&](int f, size_t s) { float v; std::memcpy(&v, &rows[(size_t)f * B + s], 4); return v; };
-  for (size_t s = 0; s < B; ++s) {
-    const int sel = (int)(rows[(size_t)af::kOwSel * B + s] & 1u);
-    const int base = af::kOwHist + sel * 3 * af::kOwTaps;
-    const int widx = (int)rows[(size_t)af::kOwWriteIdx * B + s];
-    if (gain) gain[s] = at(af::kOwGain, s);
-    if (write_idx) write_idx[s] = widx;
-    if (histories)
-      for (int k = 0; k < 3 * af::kOwTaps; ++k) histories[s * 3 * af::kOwTaps + k] = at(base + k, s);
-    if (delay)  // the frame k + 1 steps back sits k + 1 slots behind the write index (true_peak.rs:343-345)
-      for (int k = 0; k < af::kOwLookahead; ++k)
-        delay[s * af::kOwLookahead + (size_t)((widx - 1 - k + 2 * af::kOwLookahead) % af::kOwLookahead)] = at(base + k, s);
-  }
-  return AF_OK;
-}
-
-int af_output_writer_last_kernel_ms(af_output_writer *w, double *ms) {
-  if (!w) return fail(AF_ERR_INVALID_ARGUMENT, "output writer is null");
-  if (ms) *ms = 0.0;
-  if (!w->timed) return AF_OK;
-  AF_HIP(hipSetDevice(w->device));
-  AF_HIP(hipEventSynchronize(w->ev[5]));
-  float t = 0.0f;
-  AF_HIP(hipEventElapsedTime(&t, w->ev[0], w->ev[5]));
-  if (ms) *ms = t;
-  return AF_OK;
-}
-
-int af_output_writer_last_pass_ms(af_output_writer *w, double *pass_ms) {
-  if (!w || !pass_ms) return fail(AF_ERR_INVALID_ARGUMENT, "null argument");
-  for (int k = 0; k < 5; ++k) pass_ms[k] = 0.0;
-  if (!w->timed) return AF_OK;
-  AF_HIP(hipSetDevice(w->device));
-  AF_HIP(hipEventSynchronize(w->ev[5]));
-  for (int k = 0; k < 5; ++k) {
-    float t = 0.0f;
-    AF_HIP(hipEventElapsedTime(&t, w->ev[k], w->ev[k + 1]));
-    pass_ms[k] = t;
-  }
-  return AF_OK;
-}
 
 }  // extern "C"

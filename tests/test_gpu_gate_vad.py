@@ -233,6 +233,23 @@ def test_fused_gate_without_the_suppressor(core, config, kernel):
     assert np.array_equal(got, again)
 
 
+def test_ten_calls_of_growing_evidence(core):
+    """Ten calls, each one control block longer than the one before (2 .. 11 blocks of evidence per stream): every call's
+    evidence is larger than any staged before it, so the staging slots are reallocated call after call.  Then ten calls of
+    two blocks, which fit: the eight slots are reused in turn."""
+    mode, ctl = ST.CONFIGS["assisted_auto_hold200"]
+    calls = tuple(ST.BLOCK * k + 250 for k in range(1, 11)) + (ST.BLOCK + 250,) * 10  # (each ends inside a control block)
+    x = ST.audio(n=sum(calls))
+    ev = ST.evidence(calls=calls)
+    assert [e[0].shape[0] for e in ev] == list(range(2, 12)) + [2] * 10
+    eng = bare_engine(core, ST.N_STREAMS, ST.BLOCK, prefilter=True)
+    apply(eng, ST.gate_params(mode), ctl)
+    got = run_engine(eng, x, calls, ev)
+    want, want_st = V.run_batch(x, FS, calls, ST.gate_params(mode), ctl, ev, ST.BLOCK)
+    compare(eng, got, want, want_st, "fused gate, ten calls of growing evidence", audio_tol=2e-7)
+    eng.close()
+
+
 @pytest.mark.parametrize("config,kernel", [("assisted_auto_hold0", 0), ("only_auto_hold200", 2)])
 def test_fused_gate_behind_the_suppressor(core, config, kernel):
     mode, ctl = ST.CONFIGS[config]

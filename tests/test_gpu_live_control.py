@@ -123,6 +123,23 @@ def test_schedule_on_every_kernel(kernel):
     assert float(np.abs(want.astype(np.float64) - plain).max()) > 1e-3
 
 
+def test_forty_calls_each_behind_a_retune():
+    """Forty calls of one control block, one EQ band's gain changed before each (before the first the engine has not started:
+    that setter is configuration, the other 39 are live edits): every later call uploads the edit list and the parameter block
+    of the crossfade it starts, so the 32 pinned staging slots are all used more than once."""
+    calls = (960,) * 40
+    schedule = {k: [("eq_set_band_gain", (3, 6.0 if k % 2 else -4.0 + 0.125 * k))] for k in range(40)}
+    audio = LC.audio(N_STREAMS, n=sum(calls))
+    want, want_rows = RO.run_batch(audio, LC.FS, LC.BANDS, LC.SETTINGS, calls, schedule)
+    eng = _engine(N_STREAMS, "auto", live=True)
+    try:
+        got, rows, launches, pending = _run(eng, audio, calls, schedule)
+    finally:
+        eng.close()
+    assert [p > 0 for p in pending] == [False] + [True] * 39, pending
+    _compare("forty retunes", got, rows, want, want_rows, COMP_TOL)
+
+
 # ------------------------------------------------------------------------------------------------ 2. the de-esser
 _DEESSER_FORMS = [(False, "lane"), (False, "staged"), (True, "phased")]
 

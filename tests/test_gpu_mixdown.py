@@ -100,6 +100,20 @@ def test_push_device_with_strides_equals_push(core):
     m.close()
 
 
+def test_timing_read_outs_around_a_reset(core):
+    outs, diags, _ = S.reference(2, MO.PHASE_SAFE_MONO)
+    cb = S.callbacks()[0]
+    m = core.Mixdown(2, "phase_safe_mono", n_streams=S.N_STREAMS)
+    assert m.last_kernel_ms() == (0.0, 0.0)  # nothing pushed yet
+    for label in ("first push", "after reset"):
+        assert_same_output(m.push(cb), outs[0], label)
+        assert_same_diagnostics(m.diagnostics(), diags[0], label)
+        for ms in m.last_kernel_ms():
+            assert np.isfinite(ms) and ms >= 0.0, (label, ms)
+        m.reset()
+    m.close()
+
+
 def test_non_finite_host_sample_refuses_the_call_and_touches_nothing(core):
     outs, diags, _ = S.reference(2, MO.PHASE_SAFE_MONO)
     cbs = S.callbacks()

@@ -76,6 +76,21 @@ def test_every_push_equals_the_restatement(core, name):
     w.close()
 
 
+def test_timing_read_outs_around_a_reset(core):
+    name = "derived_48k"
+    push, step = stim.sequence(name)[0], _reference(name)[0]
+    w = _writer(core, name)
+    assert w.last_kernel_ms() == 0.0 and list(w.last_pass_ms()) == [0.0] * 5  # nothing pushed yet
+    for label in ("first push", "after reset"):
+        stim.apply_pre(w, push["pre"])
+        rows, written = w.push(push["x"], push["fill"], push["clean_path"])
+        _compare(w, rows, written, step, (name, label))
+        total, passes = w.last_kernel_ms(), list(w.last_pass_ms())
+        assert len(passes) == 5 and all(np.isfinite(t) and t >= 0.0 for t in passes + [total]), (label, total, passes)
+        w.reset()
+    w.close()
+
+
 def test_fresh_writer_reads_the_initial_fields(core):
     w = _writer(core, "derived_48k")
     m, c = w.meters(), w.counters()

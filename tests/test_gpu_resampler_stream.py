@@ -21,6 +21,8 @@ pytestmark = pytest.mark.gpu
 N_STREAMS = F.N_STREAMS
 CALLS = F.CALLS  # zero-output calls and a 3000-frame call among them
 OTHER_PARTITION = F.OTHER_PARTITION
+GROWING_CALLS = [64, 99, 153, 237, 367, 569, 881, 1365, 2115, 3277, 5077, 8000]  # the first fills no 256-frame chunk
+STEADY_CALLS = [700] * 10  # behind them: nothing grows any more, so the eight staging slots are reused in turn
 RATIOS = [(44_100, 48_000), (48_000, 44_100), (32_000, 48_000), (96_000, 48_000), (48_000, 16_000)]  # test_bit_exact_against_oracle's
 
 
@@ -219,6 +221,34 @@ def test_push_device_on_a_side_stream_matches_push_host(core):
         assert (y[:, made:] == 7.0).all(), "the resampler wrote past a row's frames"
         at += n
     host.close()
+    dev.close()
+    # Twelve pushes queued on the side stream with no host wait between them, each about 1.5 times the one before: every
+    # call's position records outgrow the pinned slots (which wait for the copies in flight and are reallocated) and their
+    # device buffer (replaced, the old one retired behind an event).  Then ten equal pushes that fit: the eight slots are
+    # reused in turn while earlier copies may still be in flight, each after a wait on its own event.  65 streams: one
+    # full 64-stream workgroup and a tail.  The joined output against the oracle, bit for bit.
+    kw = dict(chunk_size=256, sinc_len=64, window="hann")
+    calls = GROWING_CALLS + STEADY_CALLS
+    x = _batch(65, sum(calls), 29)
+    want = np.concatenate(_oracle_calls(x, calls, fi, fo, **kw), axis=1)
+    dev = core.StreamResampler(fi, fo, n_streams=65, **kw)
+    made = []
+    xin = torch.from_numpy(x).cuda()
+    out = torch.full((65, want.shape[1] + 5), 7.0, dtype=torch.float32, device="cuda")
+    torch.cuda.synchronize()
+    at = done = 0
+    for n in calls:
+        cap = dev.output_frames(n)
+        made.append(dev.push_device(xin.data_ptr() + 4 * at, n, x.shape[1], out.data_ptr() + 4 * done, cap, out.shape[1], side.cuda_stream))
+        assert made[-1] == cap
+        at += n
+        done += cap
+    side.synchronize()
+    assert done == want.shape[1] and made[0] == 0 and sum(m > 0 for m in made[:12]) >= 9 and min(made[12:]) > 0, made
+    y = out.cpu().numpy()
+    differ = np.flatnonzero((_bits(y[:, :done]) != _bits(want)).any(axis=1))
+    assert differ.size == 0, differ[:8].tolist()
+    assert (y[:, done:] == 7.0).all(), "the resampler wrote past a row's frames"
     dev.close()
 
 
