@@ -21,6 +21,7 @@
 #include "af_retune.h"
 #include "af_stages.h"
 #include "af_suppressor_host.hpp"
+#include "af_switches.hpp"
 
 namespace af {
 size_t lane_kernel_dynamic_lds(int lookahead_samples);
@@ -30,9 +31,6 @@ hipError_t launch_chain_ring(const LaunchArgs &args, int n_sections, int lookahe
                              bool auto_makeup, hipStream_t stream);
 hipError_t launch_chain_ring_lds(const LaunchArgs &args, size_t dyn, int variant, bool auto_makeup, hipStream_t stream);
 hipError_t launch_chain_publish_ready(int64_t *ready, int64_t samples, hipStream_t stream);
-hipError_t launch_eq_stream_part(const ChainParams *d_params, double *st64, const float *in, float *audio, BlockStats *stats,
-                                 double *block_power, int sec0, int count, bool head, int64_t n_samples, int64_t stream_stride,
-                                 int32_t n_streams, hipStream_t stream);
 hipError_t launch_chain_quad(const LaunchArgs &args, int n_sections, int lookahead_samples, bool crossfade, int waves,
                              hipStream_t stream);
 size_t quad_kernel_dynamic_lds(int n_sections, int lookahead_samples, bool crossfade);
@@ -121,7 +119,6 @@ struct af_engine {
   af::RetireList retired;
   hipStream_t syn_stream = nullptr;        // CU partition: pitch spectra + network + resynthesis (else the caller's stream)
   hipStream_t fin_stream = nullptr;        // resynthesis + overlap-add of window w beside pitch spectra + network of w+1
-  hipStream_t rnn_stream = nullptr;        // the network of window w beside the pitch spectra of w+1 (AF_RNN_STREAM=0: on syn_stream)
   hipStream_t lim_stream = nullptr;        // AF_ROLES=2: the limiter half of the chain (af_roles.hip) on CUs of its own
   hipStream_t eq_stream = nullptr;         // the window's systolic EQ (af_eq_systolic.hip), behind its overlap-add, beside the next window's synthesis
   int partition_chain_cus = 0;             // CUs reserved for the chain stream (0 = the streams are not masked)
@@ -134,7 +131,6 @@ struct af_engine {
   double vad_reliability = 0.0, noise_floor_db = 0.0, live_noise_reliability = 0.0;
   bool has_evidence = false;
   af::DeviceBuffer<int32_t> d_status;
-  bool eq_params_on_es = false;              // the EQ parameter block's last upload ran on the EQ stream (two-part EQ: who must wait for it)
   af::DeviceBuffer<int64_t> d_ready;         // samples of the running call the suppressor's side has finished (LaunchArgs::ready)
   af::DeviceBuffer<float> d_io;  // staging for the host entry point
   hipStream_t last_stream = nullptr;
@@ -248,7 +244,7 @@ af_engine::~af_engine() {
     (void)hipSetDevice(device);
     (void)hipDeviceSynchronize();
     if (borrowed_streams) aux_stream = pre_stream = ana_stream = fin_stream = eq_stream = nullptr;
-    for (hipStream_t st : {pipe.stream, lim_stream, fin_stream, rnn_stream, eq_stream, syn_stream, aux_stream, pre_stream, ana_stream})
+    for (hipStream_t st : {pipe.stream, lim_stream, fin_stream, eq_stream, syn_stream, aux_stream, pre_stream, ana_stream})
       if (st) (void)hipStreamDestroy(st);
     supp.release_all();
   }
@@ -462,32 +458,6 @@ int check_device_status(af_engine *e) {
     return fail(AF_ERR_BACKEND, "a chain kernel abandoned a stage token (device status %d); results are invalid.  (A one-launch call "
                                 "waits for kernels on other streams: if something serialises dispatches, set AF_CHAIN_PERSISTENT=0.)", st);
   return AF_OK;
-}
-
-// AF_ROLES (same-box A/B): 0 = AUTO never takes the role kernels; 1 = compressor and limiter both as role kernels;
-// 2 = the compressor stays on the token-ring kernel (which then ends at the compressor's output) and the limiter half runs as
-// the role kernel -- behind the suppressor on a stream and CUs of its own, one window behind the compressor.
-int roles_mode() {
-  static const int mode = [] {
-    const char *env = std::getenv("AF_ROLES");
-    return env ? std::atoi(env) : 0;
-  }();
-  return mode;
-}
-
-// AF_CHAIN_PERSISTENT=0 / 1; default on, except under tools that serialise dispatches: a launch that waits for kernels on other
-// streams needs them to run beside it (counter collection of rocprofv3 `--pmc`, the runtime's blocking-launch debug switches).
-bool one_launch_calls_enabled() {
-  static const bool on = [] {
-    const char *env = std::getenv("AF_CHAIN_PERSISTENT");
-    if (env) return std::atoi(env) != 0;
-    for (const char *name : {"ROCPROF_COUNTER_COLLECTION", "AMD_SERIALIZE_KERNEL", "HIP_LAUNCH_BLOCKING", "CUDA_LAUNCH_BLOCKING"}) {
-      const char *v = std::getenv(name);
-      if (v && std::atoi(v) != 0) return false;
-    }
-    return true;
-  }();
-  return on;
 }
 
 // after a launch of n samples: advance the (stream-uniform) crossfade counters
@@ -814,7 +784,7 @@ int launch_chain_segment(af_engine *e, const af::ChainParams &run_in, bool run_m
   // `ready`: the segment is a whole call whose input arrives window by window (LaunchArgs::ready); only the plain one-launch form
   // of the token-ring kernel follows such a counter -- the caller has checked that this is what the configuration takes
   const bool followed_counter = ready != nullptr;
-  if (ready && (!e->extra_presets.empty() || e->kernel == AF_KERNEL_ROLES || roles_mode() != 0))
+  if (ready && (!e->extra_presets.empty() || e->kernel == AF_KERNEL_ROLES || af::switches().roles != 0))
     return fail(AF_ERR_BACKEND, "internal: only the plain token-ring launch follows a ready counter");
   if (!e->extra_presets.empty())
     return launch_chain_multi(e, e->host_params.flags & ~run_in.flags, run_in.flags & af::kFlagInputDone, in, out, n_samples,
@@ -858,7 +828,7 @@ int launch_chain_segment(af_engine *e, const af::ChainParams &run_in, bool run_m
   // waves, LDS hand-over; the EQ and the block input statistics are the systolic EQ kernel's.  Where it serves the
   // configuration it replaces the token-ring launch (same state planes: the two can alternate mid-stream).
   {
-    const int roles_env = roles_mode();
+    const int roles_env = af::switches().roles;
     const bool input_done = (run.flags & af::kFlagInputDone) != 0;
     const bool eq_pre_ok = layout == AF_LAYOUT_STREAM_MAJOR && !(run.flags & (af::kFlagDcBlock | af::kFlagPreHighpass)) &&
                            (!(run.flags & af::kFlagEq) || run.n_eq_sections <= 16);
@@ -1293,11 +1263,7 @@ int stage_diag_step(af_engine *e, const af::ChainParams &run, const StagePlan &p
   d.auto_makeup = (run.flags & af::kFlagCompressor) && run.comp.auto_makeup_enabled;
   d.base.stream_stride = sp.call_stride;
   d.deesser = (run.flags & af::kFlagDeesser) ? 1 : 0;
-  static const int debug_skip = [] {  // AF_STAGE_SKIP=<StageId>: timing probe (that stage does nothing; results are garbage)
-    const char *env = std::getenv("AF_STAGE_SKIP");
-    return env ? std::atoi(env) : -1;
-  }();
-  d.debug_skip = debug_skip;
+  d.debug_skip = af::switches().stage_skip;  // AF_STAGE_SKIP=<StageId>: timing probe (that stage does nothing; results are garbage)
   // two dispatches per step: the one-wave workgroups (serial stages and F4), then the wide stages; with the de-esser a third
   // for its serial stages
   for (int pass = 0; pass < (d.deesser ? 3 : 2); ++pass) {
@@ -1330,18 +1296,10 @@ int stage_diag_step(af_engine *e, const af::ChainParams &run, const StagePlan &p
   return AF_OK;
 }
 
-bool rnn_stream_wanted() {
-  static const bool on = [] {
-    const char *env = std::getenv("AF_RNN_STREAM");
-    return env && std::atoi(env) == 1;
-  }();
-  return on;
-}
-
 // The engine's side streams (created once).  With queue CU masks: the chain stream on as many CUs as the chain has workgroups,
 // every other stream on the rest.
 int ensure_side_streams(af_engine *e, hipStream_t stream) {
-  if (std::getenv("AF_SERIAL_STREAMS")) {  // diagnostic: every stage on the caller's stream (per-kernel times without overlap)
+  if (af::switches().serial_streams) {  // AF_SERIAL_STREAMS, diagnostic: every stage on the caller's stream (per-kernel times without overlap)
     e->aux_stream = e->pre_stream = e->ana_stream = e->fin_stream = e->eq_stream = stream;
     e->borrowed_streams = true;
   }
@@ -1353,50 +1311,41 @@ int ensure_side_streams(af_engine *e, hipStream_t stream) {
     // workgroups (mask bits 0.. select the same CU indices on every XCD: tools/probe/cu_mask_probe.hip) and the
     // suppressor's streams to the rest; neither side ever waits for the other's workgroups to leave.
     int chain_cus = 0;
-    const char *env = std::getenv("AF_CU_PARTITION");
+    const int forced_cus = af::switches().cu_partition;  // AF_CU_PARTITION: 0 no masks, N > 0 that many CUs, else automatic
     const int chain_groups = (e->n_streams + 63) / 64;
     hipDeviceProp_t prop;
     AF_HIP(hipGetDeviceProperties(&prop, e->device));
     const int total_cus = prop.multiProcessorCount;
-    if (!(env && std::atoi(env) == 0) && total_cus % 32 == 0 && total_cus <= 1024) {
+    if (forced_cus != 0 && total_cus % 32 == 0 && total_cus <= 1024) {
       // (a power of two: the workgroups of a launch are dealt to the XCDs in turn and 48 or 56 enabled CUs leave some of them
       // with two workgroups each -- 3072 streams: 356 ms of chain launches per step on 48 CUs, 197 on 64)
       int pow2 = 8;
       while (pow2 < chain_groups) pow2 *= 2;
-      chain_cus = env && std::atoi(env) > 0 ? std::atoi(env) : pow2;
+      chain_cus = forced_cus > 0 ? forced_cus : pow2;
       if (chain_cus * 2 > total_cus) chain_cus = 0;  // a chain that wants half the chip or more shares all of it
     }
     if (chain_cus > 0) {
       // AF_ROLES=2: the limiter half of the chain gets CUs of its own (AF_LIM_CUS, default as many as the chain), taken from
       // the suppressor's share
       int lim_cus = 0;
-      if (roles_mode() == 2) {
-        const char *lenv = std::getenv("AF_LIM_CUS");
-        lim_cus = lenv ? std::atoi(lenv) : chain_cus;
+      if (af::switches().roles == 2) {
+        lim_cus = af::switches().lim_cus >= 0 ? af::switches().lim_cus : chain_cus;
         if (lim_cus < 0 || chain_cus + lim_cus + 32 > total_cus) lim_cus = 0;
       }
       std::vector<uint32_t> chain_mask(total_cus / 32, 0u), rest_mask(total_cus / 32, 0u), lim_mask(total_cus / 32, 0u);
-      // AF_CU_PATTERN (placement probe): 0 = the chain takes mask bits 0.. (CU indices 0.. of every XCD); 1 = every other CU
-      // index (bit / 8 even); 2 = the highest bits
-      static const int pattern = [] { const char *v = std::getenv("AF_CU_PATTERN"); return v ? std::atoi(v) : 0; }();
-      for (int bit = 0; bit < total_cus; ++bit) {
-        int rank = bit;  // the chain takes ranks 0 .. chain_cus-1
-        if (pattern == 1) rank = ((bit / 8) % 2 == 0) ? (bit / 16) * 8 + bit % 8 : total_cus / 2 + (bit / 16) * 8 + bit % 8;
-        else if (pattern == 2) rank = total_cus - 1 - bit;
-        (rank < chain_cus ? chain_mask : (rank < chain_cus + lim_cus ? lim_mask : rest_mask))[bit >> 5] |= 1u << (bit & 31);
-      }
+      // the chain takes mask bits 0.. (CU indices 0.. of every XCD), the limiter half the next ones
+      for (int bit = 0; bit < total_cus; ++bit)
+        (bit < chain_cus ? chain_mask : (bit < chain_cus + lim_cus ? lim_mask : rest_mask))[bit >> 5] |= 1u << (bit & 31);
       hipError_t err = hipExtStreamCreateWithCUMask(&e->aux_stream, (uint32_t)chain_mask.size(), chain_mask.data());
       if (err == hipSuccess && lim_cus > 0) err = hipExtStreamCreateWithCUMask(&e->lim_stream, (uint32_t)lim_mask.size(), lim_mask.data());
       if (err == hipSuccess) err = hipExtStreamCreateWithCUMask(&e->pre_stream, (uint32_t)rest_mask.size(), rest_mask.data());
       if (err == hipSuccess) err = hipExtStreamCreateWithCUMask(&e->ana_stream, (uint32_t)rest_mask.size(), rest_mask.data());
       if (err == hipSuccess) err = hipExtStreamCreateWithCUMask(&e->syn_stream, (uint32_t)rest_mask.size(), rest_mask.data());
       if (err == hipSuccess) err = hipExtStreamCreateWithCUMask(&e->fin_stream, (uint32_t)rest_mask.size(), rest_mask.data());
-      if (err == hipSuccess && rnn_stream_wanted()) err = hipExtStreamCreateWithCUMask(&e->rnn_stream, (uint32_t)rest_mask.size(), rest_mask.data());
       if (err == hipSuccess) err = hipExtStreamCreateWithCUMask(&e->eq_stream, (uint32_t)rest_mask.size(), rest_mask.data());
       if (err != hipSuccess) {  // platform without queue CU masks: plain streams
         (void)hipGetLastError();
-        for (hipStream_t *sp : {&e->aux_stream, &e->pre_stream, &e->ana_stream, &e->syn_stream, &e->fin_stream, &e->eq_stream, &e->lim_stream,
-                                &e->rnn_stream}) {
+        for (hipStream_t *sp : {&e->aux_stream, &e->pre_stream, &e->ana_stream, &e->syn_stream, &e->fin_stream, &e->eq_stream, &e->lim_stream}) {
           if (*sp) (void)hipStreamDestroy(*sp);
           *sp = nullptr;
         }
@@ -1409,7 +1358,6 @@ int ensure_side_streams(af_engine *e, hipStream_t stream) {
   if (!e->pre_stream) AF_HIP(hipStreamCreateWithFlags(&e->pre_stream, hipStreamNonBlocking));
   if (!e->ana_stream) AF_HIP(hipStreamCreateWithFlags(&e->ana_stream, hipStreamNonBlocking));
   if (!e->fin_stream) AF_HIP(hipStreamCreateWithFlags(&e->fin_stream, hipStreamNonBlocking));
-  if (!e->rnn_stream && !e->borrowed_streams && rnn_stream_wanted()) AF_HIP(hipStreamCreateWithFlags(&e->rnn_stream, hipStreamNonBlocking));
   if (!e->eq_stream) AF_HIP(hipStreamCreateWithFlags(&e->eq_stream, hipStreamNonBlocking));
   return AF_OK;
 }
@@ -2070,6 +2018,506 @@ static const char *const kWriterStreamOnlyMessage =
 static const char *const kChannelsStreamOnlyMessage =
     "this engine takes multichannel input (af_engine_set_input_channels): use af_engine_stream_host";
 
+// ---- what the three paths of a process call share
+// one accepted call's arguments, as the paths below take them
+struct CallArgs {
+  const float *chain_in;  // what the chain reads: the caller's `in`, or `out` behind the noise gate's pre-pass
+  float *out;
+  int64_t n_samples, stream_stride;
+  int32_t layout;
+  hipStream_t stream;
+  uint32_t gate_strip;  // the front-end flags the noise gate's pre-pass has taken over (0: there was none)
+  int64_t rows;         // statistics rows of the call: control blocks x streams
+};
+
+static_assert(af::kRnnFrame == 480, "af::supp_window_unit counts 480-sample frames");
+static int64_t whole_blocks(int cb, int64_t samples) { return (int64_t)cb * std::max<int64_t>(1, samples / cb); }
+constexpr int64_t kStageWindowSamples = 2880;  // the stage pipeline's window behind the suppressor (Switches::stage_window without it)
+
+static bool eq_crossfade_pending(const af::ChainParams &hp) {
+  bool xf = false;
+  for (int j = 0; j < hp.n_eq_sections; ++j) xf = xf || hp.eq[j].xf_remaining > 0;
+  return xf;
+}
+
+// Whether the chain of `hp` can run with its EQ launched beside it (af_eq_systolic.hip) and the rest as the plain one-launch
+// form of the token-ring kernel.  `also_barred`: flags that keep this caller off the form besides the de-esser and the
+// sample-serial front end; `crossfade_lds`: size the launch's LDS for a coefficient crossfade.
+static bool eq_side_launch_serves(const af::ChainParams &hp, uint32_t also_barred, bool crossfade_lds) {
+  return !(hp.flags & (af::kFlagDeesser | af::kFlagDcBlock | af::kFlagPreHighpass | also_barred)) && hp.n_eq_sections <= 16 &&
+         af::ring_kernel_dynamic_lds(hp.n_eq_sections, hp.lim.lookahead_samples, crossfade_lds) <= af::kMaxLdsBytes;
+}
+
+// window number `index` of this call in the stage pipeline: `n` samples from sample `t0` of the call, its rows from `blocks_at`
+static af::DiagWin diag_window(const af_engine *e, int64_t index, int64_t t0, int64_t n, int64_t blocks_at, const float *in, float *out) {
+  af::DiagWin wd{};
+  wd.n0 = e->samples_processed + t0;
+  wd.n = n;
+  wd.stats = e->d_stats + blocks_at * e->n_streams;
+  wd.mk = e->pipe.d_mk + ((e->pipe.windows + index) % af_engine::StagePipe::kMkSets) * e->pipe.mk_rows;
+  wd.bp = e->pipe.d_bp + ((e->pipe.windows + index) % af_engine::StagePipe::kBpSets) * e->pipe.mk_rows;
+  wd.vad = e->has_evidence ? e->d_vad + blocks_at * e->n_streams : nullptr;
+  wd.in = in;
+  wd.out = out;
+  return wd;
+}
+
+// the realtime front end (clamp + DC block + 80 Hz HP, routing.rs:802-843) as a sample-serial pre-pass runs it: which of
+// `flags` it takes over, the high-pass of `hp`, the chain's state planes (`front_scrub` is the caller's)
+static void supp_front_end(const af_engine *e, const af::ChainParams &hp, uint32_t flags, af::SuppArgs &sa) {
+  sa.front_clamp = (flags & af::kFlagInputClamp) ? 1 : 0;
+  sa.front_dc = (flags & af::kFlagDcBlock) ? 1 : 0;
+  sa.front_hp = (flags & af::kFlagPreHighpass) ? 1 : 0;
+  sa.hp_b0 = hp.pre_hp.b0; sa.hp_b1 = hp.pre_hp.b1; sa.hp_b2 = hp.pre_hp.b2;
+  sa.hp_a1 = hp.pre_hp.a1; sa.hp_a2 = hp.pre_hp.a2;
+  sa.chain_st64 = e->d_st64;
+  sa.chain_st32 = e->d_st32;
+  sa.f64_pre_z1 = af::kPreZ1;
+  sa.f32_dc_x1 = af::kDcX1;
+}
+
+// `d_params_eq` holds kEqParamSlots blocks per preset (sized as the stage pipeline sizes it)
+static int ensure_eq_params(af_engine *e, int n_presets) {
+  if (!e->d_params_eq || e->eq_params_presets != n_presets) {
+    e->d_params_eq.release();
+    AF_HIP(e->d_params_eq.reserve_exact(sizeof(af::ChainParams) * n_presets * kEqParamSlots));
+    e->eq_params_presets = n_presets;
+    e->uploaded_eq.clear();
+  }
+  return AF_OK;
+}
+
+// `d_params_eq` <- `runs`, on `stream`, unless that is what it holds
+static int upload_eq_params_if_changed(af_engine *e, const std::vector<af::ChainParams> &runs, hipStream_t stream) {
+  if (e->uploaded_eq.size() == runs.size() && std::memcmp(e->uploaded_eq.data(), runs.data(), sizeof(af::ChainParams) * runs.size()) == 0)
+    return AF_OK;
+  e->uploaded_eq = runs;
+  return stage_upload(e, e->d_params_eq, runs.data(), runs.size(), stream);
+}
+
+// ---- path 1: the chain as a pipeline of stage kernels over windows of whole control blocks (af_stages.hip)
+// (a launch step costs ~20 us, the pipeline's fill is depth x window time: 960 samples 45.7 ms per 10 s at 256 streams,
+// 1920 41.2, 2880 39.7, 4800 42.7, 9600 40.3)
+static int run_stage_pipeline(af_engine *e, const CallArgs &c) {
+  const int cb = e->host_params.control_block;
+  const int64_t tw = whole_blocks(cb, af::switches().stage_window);
+  if (int rc = stage_pipe_prepare(e, std::max<int64_t>(tw, e->pipe.tw_max))) return rc;
+  e->pipe.strip = e->host_params.flags & c.gate_strip;
+  if (int rc = stage_chain_params(e, c.stream)) return rc;  // what the stage kernels read (everything but the EQ sections)
+  e->last_kernel_used = AF_KERNEL_STAGED;
+  // one launch step per window on the caller's stream: step j runs every stage on the window it has reached
+  const StagePlan plan = stage_plan(e->host_params);
+  std::vector<af::DiagWin> wins;
+  int64_t blocks_at = 0;
+  for (int64_t t0 = 0; t0 < c.n_samples; t0 += tw) {
+    const int64_t n_w = std::min<int64_t>(tw, c.n_samples - t0);
+    wins.push_back(diag_window(e, (int64_t)wins.size(), t0, n_w, blocks_at, c.chain_in + t0, c.out + t0));
+    blocks_at += (n_w + cb - 1) / cb;
+  }
+  e->pipe.call_stride = c.stream_stride;
+  AF_HIP(hipMemsetAsync(e->d_stats, 0, sizeof(af::BlockStats) * c.rows, c.stream));
+  const int64_t steps = (int64_t)wins.size() + plan.depth;
+  for (int64_t j = 0; j < steps; ++j) {
+    if (j < (int64_t)wins.size()) {  // window j enters: its EQ stage reads the section parameters as they stand now
+      bool crossfade = false;
+      if (int rc = stage_diag_eq_params(e, c.stream, &crossfade, &wins[(size_t)j].eq_slot)) return rc;
+      wins[(size_t)j].eq_crossfade = crossfade ? 1 : 0;
+      advance_crossfades(e, wins[(size_t)j].n);
+    }
+    if (int rc = stage_diag_step(e, e->host_params, plan, wins, j, c.stream)) return rc;
+  }
+  e->pipe.windows += (int64_t)wins.size();
+  return AF_OK;
+}
+
+// ---- path 2: the chain as one launch.  Large batches without the suppressor (round 3): the chain can use one CU per 64
+// streams and nothing else, so the EQ -- a quarter of the token-ring kernel's time -- runs as the systolic kernel on the CUs
+// the chain leaves idle, window by window, and the chain is ONE launch that follows it through the ready counter (the form
+// the suppressor's pipeline uses).  Taken when the streams can be CU-partitioned and the EQ kernel serves the
+// configuration; everything else is the plain segment launch on the caller's stream.
+static int run_chain_launch(af_engine *e, const CallArgs &c) {
+  const int cb = e->host_params.control_block;
+  const hipStream_t stream = c.stream;
+  af::ChainParams hp = e->host_params;  // (a copy: with the gate on, the front end is the pre-pass's)
+  hp.flags &= ~c.gate_strip;
+  const bool auto_mk = (hp.flags & af::kFlagCompressor) && hp.comp.auto_makeup_enabled;
+  const int64_t window = whole_blocks(cb, 9600);
+  // (the chain launch lays out its LDS for a crossfade only when one is pending at the call's start, as
+  // launch_chain_segment sizes it: checking the crossfade layout always kept 15 and 16 sections off this form)
+  bool offload = af::switches().chain_persistent && af::switches().eq_offload && (e->kernel == AF_KERNEL_AUTO || e->kernel == AF_KERNEL_PHASED) &&
+                 (e->ring_variant == 0 || e->ring_variant == 1604) && e->extra_presets.empty() && af::switches().roles == 0 &&
+                 c.layout == AF_LAYOUT_STREAM_MAJOR && (hp.flags & af::kFlagEq) && hp.n_eq_sections > 0 &&
+                 eq_side_launch_serves(hp, af::kFlagPrePass, eq_crossfade_pending(hp)) && c.n_samples >= 2 * window &&
+                 !af::switches().serial_streams;
+  if (offload) {
+    if (int rc = ensure_side_streams(e, stream)) return rc;
+    offload = e->partition_chain_cus > 0 && !e->borrowed_streams;
+  }
+  if (!offload)  // (no suppressor: everything is chain time)
+    return launch_chain_segment(e, hp, c.gate_strip != 0, c.chain_in, c.out, c.n_samples, c.stream_stride, c.layout, e->samples_processed,
+                                e->d_stats, e->has_evidence ? e->d_vad : nullptr, stream, stream);
+  if (auto_mk) AF_HIP(e->d_block_power.reserve_retiring(sizeof(double) * c.rows, e->retired, stream));
+  AF_HIP(hipMemsetAsync(e->d_stats, 0, sizeof(af::BlockStats) * c.rows, stream));
+  AF_HIP(e->d_ready.reserve_exact(sizeof(int64_t)));
+  AF_HIP(hipMemsetAsync(e->d_ready, 0, sizeof(int64_t), stream));
+  hipEvent_t ev;
+  if (int rc = engine_event(e, &ev)) return rc;
+  AF_HIP(hipEventRecord(ev, stream));
+  AF_HIP(hipStreamWaitEvent(e->aux_stream, ev, 0));
+  AF_HIP(hipStreamWaitEvent(e->eq_stream, ev, 0));
+  af::ChainParams run_p = hp;  // the EQ kernel scrubs / clamps the input and keeps the block input statistics
+  run_p.flags = (run_p.flags & ~(af::kFlagEq | af::kFlagInputScrub | af::kFlagInputClamp)) | af::kFlagInputDone;
+  if (int rc = launch_chain_segment(e, run_p, true, c.out, c.out, c.n_samples, c.stream_stride, c.layout, e->samples_processed, e->d_stats,
+                                    e->has_evidence ? e->d_vad : nullptr, e->aux_stream, stream, /*stats_cleared=*/true,
+                                    auto_mk ? e->d_block_power : nullptr, e->d_ready))
+    return rc;
+  if (int rc = ensure_eq_params(e, 1)) return rc;
+  int64_t blocks_done = 0;
+  for (int64_t seg0 = 0; seg0 < c.n_samples; seg0 += window) {
+    const int64_t seg_n = std::min<int64_t>(window, c.n_samples - seg0);
+    std::vector<af::ChainParams> run_eq(1, e->host_params);  // (as the crossfade counters stand at this window)
+    run_eq[0].flags &= ~c.gate_strip;
+    if (int rc = upload_eq_params_if_changed(e, run_eq, e->eq_stream)) return rc;
+    AF_HIP(af::launch_eq_systolic(e->d_params_eq, nullptr, e->d_st64, c.chain_in + seg0, c.out + seg0, nullptr, nullptr, 0, 0,
+                                  e->d_stats + blocks_done * e->n_streams, eq_crossfade_pending(run_eq[0]), seg_n, c.stream_stride, e->n_streams,
+                                  e->eq_stream,
+                                  auto_mk ? e->d_block_power + blocks_done * e->n_streams : nullptr));  // (the systolic form: here the EQ's own latency per window is what the chain follows)
+    AF_HIP(af::launch_chain_publish_ready(e->d_ready, seg0 + seg_n, e->eq_stream));
+    e->last_launches += 2;
+    advance_crossfades(e, seg_n);
+    blocks_done += (seg_n + cb - 1) / cb;
+  }
+  for (hipStream_t side : {e->aux_stream, e->eq_stream}) {
+    if (int rc = engine_event(e, &ev)) return rc;
+    AF_HIP(hipEventRecord(ev, side));
+    AF_HIP(hipStreamWaitEvent(stream, ev, 0));
+  }
+  return AF_OK;
+}
+
+// ---- path 3: the RNNoise suppressor ahead of the chain (realtime order, dsp_loop.rs:1222-1250,1521-1599).
+// The call is cut into windows of frames and runs as a four-stage pipeline over them, one HIP stream each:
+//   pre stream    : window w+2's sample-serial pre-pass (front end + model-input high-pass; 64 waves whose
+//                   duration is set by recurrence latency, so it costs the chip almost nothing)
+//   analysis      : window w+1's spectra and pitch search (the pitch kernel walks each stream's frames in
+//                   order, one wave per stream: latency bound, it leaves most issue slots free)
+//   caller stream : window w's pitch-aligned spectra, network, resynthesis, overlap-add
+//   chain stream  : window w-1's chain launch (64 streams per workgroup, a quarter of the CUs at batch 4096)
+// ordered by events; buffers that cross a stage boundary rotate (af_suppressor_host.hpp).
+// `src` / `src_stride`: the call's whole frames (the caller's input or the engine's assembly buffer); `vad_args` with
+// `fused_gate`: the VAD-fused gate modes' pass instead of the plain pre-pass.
+static int run_suppressor_pipeline(af_engine *e, const CallArgs &c, const float *src, int64_t src_stride, bool fused_gate,
+                                   const af::VadGateArgs &vad_args) {
+  const af::Switches &sw = af::switches();
+  const int cb = e->host_params.control_block;
+  const hipStream_t stream = c.stream;
+  float *const out = c.out;
+  const int64_t stream_stride = c.stream_stride;
+  if (e->supp.weights_dirty) AF_HIP(e->supp.upload());
+  af::ChainParams run = e->host_params;
+  bool run_modified = false;
+  const uint32_t front = af::kFlagInputClamp | af::kFlagDcBlock | af::kFlagPreHighpass;
+  const uint32_t front_flags = run.flags & front;
+  const bool strip_front = front_flags || e->gate_enabled;  // the gate runs in the pre-pass too, after the front end
+  if (strip_front) {
+    // the realtime front end runs inside the suppressor's own sample-serial pre-pass, so the chain launches must not repeat it
+    run.flags &= ~(front | af::kFlagInputScrub);
+    run_modified = true;
+  }
+  const int64_t frames = c.n_samples / af::kRnnFrame;
+  const std::vector<af::SuppWindow> wins = af::supp_window_schedule(frames, af::supp_window_unit(cb), e->supp_window_frames, e->pipe.active, sw);
+  {
+    int64_t longest = 1;
+    for (const af::SuppWindow &win : wins) longest = std::max(longest, win.nf);
+    AF_HIP(e->supp.ensure_workspace(e->n_streams, (int)longest));
+  }
+  if (e->trace) {
+    if (sizeof(int32_t) * 2 * frames * e->n_streams > e->d_trace.bytes()) {
+      AF_HIP(hipDeviceSynchronize());
+      AF_HIP(e->d_trace.reserve_exact(sizeof(int32_t) * 2 * frames * e->n_streams));
+    }
+    e->trace_frames = frames;
+  }
+  // (a suppressor window enters the stage pipeline in pieces of the pipeline's own window length: the rings stay as small as
+  // without the suppressor)
+  const int64_t chain_tw = whole_blocks(cb, kStageWindowSamples);
+  if (e->pipe.active) {
+    if (int rc = stage_pipe_prepare(e, std::max<int64_t>(chain_tw, e->pipe.tw_max))) return rc;
+    e->pipe.strip = e->host_params.flags & ~run.flags;  // what the pre-pass has taken over
+    if (int rc = stage_chain_params(e, stream)) return rc;  // (everything but the EQ sections is read from here)
+  }
+  if (int rc = ensure_side_streams(e, stream)) return rc;
+  const hipStream_t fin = sw.synth_split ? e->fin_stream : nullptr;
+  const hipStream_t syn = e->syn_stream ? e->syn_stream : stream;  // where the synthesis stage runs
+  const hipStream_t last_supp = (fin && fin != syn) ? fin : syn;   // where a window's last suppressor kernel runs
+  int64_t blocks_done = 0;
+  std::vector<af::DiagWin> diag_wins;                 // the call's windows in the stage pipeline (one launch per step)
+  const StagePlan diag_plan = stage_plan(run);
+  const bool eq_offload = sw.eq_offload && (e->kernel == AF_KERNEL_AUTO || e->kernel == AF_KERNEL_PHASED || e->kernel == AF_KERNEL_ROLES) &&
+                          (e->ring_variant == 0 || e->ring_variant == 1604) && (run.flags & af::kFlagEq);
+  bool eq_needs_chain_done = true;  // (the previous call's last chain launch has ended: the caller's stream waited for it)
+  const bool auto_makeup_call = (run.flags & af::kFlagCompressor) && run.comp.auto_makeup_enabled;
+  if (eq_offload && auto_makeup_call && !e->pipe.active) {
+    // the systolic EQ kernel is then also the pre-pass of every window (it leaves the compressor-input block powers here)
+    AF_HIP(e->d_block_power.reserve_retiring(sizeof(double) * c.rows, e->retired, stream));
+  }
+  auto next_event = [&](hipEvent_t *out_ev) -> int { return engine_event(e, out_ev); };
+  // The call's statistics rows are cleared ONCE, here (their fields are written by the kernels that own them).  Round 2 cleared
+  // every window's rows in front of its EQ launch: a fill kernel on the suppressor's crowded CUs, 0.05-0.45 ms between the
+  // window's overlap-add and its EQ -- on the path the first chain launches wait for.
+  AF_HIP(hipMemsetAsync(e->d_stats, 0, sizeof(af::BlockStats) * c.rows, stream));
+  // ---- ONE chain launch per call (round 3).  With the chain's CUs its own, the EQ on the suppressor's side and nothing that
+  // changes the parameter block between windows, the token-ring kernel is launched once, for the whole call, before the first
+  // window: a chunk waits until the counter `d_ready` covers its samples, and every window's EQ launch is followed by a
+  // one-thread kernel that publishes the new count.  What that removes from the chain's stream: 53 dispatches and their
+  // cross-stream dependencies (~0.1 ms each while six other queues are busy: the trace of tools/step_timeline.py), the
+  // state planes' load and write-back per window, and the fill / drain of the 16-wave pipeline per launch.
+  // AF_CHAIN_PERSISTENT=0 restores one launch per window (A/B runs).
+  const bool persistent = sw.chain_persistent && eq_offload && e->partition_chain_cus > 0 && !e->pipe.active && !sw.diag_skip_chain &&
+                          e->extra_presets.empty() && sw.roles == 0 && (e->kernel == AF_KERNEL_AUTO || e->kernel == AF_KERNEL_PHASED) &&
+                          c.layout == AF_LAYOUT_STREAM_MAJOR && eq_side_launch_serves(run, 0, false) &&
+                          (!auto_makeup_call || e->d_block_power != nullptr) && wins.size() >= 2;
+  if (persistent) {
+    AF_HIP(e->d_ready.reserve_exact(sizeof(int64_t)));
+    AF_HIP(hipMemsetAsync(e->d_ready, 0, sizeof(int64_t), stream));
+  }
+  {  // the side streams start after whatever the caller queued before this call
+    hipEvent_t ev;
+    if (int rc = next_event(&ev)) return rc;
+    AF_HIP(hipEventRecord(ev, stream));
+    AF_HIP(hipStreamWaitEvent(e->aux_stream, ev, 0));
+    AF_HIP(hipStreamWaitEvent(e->pre_stream, ev, 0));
+    AF_HIP(hipStreamWaitEvent(e->ana_stream, ev, 0));
+    if (syn != stream) AF_HIP(hipStreamWaitEvent(syn, ev, 0));
+    if (fin && fin != stream) AF_HIP(hipStreamWaitEvent(fin, ev, 0));
+    if (e->eq_stream != stream) AF_HIP(hipStreamWaitEvent(e->eq_stream, ev, 0));
+    if (e->lim_stream) AF_HIP(hipStreamWaitEvent(e->lim_stream, ev, 0));
+  }
+  constexpr int kXh = af::SuppressorHost::kXhBuffers;
+  // Pipeline depth.  The spectrum / record buffers of window w are free again when its synthesis has ended, and the synthesis
+  // of w needs the analysis of w: with D buffer sets the loop analysis(w + D) <- synthesis(w) <- network(w) <- pitch spectra(w)
+  // <- analysis(w) bounds the window period by (sum of those kernels) / D.  Round 2 ran D = 2 (the trace showed exactly that
+  // period: 7.3 ms of dependent kernels per two windows); AF_SUPP_DEPTH=2 restores it for A/B runs.
+  const int depth = sw.supp_depth;
+  const int ana_ahead = depth - 1, pre_ahead = depth;  // windows the analysis / the pre-pass run ahead of the synthesis
+  auto window_args = [&](int64_t index) {
+    af::SuppArgs sa{};
+    sa.in = src;
+    sa.in_stride = src_stride;
+    sa.out = out;
+    sa.xh = e->supp.d_xh + (size_t)(index % kXh) * e->supp.xh_floats;
+    sa.X = e->supp.d_X + (size_t)(index % depth) * e->supp.ws_cells * af::kRnnFreq;
+    sa.P = e->supp.d_P + (size_t)(index % depth) * e->supp.ws_cells * af::kRnnFreq;
+    sa.ds = e->supp.d_ds;
+    sa.rec = e->supp.d_rec + (size_t)(index % depth) * e->supp.ws_cells;
+    sa.state = e->supp.d_state;
+    sa.stream_stride = stream_stride;
+    sa.n_streams = e->n_streams;
+    sa.n_frames = (int)wins[index].nf;
+    sa.frame0 = wins[index].f0;
+    sa.strength = e->supp.strength;
+    sa.smoothing_coeff = 1.0f - std::exp(-((480.0f / 48000.0f) / (15.0f / 1000.0f)));  // rnnoise.rs:45-51
+    sa.raw_protocol = e->supp.raw_protocol ? 1 : 0;
+    supp_front_end(e, run, front_flags, sa);
+    if (e->gate_enabled) {
+      sa.front_scrub = (front_flags || (e->host_params.flags & af::kFlagInputScrub)) ? 1 : 0;
+      gate_args(e, sa);
+    }
+    if (index > 0) {  // history = tail of the previous window's buffer
+      sa.xh_prev = e->supp.d_xh + (size_t)((index - 1) % kXh) * e->supp.xh_floats;
+      sa.xh_prev_stride = af::kPitchBuf + wins[index - 1].nf * af::kRnnFrame;
+    }
+    return sa;
+  };
+  const int64_t n_windows = (int64_t)wins.size();
+  std::vector<hipEvent_t> pre_done(n_windows), ana_done(n_windows), syn_done(n_windows);
+  std::vector<hipEvent_t> rnn_done(n_windows);
+  for (int64_t w = 0; w < n_windows; ++w) {
+    if (int rc = next_event(&rnn_done[w])) return rc;
+    if (int rc = next_event(&pre_done[w])) return rc;
+    if (int rc = next_event(&ana_done[w])) return rc;
+    if (int rc = next_event(&syn_done[w])) return rc;
+  }
+  // Stages are enqueued in pipeline order (the pre-pass two windows and the analysis one window ahead of the
+  // synthesis), so that every event a stage waits on has been recorded before the wait is enqueued.
+  auto enqueue_pre = [&](int64_t w) -> int {
+    if (w >= kXh) AF_HIP(hipStreamWaitEvent(e->pre_stream, syn_done[w - kXh], 0));  // its model-input buffer is free
+    if (fused_gate) {  // (a window holds whole control blocks: its first block is f0 x 480 / cb)
+      af::VadGateArgs va = vad_args;
+      va.block0 = wins[w].f0 * af::kRnnFrame / cb;
+      AF_HIP(af::launch_vad_gate_pass(window_args(w), va, e->pre_stream));
+      e->last_launches += 1;  // the control pass (the per-sample pass stands where the expander pre-pass is counted)
+    } else {
+      AF_HIP(af::launch_suppressor_prefilter(window_args(w), e->pre_stream));
+    }
+    AF_HIP(hipEventRecord(pre_done[w], e->pre_stream));
+    return AF_OK;
+  };
+  auto enqueue_ana = [&](int64_t w) -> int {
+    AF_HIP(hipStreamWaitEvent(e->ana_stream, pre_done[w], 0));
+    if (w >= depth) AF_HIP(hipStreamWaitEvent(e->ana_stream, syn_done[w - depth], 0));  // its spectrum / record buffers are free
+    // ORDERING THAT IS LOAD-BEARING: the pitch search of window w + 1 and the pitch tracker of window w must stay on this ONE
+    // stream, in this order.  The whitened pitch buffers (`d_ds`, 3.4 KB per frame and stream) are a single set: the tracker of
+    // window w reads what the search of window w wrote, and nothing but stream order keeps the search of w + 1 from overwriting
+    // it first.  (Round 2 moved the tracker to the pre-pass stream to shorten this stream: run-to-run bit-identity was lost --
+    // that race.  Moving either kernel needs a second `d_ds` set and an event from the tracker to the next search.)  The
+    // tracker also owns the stream's pitch state rows (last period / gain, cepstral ring, the 1728-sample history a NEW call's
+    // first pre-pass reads: ordered through the caller's stream at the end of the call).
+    AF_HIP(af::launch_suppressor_analysis(window_args(w), e->supp.tables, e->ana_stream));
+    AF_HIP(hipEventRecord(ana_done[w], e->ana_stream));
+    return AF_OK;
+  };
+  // a window is behind us: crossfade bookkeeping may have moved the parameters on
+  auto window_done = [&](int64_t seg_n) {
+    run = e->host_params;
+    if (strip_front) run.flags &= ~(front | af::kFlagInputScrub);
+    blocks_done += (seg_n + cb - 1) / cb;
+  };
+  if (persistent) {  // the call's one chain launch: resident on the chain's CUs from here on, following `d_ready`
+    af::ChainParams run_p = run;
+    run_p.flags = (run_p.flags & ~af::kFlagEq) | af::kFlagInputDone;  // (what every window's launch was given)
+    const int64_t total = frames * af::kRnnFrame;
+    if (int rc = launch_chain_segment(e, run_p, run_modified, out, out, total, stream_stride, c.layout, e->samples_processed, e->d_stats,
+                                      e->has_evidence ? e->d_vad : nullptr, e->aux_stream, stream, /*stats_cleared=*/true,
+                                      auto_makeup_call ? e->d_block_power : nullptr, e->d_ready))
+      return rc;
+    eq_needs_chain_done = false;  // (an event behind THIS launch would make the first EQ wait for the launch that waits for it)
+  }
+  for (int64_t w = 0; w < std::min<int64_t>(pre_ahead, n_windows); ++w)
+    if (int rc = enqueue_pre(w)) return rc;
+  for (int64_t w = 0; w < std::min<int64_t>(ana_ahead, n_windows); ++w)
+    if (int rc = enqueue_ana(w)) return rc;
+  for (int64_t w = 0; w < n_windows; ++w) {
+    const int64_t f0 = wins[w].f0, nf = wins[w].nf;
+    AF_HIP(hipStreamWaitEvent(syn, ana_done[w], 0));
+    if (fin && fin != syn && w >= depth) AF_HIP(hipStreamWaitEvent(syn, syn_done[w - depth], 0));  // its pitch-spectrum buffer is free
+    AF_HIP(af::launch_suppressor_synthesis(window_args(w), e->supp.tables, e->supp.dw, syn, rnn_done[w], fin));
+    if (e->trace) {  // the window's (silence, pitch index) decisions, before its record buffer is handed back to the analysis
+      const af::SuppArgs sa = window_args(w);
+      AF_HIP(hipMemcpy2DAsync(e->d_trace + 2 * f0 * e->n_streams, 2 * sizeof(int32_t),
+                              reinterpret_cast<const char *>(sa.rec) + offsetof(af::SuppFrameRec, silence), sizeof(af::SuppFrameRec),
+                              2 * sizeof(int32_t), (size_t)(nf * e->n_streams), hipMemcpyDeviceToDevice, last_supp));
+    }
+    AF_HIP(hipEventRecord(syn_done[w], last_supp));
+    e->last_launches += 7;
+    if (w + pre_ahead < n_windows)
+      if (int rc = enqueue_pre(w + pre_ahead)) return rc;
+    if (w + ana_ahead < n_windows)
+      if (int rc = enqueue_ana(w + ana_ahead)) return rc;
+    const int64_t seg0 = f0 * af::kRnnFrame, seg_n = nf * af::kRnnFrame;
+    af::ChainParams run_w = run;
+    bool eq_offloaded = false;
+    double *power_w = nullptr;  // the window's block powers, when its systolic EQ launch was an auto-makeup pre-pass
+    if (e->pipe.active && !sw.diag_skip_chain) {
+      // ---- the window's chain as one more step of the stage pipeline (af_stages.hip; small and medium batches): this window
+      // enters (its EQ stage reads the overlap-add output), the windows before it move one stage on
+      const hipStream_t ds = e->pipe.stream;
+      AF_HIP(hipStreamWaitEvent(ds, syn_done[w], 0));
+      e->last_kernel_used = AF_KERNEL_STAGED;
+      e->pipe.call_stride = stream_stride;
+      int64_t sub_blocks = 0;
+      for (int64_t off = 0; off < seg_n; off += chain_tw) {
+        const int64_t n_sub = std::min<int64_t>(chain_tw, seg_n - off);
+        af::DiagWin wd = diag_window(e, (int64_t)diag_wins.size(), seg0 + off, n_sub, blocks_done + sub_blocks, out + seg0 + off, out + seg0 + off);
+        bool crossfade = false;
+        if (int rc = stage_diag_eq_params(e, ds, &crossfade, &wd.eq_slot)) return rc;
+        wd.eq_crossfade = crossfade ? 1 : 0;
+        diag_wins.push_back(wd);
+        if (int rc = stage_diag_step(e, run, diag_plan, diag_wins, (int64_t)diag_wins.size() - 1, ds)) return rc;
+        advance_crossfades(e, n_sub);
+        sub_blocks += (n_sub + cb - 1) / cb;
+      }
+      window_done(seg_n);
+      continue;
+    }
+    // ---- the window's EQ on the suppressor's side (af_eq_systolic.hip), when the chain's launch would be the plain
+    // one-launch form of the token-ring kernel
+    if (eq_offload && !sw.diag_skip_chain) {
+      const int n_presets = 1 + (int)e->extra_presets.size();
+      bool ok = true, xf_w = false;
+      std::vector<af::ChainParams> runs_eq((size_t)n_presets);
+      for (int k = 0; k < n_presets && ok; ++k) {
+        runs_eq[k] = preset_params(e, k);
+        runs_eq[k].flags &= ~(e->host_params.flags & ~run.flags);  // what the pre-pass has taken over
+        ok = eq_side_launch_serves(runs_eq[k], 0, false);
+        // (a pending coefficient crossfade -- the 72 samples the legacy setters open a stream with -- runs in the systolic
+        // kernel's general form; round 2 kept such windows' EQ inside the chain launch)
+        xf_w = xf_w || eq_crossfade_pending(runs_eq[k]);
+      }
+      if (ok) {
+        const hipStream_t es = e->eq_stream;  // behind the window's overlap-add, beside the next window's synthesis
+        AF_HIP(hipStreamWaitEvent(es, syn_done[w], 0));
+        if (int rc = ensure_eq_params(e, n_presets)) return rc;
+        // (always on the EQ stream, never the caller's: a copy on the legacy default stream waits for every other stream --
+        // the resident chain launch included, which waits for this window: the call would run into the launch's bound)
+        if (int rc = upload_eq_params_if_changed(e, runs_eq, es)) return rc;
+        if (eq_needs_chain_done) {  // the previous window's EQ ran inside its chain launch: that launch owns the memories until it ends
+          hipEvent_t chain_done;
+          if (int rc = next_event(&chain_done)) return rc;
+          AF_HIP(hipEventRecord(chain_done, e->aux_stream));
+          AF_HIP(hipStreamWaitEvent(es, chain_done, 0));
+          eq_needs_chain_done = false;
+        }
+        power_w = auto_makeup_call ? e->d_block_power + blocks_done * e->n_streams : nullptr;
+        AF_HIP(af::launch_eq_systolic(e->d_params_eq, e->extra_presets.empty() ? nullptr : e->d_group_preset, e->d_st64, out + seg0, out + seg0, nullptr, nullptr, 0, 0,
+                                      e->d_stats + blocks_done * e->n_streams, xf_w, seg_n, stream_stride, e->n_streams, es, power_w,
+                                      // the lane-per-stream form where the suppressor's kernels want the issue slots and nothing waits
+                                      // for the EQ's own latency (an auto-makeup window's block powers do): 184.5 -> 182.4 ms per step
+                                      (n_presets == 1 && (!power_w || sw.eq_stream_power) && (runs_eq[0].flags & af::kFlagEq)) ? runs_eq[0].n_eq_sections : -1));
+        e->last_launches += 1;
+        if (persistent) {  // the running chain launch picks the window up from here
+          AF_HIP(af::launch_chain_publish_ready(e->d_ready, seg0 + seg_n, es));
+          advance_crossfades(e, seg_n);  // (the one chain launch did not: the EQ's counters move window by window)
+          window_done(seg_n);
+          continue;
+        }
+        hipEvent_t eq_done;
+        if (int rc = next_event(&eq_done)) return rc;
+        AF_HIP(hipEventRecord(eq_done, es));
+        AF_HIP(hipStreamWaitEvent(e->aux_stream, eq_done, 0));
+        run_w.flags = (run_w.flags & ~af::kFlagEq) | af::kFlagInputDone;
+        eq_offloaded = true;
+      }
+    }
+    if (persistent) return fail(AF_ERR_BACKEND, "internal: a window of a one-launch call could not take the EQ on the suppressor's side");
+    if (!eq_offloaded) {
+      AF_HIP(hipStreamWaitEvent(e->aux_stream, syn_done[w], 0));
+      eq_needs_chain_done = true;
+    }
+    if (!sw.diag_skip_chain)
+      if (int rc = launch_chain_segment(e, run_w, run_modified, out + seg0, out + seg0, seg_n, stream_stride, c.layout,
+                                        e->samples_processed + seg0, e->d_stats + blocks_done * e->n_streams,
+                                        e->has_evidence ? e->d_vad + blocks_done * e->n_streams : nullptr, e->aux_stream, stream,
+                                        /*stats_cleared=*/true, power_w))
+        return rc;
+    window_done(seg_n);
+  }
+  if (e->timing) AF_HIP(hipEventRecord(e->ev_mid.get(), last_supp));  // last suppressor kernel done
+  if (syn != stream && n_windows > 0) AF_HIP(hipStreamWaitEvent(stream, syn_done[n_windows - 1], 0));
+  {
+    hipEvent_t ev;
+    if (int rc = next_event(&ev)) return rc;
+    AF_HIP(hipEventRecord(ev, e->aux_stream));
+    AF_HIP(hipStreamWaitEvent(stream, ev, 0));
+    if (e->lim_stream) {
+      if (int rc = next_event(&ev)) return rc;
+      AF_HIP(hipEventRecord(ev, e->lim_stream));
+      AF_HIP(hipStreamWaitEvent(stream, ev, 0));
+    }
+  }
+  if (e->pipe.active && !diag_wins.empty()) {
+    const hipStream_t ds = e->pipe.stream;
+    for (int64_t j = (int64_t)diag_wins.size(); j < (int64_t)diag_wins.size() + diag_plan.depth; ++j)  // the pipeline empties
+      if (int rc = stage_diag_step(e, run, diag_plan, diag_wins, j, ds)) return rc;
+    e->pipe.windows += (int64_t)diag_wins.size();
+    hipEvent_t ev;
+    if (int rc = next_event(&ev)) return rc;
+    AF_HIP(hipEventRecord(ev, ds));
+    AF_HIP(hipStreamWaitEvent(stream, ev, 0));
+  }
+  return AF_OK;
+}
+
 static int process_device_impl(af_engine *e, const float *in, float *out, int64_t n_samples, int64_t stream_stride, int32_t layout,
                                void *hip_stream) {
   if (!e) return fail(AF_ERR_INVALID_ARGUMENT, "engine is null");
@@ -2108,10 +2556,7 @@ static int process_device_impl(af_engine *e, const float *in, float *out, int64_
     af::ChainParams probe = e->host_params;
     if (e->supp.enabled || e->gate_enabled) probe.flags &= ~(af::kFlagInputClamp | af::kFlagDcBlock | af::kFlagPreHighpass | af::kFlagInputScrub);
     const bool serves = stage_pipe_serves(e, probe, layout);
-    static const int env_staged = [] {  // AF_STAGED=0 / 1: keep AUTO off / on the stage pipeline (A/B runs)
-      const char *env = std::getenv("AF_STAGED");
-      return env ? std::atoi(env) : -1;
-    }();
+    const int env_staged = af::switches().staged;  // AF_STAGED=0 / 1: keep AUTO off / on the stage pipeline (A/B runs)
     if (e->kernel == AF_KERNEL_STAGED && !serves)
       return fail(AF_ERR_UNSUPPORTED, "the stage pipeline does not build this configuration (EQ-before-de-esser order, front end without the "
                                       "suppressor, more than 16 EQ sections, presets that differ in which stages run, time-major audio)");
@@ -2198,15 +2643,7 @@ static int process_device_impl(af_engine *e, const float *in, float *out, int64_
     sa.n_streams = e->n_streams;
     sa.n_samples = n_samples;
     sa.front_scrub = (hp.flags & af::kFlagInputScrub) ? 1 : 0;
-    sa.front_clamp = (hp.flags & af::kFlagInputClamp) ? 1 : 0;
-    sa.front_dc = (hp.flags & af::kFlagDcBlock) ? 1 : 0;
-    sa.front_hp = (hp.flags & af::kFlagPreHighpass) ? 1 : 0;
-    sa.hp_b0 = hp.pre_hp.b0; sa.hp_b1 = hp.pre_hp.b1; sa.hp_b2 = hp.pre_hp.b2;
-    sa.hp_a1 = hp.pre_hp.a1; sa.hp_a2 = hp.pre_hp.a2;
-    sa.chain_st64 = e->d_st64;
-    sa.chain_st32 = e->d_st32;
-    sa.f64_pre_z1 = af::kPreZ1;
-    sa.f32_dc_x1 = af::kDcX1;
+    supp_front_end(e, hp, hp.flags, sa);
     if (e->gate_enabled) gate_args(e, sa);  // (else the pass runs the front end alone and leaves the gate's state alone)
     if (fused_gate) {  // modes 1 / 2 with the controller attached: control pass + fused per-sample pass
       AF_HIP(af::launch_vad_gate_pass(sa, vad_args, stream));
@@ -2218,671 +2655,16 @@ static int process_device_impl(af_engine *e, const float *in, float *out, int64_
     if (e->timing) AF_HIP(hipEventRecord(e->ev_mid.get(), stream));  // the pre-pass counts as suppressor-side time
     chain_in = out;
   }
-  if (!e->supp.enabled && e->pipe.active) {
-    // ---- the chain as a pipeline of stage kernels over windows of whole control blocks (af_stages.hip)
-    // (a launch step costs ~20 us, the pipeline's fill is depth x window time: 960 samples 45.7 ms per 10 s at 256 streams,
-    // 1920 41.2, 2880 39.7, 4800 42.7, 9600 40.3)
-    int64_t tw = (int64_t)cb * std::max<int64_t>(1, 2880 / cb);
-    if (const char *env = std::getenv("AF_STAGE_WINDOW")) tw = (int64_t)cb * std::max<int64_t>(1, std::atoll(env) / cb);
-    if (int rc = stage_pipe_prepare(e, std::max<int64_t>(tw, e->pipe.tw_max))) return rc;
-    e->pipe.strip = e->host_params.flags & gate_strip;
-    if (int rc = stage_chain_params(e, stream)) return rc;  // what the stage kernels read (everything but the EQ sections)
-    e->last_kernel_used = AF_KERNEL_STAGED;
-    {
-      // one launch step per window on the caller's stream: step j runs every stage on the window it has reached
-      const StagePlan plan = stage_plan(e->host_params);
-      std::vector<af::DiagWin> wins;
-      int64_t blocks_at = 0;
-      for (int64_t t0 = 0; t0 < n_samples; t0 += tw) {
-        const int64_t n_w = std::min<int64_t>(tw, n_samples - t0);
-        af::DiagWin wd{};
-        wd.n0 = e->samples_processed + t0;
-        wd.n = n_w;
-        wd.stats = e->d_stats + blocks_at * e->n_streams;
-        wd.mk = e->pipe.d_mk + ((e->pipe.windows + (int64_t)wins.size()) % af_engine::StagePipe::kMkSets) * e->pipe.mk_rows;
-        wd.bp = e->pipe.d_bp + ((e->pipe.windows + (int64_t)wins.size()) % af_engine::StagePipe::kBpSets) * e->pipe.mk_rows;
-        wd.vad = e->has_evidence ? e->d_vad + blocks_at * e->n_streams : nullptr;
-        wd.in = chain_in + t0;
-        wd.out = out + t0;
-        wins.push_back(wd);
-        blocks_at += (n_w + cb - 1) / cb;
-      }
-      e->pipe.call_stride = stream_stride;
-      AF_HIP(hipMemsetAsync(e->d_stats, 0, sizeof(af::BlockStats) * rows, stream));
-      const int64_t steps = (int64_t)wins.size() + plan.depth;
-      for (int64_t j = 0; j < steps; ++j) {
-        if (j < (int64_t)wins.size()) {  // window j enters: its EQ stage reads the section parameters as they stand now
-          bool crossfade = false;
-          if (int rc = stage_diag_eq_params(e, stream, &crossfade, &wins[(size_t)j].eq_slot)) return rc;
-          wins[(size_t)j].eq_crossfade = crossfade ? 1 : 0;
-          advance_crossfades(e, wins[(size_t)j].n);
-        }
-        if (int rc = stage_diag_step(e, e->host_params, plan, wins, j, stream)) return rc;
-      }
-      e->pipe.windows += (int64_t)wins.size();
-      if (e->timing) {
-        if (!gate_strip) AF_HIP(hipEventRecord(e->ev_mid.get(), stream));
-        AF_HIP(hipEventRecord(e->ev_stop.get(), stream));
-      }
-      e->samples_processed += n_samples;
-      return AF_OK;
-    }
+  const CallArgs call{chain_in, out, n_samples, stream_stride, layout, stream, gate_strip, rows};
+  int rc;
+  if (e->supp.enabled) rc = run_suppressor_pipeline(e, call, src, src_stride, fused_gate, vad_args);
+  else if (e->pipe.active) rc = run_stage_pipeline(e, call);
+  else rc = run_chain_launch(e, call);
+  if (rc) return rc;
+  if (e->timing) {  // ev_mid: suppressor-side time ends (the suppressor's path and the gate's pre-pass have recorded theirs)
+    if (!e->supp.enabled && !gate_strip) AF_HIP(hipEventRecord(e->ev_mid.get(), stream));
+    AF_HIP(hipEventRecord(e->ev_stop.get(), stream));
   }
-  if (!e->supp.enabled) {
-    // ---- Large batches without the suppressor (round 3): the chain can use one CU per 64 streams and nothing else, so the EQ
-    // -- a quarter of the token-ring kernel's time -- runs as the systolic kernel on the CUs the chain leaves idle, window by
-    // window, and the chain is ONE launch that follows it through the ready counter (the form the suppressor's pipeline
-    // uses).  Taken when the streams can be CU-partitioned and the EQ kernel serves the configuration.
-    {
-      af::ChainParams hp = e->host_params;  // (a copy: with the gate on, the front end is the pre-pass's)
-      hp.flags &= ~gate_strip;
-      static const bool eq_offload_on = [] {
-        const char *env = std::getenv("AF_EQ_OFFLOAD");
-        return !env || std::atoi(env) != 0;
-      }();
-      const bool auto_mk = (hp.flags & af::kFlagCompressor) && hp.comp.auto_makeup_enabled;
-      const int64_t window = (int64_t)cb * std::max<int64_t>(1, 9600 / cb);
-      // (the chain launch lays out its LDS for a crossfade only when one is pending at the call's start, as
-      // launch_chain_segment sizes it: checking the crossfade layout always kept 15 and 16 sections off this form)
-      bool xf_now = false;
-      for (int j = 0; j < hp.n_eq_sections; ++j) xf_now = xf_now || hp.eq[j].xf_remaining > 0;
-      bool offload = one_launch_calls_enabled() && eq_offload_on && (e->kernel == AF_KERNEL_AUTO || e->kernel == AF_KERNEL_PHASED) &&
-                     (e->ring_variant == 0 || e->ring_variant == 1604) && e->extra_presets.empty() && roles_mode() == 0 &&
-                     layout == AF_LAYOUT_STREAM_MAJOR && (hp.flags & af::kFlagEq) && hp.n_eq_sections > 0 && hp.n_eq_sections <= 16 &&
-                     !(hp.flags & (af::kFlagDeesser | af::kFlagDcBlock | af::kFlagPreHighpass | af::kFlagPrePass)) &&
-                     af::ring_kernel_dynamic_lds(hp.n_eq_sections, hp.lim.lookahead_samples, xf_now) <= af::kMaxLdsBytes &&
-                     n_samples >= 2 * window && !std::getenv("AF_SERIAL_STREAMS");
-      if (offload) {
-        if (int rc = ensure_side_streams(e, stream)) return rc;
-        offload = e->partition_chain_cus > 0 && !e->borrowed_streams;
-      }
-      if (offload) {
-        if (auto_mk) {
-          AF_HIP(e->d_block_power.reserve_retiring(sizeof(double) * rows, e->retired, stream));
-        }
-        AF_HIP(hipMemsetAsync(e->d_stats, 0, sizeof(af::BlockStats) * rows, stream));
-        AF_HIP(e->d_ready.reserve_exact(sizeof(int64_t)));
-        AF_HIP(hipMemsetAsync(e->d_ready, 0, sizeof(int64_t), stream));
-        hipEvent_t ev;
-        if (int rc = engine_event(e, &ev)) return rc;
-        AF_HIP(hipEventRecord(ev, stream));
-        AF_HIP(hipStreamWaitEvent(e->aux_stream, ev, 0));
-        AF_HIP(hipStreamWaitEvent(e->eq_stream, ev, 0));
-        af::ChainParams run_p = hp;  // the EQ kernel scrubs / clamps the input and keeps the block input statistics
-        run_p.flags = (run_p.flags & ~(af::kFlagEq | af::kFlagInputScrub | af::kFlagInputClamp)) | af::kFlagInputDone;
-        if (int rc = launch_chain_segment(e, run_p, true, out, out, n_samples, stream_stride, layout, e->samples_processed, e->d_stats,
-                                          e->has_evidence ? e->d_vad : nullptr, e->aux_stream, stream, /*stats_cleared=*/true,
-                                          auto_mk ? e->d_block_power : nullptr, e->d_ready))
-          return rc;
-        if (!e->d_params_eq || e->eq_params_presets != 1) {
-          e->d_params_eq.release();
-          AF_HIP(e->d_params_eq.reserve_exact(sizeof(af::ChainParams) * kEqParamSlots));
-          e->eq_params_presets = 1;
-          e->uploaded_eq.clear();
-        }
-        int64_t blocks_done = 0;
-        for (int64_t seg0 = 0; seg0 < n_samples; seg0 += window) {
-          const int64_t seg_n = std::min<int64_t>(window, n_samples - seg0);
-          std::vector<af::ChainParams> run_eq(1, e->host_params);  // (as the crossfade counters stand at this window)
-          run_eq[0].flags &= ~gate_strip;
-          bool xf_w = false;
-          for (int j = 0; j < run_eq[0].n_eq_sections; ++j) xf_w = xf_w || run_eq[0].eq[j].xf_remaining > 0;
-          if (e->uploaded_eq.size() != 1 || std::memcmp(e->uploaded_eq.data(), run_eq.data(), sizeof(af::ChainParams)) != 0) {
-            e->uploaded_eq = run_eq;
-            if (int rc = stage_upload(e, e->d_params_eq, run_eq.data(), 1, e->eq_stream)) return rc;
-          }
-          AF_HIP(af::launch_eq_systolic(e->d_params_eq, nullptr, e->d_st64, chain_in + seg0, out + seg0, nullptr, nullptr, 0, 0,
-                                        e->d_stats + blocks_done * e->n_streams, xf_w, seg_n, stream_stride, e->n_streams, e->eq_stream,
-                                        auto_mk ? e->d_block_power + blocks_done * e->n_streams : nullptr));  // (the systolic form: here the EQ's own latency per window is what the chain follows)
-          AF_HIP(af::launch_chain_publish_ready(e->d_ready, seg0 + seg_n, e->eq_stream));
-          e->last_launches += 2;
-          advance_crossfades(e, seg_n);
-          blocks_done += (seg_n + cb - 1) / cb;
-        }
-        for (hipStream_t side : {e->aux_stream, e->eq_stream}) {
-          if (int rc = engine_event(e, &ev)) return rc;
-          AF_HIP(hipEventRecord(ev, side));
-          AF_HIP(hipStreamWaitEvent(stream, ev, 0));
-        }
-        if (e->timing) {
-          if (!gate_strip) AF_HIP(hipEventRecord(e->ev_mid.get(), stream));
-          AF_HIP(hipEventRecord(e->ev_stop.get(), stream));
-        }
-        e->samples_processed += n_samples;
-        return AF_OK;
-      }
-    }
-    int rc;
-    if (gate_strip) {
-      af::ChainParams run_g = e->host_params;
-      run_g.flags &= ~gate_strip;
-      rc = launch_chain_segment(e, run_g, true, chain_in, out, n_samples, stream_stride, layout, e->samples_processed,
-                                e->d_stats, e->has_evidence ? e->d_vad : nullptr, stream, stream);
-    } else {
-      rc = launch_chain_segment(e, e->host_params, false, in, out, n_samples, stream_stride, layout, e->samples_processed,
-                                e->d_stats, e->has_evidence ? e->d_vad : nullptr, stream, stream);
-    }
-    if (rc) return rc;
-    if (e->timing) {
-      if (!gate_strip) AF_HIP(hipEventRecord(e->ev_mid.get(), stream));  // no suppressor: everything is chain time
-      AF_HIP(hipEventRecord(e->ev_stop.get(), stream));
-    }
-    e->samples_processed += n_samples;
-    return AF_OK;
-  }
-
-  // ---- RNNoise suppressor ahead of the chain (realtime order, dsp_loop.rs:1222-1250,1521-1599).
-  // The call is cut into windows of frames and runs as a four-stage pipeline over them, one HIP stream each:
-  //   pre stream    : window w+2's sample-serial pre-pass (front end + model-input high-pass; 64 waves whose
-  //                   duration is set by recurrence latency, so it costs the chip almost nothing)
-  //   analysis      : window w+1's spectra and pitch search (the pitch kernel walks each stream's frames in
-  //                   order, one wave per stream: latency bound, it leaves most issue slots free)
-  //   caller stream : window w's pitch-aligned spectra, network, resynthesis, overlap-add
-  //   chain stream  : window w-1's chain launch (64 streams per workgroup, a quarter of the CUs at batch 4096)
-  // ordered by events; buffers that cross a stage boundary rotate (af_suppressor_host.hpp).
-  if (e->supp.weights_dirty) AF_HIP(e->supp.upload());
-  af::ChainParams run = e->host_params;
-  bool run_modified = false;
-  const uint32_t front = af::kFlagInputClamp | af::kFlagDcBlock | af::kFlagPreHighpass;
-  const uint32_t front_flags = run.flags & front;
-  const bool strip_front = front_flags || e->gate_enabled;  // the gate runs in the pre-pass too, after the front end
-  if (strip_front) {
-    // the realtime front end (clamp + DC block + 80 Hz HP, routing.rs:802-843) runs inside the suppressor's
-    // own sample-serial pre-pass, so the chain launches must not repeat it
-    run.flags &= ~(front | af::kFlagInputScrub);
-    run_modified = true;
-  }
-  const int64_t frames = n_samples / af::kRnnFrame;
-  // a window must hold whole control blocks, or block boundaries (hence per-block semantics) would move
-  int64_t unit = 1;
-  while ((unit * af::kRnnFrame) % cb != 0) ++unit;
-  int window_frames = e->supp_window_frames;
-  if (const char *env = std::getenv("AF_SUPP_WINDOW_FRAMES")) window_frames = std::max(1, std::atoi(env));  // tuning runs
-  // Only the last control block of a call can be short, so the call is scheduled as aligned windows over its whole control
-  // blocks plus one short final window for a ragged end: block boundaries do not move and the pipeline keeps its overlap.
-  const int64_t aligned = (frames / unit) * unit, ragged = frames - aligned;
-  int64_t window = std::max<int64_t>(unit, (window_frames / unit) * unit);
-  window = std::min<int64_t>(window, std::max<int64_t>(aligned, unit));
-  // Window schedule.  The first chain launch cannot start before one window has been through the pre-pass, the analysis
-  // and the synthesis, and the last chain launch runs after everything else is done: with uniform windows that is ~2.5
-  // window times of a 20-window call during which most of the chip idles.  So the call opens with short windows that
-  // double up to the full size and closes with the mirror image (every size a whole number of control blocks).
-  std::vector<int64_t> win_f0, win_nf;
-  {
-    static const bool ramp = [] {
-      const char *env = std::getenv("AF_SUPP_RAMP");
-      return !env || std::atoi(env) != 0;
-    }();
-    std::vector<int64_t> up;
-    static const std::vector<int64_t> up_env = [] {  // AF_SUPP_RAMP_LIST=4,4,8,8,16: the opening windows, in frames (tuning runs)
-      std::vector<int64_t> v;
-      if (const char *env = std::getenv("AF_SUPP_RAMP_LIST"))
-        for (const char *p = env; *p;) {
-          char *end = nullptr;
-          const long n = std::strtol(p, &end, 10);
-          if (end == p) break;
-          if (n > 0) v.push_back(n);
-          p = *end ? end + 1 : end;
-        }
-      return v;
-    }();
-    // The mirror image at the end of the call shortens what runs after the suppressor's last kernel -- when that is the stage
-    // pipeline emptying.  Behind the token-ring kernel the chain is the longer side and trails the suppressor by more than a
-    // window anyway: there the small windows only cost launches (189.3 against 190.0 ms per bench step).  AF_SUPP_RAMP_END=0 / 1.
-    static const int ramp_down_env = [] {
-      const char *env = std::getenv("AF_SUPP_RAMP_END");
-      return env ? std::atoi(env) : -1;
-    }();
-    const bool ramp_down = ramp_down_env >= 0 ? ramp_down_env != 0 : e->pipe.active;
-    if (!up_env.empty()) {
-      for (int64_t n : up_env) up.push_back(std::min<int64_t>(window, ((n + unit - 1) / unit) * unit));
-    } else {
-      for (int64_t n = ((4 + unit - 1) / unit) * unit; n < window; n *= 2) up.push_back(n);
-    }
-    int64_t up_total = 0;
-    for (int64_t n : up) up_total += n;
-    if (ramp && !up.empty() && aligned >= 2 * up_total + 2 * window) {
-      int64_t f = 0;
-      for (int64_t n : up) { win_f0.push_back(f); win_nf.push_back(n); f += n; }
-      const int64_t body_end = ramp_down ? aligned - up_total : aligned;
-      while (f < body_end) {
-        const int64_t n = std::min<int64_t>(window, body_end - f);
-        win_f0.push_back(f); win_nf.push_back(n); f += n;
-      }
-      if (ramp_down)
-        for (auto it = up.rbegin(); it != up.rend(); ++it) { win_f0.push_back(f); win_nf.push_back(*it); f += *it; }
-    } else {
-      for (int64_t f = 0; f < aligned; f += window) { win_f0.push_back(f); win_nf.push_back(std::min<int64_t>(window, aligned - f)); }
-    }
-    if (ragged > 0) { win_f0.push_back(aligned); win_nf.push_back(ragged); }
-  }
-  {
-    int64_t longest = 1;
-    for (int64_t n : win_nf) longest = std::max(longest, n);
-    AF_HIP(e->supp.ensure_workspace(e->n_streams, (int)longest));
-  }
-  if (e->trace) {
-    if (sizeof(int32_t) * 2 * frames * e->n_streams > e->d_trace.bytes()) {
-      AF_HIP(hipDeviceSynchronize());
-      AF_HIP(e->d_trace.reserve_exact(sizeof(int32_t) * 2 * frames * e->n_streams));
-    }
-    e->trace_frames = frames;
-  }
-  if (e->pipe.active) {
-    // (a suppressor window enters the pipeline in pieces of the pipeline's own window length: the rings stay as small as
-    // without the suppressor)
-    const int64_t chain_tw = (int64_t)cb * std::max<int64_t>(1, 2880 / cb);
-    if (int rc = stage_pipe_prepare(e, std::max<int64_t>(chain_tw, e->pipe.tw_max))) return rc;
-    e->pipe.strip = e->host_params.flags & ~run.flags;  // what the pre-pass has taken over
-    if (int rc = stage_chain_params(e, stream)) return rc;  // (everything but the EQ sections is read from here)
-  }
-  if (int rc = ensure_side_streams(e, stream)) return rc;
-  static const bool split_synthesis = [] {  // AF_SYNTH_SPLIT=0: resynthesis + overlap-add stay behind the network on one stream
-    const char *env = std::getenv("AF_SYNTH_SPLIT");
-    return !env || std::atoi(env) != 0;
-  }();
-  const hipStream_t fin = split_synthesis ? e->fin_stream : nullptr;
-  // The network kernel (a dependent chain of matrix instructions per 16 streams: long, and light on the chip) on a stream of its
-  // own: behind the pitch spectra on ONE stream the pair took 3.0 of a window's 3.16 ms -- that stream was the pipeline's period.
-  // MEASURED AND OFF: the eighth stream alone -- created, not even used -- takes the step from 172 to 184 ms, and with the network
-  // on it 187-189 ms: HIP multiplexes a process's streams onto a handful of hardware queues, and one more stream makes two of
-  // the pipeline's stages share a queue (false serialisation).  AF_RNN_STREAM=1 creates and uses it (A/B runs).
-  static const bool rnn_own_stream = rnn_stream_wanted();
-  static const bool rnn_on_caller = [] {  // AF_RNN_STREAM=2
-    const char *env = std::getenv("AF_RNN_STREAM");
-    return env && std::atoi(env) == 2;
-  }();
-  const hipStream_t syn = e->syn_stream ? e->syn_stream : stream;  // where the synthesis stage runs
-  int64_t blocks_done = 0;
-  std::vector<af::DiagWin> diag_wins;                 // the call's windows in the stage pipeline (one launch per step)
-  const StagePlan diag_plan = stage_plan(run);
-  static const bool eq_offload_env = [] {  // AF_EQ_OFFLOAD=0: the EQ stays inside the chain launches (A/B runs)
-    const char *env = std::getenv("AF_EQ_OFFLOAD");
-    return !env || std::atoi(env) != 0;
-  }();
-  const bool eq_offload = eq_offload_env && (e->kernel == AF_KERNEL_AUTO || e->kernel == AF_KERNEL_PHASED || e->kernel == AF_KERNEL_ROLES) &&
-                          (e->ring_variant == 0 || e->ring_variant == 1604) && (run.flags & af::kFlagEq);
-  bool eq_needs_chain_done = true;  // (the previous call's last chain launch has ended: the caller's stream waited for it)
-  const bool auto_makeup_call = (run.flags & af::kFlagCompressor) && run.comp.auto_makeup_enabled;
-  if (eq_offload && auto_makeup_call && !e->pipe.active) {
-    // the systolic EQ kernel is then also the pre-pass of every window (it leaves the compressor-input block powers here)
-    AF_HIP(e->d_block_power.reserve_retiring(sizeof(double) * rows, e->retired, stream));
-  }
-  auto next_event = [&](hipEvent_t *out_ev) -> int { return engine_event(e, out_ev); };
-  // The call's statistics rows are cleared ONCE, here (their fields are written by the kernels that own them).  Round 2 cleared
-  // every window's rows in front of its EQ launch: a fill kernel on the suppressor's crowded CUs, 0.05-0.45 ms between the
-  // window's overlap-add and its EQ -- on the path the first chain launches wait for.
-  static const bool clear_per_window = [] {  // AF_STATS_CLEAR=window: round 2's per-window fills (A/B runs)
-    const char *env = std::getenv("AF_STATS_CLEAR");
-    return env && std::strcmp(env, "window") == 0;
-  }();
-  if (!clear_per_window) AF_HIP(hipMemsetAsync(e->d_stats, 0, sizeof(af::BlockStats) * rows, stream));
-  // ---- ONE chain launch per call (round 3).  With the chain's CUs its own, the EQ on the suppressor's side and nothing that
-  // changes the parameter block between windows, the token-ring kernel is launched once, for the whole call, before the first
-  // window: a chunk waits until the counter `d_ready` covers its samples, and every window's EQ launch is followed by a
-  // one-thread kernel that publishes the new count.  What that removes from the chain's stream: 53 dispatches and their
-  // cross-stream dependencies (~0.1 ms each while six other queues are busy: the trace of tools/step_timeline.py), the
-  // state planes' load and write-back per window, and the fill / drain of the 16-wave pipeline per launch.
-  // AF_CHAIN_PERSISTENT=0 restores one launch per window (A/B runs).
-  const bool persistent_env = one_launch_calls_enabled();
-  bool persistent = persistent_env && eq_offload && !clear_per_window && e->partition_chain_cus > 0 && !e->pipe.active &&
-                    !std::getenv("AF_DIAG_SKIP_CHAIN") && e->extra_presets.empty() && roles_mode() == 0 &&
-                    (e->kernel == AF_KERNEL_AUTO || e->kernel == AF_KERNEL_PHASED) && layout == AF_LAYOUT_STREAM_MAJOR &&
-                    !(run.flags & (af::kFlagDeesser | af::kFlagDcBlock | af::kFlagPreHighpass)) && run.n_eq_sections <= 16 &&
-                    af::ring_kernel_dynamic_lds(run.n_eq_sections, run.lim.lookahead_samples, false) <= af::kMaxLdsBytes &&
-                    (!auto_makeup_call || e->d_block_power != nullptr) && win_f0.size() >= 2;
-  if (persistent) {
-    AF_HIP(e->d_ready.reserve_exact(sizeof(int64_t)));
-    AF_HIP(hipMemsetAsync(e->d_ready, 0, sizeof(int64_t), stream));
-  }
-  {  // the side streams start after whatever the caller queued before this call
-    hipEvent_t ev;
-    if (int rc = next_event(&ev)) return rc;
-    AF_HIP(hipEventRecord(ev, stream));
-    AF_HIP(hipStreamWaitEvent(e->aux_stream, ev, 0));
-    AF_HIP(hipStreamWaitEvent(e->pre_stream, ev, 0));
-    AF_HIP(hipStreamWaitEvent(e->ana_stream, ev, 0));
-    if (syn != stream) AF_HIP(hipStreamWaitEvent(syn, ev, 0));
-    if (fin && fin != stream) AF_HIP(hipStreamWaitEvent(fin, ev, 0));
-    if (e->eq_stream != stream) AF_HIP(hipStreamWaitEvent(e->eq_stream, ev, 0));
-    if (e->lim_stream) AF_HIP(hipStreamWaitEvent(e->lim_stream, ev, 0));
-    if (e->rnn_stream) AF_HIP(hipStreamWaitEvent(e->rnn_stream, ev, 0));
-  }
-  constexpr int kXh = af::SuppressorHost::kXhBuffers;
-  // Pipeline depth.  The spectrum / record buffers of window w are free again when its synthesis has ended, and the synthesis
-  // of w needs the analysis of w: with D buffer sets the loop analysis(w + D) <- synthesis(w) <- network(w) <- pitch spectra(w)
-  // <- analysis(w) bounds the window period by (sum of those kernels) / D.  Round 2 ran D = 2 (the trace showed exactly that
-  // period: 7.3 ms of dependent kernels per two windows); AF_SUPP_DEPTH=2 restores it for A/B runs.
-  static const int depth = [] {
-    const char *env = std::getenv("AF_SUPP_DEPTH");
-    const int d = env ? std::atoi(env) : af::SuppressorHost::kSpecBuffers;
-    return d < 2 ? 2 : (d > af::SuppressorHost::kSpecBuffers ? af::SuppressorHost::kSpecBuffers : d);
-  }();
-  const int ana_ahead = depth - 1, pre_ahead = depth;  // windows the analysis / the pre-pass run ahead of the synthesis
-  auto window_args = [&](int64_t f0, int64_t nf, int64_t index) {
-    af::SuppArgs sa{};
-    sa.in = src;
-    sa.in_stride = src_stride;
-    sa.out = out;
-    sa.xh = e->supp.d_xh + (size_t)(index % kXh) * e->supp.xh_floats;
-    sa.X = e->supp.d_X + (size_t)(index % depth) * e->supp.ws_cells * af::kRnnFreq;
-    sa.P = e->supp.d_P + (size_t)(index % depth) * e->supp.ws_cells * af::kRnnFreq;
-    sa.ds = e->supp.d_ds;
-    sa.rec = e->supp.d_rec + (size_t)(index % depth) * e->supp.ws_cells;
-    sa.state = e->supp.d_state;
-    sa.stream_stride = stream_stride;
-    sa.n_streams = e->n_streams;
-    sa.n_frames = (int)nf;
-    sa.frame0 = f0;
-    sa.strength = e->supp.strength;
-    sa.smoothing_coeff = 1.0f - std::exp(-((480.0f / 48000.0f) / (15.0f / 1000.0f)));  // rnnoise.rs:45-51
-    sa.raw_protocol = e->supp.raw_protocol ? 1 : 0;
-    sa.front_clamp = (front_flags & af::kFlagInputClamp) ? 1 : 0;
-    sa.front_dc = (front_flags & af::kFlagDcBlock) ? 1 : 0;
-    sa.front_hp = (front_flags & af::kFlagPreHighpass) ? 1 : 0;
-    sa.hp_b0 = run.pre_hp.b0; sa.hp_b1 = run.pre_hp.b1; sa.hp_b2 = run.pre_hp.b2;
-    sa.hp_a1 = run.pre_hp.a1; sa.hp_a2 = run.pre_hp.a2;
-    sa.chain_st64 = e->d_st64;
-    sa.chain_st32 = e->d_st32;
-    sa.f64_pre_z1 = af::kPreZ1;
-    sa.f32_dc_x1 = af::kDcX1;
-    if (e->gate_enabled) {
-      sa.front_scrub = (front_flags || (e->host_params.flags & af::kFlagInputScrub)) ? 1 : 0;
-      gate_args(e, sa);
-    }
-    if (index > 0) {  // history = tail of the previous window's buffer
-      sa.xh_prev = e->supp.d_xh + (size_t)((index - 1) % kXh) * e->supp.xh_floats;
-      sa.xh_prev_stride = af::kPitchBuf + win_nf[index - 1] * af::kRnnFrame;
-    }
-    return sa;
-  };
-  const int64_t n_windows = (int64_t)win_f0.size();
-  std::vector<hipEvent_t> pre_done(n_windows), ana_done(n_windows), syn_done(n_windows);
-  std::vector<hipEvent_t> rnn_done(n_windows);
-  for (int64_t w = 0; w < n_windows; ++w) {
-    if (int rc = next_event(&rnn_done[w])) return rc;
-    if (int rc = next_event(&pre_done[w])) return rc;
-    if (int rc = next_event(&ana_done[w])) return rc;
-    if (int rc = next_event(&syn_done[w])) return rc;
-  }
-  // Stages are enqueued in pipeline order (the pre-pass two windows and the analysis one window ahead of the
-  // synthesis), so that every event a stage waits on has been recorded before the wait is enqueued.
-  auto enqueue_pre = [&](int64_t w) -> int {
-    const int64_t f0 = win_f0[w], nf = win_nf[w];
-    if (w >= kXh) AF_HIP(hipStreamWaitEvent(e->pre_stream, syn_done[w - kXh], 0));  // its model-input buffer is free
-    if (fused_gate) {  // (a window holds whole control blocks: its first block is f0 x 480 / cb)
-      af::VadGateArgs va = vad_args;
-      va.block0 = f0 * af::kRnnFrame / cb;
-      AF_HIP(af::launch_vad_gate_pass(window_args(f0, nf, w), va, e->pre_stream));
-      e->last_launches += 1;  // the control pass (the per-sample pass stands where the expander pre-pass is counted)
-    } else {
-      AF_HIP(af::launch_suppressor_prefilter(window_args(f0, nf, w), e->pre_stream));
-    }
-    AF_HIP(hipEventRecord(pre_done[w], e->pre_stream));
-    return AF_OK;
-  };
-  auto enqueue_ana = [&](int64_t w) -> int {
-    const int64_t f0 = win_f0[w], nf = win_nf[w];
-    AF_HIP(hipStreamWaitEvent(e->ana_stream, pre_done[w], 0));
-    if (w >= depth) AF_HIP(hipStreamWaitEvent(e->ana_stream, syn_done[w - depth], 0));  // its spectrum / record buffers are free
-    static const bool order_pitch = [] {  // AF_ORDER_PITCH=1: hold the pitch search back until the previous window's network ran
-      const char *env = std::getenv("AF_ORDER_PITCH");
-      return env && std::atoi(env) != 0;  // off: it only moves the starvation to the resynthesis kernel (313 vs 296 ms)
-    }();
-    // ORDERING THAT IS LOAD-BEARING: the pitch search of window w + 1 and the pitch tracker of window w must stay on this ONE
-    // stream, in this order.  The whitened pitch buffers (`d_ds`, 3.4 KB per frame and stream) are a single set: the tracker of
-    // window w reads what the search of window w wrote, and nothing but stream order keeps the search of w + 1 from overwriting
-    // it first.  (Round 2 moved the tracker to the pre-pass stream to shorten this stream: run-to-run bit-identity was lost --
-    // that race.  Moving either kernel needs a second `d_ds` set and an event from the tracker to the next search.)  The
-    // tracker also owns the stream's pitch state rows (last period / gain, cepstral ring, the 1728-sample history a NEW call's
-    // first pre-pass reads: ordered through the caller's stream at the end of the call).
-    AF_HIP(af::launch_suppressor_analysis(window_args(f0, nf, w), e->supp.tables, e->ana_stream,
-                                          (order_pitch && w >= 1) ? rnn_done[w - 1] : nullptr));
-    AF_HIP(hipEventRecord(ana_done[w], e->ana_stream));
-    return AF_OK;
-  };
-  static const bool diag_no_chain_kernel = [] {  // AF_DIAG_NO_CHAIN_KERNEL=1 (timing experiments): everything but the chain launch
-    const char *env = std::getenv("AF_DIAG_NO_CHAIN_KERNEL");
-    return env && std::atoi(env) != 0;
-  }();
-  if (persistent && !diag_no_chain_kernel) {  // the call's one chain launch: resident on the chain's CUs from here on, following `d_ready`
-    af::ChainParams run_p = run;
-    run_p.flags = (run_p.flags & ~af::kFlagEq) | af::kFlagInputDone;  // (what every window's launch was given)
-    const int64_t total = frames * af::kRnnFrame;
-    if (int rc = launch_chain_segment(e, run_p, run_modified, out, out, total, stream_stride, layout, e->samples_processed, e->d_stats,
-                                      e->has_evidence ? e->d_vad : nullptr, e->aux_stream, stream, /*stats_cleared=*/true,
-                                      auto_makeup_call ? e->d_block_power : nullptr, e->d_ready))
-      return rc;
-    eq_needs_chain_done = false;  // (an event behind THIS launch would make the first EQ wait for the launch that waits for it)
-  }
-  for (int64_t w = 0; w < std::min<int64_t>(pre_ahead, n_windows); ++w)
-    if (int rc = enqueue_pre(w)) return rc;
-  for (int64_t w = 0; w < std::min<int64_t>(ana_ahead, n_windows); ++w)
-    if (int rc = enqueue_ana(w)) return rc;
-  for (int64_t w = 0; w < n_windows; ++w) {
-    const int64_t f0 = win_f0[w], nf = win_nf[w];
-    AF_HIP(hipStreamWaitEvent(syn, ana_done[w], 0));
-    if (fin && fin != syn && w >= depth) AF_HIP(hipStreamWaitEvent(syn, syn_done[w - depth], 0));  // its pitch-spectrum buffer is free
-    {
-      hipStream_t net = nullptr;
-      hipEvent_t spec_done = nullptr;
-      if (rnn_own_stream && fin && fin != syn && e->rnn_stream) {
-        net = e->rnn_stream;
-        if (int rc = next_event(&spec_done)) return rc;
-      } else if (rnn_on_caller && persistent && fin && fin != syn && syn != stream) {
-        net = stream;  // the caller's stream: a queue the process has anyway, idle between the call's fork and its join
-        if (int rc = next_event(&spec_done)) return rc;
-      }
-      AF_HIP(af::launch_suppressor_synthesis(window_args(f0, nf, w), e->supp.tables, e->supp.dw, syn, rnn_done[w], fin, net, spec_done));
-    }
-    if (e->trace) {  // the window's (silence, pitch index) decisions, before its record buffer is handed back to the analysis
-      const af::SuppArgs sa = window_args(f0, nf, w);
-      AF_HIP(hipMemcpy2DAsync(e->d_trace + 2 * f0 * e->n_streams, 2 * sizeof(int32_t),
-                              reinterpret_cast<const char *>(sa.rec) + offsetof(af::SuppFrameRec, silence), sizeof(af::SuppFrameRec),
-                              2 * sizeof(int32_t), (size_t)(nf * e->n_streams), hipMemcpyDeviceToDevice, (fin && fin != syn) ? fin : syn));
-    }
-    AF_HIP(hipEventRecord(syn_done[w], (fin && fin != syn) ? fin : syn));
-    e->last_launches += 7;
-    if (w + pre_ahead < n_windows)
-      if (int rc = enqueue_pre(w + pre_ahead)) return rc;
-    if (w + ana_ahead < n_windows)
-      if (int rc = enqueue_ana(w + ana_ahead)) return rc;
-    const int64_t seg0 = f0 * af::kRnnFrame, seg_n = nf * af::kRnnFrame;
-    const double *vad = e->has_evidence ? e->d_vad + blocks_done * e->n_streams : nullptr;
-    static const bool diag_skip_chain = std::getenv("AF_DIAG_SKIP_CHAIN") != nullptr;  // timing experiments only
-    // ---- the window's EQ on the suppressor's side (af_eq_systolic.hip), when the chain's launch would be the plain
-    // one-launch form of the token-ring kernel and no coefficient crossfade is running
-    af::ChainParams run_w = run;
-    bool eq_offloaded = false;
-    double *power_w = nullptr;  // the window's block powers, when its systolic EQ launch was an auto-makeup pre-pass
-    if (e->pipe.active && !diag_skip_chain) {
-      // ---- the window's chain as one more step of the stage pipeline (af_stages.hip; small and medium batches): this window
-      // enters (its EQ stage reads the overlap-add output), the windows before it move one stage on
-      const hipStream_t ds = e->pipe.stream;
-      const int64_t chain_tw = (int64_t)cb * std::max<int64_t>(1, 2880 / cb);
-      AF_HIP(hipStreamWaitEvent(ds, syn_done[w], 0));
-      if (clear_per_window)
-        AF_HIP(hipMemsetAsync(e->d_stats + blocks_done * e->n_streams, 0, sizeof(af::BlockStats) * ((seg_n + cb - 1) / cb) * e->n_streams, ds));
-      e->last_kernel_used = AF_KERNEL_STAGED;
-      e->pipe.call_stride = stream_stride;
-      int64_t sub_blocks = 0;
-      for (int64_t off = 0; off < seg_n; off += chain_tw) {
-        const int64_t n_sub = std::min<int64_t>(chain_tw, seg_n - off);
-        af::DiagWin wd{};
-        wd.n0 = e->samples_processed + seg0 + off;
-        wd.n = n_sub;
-        wd.stats = e->d_stats + (blocks_done + sub_blocks) * e->n_streams;
-        wd.mk = e->pipe.d_mk + ((e->pipe.windows + (int64_t)diag_wins.size()) % af_engine::StagePipe::kMkSets) * e->pipe.mk_rows;
-        wd.bp = e->pipe.d_bp + ((e->pipe.windows + (int64_t)diag_wins.size()) % af_engine::StagePipe::kBpSets) * e->pipe.mk_rows;
-        wd.vad = vad ? vad + sub_blocks * e->n_streams : nullptr;
-        wd.in = out + seg0 + off;
-        wd.out = out + seg0 + off;
-        bool crossfade = false;
-        if (int rc2 = stage_diag_eq_params(e, ds, &crossfade, &wd.eq_slot)) return rc2;
-        wd.eq_crossfade = crossfade ? 1 : 0;
-        diag_wins.push_back(wd);
-        if (int rc2 = stage_diag_step(e, run, diag_plan, diag_wins, (int64_t)diag_wins.size() - 1, ds)) return rc2;
-        advance_crossfades(e, n_sub);
-        sub_blocks += (n_sub + cb - 1) / cb;
-      }
-      run = e->host_params;  // crossfade bookkeeping may have moved on
-      if (strip_front) run.flags &= ~(front | af::kFlagInputScrub);
-      blocks_done += (seg_n + cb - 1) / cb;
-      continue;
-    }
-    if (eq_offload && !diag_skip_chain) {
-      const int n_presets = 1 + (int)e->extra_presets.size();
-      bool ok = true, xf_w = false;
-      std::vector<af::ChainParams> runs_eq((size_t)n_presets);
-      for (int k = 0; k < n_presets && ok; ++k) {
-        runs_eq[k] = preset_params(e, k);
-        runs_eq[k].flags &= ~(e->host_params.flags & ~run.flags);  // what the pre-pass has taken over
-        const af::ChainParams &hp = runs_eq[k];
-        ok = !(hp.flags & af::kFlagDeesser) && hp.n_eq_sections <= 16 && !(hp.flags & (af::kFlagDcBlock | af::kFlagPreHighpass)) &&
-             af::ring_kernel_dynamic_lds(hp.n_eq_sections, hp.lim.lookahead_samples, false) <= af::kMaxLdsBytes;
-        // (a pending coefficient crossfade -- the 72 samples the legacy setters open a stream with -- runs in the systolic
-        // kernel's general form; round 2 kept such windows' EQ inside the chain launch)
-        for (int j = 0; j < hp.n_eq_sections; ++j) xf_w = xf_w || hp.eq[j].xf_remaining > 0;
-      }
-      if (ok) {
-        // behind the window's overlap-add, beside the next window's synthesis (AF_EQ_ON_FIN=1: on the synthesis' own stream)
-        static const bool eq_on_fin = [] {
-          const char *env = std::getenv("AF_EQ_ON_FIN");
-          return env && std::atoi(env) != 0;
-        }();
-        const hipStream_t es = (eq_on_fin && fin && fin != syn) ? fin : e->eq_stream;
-        AF_HIP(hipStreamWaitEvent(es, syn_done[w], 0));
-        if (!e->d_params_eq || e->eq_params_presets != n_presets) {
-          e->d_params_eq.release();
-          AF_HIP(e->d_params_eq.reserve_exact(sizeof(af::ChainParams) * n_presets * kEqParamSlots));  // (sized as the stage pipeline sizes it)
-          e->eq_params_presets = n_presets;
-          e->uploaded_eq.clear();
-        }
-        // AF_EQ_PARTS=2 (MEASURED, OFF): the window's EQ as TWO launches of the lane-per-stream kernel, sections [0, h) on the
-        // caller's stream and [h, n) on the EQ stream, so that the second half of window w runs beside the first half of w + 1.
-        // (With the chain launch left out of the step the EQ stream is the last to finish -- 52 x 3.2 ms = 166 ms -- hence the
-        // attempt.)  Bit-identical; on a caller-owned stream 178.0 against 176.9-178.3 ms per step: nothing, and the caller's own
-        // stream costs more than the default one (one more hardware queue).  On the legacy default stream it cannot run at all.
-        static const bool eq_two_parts_env = [] {
-          const char *env = std::getenv("AF_EQ_PARTS");
-          return env && std::atoi(env) == 2;
-        }();
-        const bool two_parts = eq_two_parts_env && persistent && n_presets == 1 && !xf_w && (runs_eq[0].flags & af::kFlagEq) &&
-                               runs_eq[0].n_eq_sections >= 2 && runs_eq[0].n_eq_sections <= 32 && stream != es && (stream_stride % 4) == 0 &&
-                               // (not the legacy default stream -- or the per-thread one: work enqueued there waits for the other
-                               // streams' earlier work, the resident chain launch included, which waits for this window; measured: the
-                               // call runs into the launch's bound.  A caller on a stream of its own gets the two-part EQ.)
-                               reinterpret_cast<uintptr_t>(stream) > 2 &&
-                               (reinterpret_cast<uintptr_t>(out + seg0) & 15) == 0 && !std::getenv("AF_EQ_STREAM_OFF");
-        if (e->uploaded_eq.size() != runs_eq.size() ||
-            std::memcmp(e->uploaded_eq.data(), runs_eq.data(), sizeof(af::ChainParams) * runs_eq.size()) != 0) {
-          e->uploaded_eq = runs_eq;
-          // (always on the EQ stream, never the caller's: a copy on the legacy default stream waits for every other stream --
-          // the resident chain launch included, which waits for this window: the call would run into the launch's bound)
-          if (int rc2 = stage_upload(e, e->d_params_eq, runs_eq.data(), runs_eq.size(), es)) return rc2;
-          if (stream != es) e->eq_params_on_es = true;
-        }
-        if (eq_needs_chain_done) {  // the previous window's EQ ran inside its chain launch: that launch owns the memories until it ends
-          hipEvent_t chain_done;
-          if (int rc2 = next_event(&chain_done)) return rc2;
-          AF_HIP(hipEventRecord(chain_done, e->aux_stream));
-          AF_HIP(hipStreamWaitEvent(es, chain_done, 0));
-          eq_needs_chain_done = false;
-        }
-        static const bool eq_stream_with_power = [] {  // AF_EQ_STREAM_POWER=0: auto-makeup windows keep the systolic kernel
-          const char *env = std::getenv("AF_EQ_STREAM_POWER");
-          return !env || std::atoi(env) != 0;
-        }();
-        af::BlockStats *rows_w = e->d_stats + blocks_done * e->n_streams;
-        if (clear_per_window) AF_HIP(hipMemsetAsync(rows_w, 0, sizeof(af::BlockStats) * ((seg_n + cb - 1) / cb) * e->n_streams, es));
-        power_w = auto_makeup_call ? e->d_block_power + blocks_done * e->n_streams : nullptr;
-        if (two_parts) {
-          const int nsec = runs_eq[0].n_eq_sections, h = nsec / 2;
-          if (e->eq_params_on_es) {  // (an upload the EQ stream made for an earlier window: the caller's stream reads the block now)
-            hipEvent_t up;
-            if (int rc2 = next_event(&up)) return rc2;
-            AF_HIP(hipEventRecord(up, es));
-            AF_HIP(hipStreamWaitEvent(stream, up, 0));
-            e->eq_params_on_es = false;
-          }
-          AF_HIP(hipStreamWaitEvent(stream, syn_done[w], 0));
-          AF_HIP(af::launch_eq_stream_part(e->d_params_eq, e->d_st64, out + seg0, out + seg0, rows_w, nullptr, 0, h, true, seg_n,
-                                           stream_stride, e->n_streams, stream));
-          hipEvent_t half;
-          if (int rc2 = next_event(&half)) return rc2;
-          AF_HIP(hipEventRecord(half, stream));
-          AF_HIP(hipStreamWaitEvent(es, half, 0));
-          AF_HIP(af::launch_eq_stream_part(e->d_params_eq, e->d_st64, out + seg0, out + seg0, power_w ? rows_w : nullptr, power_w, h, nsec - h,
-                                           false, seg_n, stream_stride, e->n_streams, es));
-          e->last_launches += 2;
-          AF_HIP(af::launch_chain_publish_ready(e->d_ready, seg0 + seg_n, es));
-          advance_crossfades(e, seg_n);
-          run = e->host_params;
-          if (strip_front) run.flags &= ~(front | af::kFlagInputScrub);
-          blocks_done += (seg_n + cb - 1) / cb;
-          continue;
-        }
-        AF_HIP(af::launch_eq_systolic(e->d_params_eq, e->extra_presets.empty() ? nullptr : e->d_group_preset, e->d_st64, out + seg0, out + seg0, nullptr, nullptr, 0, 0,
-                                      rows_w, xf_w, seg_n, stream_stride, e->n_streams, es, power_w,
-                                      // the lane-per-stream form where the suppressor's kernels want the issue slots and nothing waits
-                                      // for the EQ's own latency (an auto-makeup window's block powers do): 184.5 -> 182.4 ms per step
-                                      (n_presets == 1 && (!power_w || eq_stream_with_power) && (runs_eq[0].flags & af::kFlagEq)) ? runs_eq[0].n_eq_sections : -1));
-        e->last_launches += 1;
-        if (persistent) {  // the running chain launch picks the window up from here
-          AF_HIP(af::launch_chain_publish_ready(e->d_ready, seg0 + seg_n, es));
-          advance_crossfades(e, seg_n);  // (the one chain launch did not: the EQ's counters move window by window)
-          run = e->host_params;
-          if (strip_front) run.flags &= ~(front | af::kFlagInputScrub);
-          blocks_done += (seg_n + cb - 1) / cb;
-          continue;
-        }
-        hipEvent_t eq_done;
-        if (int rc2 = next_event(&eq_done)) return rc2;
-        AF_HIP(hipEventRecord(eq_done, es));
-        AF_HIP(hipStreamWaitEvent(e->aux_stream, eq_done, 0));
-        run_w.flags = (run_w.flags & ~af::kFlagEq) | af::kFlagInputDone;
-        eq_offloaded = true;
-      }
-    }
-    if (persistent) return fail(AF_ERR_BACKEND, "internal: a window of a one-launch call could not take the EQ on the suppressor's side");
-    if (!eq_offloaded) {
-      AF_HIP(hipStreamWaitEvent(e->aux_stream, syn_done[w], 0));
-      eq_needs_chain_done = true;
-    }
-    int rc = AF_OK;
-    if (!diag_skip_chain)
-      rc = launch_chain_segment(e, run_w, run_modified, out + seg0, out + seg0, seg_n, stream_stride, layout,
-                                e->samples_processed + seg0, e->d_stats + blocks_done * e->n_streams, vad, e->aux_stream, stream,
-                                /*stats_cleared=*/!clear_per_window || eq_offloaded, power_w);
-    if (rc) return rc;
-    run = e->host_params;  // crossfade bookkeeping may have moved on
-    if (strip_front) run.flags &= ~(front | af::kFlagInputScrub);
-    blocks_done += (seg_n + cb - 1) / cb;
-  }
-  if (e->timing) AF_HIP(hipEventRecord(e->ev_mid.get(), (fin && fin != syn) ? fin : syn));  // last suppressor kernel done
-  if (syn != stream && n_windows > 0) AF_HIP(hipStreamWaitEvent(stream, syn_done[n_windows - 1], 0));
-  {
-    hipEvent_t ev;
-    if (int rc = next_event(&ev)) return rc;
-    AF_HIP(hipEventRecord(ev, e->aux_stream));
-    AF_HIP(hipStreamWaitEvent(stream, ev, 0));
-    if (e->lim_stream) {
-      if (int rc = next_event(&ev)) return rc;
-      AF_HIP(hipEventRecord(ev, e->lim_stream));
-      AF_HIP(hipStreamWaitEvent(stream, ev, 0));
-    }
-  }
-  if (e->pipe.active && !diag_wins.empty()) {
-    const hipStream_t ds = e->pipe.stream;
-    for (int64_t j = (int64_t)diag_wins.size(); j < (int64_t)diag_wins.size() + diag_plan.depth; ++j)  // the pipeline empties
-      if (int rc = stage_diag_step(e, run, diag_plan, diag_wins, j, ds)) return rc;
-    e->pipe.windows += (int64_t)diag_wins.size();
-    hipEvent_t ev;
-    if (int rc = next_event(&ev)) return rc;
-    AF_HIP(hipEventRecord(ev, ds));
-    AF_HIP(hipStreamWaitEvent(stream, ev, 0));
-  }
-  if (e->timing) AF_HIP(hipEventRecord(e->ev_stop.get(), stream));
   e->samples_processed += n_samples;
   return AF_OK;
 }

@@ -9,6 +9,7 @@
 
 #include "af_api_internal.hpp"
 #include "af_resampler_host.hpp"
+#include "af_switches.hpp"
 
 namespace af {
 hipError_t launch_resample(const double *in, double *out, const ResamplePos *pos, const double *table, int64_t n_in,
@@ -96,7 +97,7 @@ int af_resampler_create(uint32_t input_rate, uint32_t output_rate, int64_t chunk
   af_resampler *r = new af_resampler();
   r->device = device;
   r->plan.build(input_rate, output_rate, chunk_size, sinc_len, window);
-  if (const char *env = std::getenv("AF_RESAMPLER_VARIANT")) r->variant = std::strcmp(env, "valu") == 0 ? 1 : (std::strcmp(env, "mfma32") == 0 ? 2 : 0);
+  af::resampler_variant_override(r->variant);
   *out = r;
   return AF_OK;
 }

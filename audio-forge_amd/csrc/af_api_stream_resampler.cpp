@@ -9,6 +9,7 @@
 
 #include "af_api_internal.hpp"
 #include "af_resampler_host.hpp"
+#include "af_switches.hpp"
 
 namespace af {
 hipError_t launch_resample_stream(const float *plane, const float *in, float *out, const ResamplePos *pos, const double *table,
@@ -143,7 +144,7 @@ int af_stream_resampler_create(uint32_t input_rate, uint32_t output_rate, int64_
   r->plan.build(input_rate, output_rate, chunk_size, sinc_len, window);
   r->plane_stride = (int32_t)(2 * r->plan.sinc_len + chunk_size - 1);
   r->last_index = r->plan.initial_index();
-  if (const char *env = std::getenv("AF_RESAMPLER_VARIANT")) r->variant = std::strcmp(env, "valu") == 0 ? 1 : (std::strcmp(env, "mfma32") == 0 ? 2 : 0);
+  af::resampler_variant_override(r->variant);
   *out = r;
   return AF_OK;
 }

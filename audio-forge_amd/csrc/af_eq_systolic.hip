@@ -25,6 +25,7 @@
 
 #include "af_dsp.h"
 #include "af_eq_systolic_body.h"
+#include "af_switches.hpp"
 
 namespace af {
 
@@ -44,6 +45,8 @@ __global__ __launch_bounds__(64) void eq_systolic_kernel(EqSystolicArgs a) {
 // kernel's EQ units: the same bits.  Serves windows without a pending crossfade, one preset, stream-major audio with 16-byte
 // rows; everything else takes the systolic kernel.
 // `sec0`: the first of this launch's kSec sections; `head`: the launch takes the raw input (scrub / clamp apply; kStats only there).
+// Both are constant leftovers of a removed two-launch form: every launch passes sec0 = 0, head = 1 (launch_eq_stream_sections).
+// They stay kernel arguments so that the kernel's code and register use are what was measured.
 // A window's EQ may run as TWO launches, sections [0, h) and [h, n), on two streams: the sample between two sections is an f32
 // in the reference, so the hand-over through the audio buffer is exact, and the second half of window w runs beside the first
 // half of window w + 1 -- the EQ's period per window halves (one launch per window was the pipeline's longest stage).
@@ -366,42 +369,24 @@ static bool launch_eq_stream2(const EqSystolicArgs &a, int n_sections, bool stat
 }
 
 template <int kSec>
-static void launch_eq_stream_sections(const EqSystolicArgs &a, bool stats, bool power, int sec0, bool head, hipStream_t stream) {
+static void launch_eq_stream_sections(const EqSystolicArgs &a, bool stats, bool power, hipStream_t stream) {
   const unsigned groups = (unsigned)((a.n_streams + 63) / 64);
   const dim3 grid((groups + kEqStreamWaves - 1) / kEqStreamWaves), block(64 * kEqStreamWaves);
-  const int h = head ? 1 : 0;
-  if (power && stats) hipLaunchKernelGGL((eq_stream_kernel<kSec, true, true>), grid, block, 0, stream, a, sec0, h);
-  else if (power) hipLaunchKernelGGL((eq_stream_kernel<kSec, false, true>), grid, block, 0, stream, a, sec0, h);
-  else if (stats) hipLaunchKernelGGL((eq_stream_kernel<kSec, true, false>), grid, block, 0, stream, a, sec0, h);
-  else hipLaunchKernelGGL((eq_stream_kernel<kSec, false, false>), grid, block, 0, stream, a, sec0, h);
+  // (every launch runs all kSec sections from section 0 on the raw input: the kernel's `sec0` = 0, `head` = 1)
+  if (power && stats) hipLaunchKernelGGL((eq_stream_kernel<kSec, true, true>), grid, block, 0, stream, a, 0, 1);
+  else if (power) hipLaunchKernelGGL((eq_stream_kernel<kSec, false, true>), grid, block, 0, stream, a, 0, 1);
+  else if (stats) hipLaunchKernelGGL((eq_stream_kernel<kSec, true, false>), grid, block, 0, stream, a, 0, 1);
+  else hipLaunchKernelGGL((eq_stream_kernel<kSec, false, false>), grid, block, 0, stream, a, 0, 1);
 }
-static bool launch_eq_stream(const EqSystolicArgs &a, int n_sections, bool stats, bool power, hipStream_t stream, int sec0 = 0,
-                             bool head = true) {
+static bool launch_eq_stream(const EqSystolicArgs &a, int n_sections, bool stats, bool power, hipStream_t stream) {
   switch (n_sections) {
-#define AF_EQ_STREAM_CASE(k) case k: launch_eq_stream_sections<k>(a, stats, power, sec0, head, stream); return true;
+#define AF_EQ_STREAM_CASE(k) case k: launch_eq_stream_sections<k>(a, stats, power, stream); return true;
     AF_EQ_STREAM_CASE(1) AF_EQ_STREAM_CASE(2) AF_EQ_STREAM_CASE(3) AF_EQ_STREAM_CASE(4) AF_EQ_STREAM_CASE(5) AF_EQ_STREAM_CASE(6)
     AF_EQ_STREAM_CASE(7) AF_EQ_STREAM_CASE(8) AF_EQ_STREAM_CASE(9) AF_EQ_STREAM_CASE(10) AF_EQ_STREAM_CASE(11) AF_EQ_STREAM_CASE(12)
     AF_EQ_STREAM_CASE(13) AF_EQ_STREAM_CASE(14) AF_EQ_STREAM_CASE(15) AF_EQ_STREAM_CASE(16)
 #undef AF_EQ_STREAM_CASE
     default: return false;
   }
-}
-
-// One half of a window's EQ in the lane-per-stream form: sections [sec0, sec0 + count) of the single preset.  `head`: this launch
-// takes the raw input (scrub / clamp, block input statistics into `stats`); a launch that ends at the last section may keep the
-// block powers (`block_power`).  Returns hipErrorNotSupported when the form does not serve the buffers (the caller then runs the
-// whole EQ through launch_eq_systolic).
-hipError_t launch_eq_stream_part(const ChainParams *d_params, double *st64, const float *in, float *audio, BlockStats *stats,
-                                 double *block_power, int sec0, int count, bool head, int64_t n_samples, int64_t stream_stride,
-                                 int32_t n_streams, hipStream_t stream) {
-  if (count <= 0 || count > 16 || (stream_stride % 4) != 0 || !audio ||
-      ((reinterpret_cast<uintptr_t>(in) | reinterpret_cast<uintptr_t>(audio)) & 15) != 0)
-    return hipErrorNotSupported;
-  EqSystolicArgs a{d_params, nullptr, st64, in, audio, nullptr, nullptr, head ? stats : nullptr, n_samples, stream_stride, 0, n_streams, 0,
-                   block_power};
-  // (block powers are kept together with block rows: the kernel's flush writes both; without `stats` the rows are skipped)
-  if (!launch_eq_stream(a, count, head && stats != nullptr, block_power != nullptr, stream, sec0, head)) return hipErrorNotSupported;
-  return hipGetLastError();
 }
 
 // `audio`: stream-major output (may be `in`); or null and `ring` / `ring_in` / `ring_rows` / `n0`: the stage pipeline's rings.
@@ -415,18 +400,12 @@ hipError_t launch_eq_systolic(const ChainParams *d_params, const int32_t *d_grou
   EqSystolicArgs a{d_params, d_group_preset, st64, in, audio, ring, ring_in, stats, n_samples, stream_stride, n0, n_streams, ring_rows,
                    block_power};
   // `n_sections` > 0: the caller knows the (single) preset runs that many EQ sections -- the lane-per-stream kernel where it
-  // serves the launch (AF_EQ_STREAM=0: always the systolic kernel)
-  static const bool stream_form = [] {
-    const char *env = std::getenv("AF_EQ_STREAM");
-    return !env || std::atoi(env) != 0;
-  }();
-  if (stream_form && n_sections > 0 && !crossfade && !d_group_preset && audio && !ring && (stream_stride % 4) == 0 &&
+  // serves the launch (AF_EQ_STREAM=0: always the systolic kernel; =1: one wave per group runs all sections; default: two
+  // waves, the sections split between them)
+  const int eq_stream = switches().eq_stream;
+  if (eq_stream != 0 && n_sections > 0 && !crossfade && !d_group_preset && audio && !ring && (stream_stride % 4) == 0 &&
       ((reinterpret_cast<uintptr_t>(in) | reinterpret_cast<uintptr_t>(audio)) & 15) == 0 && (!block_power || stats)) {
-    static const bool two_waves = [] {  // AF_EQ_STREAM=1: one wave per group (all sections); default: two waves, sections split
-      const char *env = std::getenv("AF_EQ_STREAM");
-      return !env || std::atoi(env) != 1;
-    }();
-    if (two_waves && launch_eq_stream2(a, n_sections, stats != nullptr, block_power != nullptr, stream)) return hipGetLastError();
+    if (eq_stream != 1 && launch_eq_stream2(a, n_sections, stats != nullptr, block_power != nullptr, stream)) return hipGetLastError();
     if (launch_eq_stream(a, n_sections, stats != nullptr, block_power != nullptr, stream)) return hipGetLastError();
   }
   const dim3 grid((unsigned)((n_streams + 3) / 4)), block(64);

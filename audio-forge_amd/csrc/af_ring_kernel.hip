@@ -26,6 +26,7 @@
 #include <type_traits>
 
 #include "af_dsp.h"
+#include "af_switches.hpp"
 
 namespace af {
 
@@ -1119,12 +1120,9 @@ hipError_t launch_chain_ring_lds(const LaunchArgs &args, size_t dyn, int variant
   if (auto_makeup) {
     // AF_AUTO_WAVES=8|12|16 (same-box A/B): 8 waves hold everything in 235 VGPRs; 12 and 16 spill a little and keep more chunks
     // in flight (the kernel is a closed queueing network of its waves)
-    static const int waves = [] {
-      const char *env = std::getenv("AF_AUTO_WAVES");
-      // full bench step with auto-makeup, same box: round 3's first build 8 -> 276 ms, 12 -> 228, 16 -> 232 (plain chain: 203); final
-      // build (EQ off this kernel, one launch per call, the last unit freed of the detector's FIR): 8 -> 222.7, 12 -> 184.4, 16 -> 179.9
-      return env ? std::atoi(env) : 16;
-    }();
+    // full bench step with auto-makeup, same box: round 3's first build 8 -> 276 ms, 12 -> 228, 16 -> 232 (plain chain: 203); final
+    // build (EQ off this kernel, one launch per call, the last unit freed of the detector's FIR): 8 -> 222.7, 12 -> 184.4, 16 -> 179.9
+    const int waves = switches().auto_waves;
     if (waves == 8) return launch_variant<8, 4, true>(args, dyn, stream);
     if (waves == 12) return launch_variant<12, 4, true>(args, dyn, stream);
     return launch_variant<16, 4, true>(args, dyn, stream);

@@ -24,15 +24,16 @@
 //                          budget.  The f32-input MFMA is an exact k-ordered fmaf chain, which lets
 //                          this stage match the CPU restatement, and at ~0.2 GFLOP per stream-second
 //                          the network is three orders of magnitude below even that unit's rate.
-//   supp_resynth_kernel    wave per (frame, stream): pitch comb filter, band-gain interpolation, inverse
-//                          transform, synthesis window.
-//   supp_overlap_kernel    wave per stream, frames in order: overlap-add, /32768, smoothed wet/dry mix.
+//   supp_pitchsearch4_kernel  four frames of a stream per workgroup: 2x decimation, LPC-4 whitening, coarse + fine search.
+//   supp_synth_kernel      wave per stream, frames in order: pitch comb filter, band-gain interpolation, inverse
+//                          transform, synthesis window, overlap-add, /32768, smoothed wet/dry mix.
 #include <hip/hip_runtime.h>
 #include <cstdlib>
 
 #include "af_dsp.h"
 #include "af_fft_consts.h"
 #include "af_suppressor.h"
+#include "af_switches.hpp"
 
 namespace af {
 
@@ -1385,13 +1386,7 @@ __device__ __forceinline__ float wave_allsum_xor(float acc) {
   acc = acc + dpp_move<0xB1>(acc);   // quad_perm:[1,0,3,2]
   return acc;
 }
-__device__ __forceinline__ float wave_dot64(const float *x, const float *y, int n, int lane) {
-  float acc = 0.0f;
-#pragma unroll 4
-  for (int i = lane; i < n; i += 64) acc = acc + x[i] * y[i];
-  return wave_allsum_xor(acc);
-}
-// The same sum for a length known at compile time (every call site's is): written out, the reads carry immediate offsets and only
+// A wave's dot product for a length known at compile time (every call site's is): written out, the reads carry immediate offsets and only
 // the last, partial round is masked -- the counted loop spent three instructions per round on its bookkeeping beside the one
 // multiply-add (the pitch tracker forms 33 such sums of 240 products per frame, the search 16 of up to 864).
 template <int kN>
@@ -1555,229 +1550,6 @@ struct PitchLds {  // (6.2 KB: 4096 one-wave workgroups fit the chip in ONE roun
 //      would have shown it.  (The first form walked all lags one at a time on every lane: ~35 instructions per lag,
 //      441 lags per frame, most of this kernel's instructions.)
 template <int MP>
-__device__ __forceinline__ void best_pitch_scan(const float *numa, const float *da, float *syy, float Syy, int lane, int &bp0,
-                                                int &bp1) {
-#pragma unroll 8
-  for (int i = 0; i < MP; ++i) {
-    syy[i] = Syy;  // same address, same value from every lane
-    Syy = fmaxf(1.0f, Syy + da[i]);
-  }
-  __syncthreads();
-  float bn0 = -1, bn1 = -1, bd0 = 0, bd1 = 0;
-  bp0 = 0;
-  bp1 = 1;
-#pragma unroll
-  for (int base = 0; base < MP; base += 64) {
-    const int i = base + lane;
-    const float num = i < MP ? numa[i] : -1.0f;
-    const float sy = i < MP ? syy[i] : 1.0f;
-    unsigned long long todo = ~0ull;  // lanes whose lag comes after the last applied one
-    for (;;) {
-      const bool pass = num >= 0.0f && num * bd1 > bn1 * sy;
-      const unsigned long long m = __ballot(pass) & todo;
-      if (m == 0) break;
-      const int k = __ffsll((long long)m) - 1;
-      const float nk = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(num), k));
-      const float sk = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(sy), k));
-      if (nk * bd0 > bn0 * sk) {
-        bn1 = bn0; bd1 = bd0; bp1 = bp0;
-        bn0 = nk; bd0 = sk; bp0 = base + k;
-      } else {
-        bn1 = nk; bd1 = sk; bp1 = base + k;
-      }
-      todo = k == 63 ? 0ull : ~0ull << (k + 1);
-    }
-  }
-}
-
-// ---- pitch, part 1: everything that depends on the frame alone (wave per (frame, stream), fully parallel):
-// 2x decimation + LPC-4 whitening, coarse and fine cross-correlation search.  Leaves the whitened buffer and
-// the candidate period for part 2.
-struct alignas(16) PitchSearchLds {
-  float ds[kPitchBuf / 2];
-  float xc[304];
-  float numa[304], da[304];
-  float syy[304];
-  float d4[kPitchBuf / 4];  // every second sample of ds: the 4x-decimated buffer, contiguous (stride-2 reads of ds are 2-way bank conflicts)
-};
-extern "C" __global__ __launch_bounds__(64, 4) void supp_pitchsearch_kernel(SuppArgs a, SuppTables tb) {
-  __shared__ PitchSearchLds L;
-  const int lane = threadIdx.x;
-  const int s = (int)(blockIdx.x / a.n_frames), f = (int)(blockIdx.x % a.n_frames);
-  const int64_t n = (int64_t)a.n_frames * kRnnFrame;
-  const float *xh = a.xh + (int64_t)s * (kPitchBuf + n);
-  const int64_t cell = (int64_t)f * a.n_streams + s;
-  {
-    const float *pb = xh + (int64_t)(f + 1) * kRnnFrame;  // pitch_buf after shifting frame f in = pb[0 .. 1728)
-    SuppFrameRec *rec = a.rec + cell;
-    // ---------------- pitch_downsample (pitch.c): 2x decimation, LPC-4 whitening
-    for (int i = lane; i < kPitchBuf / 2; i += 64)
-      L.ds[i] = i == 0 ? .5f * (.5f * pb[1] + pb[0]) : .5f * (.5f * (pb[2 * i - 1] + pb[2 * i + 1]) + pb[2 * i]);
-    __syncthreads();
-    float n0, n1, n2, n3, n4;
-    {
-      float ac[5];
-#pragma unroll
-      for (int k = 0; k < 5; ++k) ac[k] = wave_dot64(L.ds + k, L.ds, kPitchBuf / 2 - k, lane);
-      ac[0] *= 1.0001f;
-      for (int i = 1; i <= 4; ++i) ac[i] -= ac[i] * (.008f * i) * (.008f * i);
-      float lpc[4] = {0, 0, 0, 0};
-      float error = ac[0];
-      if (ac[0] != 0) {
-        for (int i = 0; i < 4; ++i) {
-          float rr = 0;
-          for (int j = 0; j < i; ++j) rr += lpc[j] * ac[i - j];
-          rr += ac[i + 1];
-          const float r = -rr / error;
-          lpc[i] = r;
-          for (int j = 0; j < (i + 1) >> 1; ++j) {
-            const float t1 = lpc[j], t2 = lpc[i - 1 - j];
-            lpc[j] = t1 + r * t2;
-            lpc[i - 1 - j] = t2 + r * t1;
-          }
-          error = error - r * r * error;
-          if (error < .001f * ac[0]) break;
-        }
-      }
-      float tmp = 1.0f;
-      for (int i = 0; i < 4; ++i) {
-        tmp = .9f * tmp;
-        lpc[i] = lpc[i] * tmp;
-      }
-      const float c1 = .8f;
-      n0 = lpc[0] + .8f;
-      n1 = lpc[1] + c1 * lpc[0];
-      n2 = lpc[2] + c1 * lpc[1];
-      n3 = lpc[3] + c1 * lpc[2];
-      n4 = c1 * lpc[3];
-    }
-    {
-      // celt_fir5 with zero initial memory: y[i] = x[i] + n0 x[i-1] + ... + n4 x[i-5], in that order
-      float yv[14];
-      int cnt = 0;
-      for (int i = lane; i < kPitchBuf / 2; i += 64, ++cnt) {
-        float sum = L.ds[i];
-        sum += n0 * (i >= 1 ? L.ds[i - 1] : 0.0f);
-        sum += n1 * (i >= 2 ? L.ds[i - 2] : 0.0f);
-        sum += n2 * (i >= 3 ? L.ds[i - 3] : 0.0f);
-        sum += n3 * (i >= 4 ? L.ds[i - 4] : 0.0f);
-        sum += n4 * (i >= 5 ? L.ds[i - 5] : 0.0f);
-        yv[cnt] = sum;
-      }
-      __syncthreads();
-      cnt = 0;
-      for (int i = lane; i < kPitchBuf / 2; i += 64, ++cnt) L.ds[i] = yv[cnt];
-    }
-    __syncthreads();
-    // ---------------- pitch_search(x_lp = ds + 384, y = ds, len 960, max_pitch 588)
-    const int max_pitch = kPitchMax - 3 * kPitchMin;  // 588
-    const float *x_lp = L.ds + (kPitchMax >> 1);
-    int best0, best1;
-    {
-      // coarse: 4x decimated, 147 lags x 240 products (lane per lag, left-to-right order)
-      constexpr int len = kRnnWindow >> 2, mp = (kPitchMax - 3 * kPitchMin) >> 2;
-      for (int i = lane; i < kPitchBuf / 4; i += 64) L.d4[i] = L.ds[2 * i];
-      __syncthreads();
-      {
-        // xcorr[lag] = sum_j x[j] y[j + lag] on the matrix cores.  Write lag = 16 c + i and j = 4 s + k - 16 c: then
-        //   D[i][c] += A[i][k] B[k][c],  A[i][k] = y[4 s + k + i],  B[k][c] = x[4 s + k - 16 c] (0 outside the frame),
-        // summed over the steps s = 0..95, visits every j in ascending order for each (i, c), one fused multiply-add
-        // per term (v_mfma_f32_16x16x4_f32 accumulates its four k in order): exactly inner_prod_fma of the CPU
-        // restatement.  A zero B entry leaves the accumulator unchanged.  ~4 vector instructions per step instead of the
-        // 16 (and 10 LDS reads) of the lane-per-lag loop this replaces.
-        typedef float v4f_ps __attribute__((ext_vector_type(4)));
-        v4f_ps acc = {0.0f, 0.0f, 0.0f, 0.0f};
-        const int col = lane & 15, kq = lane >> 4;
-        const float *ap = L.d4 + kq + col;                    // y[4 s + k + i]
-        const float *x4 = L.d4 + (kPitchMax >> 2);            // x[j] = x_lp[2 j]
-        int xi = kq - 16 * col;                               // 4 s + k - 16 c at s = 0
-#pragma unroll 4
-        for (int s = 0; s < 96; ++s) {
-          const float av = ap[4 * s];
-          const bool in = (unsigned)xi < (unsigned)len;
-          const float bv = in ? x4[in ? xi : 0] : 0.0f;
-          acc = __builtin_amdgcn_mfma_f32_16x16x4f32(av, bv, acc, 0, 0, 0);
-          xi += 4;
-        }
-        // acc[r]: row i = (lane >> 4) * 4 + r, column c = lane & 15
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          const int lag = 16 * col + kq * 4 + r;
-          if (lag < mp) {
-            const float sum = acc[r];
-            const float x16 = sum * 1e-12f;
-            L.numa[lag] = sum > 0 ? x16 * x16 : -1.0f;
-            const float ya = L.d4[lag + len], yb = L.d4[lag];
-            L.da[lag] = ya * ya - yb * yb;
-          }
-        }
-      }
-      float Syy0;
-      {
-        float acc = 0.0f;
-        for (int i = lane; i < len; i += 64) acc = acc + L.d4[i] * L.d4[i];
-        Syy0 = 1.0f + wave_allsum_xor(acc);
-      }
-      __syncthreads();
-      static_assert(mp == 147, "coarse lag count");
-      best_pitch_scan<mp>(L.numa, L.da, L.syy, Syy0, lane, best0, best1);
-    }
-    __syncthreads();
-    {
-      // fine: 2x decimated, only within +-2 of the two coarse candidates (at most ten lags)
-      constexpr int len = kRnnWindow >> 1, mp = (kPitchMax - 3 * kPitchMin) >> 1;
-      for (int i = lane; i < mp; i += 64) {
-        L.xc[i] = 0.0f;
-        L.numa[i] = -1.0f;
-        const float ya = L.ds[i + len], yb = L.ds[i];
-        L.da[i] = ya * ya - yb * yb;
-      }
-      __syncthreads();
-      for (int c = 0; c < 2; ++c) {
-        const int centre = 2 * (c == 0 ? best0 : best1);
-        for (int i = centre - 2; i <= centre + 2; ++i) {
-          if (i < 0 || i >= mp) continue;
-          if (c == 1) {
-            const int d0 = i - 2 * best0;
-            if (d0 <= 2 && d0 >= -2) continue;  // already done for the first candidate
-          }
-          const float v = fmaxf(-1.0f, wave_dot64(x_lp, L.ds + i, len, lane));
-          if (lane == 0) {
-            L.xc[i] = v;
-            const float x16 = v * 1e-12f;
-            L.numa[i] = v > 0 ? x16 * x16 : -1.0f;
-          }
-        }
-      }
-      const float Syy0 = 1.0f + wave_dot64(L.ds, L.ds, len, lane);
-      __syncthreads();
-      best_pitch_scan<mp>(L.numa, L.da, L.syy, Syy0, lane, best0, best1);
-    }
-    int pitch_index;
-    {
-      int offset = 0;
-      if (best0 > 0 && best0 < (max_pitch >> 1) - 1) {
-        const float pa = L.xc[best0 - 1], pbv = L.xc[best0], pc = L.xc[best0 + 1];
-        if ((pc - pa) > .7f * (pbv - pa)) offset = 1;
-        else if ((pa - pc) > .7f * (pbv - pc)) offset = -1;
-      }
-      pitch_index = kPitchMax - (2 * best0 - offset);
-    }
-    __syncthreads();
-    __syncthreads();
-    float *dsg = a.ds + cell * (kPitchBuf / 2);
-    for (int i = lane; i < kPitchBuf / 2; i += 64) dsg[i] = L.ds[i];
-    if (lane == 0) rec->pitch_index = pitch_index;
-  }
-}
-
-// ---- pitch, part 1, round 3: FOUR frames of one stream per workgroup (a wave each).  Consecutive frames' 1728-sample windows
-// overlap by 1248 samples, so the workgroup fetches the span once -- coalesced 16-byte loads, all in flight together --
-// into LDS and every wave decimates its frame from there (the one-wave form read 6.9 KB per frame through 42 scalar loads per
-// lane, a few at a time: 28 GB per bench step, and most of a wave's life spent waiting for them).  After the decimation the
-// span's LDS becomes the waves' scan arrays (one workgroup barrier); from there on a wave only ever synchronises with itself.
-// Arithmetic and evaluation orders are the one-wave kernel's: the whitened buffers and pitch indices agree bit for bit.
-template <int MP>
 __device__ __forceinline__ void best_pitch_scan_wave(const float *numa, const float *da, float *syy, float Syy, int lane, int &bp0, int &bp1) {
 #pragma unroll 8
   for (int i = 0; i < MP; ++i) {
@@ -1812,6 +1584,13 @@ __device__ __forceinline__ void best_pitch_scan_wave(const float *numa, const fl
   }
 }
 
+// ---- pitch, part 1 (everything that depends on the frame alone: 2x decimation + LPC-4 whitening, coarse and fine cross-correlation
+// search; leaves the whitened buffer and the candidate period for part 2), round 3: FOUR frames of one stream per workgroup (a wave each).  Consecutive frames' 1728-sample windows
+// overlap by 1248 samples, so the workgroup fetches the span once -- coalesced 16-byte loads, all in flight together --
+// into LDS and every wave decimates its frame from there (round 2's kernel, one frame per one-wave workgroup, removed since, read 6.9 KB per frame through 42 scalar loads per
+// lane, a few at a time: 28 GB per bench step, and most of a wave's life spent waiting for them).  After the decimation the
+// span's LDS becomes the waves' scan arrays (one workgroup barrier); from there on a wave only ever synchronises with itself.
+// Arithmetic and evaluation orders are those of that removed kernel: the whitened buffers and pitch indices agreed bit for bit.
 constexpr int kPsFrames = 4;                                   // frames (waves) per workgroup
 constexpr int kPsX0 = 255;                                     // first data word of PsScan::c.x4z (17 x 15 guard words below it)
 constexpr int kPsRaw = kPitchBuf + (kPsFrames - 1) * kRnnFrame;  // samples of the shared span: 3168
@@ -1972,7 +1751,13 @@ extern "C" __global__ __launch_bounds__(64 * kPsFrames, 4) void supp_pitchsearch
   const float *x_lp = ds + (kPitchMax >> 1);
   int best0, best1;
   {
-    // coarse: 4x decimated, 147 lags x 240 products on the matrix cores (see the one-wave kernel above)
+    // coarse: 4x decimated, 147 lags x 240 products on the matrix cores.
+    // xcorr[lag] = sum_j x[j] y[j + lag].  Write lag = 16 c + i and j = 4 s + k - 16 c: then
+    //   D[i][c] += A[i][k] B[k][c],  A[i][k] = y[4 s + k + i],  B[k][c] = x[4 s + k - 16 c] (0 outside the frame),
+    // summed over the steps s = 0..95, visits every j in ascending order for each (i, c), one fused multiply-add
+    // per term (v_mfma_f32_16x16x4_f32 accumulates its four k in order): exactly inner_prod_fma of the CPU
+    // restatement.  A zero B entry leaves the accumulator unchanged.  ~4 vector instructions per step instead of the
+    // 16 (and 10 LDS reads) of a lane-per-lag loop.
     constexpr int len = kRnnWindow >> 2, mp = (kPitchMax - 3 * kPitchMin) >> 2;
     static_assert(kPsX0 + (len - 1) + ((len - 1) >> 4) < 672 && 3 + 4 * 95 + 23 + kPsX0 < 672, "x4z holds the data and both guards");
     for (int i = lane; i < kPsX0; i += 64) S.c.x4z[i] = 0.0f;
@@ -2811,110 +2596,6 @@ __global__ __launch_bounds__(64 * kWaves, 2) void supp_rnn_kernel(SuppArgs a, Rn
 }
 
 // ============================================================================== synthesis
-// One wave per (stream, group of frames): comb filter, gains, inverse transform, synthesis window.  The 960 windowed
-// samples of the frame overwrite the cell's P spectrum (no longer needed: 481 complex = 962 floats >= 960).
-// X and P are elementwise work on a lane's own bins (lane + 64 j), so they live in registers; the transform buffer is
-// free until the inverse transform and lends its space to the band sums.
-extern "C" __global__ __launch_bounds__(64 * kFftWaves, 3) void supp_resynth_kernel(SuppArgs a, SuppTables tb) {
-  __shared__ FftShared S;
-  __shared__ FftUnitLds U[kFftWaves];
-  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
-  fft_shared_init(S, tb, tid, 64 * kFftWaves);
-  __syncthreads();
-  const int groups = (a.n_frames + kFramesPerWave - 1) / kFramesPerWave;
-  const int64_t unit = (int64_t)blockIdx.x * kFftWaves + wave;
-  if (unit >= (int64_t)a.n_streams * groups) return;
-  const int s = (int)(unit / groups), fg = (int)(unit % groups);
-  FftUnitLds &L = U[wave];
-  float *prod = L.prod();
-  float *rv = L.small(), *normv = rv + 32, *gv = rv + 64;  // band vectors the per-bin interpolation gathers from
-  const int f_end = (fg + 1) * kFramesPerWave < a.n_frames ? (fg + 1) * kFramesPerWave : a.n_frames;
-  for (int f = fg * kFramesPerWave; f < f_end; ++f) {
-    const int64_t cell = (int64_t)f * a.n_streams + s;
-    const SuppFrameRec *rec = a.rec + cell;
-    const float2 *Xg = a.X + cell * kRnnFreq;
-    float2 *Pg = a.P + cell * kRnnFreq;
-    float2 Xr[8], Pr[8];
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      const int i = lane + 64 * j;
-      Xr[j] = i < kRnnFreq ? Xg[i] : make_float2(0.0f, 0.0f);
-      Pr[j] = i < kRnnFreq ? Pg[i] : make_float2(0.0f, 0.0f);
-    }
-    float Ex = 0.0f, Ep = 0.0f, Exp = 0.0f, g = 0.0f, graw = 0.0f;
-    if (lane < kRnnBands) {
-      Ex = rec->Ex[lane];
-      Ep = rec->Ep[lane];
-      Exp = rec->Exp[lane];
-      g = rec->gains[lane];
-      graw = rec->gains_raw[lane];
-    }
-    const bool silence = rec->silence != 0;
-    if (!silence) {
-      // ---- pitch_filter (denoise.c): comb-filter the bands the network trusts less than the pitch
-      if (lane < kRnnBands) {
-        const float e = Exp;
-        float r;
-        if (e > graw) r = 1;
-        else r = e * e * (1 - graw * graw) / (.001f + graw * graw * (1 - e * e));
-        r = sqrtf(fminf(1.0f, fmaxf(0.0f, r)));
-        r *= sqrtf(Ex / (1e-8f + Ep));
-        rv[lane] = r;
-        gv[lane] = g;
-      }
-      wave_lds_fence();
-#pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        const int i = lane + 64 * j;
-        if (i < kRnnFreq) {
-          const float rf = interp_gain(rv, S, i);
-          Xr[j].x += rf * Pr[j].x;
-          Xr[j].y += rf * Pr[j].y;
-          if (i < 400) prod[band_skew(i)] = Xr[j].x * Xr[j].x + Xr[j].y * Xr[j].y;
-        }
-      }
-      {
-        const float newE = band_sums_wave(prod, L.scratch(), S, lane);
-        if (lane < kRnnBands) normv[lane] = sqrtf(Ex / (1e-8f + newE));
-      }
-      wave_lds_fence();
-#pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        const int i = lane + 64 * j;
-        if (i < kRnnFreq) {
-          const float nf = interp_gain(normv, S, i);
-          float2 v = Xr[j];
-          v.x *= nf;
-          v.y *= nf;
-          const float gf = interp_gain(gv, S, i);  // band gains after the lastg floor
-          v.x *= gf;
-          v.y *= gf;
-          Xr[j] = v;
-        }
-      }
-      wave_lds_fence();  // every gather from the band vectors is done: the transform buffer may be filled
-    }
-    // ---- frame_synthesis: inverse transform through the forward FFT of the Hermitian extension
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      const int i = lane + 64 * j;
-      if (i < kRnnFreq) {
-        L.fa[i] = Xr[j];
-        if (i > 0 && i < kRnnFrame) L.fa[kRnnWindow - i] = make_float2(Xr[j].x, -Xr[j].y);
-      }
-    }
-    wave_lds_fence();
-    fft960_wave(L.fa, S, lane, 1.0f);
-    float *y = reinterpret_cast<float *>(Pg);
-#pragma unroll
-    for (int j = 0; j < 15; ++j) {
-      const int i = lane + 64 * j;
-      y[i] = L.fa[(kRnnWindow - i) % kRnnWindow].x * window_at(S, i);
-    }
-    wave_lds_fence();
-  }
-}
-
 // Resynthesis and overlap-add as ONE kernel (round 3): a wave takes a stream through ALL frames of the window in order, so the
 // 960 windowed samples of a frame never leave the CU -- the first half meets the previous frame's second half (eight values
 // per lane, in registers; across windows: the stream's synthesis memory) and goes out as finished audio, the second half
@@ -3046,35 +2727,6 @@ extern "C" __global__ __launch_bounds__(64 * kFftWaves, 3) void supp_synth_kerne
   if (lane == 0) st[SuppState::kSmoothedStrength] = smoothed;
 }
 
-// One wave per stream, frames in order: overlap-add of the windowed frames, /32768, smoothed wet/dry mix.
-extern "C" __global__ __launch_bounds__(64) void supp_overlap_kernel(SuppArgs a) {
-  const int lane = threadIdx.x;
-  const int s = blockIdx.x;
-  float *st = a.state + (int64_t)s * SuppState::kCount;
-  float smoothed = st[SuppState::kSmoothedStrength];
-  for (int f = 0; f < a.n_frames; ++f) {
-    const float *y = reinterpret_cast<const float *>(a.P + ((int64_t)f * a.n_streams + s) * kRnnFreq);
-    const float *prev = f == 0 ? st + SuppState::kSynthMem
-                               : reinterpret_cast<const float *>(a.P + ((int64_t)(f - 1) * a.n_streams + s) * kRnnFreq) + kRnnFrame;
-    // wet/dry smoothing, rnnoise.rs:81-86 (once per frame)
-    smoothed = a.strength * a.smoothing_coeff + smoothed * (1.0f - a.smoothing_coeff);
-    const int64_t base = (int64_t)s * a.stream_stride + (a.frame0 + f) * kRnnFrame;
-#pragma unroll
-    for (int i = lane; i < kRnnFrame; i += 64) {
-      float wet = (y[i] + prev[i]) / 32768.0f;
-      if (!a.raw_protocol && smoothed < 1.0f) {
-        const float dry = (a.front_clamp || a.front_dc || a.gate) ? a.out[base + i] : a.in[(int64_t)s * a.in_stride + (a.frame0 + f) * kRnnFrame + i];
-        wet = (smoothed * wet) + ((1.0f - smoothed) * dry);
-      }
-      a.out[base + i] = wet;
-    }
-  }
-  __syncthreads();  // frame 0 read the old synthesis memory above
-  const float *last = reinterpret_cast<const float *>(a.P + ((int64_t)(a.n_frames - 1) * a.n_streams + s) * kRnnFreq) + kRnnFrame;
-  for (int i = lane; i < kRnnFrame; i += 64) st[SuppState::kSynthMem + i] = last[i];
-  if (lane == 0) st[SuppState::kSmoothedStrength] = smoothed;
-}
-
 // ============================================================================== launch
 // The sample-serial pre-pass of a window (independent of the other kernels: it may run a window ahead).
 template <bool kClamp, bool kDcHp, bool kRaw>
@@ -3141,56 +2793,28 @@ hipError_t launch_suppressor_prefilter(const SuppArgs &a, hipStream_t stream) {
 }
 
 // Analysis of one window: spectra, then pitch + cepstral features (frames in order per stream).
-// `before_pitch` (optional) is waited on between the spectra and the pitch search: the pitch search is 50 one-wave
-// workgroups per stream with a small footprint, and while its grid drains, kernels with larger workgroups (the network:
-// 256 VGPRs per wave) are not dispatched at all -- so the caller orders it after the previous window's network launch.
-hipError_t launch_suppressor_analysis(const SuppArgs &a, const SuppTables &tb, hipStream_t stream, hipEvent_t before_pitch) {
+hipError_t launch_suppressor_analysis(const SuppArgs &a, const SuppTables &tb, hipStream_t stream) {
   const int64_t units = (int64_t)a.n_streams * ((a.n_frames + kFramesPerWave - 1) / kFramesPerWave);
   const unsigned cells = (unsigned)((units + kFftWaves - 1) / kFftWaves);  // four units (waves) per transform workgroup
   hipLaunchKernelGGL(supp_spectrum_kernel, dim3(cells), dim3(64 * kFftWaves), 0, stream, a, tb);
-  if (before_pitch) {
-    hipError_t err = hipStreamWaitEvent(stream, before_pitch, 0);
-    if (err != hipSuccess) return err;
-  }
-  static const bool search4 = [] {  // AF_PITCHSEARCH4=0: the round-2 form, one frame (wave) per workgroup (same-box A/B)
-    const char *env = std::getenv("AF_PITCHSEARCH4");
-    return !env || std::atoi(env) != 0;
-  }();
-  if (search4) {
-    const unsigned groups = (unsigned)((a.n_frames + kPsFrames - 1) / kPsFrames);
-    hipLaunchKernelGGL(supp_pitchsearch4_kernel, dim3((unsigned)a.n_streams * groups), dim3(64 * kPsFrames), 0, stream, a, tb);
-  } else {
-    hipLaunchKernelGGL(supp_pitchsearch_kernel, dim3((unsigned)((int64_t)a.n_streams * a.n_frames)), dim3(64), 0, stream, a, tb);
-  }
+  const unsigned groups = (unsigned)((a.n_frames + kPsFrames - 1) / kPsFrames);
+  hipLaunchKernelGGL(supp_pitchsearch4_kernel, dim3((unsigned)a.n_streams * groups), dim3(64 * kPsFrames), 0, stream, a, tb);
   hipLaunchKernelGGL(supp_pitch_kernel, dim3(a.n_streams), dim3(64), 0, stream, a, tb);
   return hipGetLastError();
 }
 
 // The rest of the window: pitch-aligned spectra, the network, resynthesis, overlap-add.
-// `after_network` (optional) is recorded right behind the network launch (see launch_suppressor_analysis).
+// `after_network` (optional) is recorded right behind the network launch.
 // `finish_stream` (optional, needs `after_network`): resynthesis and overlap-add run there, so that the next window's
 // pitch spectra and network launch can start while they run.
-// `network_stream` + `after_spectra` (both or neither): the network kernel runs there, behind the pitch-spectrum kernel's event --
-// the two are the longest pair of dependent kernels of a window, and one stream ran them back to back window after window.
 hipError_t launch_suppressor_synthesis(const SuppArgs &a, const SuppTables &tb, const RnnDeviceWeights &w, hipStream_t stream,
-                                       hipEvent_t after_network, hipStream_t finish_stream, hipStream_t network_stream,
-                                       hipEvent_t after_spectra) {
+                                       hipEvent_t after_network, hipStream_t finish_stream) {
   const int64_t units = (int64_t)a.n_streams * ((a.n_frames + kFramesPerWave - 1) / kFramesPerWave);
   const unsigned cells = (unsigned)((units + kFftWaves - 1) / kFftWaves);  // four units (waves) per transform workgroup
   hipLaunchKernelGGL(supp_pitchspec_kernel, dim3(cells), dim3(64 * kFftWaves), 0, stream, a, tb);
-  if (network_stream && after_spectra && network_stream != stream) {
-    hipError_t err = hipEventRecord(after_spectra, stream);
-    if (err == hipSuccess) err = hipStreamWaitEvent(network_stream, after_spectra, 0);
-    if (err != hipSuccess) return err;
-    stream = network_stream;  // (what follows -- the network, its event -- is this stream's)
-  }
   {
     // AF_RNN_VARIANT = waves (16 streams each) per workgroup: 1, 2 or 4.  Measured on one box, full bench step:
     // 4 -> 287-290 ms, 1 -> 298 ms (the round's first network kernel, a 4-wave workgroup per 16 streams: 301 ms)
-    static const int variant = [] {
-      const char *env = std::getenv("AF_RNN_VARIANT");
-      return env ? std::atoi(env) : 4;
-    }();
     static bool attr_set = false;
     if (!attr_set) {
       hipError_t err = hipFuncSetAttribute(reinterpret_cast<const void *>(supp_rnn_kernel<4>), hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024);
@@ -3198,7 +2822,7 @@ hipError_t launch_suppressor_synthesis(const SuppArgs &a, const SuppTables &tb, 
       attr_set = true;
     }
     const unsigned groups = (unsigned)((a.n_streams + 15) / 16);
-    switch (variant) {
+    switch (switches().rnn_variant) {
       case 1: hipLaunchKernelGGL(supp_rnn_kernel<1>, dim3(groups), dim3(64), rnn_lds_bytes(1), stream, a, w); break;
       case 2: hipLaunchKernelGGL(supp_rnn_kernel<2>, dim3((groups + 1) / 2), dim3(128), rnn_lds_bytes(2), stream, a, w); break;
       default: hipLaunchKernelGGL(supp_rnn_kernel<4>, dim3((groups + 3) / 4), dim3(256), rnn_lds_bytes(4), stream, a, w); break;
@@ -3214,16 +2838,7 @@ hipError_t launch_suppressor_synthesis(const SuppArgs &a, const SuppTables &tb, 
     if (err != hipSuccess) return err;
     fin = finish_stream;
   }
-  static const bool fused_synthesis = [] {  // AF_SYNTH_FUSED=0: resynthesis and overlap-add as two kernels (round 2; same-box A/B)
-    const char *env = std::getenv("AF_SYNTH_FUSED");
-    return !env || std::atoi(env) != 0;
-  }();
-  if (fused_synthesis) {
-    hipLaunchKernelGGL(supp_synth_kernel, dim3((unsigned)((a.n_streams + kFftWaves - 1) / kFftWaves)), dim3(64 * kFftWaves), 0, fin, a, tb);
-  } else {
-    hipLaunchKernelGGL(supp_resynth_kernel, dim3(cells), dim3(64 * kFftWaves), 0, fin, a, tb);
-    hipLaunchKernelGGL(supp_overlap_kernel, dim3(a.n_streams), dim3(64), 0, fin, a);
-  }
+  hipLaunchKernelGGL(supp_synth_kernel, dim3((unsigned)((a.n_streams + kFftWaves - 1) / kFftWaves)), dim3(64 * kFftWaves), 0, fin, a, tb);
   return hipGetLastError();
 }
 

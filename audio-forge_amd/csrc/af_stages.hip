@@ -32,6 +32,7 @@
 #include "af_dsp.h"
 #include "af_eq_systolic_body.h"
 #include "af_stages.h"
+#include "af_switches.hpp"
 
 namespace af {
 namespace {
@@ -1964,10 +1965,7 @@ unsigned stage_role_blocks(int stage, int64_t n0, int64_t n, int32_t n_streams, 
 }
 
 int stage_dispatch_kind(int stage) {
-  static const bool own_dispatch = [] {  // AF_DEESSER_DISPATCH=1: the de-esser's serial stages as a third dispatch per step
-    const char *env = std::getenv("AF_DEESSER_DISPATCH");
-    return env && std::atoi(env) != 0;
-  }();
+  const bool own_dispatch = switches().deesser_dispatch;  // AF_DEESSER_DISPATCH=1: the de-esser's serial stages as a third dispatch per step
   switch (stage) {
     case kStF1: case kStF2: case kStFR: case kStF3: case kStF3a: case kStF5: case kStF6: case kStDe0: case kStDe2: case kStDe5: return 1;
     case kStDe1a: case kStDe1b: case kStDe1c: case kStDe3a: case kStDe3b: case kStDe3c: case kStDe4s: case kStDe4a: case kStDe4b: case kStDe4c: case kStDe4t: case kStDe6a: case kStDe6b: case kStDe6c:

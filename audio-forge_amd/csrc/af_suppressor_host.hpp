@@ -8,13 +8,13 @@
 #include <vector>
 
 #include "af_suppressor.h"
+#include "af_switches.hpp"
 
 namespace af {
 
-hipError_t launch_suppressor_analysis(const SuppArgs &a, const SuppTables &tb, hipStream_t stream, hipEvent_t before_pitch);
+hipError_t launch_suppressor_analysis(const SuppArgs &a, const SuppTables &tb, hipStream_t stream);
 hipError_t launch_suppressor_synthesis(const SuppArgs &a, const SuppTables &tb, const RnnDeviceWeights &w, hipStream_t stream,
-                                       hipEvent_t after_network, hipStream_t finish_stream, hipStream_t network_stream = nullptr,
-                                       hipEvent_t after_spectra = nullptr);
+                                       hipEvent_t after_network, hipStream_t finish_stream);
 hipError_t launch_suppressor_prefilter(const SuppArgs &a, hipStream_t stream);
 hipError_t launch_gate_prepass(const SuppArgs &a, hipStream_t stream);  // the gated front end without the suppressor
 // the VAD-fused gate modes: control pass + per-sample pass (a.n_samples > 0: without the suppressor, else one window of frames)
@@ -86,7 +86,7 @@ struct SuppressorHost {
   float *d_xh = nullptr;
   float *d_ds = nullptr;
   static constexpr int kXhBuffers = 4;    // model-input buffers: the pre-pass runs up to three windows ahead of the synthesis
-  static constexpr int kSpecBuffers = 3;  // spectrum / pitch-spectrum / record buffers: the analysis runs up to two windows ahead
+  static constexpr int kSpecBuffers = kSuppSpecBuffers;  // spectrum / pitch-spectrum / record buffers: the analysis runs up to two windows ahead
   size_t xh_floats = 0;  // floats per model-input buffer
   size_t ws_cells = 0;   // (frame, stream) cells per spectrum / record buffer
   float2 *d_X = nullptr, *d_P = nullptr;
