@@ -37,6 +37,9 @@ _OPERATORS = (
     "eq_magnitude_response",
     "eq_magnitude_response_v2",
     "measure_integrated_loudness",
+    "compute_voice_spectrum",
+    "compute_voice_spectrum_batch",
+    "measure_voice_spectra",
     "suppress",
     "rnnoise_benchmark",
 )
@@ -49,8 +52,9 @@ NoiseSuppressor = getattr(_core_module, "NoiseSuppressor", None) if _core_module
 NoiseModel = getattr(_core_module, "NoiseModel", None) if _core_module is not None else None
 StreamResampler = getattr(_core_module, "StreamResampler", None) if _core_module is not None else None
 Mixdown = getattr(_core_module, "Mixdown", None) if _core_module is not None else None
+VoiceSpectrum = getattr(_core_module, "VoiceSpectrum", None) if _core_module is not None else None
 new_noise_suppression_engine = (getattr(_core_module, "new_noise_suppression_engine", _missing_core)
                                 if _core_module is not None else _missing_core)
 
-__all__ = ["CORE_AVAILABLE", "Engine", "NoiseSuppressor", "NoiseModel", "StreamResampler", "Mixdown", "new_noise_suppression_engine", *_OPERATORS, "LAYOUT_STREAM_MAJOR", "LAYOUT_TIME_MAJOR", "KERNEL_AUTO",
+__all__ = ["CORE_AVAILABLE", "Engine", "NoiseSuppressor", "NoiseModel", "StreamResampler", "Mixdown", "VoiceSpectrum", "new_noise_suppression_engine", *_OPERATORS, "LAYOUT_STREAM_MAJOR", "LAYOUT_TIME_MAJOR", "KERNEL_AUTO",
            "KERNEL_LANE_PER_STREAM", "KERNEL_PHASED", "KERNEL_QUAD", "KERNEL_STAGED"]

@@ -59,6 +59,34 @@ class BlockStats(C.Structure):
     ]
 
 
+class VoiceSpectrumRow(C.Structure):
+    _fields_ = [
+        ("frames", C.c_int32),
+        ("voiced", C.c_int32),
+        ("voiced_window_ratio", C.c_double),
+        ("vad_active_window_ratio", C.c_double),
+        ("vad_probability_used", C.c_int32),
+        ("noise_reference_source", C.c_int32),
+        ("used_single_spectrum_fallback", C.c_int32),
+        ("welch_segments", C.c_int32),
+    ]
+
+
+class VoiceSpectrumOutputs(C.Structure):
+    _fields_ = [
+        ("rows", C.POINTER(VoiceSpectrumRow)),
+        ("speech_db", C.POINTER(C.c_double)),
+        ("noise_db", C.POINTER(C.c_double)),
+        ("spectral_snr_db", C.POINTER(C.c_double)),
+        ("welch_db", C.POINTER(C.c_double)),
+        ("welch_sum", C.POINTER(C.c_double)),
+        ("frame_power", C.POINTER(C.c_double)),
+        ("frame_rms_db", C.POINTER(C.c_double)),
+        ("voiced_mask", C.POINTER(C.c_uint8)),
+        ("keep_windows", C.c_int32),
+    ]
+
+
 # every symbol include/audioforge_mi.h declares: name -> (restype, argtypes)
 _vp, _i32, _i64, _d, _f, _sz = C.c_void_p, C.c_int32, C.c_int64, C.c_double, C.c_float, C.c_size_t
 _fp, _dp = C.POINTER(C.c_float), C.POINTER(C.c_double)
@@ -252,6 +280,15 @@ SIGNATURES = {
     "af_engine_set_input_channels": (C.c_int, [_vp, _i32, _i32]),
     "af_engine_set_input_channel_mode": (C.c_int, [_vp, _i32]),
     "af_engine_read_input_phase": (C.c_int, [_vp, _fp, C.POINTER(C.c_uint64), C.POINTER(_i32), _fp, C.POINTER(_i32), _i32]),
+    "af_voice_spectrum_create": (C.c_int, [C.c_uint32, _i32, _i32, C.POINTER(_vp)]),
+    "af_voice_spectrum_destroy": (None, [_vp]),
+    "af_voice_spectrum_bins": (_i32, [_vp]),
+    "af_voice_spectrum_frames": (_i64, [_vp, _i64]),
+    "af_voice_spectrum_octave_bands": (C.c_int, [_i32, _dp, _dp, _dp, _i32, C.POINTER(_i32)]),
+    "af_voice_spectrum_analyze_host": (C.c_int, [_vp, _fp, _i64, _i32, _i64, _dp, _i64, _fp, _i64, _i64, C.POINTER(VoiceSpectrumOutputs)]),
+    "af_voice_spectrum_analyze_device": (C.c_int, [_vp, _vp, _i64, _i32, _i64, _dp, _i64, _vp, _i64, _i64, C.POINTER(VoiceSpectrumOutputs)]),
+    "af_voice_spectrum_read_windows": (C.c_int, [_vp, _i32, _dp, _dp, _dp, _i32, C.POINTER(_i32)]),
+    "af_voice_spectrum_last_kernel_ms": (C.c_int, [_vp, _dp]),
     "af_gate_process_host": (C.c_int, [_fp, _fp, _i64, _i32, _i64, _d, _d, _d, _d, _i32, _i32, _fp, C.POINTER(C.c_uint64), _i32]),
     "af_measure_integrated_loudness_device": (C.c_int, [_vp, _i64, _i32, _i64, C.c_uint32, _i32, _dp, C.POINTER(_i32)]),
     "af_measure_integrated_loudness_host": (C.c_int, [_fp, _i64, _i32, _i64, C.c_uint32, _i32, _dp, C.POINTER(_i32)]),
@@ -277,6 +314,7 @@ VALUE_FUNCTIONS = {
     "af_stream_resampler_output_delay", "af_stream_resampler_frames_in", "af_stream_resampler_frames_out",
     "af_mixdown_destroy", "af_mixdown_mode", "af_mixdown_channels",
     "af_output_writer_destroy", "af_output_writer_max_output_frames",
+    "af_voice_spectrum_destroy", "af_voice_spectrum_bins", "af_voice_spectrum_frames",
 }
 
 _lib = None

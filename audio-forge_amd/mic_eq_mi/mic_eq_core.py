@@ -1622,3 +1622,185 @@ def simulate_gate_suppressor_order(audio, vad_probabilities: Sequence[float], su
         "suppressor_latency_samples": RNNOISE_FRAME,  # rnnoise.rs:313-315
         "runtime_ms": (time.perf_counter() - started) * 1000.0,
     }
+
+
+# ------------------------------------------------------------------ voice spectrum measurement
+NOISE_REFERENCE_SOURCES = ("unavailable", "explicit_capture", "in_capture_non_speech")  # spectrum.py:553, 577, 586
+
+
+class VoiceSpectrum:
+    """python/mic_eq/analysis/spectrum.py for a batch of captures on the device: frame levels, voiced frames (optionally fused
+    with a VAD posterior), Hamming-windowed spectra, the Welch spectrum, median speech and noise spectra, per-bin SNR and the
+    perceptual smoothing of the voiced windows.  One object per (sample rate, nperseg); scratch is kept between calls."""
+
+    def __init__(self, sample_rate: int = 48_000, nperseg: int = 4096, device: int = 0):
+        self._lib = _lib.load()
+        handle = C.c_void_p()
+        _lib.check(self._lib.af_voice_spectrum_create(int(sample_rate), int(nperseg), int(device), C.byref(handle)))
+        self._h = handle
+        self.sample_rate, self.nperseg = int(sample_rate), int(nperseg)
+        self.bins = int(self._lib.af_voice_spectrum_bins(handle))
+        self.freqs = np.arange(self.bins) * (1.0 / (self.nperseg * (1.0 / self.sample_rate)))  # np.fft.rfftfreq
+
+    def close(self) -> None:
+        if getattr(self, "_h", None):
+            self._lib.af_voice_spectrum_destroy(self._h)
+            self._h = None
+
+    __del__ = close
+
+    def frames(self, n_samples: int) -> int:
+        return int(self._lib.af_voice_spectrum_frames(self._h, int(n_samples)))
+
+    def analyze(self, audio, vad_probabilities=None, noise_audio=None, keep_windows: bool = False, device_pointers=None) -> dict:
+        """audio [n_streams, n] float32 (host), or with `device_pointers=(d_audio, n, n_streams, stride[, d_noise, n_noise,
+        noise_stride])` device memory.  Returns arrays by field: the scalars of af_voice_spectrum_row as [n_streams] arrays,
+        spectra [n_streams, bins] (NaN rows where the reference returns None), frame levels and masks [n_streams, frames]."""
+        dp, fp = C.POINTER(C.c_double), C.POINTER(C.c_float)
+        vad = None if vad_probabilities is None else np.ascontiguousarray(vad_probabilities, dtype=np.float64)
+        if device_pointers is None:
+            a = np.ascontiguousarray(audio, dtype=np.float32)
+            if a.ndim != 2:
+                raise ValueError("audio must be [n_streams, n]")
+            B, n = a.shape
+            noise = None if noise_audio is None else np.ascontiguousarray(noise_audio, dtype=np.float32)
+            if noise is not None and (noise.ndim != 2 or noise.shape[0] != B):
+                raise ValueError("noise_audio must be [n_streams, n_noise]")
+        else:
+            B, n = int(device_pointers[2]), int(device_pointers[1])
+        if vad is not None and (vad.ndim != 2 or vad.shape[0] != B):
+            raise ValueError("vad_probabilities must be [n_streams, n_vad]")
+        if n < self.nperseg:
+            raise ValueError(f"Audio too short for FFT: need {self.nperseg} samples, got {n} ({n / self.sample_rate:.2f} seconds)")
+        F, K = self.frames(n), self.bins
+        rows = (_lib.VoiceSpectrumRow * B)()
+        out = {name: np.empty((B, K)) for name in ("speech_db", "noise_db", "spectral_snr_db", "welch_db", "welch_sum")}
+        out.update(frame_power=np.empty((B, F)), frame_rms_db=np.empty((B, F)), voiced_mask=np.empty((B, F), dtype=np.uint8))
+        o = _lib.VoiceSpectrumOutputs(rows=rows, keep_windows=int(bool(keep_windows)),
+                                      voiced_mask=out["voiced_mask"].ctypes.data_as(C.POINTER(C.c_uint8)),
+                                      **{k: v.ctypes.data_as(dp) for k, v in out.items() if k != "voiced_mask"})
+        vad_args = (None, 0) if vad is None else (vad.ctypes.data_as(dp), vad.shape[1])
+        if device_pointers is None:
+            noise_args = (None, 0, 0) if noise is None else (noise.ctypes.data_as(fp), noise.shape[1], noise.shape[1])
+            rc = self._lib.af_voice_spectrum_analyze_host(self._h, a.ctypes.data_as(fp), n, B, n, *vad_args, *noise_args, C.byref(o))
+        else:
+            d_audio, _, _, stride = device_pointers[:4]
+            noise_args = tuple(device_pointers[4:7]) if len(device_pointers) >= 7 else (None, 0, 0)
+            rc = self._lib.af_voice_spectrum_analyze_device(self._h, C.c_void_p(int(d_audio)), n, B, int(stride), *vad_args,
+                                                            None if noise_args[0] is None else C.c_void_p(int(noise_args[0])),
+                                                            int(noise_args[1]), int(noise_args[2]), C.byref(o))
+        _lib.check(rc)
+        for name, _ in _lib.VoiceSpectrumRow._fields_:
+            out[name] = np.array([getattr(r, name) for r in rows])
+        return out
+
+    def windows(self, stream: int) -> tuple[np.ndarray, np.ndarray, np.ndarray]:
+        """(raw dB, smoothed dB, linear PSD), each [voiced frames, bins], of one stream of the last analyze(keep_windows=True)."""
+        dp, count = C.POINTER(C.c_double), C.c_int32()
+        _lib.check(self._lib.af_voice_spectrum_read_windows(self._h, int(stream), None, None, None, 0, C.byref(count)))
+        arrays = [np.empty((count.value, self.bins)) for _ in range(3)]
+        _lib.check(self._lib.af_voice_spectrum_read_windows(self._h, int(stream), *(x.ctypes.data_as(dp) for x in arrays), count.value,
+                                                            C.byref(count)))
+        return tuple(arrays)
+
+    def last_kernel_ms(self) -> float:
+        ms = C.c_double()
+        _lib.check(self._lib.af_voice_spectrum_last_kernel_ms(self._h, C.byref(ms)))
+        return float(ms.value)
+
+
+def compute_voice_spectrum_batch(audio, fs: int = 48_000, nperseg: int = 4096, device: int = 0) -> tuple[np.ndarray, np.ndarray]:
+    """compute_voice_spectrum (spectrum.py:110-164) of every row of audio [n_streams, n]: (freqs [bins], spectrum_db [n_streams, bins])."""
+    a = np.asarray(audio)
+    if a.ndim != 2:
+        raise ValueError("audio must be [n_streams, n]")
+    if a.shape[1] < nperseg:
+        raise ValueError(f"Audio too short for FFT: need {nperseg} samples, got {a.shape[1]} ({a.shape[1] / fs:.2f} seconds)")
+    vs = VoiceSpectrum(fs, nperseg, device)
+    try:
+        return vs.freqs, vs.analyze(a)["welch_db"]
+    finally:
+        vs.close()
+
+
+def compute_voice_spectrum(audio, fs: int = 48_000, nperseg: int = 4096) -> tuple[np.ndarray, np.ndarray]:
+    """Drop-in for spectrum.py:110-164 (samples are taken as float32, the reference's documented input)."""
+    if len(audio) < nperseg:
+        raise ValueError(f"Audio too short for FFT: need {nperseg} samples, got {len(audio)} ({len(audio) / fs:.2f} seconds)")
+    freqs, spectra = compute_voice_spectrum_batch(np.asarray(audio, dtype=np.float32).reshape(1, -1), fs, nperseg)
+    return freqs, spectra[0]
+
+
+def _estimate_snr_from_spectrum(freqs, spectrum_db, noise_spectrum_db) -> float:
+    """spectrum.py:345-365: integrated voice-band SNR against a matched noise reference (0 without one)."""
+    if noise_spectrum_db is None:
+        return 0.0
+    band = (freqs >= 80.0) & (freqs <= 8000.0)
+    if not np.any(band):
+        band = np.ones_like(freqs, dtype=bool)
+    total = np.power(10.0, spectrum_db[band] / 10.0)
+    noise = np.power(10.0, noise_spectrum_db[band] / 10.0)
+    noise_sum = max(float(np.sum(noise)), 1e-18)
+    signal_sum = max(float(np.sum(total - noise)), noise_sum * 1e-6)
+    return float(10.0 * np.log10(signal_sum / noise_sum))
+
+
+def _estimate_tilt_db_per_octave(freqs, spectrum_db) -> float:
+    """spectrum.py:368-378: least-squares slope over log2(f), 100 Hz .. 8 kHz."""
+    band = (freqs >= 100.0) & (freqs <= 8000.0)
+    if np.count_nonzero(band) < 2:
+        return 0.0
+    x = np.log2(freqs[band])
+    x = x - float(np.mean(x))
+    denom = float(np.sum(x * x))
+    if denom <= 0.0:
+        return 0.0
+    y = spectrum_db[band]
+    return float(np.dot(x, y - float(np.mean(y))) / denom)
+
+
+def measure_voice_spectra(audio, fs: int = 48_000, nperseg: int = 4096, vad_probabilities=None, noise_audio=None,
+                          return_windows: bool = False, device: int = 0) -> list[dict[str, Any]]:
+    """analyze_voice_spectrum (spectrum.py:498-645) of every row of audio [n_streams, n], one dict per stream under the field
+    names of VoiceSpectrumResult.  A stream that takes the single-spectrum fallback (:605-645) carries the complete result;
+    the others carry what precedes the robust median (the reliability statistics behind it are not built): the speech and
+    noise references, the per-bin SNR of :603, the frame levels and mask, and with `return_windows` the voiced frames' raw
+    and perceptually smoothed spectra."""
+    vs = VoiceSpectrum(fs, nperseg, device)
+    try:
+        r = vs.analyze(audio, vad_probabilities, noise_audio, keep_windows=return_windows)
+        freqs = vs.freqs
+        results = []
+        for s in range(len(r["frames"])):
+            have_noise = not np.isnan(r["noise_db"][s, 0])
+            noise = r["noise_db"][s] if have_noise else None
+            fallback = bool(r["used_single_spectrum_fallback"][s])
+            item = {
+                "freqs": freqs,
+                "voiced_window_ratio": float(r["voiced_window_ratio"][s]),
+                "used_single_spectrum_fallback": fallback,
+                "vad_probability_used": bool(r["vad_probability_used"][s]),
+                "vad_active_window_ratio": float(r["vad_active_window_ratio"][s]),
+                "spectral_snr_db": r["spectral_snr_db"][s] if have_noise else None,
+                "noise_spectrum_db": noise,
+                "noise_reference_source": NOISE_REFERENCE_SOURCES[int(r["noise_reference_source"][s])],
+                "speech_reference_db": None if np.isnan(r["speech_db"][s, 0]) else r["speech_db"][s],
+                "welch_spectrum_db": r["welch_db"][s],
+                "frame_rms_db": r["frame_rms_db"][s],
+                "voiced_mask": r["voiced_mask"][s].astype(bool),
+            }
+            if fallback:
+                spectrum = r["welch_db"][s]
+                item.update(median_spectrum_db=spectrum, window_spectra_db=np.asarray([spectrum]),
+                            snr_db=_estimate_snr_from_spectrum(freqs, spectrum, noise), spectral_repeatability=np.zeros_like(freqs),
+                            spectral_tilt_db_per_octave=_estimate_tilt_db_per_octave(freqs, spectrum), residual_confidence=0.0,
+                            measurement_coverage=0.45, outlier_rejection_ratio=0.0,
+                            measurement_uncertainty_db=np.full_like(freqs, np.inf), phonetic_coverage=0.0,
+                            effective_measurement_blocks=0.0)
+            elif return_windows:
+                raw, smoothed, _ = vs.windows(s)
+                item.update(window_spectra_db=raw, smoothed_window_spectra_db=smoothed)
+            results.append(item)
+        return results
+    finally:
+        vs.close()

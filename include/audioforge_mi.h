@@ -656,6 +656,65 @@ int af_measure_integrated_loudness_host(const float *audio, int64_t n_samples, i
                                         int64_t stream_stride, uint32_t sample_rate, int32_t device,
                                         double *lufs, int32_t *status);
 
+/* ---- voice spectrum measurement: python/mic_eq/analysis/spectrum.py ----------------------------------------------
+ * The measurement behind every EQ preset, for a batch of captures: frame energies, voiced-frame selection (optionally fused
+ * with a VAD posterior), Hamming-windowed spectra, the Welch spectrum over the voiced material, median speech and noise
+ * spectra, per-bin SNR and the perceptual smoothing of every voiced window.  In scope: spectrum.py:69-343, 519-645 (up to
+ * and including the single-spectrum fallback return) and 839-967 with strength "balanced".  Deviations: nperseg is a power of
+ * two from 256 to 8192 (anything else: AF_ERR_UNSUPPORTED); non-finite audio is refused with AF_ERR_NON_FINITE.
+ * Frames are nperseg samples at hop nperseg / 2; bins = nperseg / 2 + 1 at k * sample_rate / nperseg Hz. */
+typedef struct af_voice_spectrum af_voice_spectrum;
+enum { AF_NOISE_REFERENCE_UNAVAILABLE = 0, AF_NOISE_REFERENCE_EXPLICIT_CAPTURE = 1, AF_NOISE_REFERENCE_IN_CAPTURE_NON_SPEECH = 2 };
+/* one stream's scalars of analyze_voice_spectrum, spectrum.py:527-550, 570-586, 605, 625 */
+typedef struct af_voice_spectrum_row {
+  int32_t frames;                        /* (n_samples - nperseg) / hop + 1 */
+  int32_t voiced;                        /* frames _voiced_frame_mask kept, :200-247 */
+  double voiced_window_ratio;            /* :543; on the fallback branch max(ratio, 1 / frames), :625 */
+  double vad_active_window_ratio;        /* :545-549 */
+  int32_t vad_probability_used;          /* :550 */
+  int32_t noise_reference_source;        /* AF_NOISE_REFERENCE_*, :553-586 */
+  int32_t used_single_spectrum_fallback; /* :605 */
+  int32_t welch_segments;                /* segments signal.welch averaged over what _select_voiced_samples kept, :69-107 */
+} af_voice_spectrum_row;
+/* Where a call writes; every pointer is host memory and may be null.  Spectra are [n_streams][bins] in dB. */
+typedef struct af_voice_spectrum_outputs {
+  af_voice_spectrum_row *rows;  /* [n_streams] */
+  double *speech_db;            /* _median_frame_spectrum_db of the voiced frames, :551; NaN row where it is None */
+  double *noise_db;             /* the noise reference on the same grid, :596-602; NaN row where it is None */
+  double *spectral_snr_db;      /* _spectral_snr_db, :333-342, :603; NaN row where it is None */
+  double *welch_db;             /* compute_voice_spectrum, :110-164 */
+  double *welch_sum;            /* its sum over segments of |X|^2, before scaling */
+  double *frame_power;          /* [n_streams][frames] mean of x^2 */
+  double *frame_rms_db;         /* [n_streams][frames] _frame_rms_db, :167-169 */
+  uint8_t *voiced_mask;         /* [n_streams][frames] */
+  int32_t keep_windows;         /* != 0: smooth the voiced frames' spectra and keep them for af_voice_spectrum_read_windows
+                                   (host memory: voiced frames x bins x 3 doubles over the whole batch) */
+} af_voice_spectrum_outputs;
+int af_voice_spectrum_create(uint32_t sample_rate, int32_t nperseg, int32_t device, af_voice_spectrum **out);
+void af_voice_spectrum_destroy(af_voice_spectrum *h);
+int32_t af_voice_spectrum_bins(const af_voice_spectrum *h);                       /* VALUE */
+int64_t af_voice_spectrum_frames(const af_voice_spectrum *h, int64_t n_samples);  /* VALUE: 0 below nperseg */
+/* get_octave_frequencies(fraction), default limits and reference, :839-889.  *n_bands is always set. */
+int af_voice_spectrum_octave_bands(int32_t fraction, double *centre, double *lower, double *upper, int32_t capacity, int32_t *n_bands);
+/* analyze_voice_spectrum :519-645 and compute_voice_spectrum :110-164 for audio[n_streams][stride]; n_samples below nperseg
+ * is refused with the reference's "Audio too short for FFT" text.  vad_probabilities: null, or [n_streams][n_vad] posteriors
+ * per 32 ms model window (:172-197).  noise_audio: null, or [n_streams][noise_stride] room-noise captures of n_noise samples
+ * (:570-577; below nperseg it is ignored, :326-327).  _host takes host audio, _device device audio (on the null stream);
+ * both return after the outputs are written. */
+int af_voice_spectrum_analyze_host(af_voice_spectrum *h, const float *audio, int64_t n_samples, int32_t n_streams, int64_t stride,
+                                   const double *vad_probabilities, int64_t n_vad, const float *noise_audio, int64_t n_noise,
+                                   int64_t noise_stride, const af_voice_spectrum_outputs *out);
+int af_voice_spectrum_analyze_device(af_voice_spectrum *h, const float *d_audio, int64_t n_samples, int32_t n_streams, int64_t stride,
+                                     const double *vad_probabilities, int64_t n_vad, const float *d_noise_audio, int64_t n_noise,
+                                     int64_t noise_stride, const af_voice_spectrum_outputs *out);
+/* The voiced frames of one stream of the last call with keep_windows, in frame order, [frames][bins]: _window_spectrum_db
+ * (:293-300), smooth_spectrum_perceptual of it (:949-967) and the PSD before the dB.  *n_frames is set whenever the call
+ * succeeds; with all three arrays null it only counts.  AF_ERR_STATE when the last call kept nothing. */
+int af_voice_spectrum_read_windows(af_voice_spectrum *h, int32_t stream, double *raw_db, double *smoothed_db, double *linear_psd,
+                                   int32_t max_frames, int32_t *n_frames);
+/* GPU time of the kernels of the last call (events around them; copies and host decisions are not in it) */
+int af_voice_spectrum_last_kernel_ms(af_voice_spectrum *h, double *ms);
+
 /* ---- NoiseSuppressor: rust-core/src/dsp/noise_suppressor.rs:18-194 ----------------------------------------
  * The runtime-selected suppressor interface (`NoiseModel`, trait `NoiseSuppressor`, `new_noise_suppression_engine`) for a
  * batch of streams that advance in lock step: sample counts are per stream, audio is [stream][stride] host memory, the
