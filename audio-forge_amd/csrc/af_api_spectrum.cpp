@@ -32,10 +32,22 @@ struct af_voice_spectrum {
   af::DeviceBuffer<af::VsWindowItem> d_items;
   af::DeviceBuffer<af::VsMedianJob> d_jobs;
   af::EventChain events;  // pairs of marks around the kernels of the last call
+  std::vector<int8_t> span_kind;  // per pair from the first reliability span on: which kernel of af_spectrum_stats.hip it times
   // the voiced frames' spectra of the last call that kept them
   bool have_windows = false;
   std::vector<int64_t> win_offset;  // [n_streams + 1] rows
   std::vector<double> win_raw, win_smooth, win_linear;
+  // the reliability statistics (af_spectrum_stats.hip): opt-in; scratch per tile, results of the last call that computed them
+  bool reliability = false, have_reliability = false;
+  af::VsBandTable bands = {};
+  af::DeviceBuffer<double> d_levels, d_distance, d_rel_medians, d_rel_robust, d_rel_uncertainty, d_rel_repeat, d_rel_stats;
+  af::DeviceBuffer<int32_t> d_rel_list, d_row_centre;
+  af::DeviceBuffer<af::VsOffsetJob> d_rel_jobs;
+  af::DeviceBuffer<af::VsBlockJob> d_block_jobs;
+  int32_t rel_streams = 0, rel_frames = 0;
+  std::vector<af_voice_spectrum_reliability_row> rel_rows;
+  std::vector<double> rel_median, rel_repeat, rel_uncertainty, rel_snr, rel_distance;
+  std::vector<uint8_t> rel_inlier;
   ~af_voice_spectrum() {
     if (touched_device) { (void)hipSetDevice(device); (void)hipDeviceSynchronize(); }
   }
@@ -160,6 +172,42 @@ void vs_spectral_snr(const double *speech, const double *noise, int K, double *o
   }
 }
 
+double vs_clip(double v, double lo, double hi) { return std::min(std::max(v, lo), hi); }
+
+// _estimate_snr_from_spectrum, :345-365: the integrated SNR over 80 Hz .. 8 kHz (every bin when the band holds none)
+double vs_estimate_snr(const std::vector<double> &freqs, const double *spectrum, const double *noise /* nullable */) {
+  if (!noise) return 0.0;
+  const int K = (int)freqs.size();
+  bool any = false;
+  for (int k = 0; k < K; ++k) any = any || (freqs[(size_t)k] >= 80.0 && freqs[(size_t)k] <= 8000.0);
+  double noise_sum = 0.0, signal_sum = 0.0;
+  for (int k = 0; k < K; ++k) {
+    if (any && !(freqs[(size_t)k] >= 80.0 && freqs[(size_t)k] <= 8000.0)) continue;
+    const double total = std::pow(10.0, spectrum[k] / 10.0), np = std::pow(10.0, noise[k] / 10.0);
+    noise_sum += np;
+    signal_sum += total - np;
+  }
+  noise_sum = std::max(noise_sum, 1e-18);
+  signal_sum = std::max(signal_sum, noise_sum * 1e-6);
+  return 10.0 * std::log10(signal_sum / noise_sum);
+}
+
+// _estimate_tilt_db_per_octave, :368-378: the least-squares slope over log2(f), 100 Hz .. 8 kHz
+double vs_estimate_tilt(const std::vector<double> &freqs, const double *spectrum) {
+  std::vector<double> x, y;
+  for (size_t k = 0; k < freqs.size(); ++k)
+    if (freqs[k] >= 100.0 && freqs[k] <= 8000.0) { x.push_back(std::log2(freqs[k])); y.push_back(spectrum[k]); }
+  if (x.size() < 2) return 0.0;
+  double mx = 0.0, my = 0.0, denom = 0.0, dot = 0.0;
+  for (size_t i = 0; i < x.size(); ++i) { mx += x[i]; my += y[i]; }
+  mx /= (double)x.size();
+  my /= (double)y.size();
+  for (size_t i = 0; i < x.size(); ++i) { x[i] -= mx; denom += x[i] * x[i]; }
+  if (denom <= 0.0) return 0.0;
+  for (size_t i = 0; i < x.size(); ++i) dot += x[i] * (y[i] - my);
+  return dot / denom;
+}
+
 int vs_upload_tables(af_voice_spectrum *h) {
   if (h->d_window) return AF_OK;
   const size_t N = (size_t)h->nperseg, K = (size_t)h->bins, P = af::kVsSmoothPasses, MB = af::kVsMaxBands;
@@ -209,6 +257,214 @@ int vs_check(af_voice_spectrum *h, const float *audio, int64_t n_samples, int32_
   return AF_OK;
 }
 
+// The reliability statistics of the streams [t0, t1) of one tile, spectrum.py:647-742, from the V smoothed rows in
+// h->d_rows_smooth (stream s starts at row smooth_first[s - t0]).  Group A: row levels, the block and centre medians, the shape
+// distances and the block statistics, with no round trip between them.  The host then decides the inliers (:276-289) and group B
+// takes the robust median over them; everything O(windows) and the scalars of :673-721 are computed here.
+// medians: the tile's [stream][speech | noise][bins] references.
+int vs_reliability_tile(af_voice_spectrum *h, const std::vector<VsDecision> &dec, int t0, int t1, int F, const std::vector<int32_t> &smooth_first,
+                        size_t V, const std::vector<double> &medians, hipStream_t q) {
+  const int N = h->nperseg, hop = N / 2, K = h->bins, T = t1 - t0, LF = af::kVsLevelFields;
+  const size_t row_bytes = sizeof(double) * (size_t)K;
+  const double nan = std::numeric_limits<double>::quiet_NaN(), inf = std::numeric_limits<double>::infinity();
+  static const double targets[af::kVsCoverageBands] = {3.0, 4.0, 5.0, 6.0, 7.0};  // :391-397
+  struct Plan { int32_t sm0 = -1, blocks = 0, list_all = 0; std::vector<int32_t> independent; };
+  std::vector<Plan> plans((size_t)T);
+  std::vector<int32_t> list, row_centre(V, -1);
+  std::vector<af::VsOffsetJob> jobs;
+  std::vector<af::VsBlockJob> block_jobs;
+  int32_t median_rows = 0;
+  for (int s = t0; s < t1; ++s) {
+    const VsDecision &d = dec[(size_t)s];
+    Plan &p = plans[(size_t)(s - t0)];
+    if (d.fallback) continue;
+    p.sm0 = smooth_first[(size_t)(s - t0)];
+    int64_t next_start = -1;
+    for (int f = 0, j = 0; f < F; ++f) {  // :446-454: the voiced windows that do not overlap the one kept before
+      if (!d.mask[(size_t)f]) continue;
+      if ((int64_t)f * hop >= next_start) { p.independent.push_back(j); next_start = (int64_t)f * hop + N; }
+      ++j;
+    }
+    const int32_t row0 = median_rows, whole = (int32_t)p.independent.size() / af::kVsBlockFrames;
+    for (int32_t b = 0; b < whole; ++b) {  // :456-460: mean-level offsets
+      jobs.push_back({(int32_t)list.size(), af::kVsBlockFrames, median_rows++, 0, 0.0, 0, 0});
+      for (int i = 0; i < af::kVsBlockFrames; ++i) list.push_back(p.sm0 + p.independent[(size_t)(b * af::kVsBlockFrames + i)]);
+    }
+    if (whole == 0 && !p.independent.empty()) {  // :461-462
+      jobs.push_back({(int32_t)list.size(), (int32_t)p.independent.size(), median_rows++, 0, 0.0, 0, 0});
+      for (int32_t j : p.independent) list.push_back(p.sm0 + j);
+    }
+    p.blocks = median_rows - row0;
+    block_jobs.push_back({row0, p.blocks, s - t0, 0});
+    p.list_all = (int32_t)list.size();  // :270: the centre over all voiced windows, median-level offsets
+    jobs.push_back({p.list_all, d.voiced, median_rows, 1, 0.0, 0, 0});
+    for (int j = 0; j < d.voiced; ++j) { list.push_back(p.sm0 + j); row_centre[(size_t)(p.sm0 + j)] = median_rows; }
+    ++median_rows;
+  }
+  std::vector<double> levels(V * (size_t)LF), distance(V), stats((size_t)T * 4);
+  std::vector<double> robust((size_t)T * K), uncertainty((size_t)T * K), repeat((size_t)T * K);
+  std::vector<uint8_t> inlier_of_row(V, 0);
+  std::vector<uint8_t> closest((size_t)T, 0);
+  std::vector<int32_t> n_inliers((size_t)T, 0);
+  if (!jobs.empty()) {
+    AF_HIP(h->d_levels.reserve_exact(sizeof(double) * levels.size()));
+    AF_HIP(h->d_distance.reserve_exact(sizeof(double) * V));
+    AF_HIP(h->d_row_centre.reserve_exact(sizeof(int32_t) * V));
+    AF_HIP(h->d_rel_list.reserve_exact(sizeof(int32_t) * list.size()));
+    AF_HIP(h->d_rel_jobs.reserve_exact(sizeof(af::VsOffsetJob) * jobs.size()));
+    AF_HIP(h->d_block_jobs.reserve_exact(sizeof(af::VsBlockJob) * block_jobs.size()));
+    AF_HIP(h->d_rel_medians.reserve_exact(row_bytes * (size_t)median_rows));
+    AF_HIP(h->d_rel_robust.reserve_exact(row_bytes * (size_t)T));
+    AF_HIP(h->d_rel_uncertainty.reserve_exact(row_bytes * (size_t)T));
+    AF_HIP(h->d_rel_repeat.reserve_exact(row_bytes * (size_t)T));
+    AF_HIP(h->d_rel_stats.reserve_exact(sizeof(double) * stats.size()));
+    AF_HIP(hipMemcpy(h->d_row_centre, row_centre.data(), sizeof(int32_t) * V, hipMemcpyHostToDevice));
+    AF_HIP(hipMemcpy(h->d_rel_list, list.data(), sizeof(int32_t) * list.size(), hipMemcpyHostToDevice));
+    AF_HIP(hipMemcpy(h->d_rel_jobs, jobs.data(), sizeof(af::VsOffsetJob) * jobs.size(), hipMemcpyHostToDevice));
+    AF_HIP(hipMemcpy(h->d_block_jobs, block_jobs.data(), sizeof(af::VsBlockJob) * block_jobs.size(), hipMemcpyHostToDevice));
+    // a pair of marks per kernel (back to back on one stream: nothing waits for them), so that each one's share can be read
+    const auto span = [&](int8_t kind) {
+      h->span_kind.resize(h->events.marks() / 2, (int8_t)-1);
+      h->span_kind.push_back(kind);
+      return h->events.mark(q);
+    };
+    AF_HIP(span(0));
+    AF_HIP(af::launch_vs_row_levels(h->d_rows_smooth, (int32_t)V, K, h->bands, h->d_levels, q));
+    AF_HIP(h->events.mark(q));
+    AF_HIP(span(1));
+    AF_HIP(af::launch_vs_offset_median(h->d_rows_smooth, h->d_rel_list, h->d_levels, h->d_rel_jobs, (int32_t)jobs.size(), K,
+                                       h->d_rel_medians, q));
+    AF_HIP(h->events.mark(q));
+    AF_HIP(span(2));
+    AF_HIP(af::launch_vs_shape_distance(h->d_rows_smooth, (int32_t)V, K, h->bands, h->d_levels, h->d_row_centre, h->d_rel_medians,
+                                        h->d_distance, q));
+    AF_HIP(h->events.mark(q));
+    AF_HIP(span(3));
+    AF_HIP(af::launch_vs_block_stats(h->d_rel_medians, h->d_block_jobs, (int32_t)block_jobs.size(), K, h->d_rel_uncertainty,
+                                     h->d_rel_repeat, h->d_rel_stats, q));
+    AF_HIP(h->events.mark(q));
+    AF_HIP(hipMemcpy(levels.data(), h->d_levels, sizeof(double) * levels.size(), hipMemcpyDeviceToHost));
+    AF_HIP(hipMemcpy(distance.data(), h->d_distance, sizeof(double) * V, hipMemcpyDeviceToHost));
+    AF_HIP(hipMemcpy(stats.data(), h->d_rel_stats, sizeof(double) * stats.size(), hipMemcpyDeviceToHost));
+
+    // :276-289: the inliers of every stream, then the robust shape over them plus the inliers' median level
+    jobs.clear();
+    list.clear();
+    for (int s = t0; s < t1; ++s) {
+      const Plan &p = plans[(size_t)(s - t0)];
+      if (p.sm0 < 0) continue;
+      const int n = dec[(size_t)s].voiced;
+      const double *dist = &distance[(size_t)p.sm0];
+      const double mid = vs_median(std::vector<double>(dist, dist + n));
+      std::vector<double> dev((size_t)n);
+      for (int j = 0; j < n; ++j) dev[(size_t)j] = std::fabs(dist[j] - mid);
+      const double cutoff = mid + 4.0 * std::max(vs_median(dev), 0.25);
+      uint8_t *in = &inlier_of_row[(size_t)p.sm0];
+      int count = 0;
+      for (int j = 0; j < n; ++j) count += in[j] = dist[j] <= cutoff;
+      const int minimum = std::max(3, (int)std::ceil((double)n * 0.50));
+      if (count < minimum) {  // :281-285: the closest windows instead
+        std::vector<int32_t> order((size_t)n);
+        for (int j = 0; j < n; ++j) order[(size_t)j] = j;
+        std::stable_sort(order.begin(), order.end(), [&](int32_t a, int32_t b) { return dist[a] < dist[b]; });
+        std::fill(in, in + n, (uint8_t)0);
+        for (int j = 0; j < minimum && j < n; ++j) in[order[(size_t)j]] = 1;
+        count = std::min(minimum, n);
+        closest[(size_t)(s - t0)] = 1;
+      }
+      n_inliers[(size_t)(s - t0)] = count;
+      std::vector<double> kept;
+      const int32_t first = (int32_t)list.size();
+      for (int j = 0; j < n; ++j)
+        if (in[j]) { kept.push_back(levels[(size_t)(p.sm0 + j) * LF + 1]); list.push_back(p.sm0 + j); }
+      jobs.push_back({first, count, s - t0, 1, vs_median(kept), 1, 0});
+    }
+    AF_HIP(hipMemcpy(h->d_rel_list, list.data(), sizeof(int32_t) * list.size(), hipMemcpyHostToDevice));
+    AF_HIP(hipMemcpy(h->d_rel_jobs, jobs.data(), sizeof(af::VsOffsetJob) * jobs.size(), hipMemcpyHostToDevice));
+    AF_HIP(span(4));
+    AF_HIP(af::launch_vs_offset_median(h->d_rows_smooth, h->d_rel_list, h->d_levels, h->d_rel_jobs, (int32_t)jobs.size(), K,
+                                       h->d_rel_robust, q));
+    AF_HIP(h->events.mark(q));
+    AF_HIP(hipMemcpy(robust.data(), h->d_rel_robust, row_bytes * (size_t)T, hipMemcpyDeviceToHost));
+    AF_HIP(hipMemcpy(uncertainty.data(), h->d_rel_uncertainty, row_bytes * (size_t)T, hipMemcpyDeviceToHost));
+    AF_HIP(hipMemcpy(repeat.data(), h->d_rel_repeat, row_bytes * (size_t)T, hipMemcpyDeviceToHost));
+  }
+
+  std::vector<double> welch, sorted;
+  for (int s = t0; s < t1 && welch.empty(); ++s)
+    if (dec[(size_t)s].fallback) {  // the fallback streams' Welch rows: one copy of the tile's
+      welch.resize((size_t)T * K);
+      AF_HIP(hipMemcpy(welch.data(), h->d_welch_db + (size_t)t0 * K, row_bytes * (size_t)T, hipMemcpyDeviceToHost));
+    }
+  for (int s = t0; s < t1; ++s) {
+    const VsDecision &d = dec[(size_t)s];
+    const Plan &p = plans[(size_t)(s - t0)];
+    af_voice_spectrum_reliability_row &r = h->rel_rows[(size_t)s];
+    double *median = &h->rel_median[(size_t)s * K], *rep = &h->rel_repeat[(size_t)s * K], *unc = &h->rel_uncertainty[(size_t)s * K];
+    double *snr = &h->rel_snr[(size_t)s * K], *dist = &h->rel_distance[(size_t)s * F];
+    uint8_t *inl = &h->rel_inlier[(size_t)s * F];
+    const bool have_noise = d.voiced > 0 && d.source != af::kVsNoiseUnavailable;
+    const double *noise = have_noise ? &medians[(size_t)(s - t0) * 2 * K + K] : nullptr;
+    std::fill(dist, dist + F, nan);
+    std::fill(inl, inl + F, (uint8_t)0);
+    r = af_voice_spectrum_reliability_row{};
+    if (p.sm0 < 0) {  // the fallback return, :606-645
+      std::memcpy(median, &welch[(size_t)(s - t0) * K], row_bytes);
+      std::fill(rep, rep + K, 0.0);
+      std::fill(unc, unc + K, inf);
+      if (noise) vs_spectral_snr(&medians[(size_t)(s - t0) * 2 * K], noise, K, snr);
+      else std::fill(snr, snr + K, nan);
+      r.snr_db = vs_estimate_snr(h->smooth.freqs, median, noise);
+      r.spectral_tilt_db_per_octave = vs_estimate_tilt(h->smooth.freqs, median);
+      r.measurement_coverage = 0.45;
+      continue;
+    }
+    const int i = s - t0;
+    std::memcpy(median, &robust[(size_t)i * K], row_bytes);
+    std::memcpy(rep, &repeat[(size_t)i * K], row_bytes);
+    std::memcpy(unc, &uncertainty[(size_t)i * K], row_bytes);
+    for (int f = 0, j = 0; f < F; ++f)
+      if (d.mask[(size_t)f]) { dist[f] = distance[(size_t)(p.sm0 + j)]; inl[f] = inlier_of_row[(size_t)(p.sm0 + j)]; ++j; }
+    if (noise) vs_spectral_snr(median, noise, K, snr);  // :672
+    else std::fill(snr, snr + K, nan);
+    const double effective = stats[(size_t)i * 4 + 3];
+    double diversity = 0.0;  // _coarse_phonetic_coverage over the independent windows, :381-408
+    int scores = 0;
+    for (int b = 0; b < af::kVsCoverageBands; ++b) {
+      if (h->bands.last[b] < h->bands.first[b]) continue;
+      sorted.clear();
+      for (int32_t j : p.independent) sorted.push_back(levels[(size_t)(p.sm0 + j) * LF + 2 + b]);
+      std::sort(sorted.begin(), sorted.end());
+      const double spread = vs_percentile_sorted(sorted, 90.0) - vs_percentile_sorted(sorted, 10.0);
+      diversity += vs_clip(spread / targets[b], 0.0, 1.0);
+      ++scores;
+    }
+    diversity = scores ? diversity / (double)scores : 0.0;
+    const double duration = vs_clip(effective / af::kVsCoverageTargetBlocks, 0.0, 1.0);  // :481-487, :685-691
+    const double phonetic = std::sqrt(diversity * duration);
+    const double inlier_ratio = (double)n_inliers[(size_t)i] / (double)std::max(1, d.voiced);
+    const double snr_db = vs_estimate_snr(h->smooth.freqs, median, noise);
+    const double score = vs_median(std::vector<double>(rep + h->bands.v0, rep + h->bands.v1 + 1));  // :679-684
+    const double coverage = vs_clip(0.45 * inlier_ratio + 0.35 * phonetic + 0.20 * duration, 0.0, 1.0);
+    double confidence;
+    if (!noise) confidence = vs_clip(0.5625 * score + 0.4375 * phonetic, 0.0, 0.70);
+    else confidence = vs_clip(0.45 * score + 0.35 * phonetic + 0.20 * vs_clip((snr_db - 3.0) / 15.0, 0.0, 1.0), 0.0, 1.0);
+    r.snr_db = snr_db;
+    r.spectral_tilt_db_per_octave = vs_estimate_tilt(h->smooth.freqs, median);
+    r.residual_confidence = vs_clip(confidence * (0.75 + 0.25 * coverage), 0.0, 1.0);
+    r.measurement_coverage = coverage;
+    r.outlier_rejection_ratio = 1.0 - inlier_ratio;
+    r.phonetic_coverage = phonetic;
+    r.effective_measurement_blocks = effective;
+    r.voiced = d.voiced;
+    r.independent = (int32_t)p.independent.size();
+    r.blocks = p.blocks;
+    r.inliers = n_inliers[(size_t)i];
+    r.used_closest_windows = closest[(size_t)i];
+  }
+  return AF_OK;
+}
+
 int vs_analyze(af_voice_spectrum *h, const float *d_audio, int64_t n, int32_t B, int64_t stride, const double *vad, int64_t n_vad,
                const float *d_noise, int64_t n_noise, int64_t noise_stride, const af_voice_spectrum_outputs *out) {
   const int N = h->nperseg, hop = N / 2, K = h->bins;
@@ -218,7 +474,9 @@ int vs_analyze(af_voice_spectrum *h, const float *d_audio, int64_t n, int32_t B,
   const double nan = std::numeric_limits<double>::quiet_NaN();
   hipStream_t q = nullptr;
   h->have_windows = false;
+  h->have_reliability = false;
   h->events.restart();
+  h->span_kind.clear();
   if (int rc = vs_upload_tables(h)) return rc;
 
   // 1. chunk sums -> frame energies and means
@@ -258,7 +516,15 @@ int vs_analyze(af_voice_spectrum *h, const float *d_audio, int64_t n, int32_t B,
   AF_HIP(h->events.mark(q));
 
   // 4. window spectra, medians and smoothing, a tile of streams at a time
-  const bool keep = out->keep_windows != 0;
+  const bool keep = out->keep_windows != 0, reliability = h->reliability;
+  if (reliability) {
+    h->rel_streams = B;
+    h->rel_frames = F;
+    h->rel_rows.resize((size_t)B);
+    for (std::vector<double> *v : {&h->rel_median, &h->rel_repeat, &h->rel_uncertainty, &h->rel_snr}) v->resize((size_t)B * K);
+    h->rel_distance.resize((size_t)B * F);
+    h->rel_inlier.resize((size_t)B * F);
+  }
   if (keep) {
     h->win_offset.assign((size_t)B + 1, 0);
     for (int s = 0; s < B; ++s) h->win_offset[(size_t)s + 1] = h->win_offset[(size_t)s] + dec[(size_t)s].voiced;
@@ -275,17 +541,19 @@ int vs_analyze(af_voice_spectrum *h, const float *d_audio, int64_t n, int32_t B,
   std::vector<double> medians, middle((size_t)2 * K);
   std::vector<af::VsWindowItem> items;
   std::vector<af::VsMedianJob> jobs;
-  std::vector<int32_t> voiced_rows, first_row;
+  std::vector<int32_t> voiced_rows, first_row, smooth_first;
   for (int t0 = 0; t0 < B; t0 += tile) {
     const int t1 = std::min(B, t0 + tile);
-    items.clear(); jobs.clear(); voiced_rows.clear(); first_row.clear();
+    items.clear(); jobs.clear(); voiced_rows.clear(); first_row.clear(); smooth_first.clear();
     for (int s = t0; s < t1; ++s) {  // per stream: voiced frames | unvoiced frames (in-capture noise) | noise capture frames
       const VsDecision &d = dec[(size_t)s];
       const int32_t row0 = (int32_t)items.size();
       first_row.push_back(row0);
+      const bool smoothed = keep || (reliability && !d.fallback);  // the windows vs_smooth_kernel takes
+      smooth_first.push_back(smoothed ? (int32_t)voiced_rows.size() : -1);
       for (int f = 0; f < F; ++f)
         if (d.mask[(size_t)f]) {
-          voiced_rows.push_back((int32_t)items.size());
+          if (smoothed) voiced_rows.push_back((int32_t)items.size());
           items.push_back({0, s, f, (int32_t)items.size()});
         }
       if (d.voiced > 0) jobs.push_back({row0, d.voiced, 2 * (s - t0), 0});
@@ -300,11 +568,11 @@ int vs_analyze(af_voice_spectrum *h, const float *d_audio, int64_t n, int32_t B,
         jobs.push_back({r, Fn, 2 * (s - t0) + 1, 0});
       }
     }
-    const size_t R = items.size(), V = keep ? voiced_rows.size() : 0;
+    const size_t R = items.size(), V = voiced_rows.size();
     medians.assign((size_t)(t1 - t0) * 2 * K, nan);
     if (R > 0) {
       AF_HIP(h->d_rows_linear.reserve_exact(row_bytes * R));
-      if (keep) AF_HIP(h->d_rows_db.reserve_exact(row_bytes * R));
+      if (keep || reliability) AF_HIP(h->d_rows_db.reserve_exact(row_bytes * R));
       AF_HIP(h->d_items.reserve_exact(sizeof(af::VsWindowItem) * R));
       AF_HIP(h->d_jobs.reserve_exact(sizeof(af::VsMedianJob) * jobs.size()));
       AF_HIP(h->d_medians.reserve_exact(row_bytes * 4 * (size_t)(t1 - t0)));
@@ -317,7 +585,7 @@ int vs_analyze(af_voice_spectrum *h, const float *d_audio, int64_t n, int32_t B,
       }
       AF_HIP(h->events.mark(q));
       AF_HIP(af::launch_vs_window_spectra(d_audio, stride, h->d_sums, C, d_noise, noise_stride, h->d_noise_sums, Cn, h->d_items,
-                                          (int32_t)R, N, h->d_window, h->d_twiddles, h->sumw2, keep ? h->d_rows_db.get() : nullptr,
+                                          (int32_t)R, N, h->d_window, h->d_twiddles, h->sumw2, keep || reliability ? h->d_rows_db.get() : nullptr,
                                           h->d_rows_linear, q));
       AF_HIP(af::launch_vs_median(h->d_rows_linear, h->d_jobs, (int32_t)jobs.size(), K, h->d_medians, q));
       if (V > 0)
@@ -333,7 +601,7 @@ int vs_analyze(af_voice_spectrum *h, const float *d_audio, int64_t n, int32_t B,
           m[k] = (lo + hi) / 2.0;
         }
       }
-      if (V > 0) {
+      if (V > 0 && keep) {
         AF_HIP(hipMemcpy(&h->win_smooth[(size_t)h->win_offset[(size_t)t0] * K], h->d_rows_smooth, row_bytes * V, hipMemcpyDeviceToHost));
         for (int s = t0; s < t1; ++s) {
           const size_t cnt = (size_t)dec[(size_t)s].voiced, at = (size_t)h->win_offset[(size_t)s] * K;
@@ -356,6 +624,8 @@ int vs_analyze(af_voice_spectrum *h, const float *d_audio, int64_t n, int32_t B,
         else std::fill(snr, snr + K, nan);
       }
     }
+    if (reliability)
+      if (int rc = vs_reliability_tile(h, dec, t0, t1, F, smooth_first, R > 0 ? V : 0, medians, q)) return rc;
   }
   if (out->welch_db) AF_HIP(hipMemcpy(out->welch_db, h->d_welch_db, row_bytes * (size_t)B, hipMemcpyDeviceToHost));
   if (out->welch_sum) AF_HIP(hipMemcpy(out->welch_sum, h->d_welch_sum, row_bytes * (size_t)B, hipMemcpyDeviceToHost));
@@ -380,6 +650,7 @@ int vs_analyze(af_voice_spectrum *h, const float *d_audio, int64_t n, int32_t B,
     }
   }
   h->have_windows = keep;
+  h->have_reliability = reliability;
   return AF_OK;
 }
 
@@ -404,6 +675,7 @@ int af_voice_spectrum_create(uint32_t sample_rate, int32_t nperseg, int32_t devi
   af::vs_make_welch_window(nperseg, h->welch_window, &h->welch_sumw2);
   af::vs_make_twiddles(nperseg, h->twiddles);
   af::vs_make_smooth_tables(sample_rate, nperseg, h->smooth);
+  af::vs_make_band_table(h->smooth.freqs, h->bands);
   *out = h;
   return AF_OK;
 }
@@ -476,6 +748,44 @@ int af_voice_spectrum_read_windows(af_voice_spectrum *h, int32_t stream, double 
   if (raw_db) std::memcpy(raw_db, h->win_raw.data() + at, bytes);
   if (smoothed_db) std::memcpy(smoothed_db, h->win_smooth.data() + at, bytes);
   if (linear_psd) std::memcpy(linear_psd, h->win_linear.data() + at, bytes);
+  return AF_OK;
+}
+
+int af_voice_spectrum_set_reliability(af_voice_spectrum *h, int32_t enabled) {
+  if (!h) return fail(AF_ERR_INVALID_ARGUMENT, "voice spectrum handle is null");
+  h->reliability = enabled != 0;
+  return AF_OK;
+}
+
+int af_voice_spectrum_read_reliability(af_voice_spectrum *h, const af_voice_spectrum_reliability_outputs *out) {
+  if (!h) return fail(AF_ERR_INVALID_ARGUMENT, "voice spectrum handle is null");
+  if (!out) return fail(AF_ERR_INVALID_ARGUMENT, "outputs is null");
+  if (!h->have_reliability)
+    return fail(AF_ERR_STATE, "the last call did not compute the reliability statistics (af_voice_spectrum_set_reliability)");
+  const size_t B = (size_t)h->rel_streams, K = (size_t)h->bins, F = (size_t)h->rel_frames;
+  if (out->rows) std::copy(h->rel_rows.begin(), h->rel_rows.end(), out->rows);
+  if (out->median_spectrum_db) std::memcpy(out->median_spectrum_db, h->rel_median.data(), sizeof(double) * B * K);
+  if (out->spectral_repeatability) std::memcpy(out->spectral_repeatability, h->rel_repeat.data(), sizeof(double) * B * K);
+  if (out->measurement_uncertainty_db) std::memcpy(out->measurement_uncertainty_db, h->rel_uncertainty.data(), sizeof(double) * B * K);
+  if (out->spectral_snr_db) std::memcpy(out->spectral_snr_db, h->rel_snr.data(), sizeof(double) * B * K);
+  if (out->window_distance) std::memcpy(out->window_distance, h->rel_distance.data(), sizeof(double) * B * F);
+  if (out->inlier_mask) std::memcpy(out->inlier_mask, h->rel_inlier.data(), B * F);
+  return AF_OK;
+}
+
+int af_voice_spectrum_last_reliability_kernel_ms(af_voice_spectrum *h, double *ms, int32_t capacity) {
+  if (!h || !ms) return fail(AF_ERR_INVALID_ARGUMENT, "null argument");
+  if (capacity < 5) return fail(AF_ERR_INVALID_ARGUMENT, "ms must hold 5 values");
+  std::fill(ms, ms + 5, 0.0);
+  if (h->events.marks() == 0) return AF_OK;
+  AF_HIP(hipSetDevice(h->device));
+  AF_HIP(h->events.wait_last());
+  for (size_t i = 0; i < h->span_kind.size() && 2 * i + 1 < h->events.marks(); ++i) {
+    if (h->span_kind[i] < 0) continue;
+    double span = 0.0;
+    AF_HIP(h->events.elapsed(2 * i, 2 * i + 1, &span));
+    ms[h->span_kind[i]] += span;
+  }
   return AF_OK;
 }
 

@@ -28,12 +28,41 @@ constexpr int kVsTileStreams = 64;           // window-spectra scratch is sized 
 constexpr int kVsSmoothPasses = 3;           // 1/3, 1/6, 1/12 octave: what "balanced" reads (spectrum.py:959-967)
 constexpr int kVsMaxBands = 160;             // 1/12 octave over 20 Hz .. 20 kHz has 120
 
+constexpr int kVsBlockFrames = 3;           // UNCERTAINTY_BLOCK_FRAMES, :28
+constexpr double kVsUncertaintyScaleDb = 2.5;  // UNCERTAINTY_SCALE_DB, :29
+constexpr double kVsCoverageTargetBlocks = 12.0;  // PHONETIC_COVERAGE_TARGET_BLOCKS, :30
+constexpr int kVsCoverageBands = 5;          // _coarse_phonetic_coverage's bands, :391-397
+constexpr int kVsLevelFields = 2 + kVsCoverageBands;  // per smoothed window: voice-band mean | median | the band medians of S - mean
+
 enum VsNoiseSource : int { kVsNoiseUnavailable = 0, kVsNoiseExplicit = 1, kVsNoiseInCapture = 2 };
 
 // one window spectrum: the frame of `source` (0 the capture, 1 the noise capture) that starts at chunk `chunk`
 struct VsWindowItem { int32_t source, stream, chunk, row; };
 // one column median: rows [row0, row0 + count) of the scratch -> row `out` of the medians
 struct VsMedianJob { int32_t row0, count, out, pad; };
+
+// the bin ranges of the reliability statistics: the voice band 100 Hz <= f <= 8 kHz (every bin when it holds none, :265-267,
+// :438-442) and the coverage bands low <= f < high (:391-400; last < first: the band holds no bin and is skipped)
+struct VsBandTable { int32_t v0, v1, first[kVsCoverageBands], last[kVsCoverageBands]; };
+// one column median with per-row offsets: over list[first .. first + count) (rows of the smoothed scratch) of
+// S[row][k] - levels[row][which], plus `add` when `with_add`, into row `out`
+struct VsOffsetJob { int32_t first, count, out, which; double add; int32_t with_add, pad; };
+// the block rows [row0, row0 + count) of one stream -> row `out` of the uncertainty, the reliability and the block statistics
+struct VsBlockJob { int32_t row0, count, out, pad; };
+
+inline void vs_make_band_table(const std::vector<double> &freqs, VsBandTable &t) {
+  static const double edges[kVsCoverageBands + 1] = {100.0, 350.0, 1000.0, 2500.0, 4500.0, 8000.0};
+  const int K = (int)freqs.size();
+  t.v0 = 0; t.v1 = -1;
+  for (int k = 0, seen = 0; k < K; ++k)
+    if (freqs[(size_t)k] >= 100.0 && freqs[(size_t)k] <= 8000.0) { if (!seen) { t.v0 = k; seen = 1; } t.v1 = k; }
+  if (t.v1 < t.v0) { t.v0 = 0; t.v1 = K - 1; }
+  for (int b = 0; b < kVsCoverageBands; ++b) {
+    t.first[b] = 0; t.last[b] = -1;
+    for (int k = 0, seen = 0; k < K; ++k)
+      if (freqs[(size_t)k] >= edges[b] && freqs[(size_t)k] < edges[b + 1]) { if (!seen) { t.first[b] = k; seen = 1; } t.last[b] = k; }
+  }
+}
 
 // a fractional-octave pass on the FFT grid: the bands that hold a bin (spectrum.py:917-932 `valid`)
 struct VsSmoothTables {
@@ -165,5 +194,21 @@ hipError_t launch_vs_median(const double *rows, const VsMedianJob *jobs, int32_t
 hipError_t launch_vs_smooth(const double *rows, const int32_t *row_index, int32_t n_rows, int32_t bins, const int32_t *n_bands,
                             const double *centre, const int32_t *first, const int32_t *last, const int32_t *bin_pass,
                             const int32_t *bin_index, const double *freqs, double *out, hipStream_t stream);
+
+// ---- reliability statistics (af_spectrum_stats.hip): the second half of analyze_voice_spectrum, spectrum.py:250-290, 381-495
+// levels[row][kVsLevelFields] of every smoothed row: mean and median over the voice band, and the coverage bands' medians of
+// S - mean (NaN for a band without a bin)
+hipError_t launch_vs_row_levels(const double *smooth, int32_t n_rows, int32_t bins, const VsBandTable &bands, double *levels,
+                                hipStream_t stream);
+// per (job, bin) the median (np.median: the mean of both middles for an even count) over the job's row list
+hipError_t launch_vs_offset_median(const double *smooth, const int32_t *list, const double *levels, const VsOffsetJob *jobs,
+                                   int32_t n_jobs, int32_t bins, double *out, hipStream_t stream);
+// distance[row] = sqrt(mean over the voice band of (S - median level - centres[row_centre[row]])^2); NaN where row_centre < 0
+hipError_t launch_vs_shape_distance(const double *smooth, int32_t n_rows, int32_t bins, const VsBandTable &bands, const double *levels,
+                                    const int32_t *row_centre, const double *centres, double *distance, hipStream_t stream);
+// per job: stats[out][4] = lag-one dot product, left and right squared norms of the blocks minus their column median, effective
+// block count (:411-424); uncertainty[out][bins] (:470-477) and reliability[out][bins] (:478, clipped); +inf and 0 below two blocks
+hipError_t launch_vs_block_stats(const double *block_rows, const VsBlockJob *jobs, int32_t n_jobs, int32_t bins, double *uncertainty,
+                                 double *reliability, double *stats, hipStream_t stream);
 
 }  // namespace af

@@ -40,6 +40,8 @@ _OPERATORS = (
     "compute_voice_spectrum",
     "compute_voice_spectrum_batch",
     "measure_voice_spectra",
+    "analyze_voice_spectrum",
+    "analyze_voice_spectrum_batch",
     "suppress",
     "rnnoise_benchmark",
 )
@@ -53,8 +55,9 @@ NoiseModel = getattr(_core_module, "NoiseModel", None) if _core_module is not No
 StreamResampler = getattr(_core_module, "StreamResampler", None) if _core_module is not None else None
 Mixdown = getattr(_core_module, "Mixdown", None) if _core_module is not None else None
 VoiceSpectrum = getattr(_core_module, "VoiceSpectrum", None) if _core_module is not None else None
+VoiceSpectrumResult = getattr(_core_module, "VoiceSpectrumResult", None) if _core_module is not None else None
 new_noise_suppression_engine = (getattr(_core_module, "new_noise_suppression_engine", _missing_core)
                                 if _core_module is not None else _missing_core)
 
-__all__ = ["CORE_AVAILABLE", "Engine", "NoiseSuppressor", "NoiseModel", "StreamResampler", "Mixdown", "VoiceSpectrum", "new_noise_suppression_engine", *_OPERATORS, "LAYOUT_STREAM_MAJOR", "LAYOUT_TIME_MAJOR", "KERNEL_AUTO",
+__all__ = ["CORE_AVAILABLE", "Engine", "NoiseSuppressor", "NoiseModel", "StreamResampler", "Mixdown", "VoiceSpectrum", "VoiceSpectrumResult", "new_noise_suppression_engine", *_OPERATORS, "LAYOUT_STREAM_MAJOR", "LAYOUT_TIME_MAJOR", "KERNEL_AUTO",
            "KERNEL_LANE_PER_STREAM", "KERNEL_PHASED", "KERNEL_QUAD", "KERNEL_STAGED"]

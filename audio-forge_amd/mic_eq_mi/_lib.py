@@ -87,6 +87,36 @@ class VoiceSpectrumOutputs(C.Structure):
     ]
 
 
+class VoiceSpectrumReliabilityRow(C.Structure):
+    _fields_ = [
+        ("snr_db", C.c_double),
+        ("spectral_tilt_db_per_octave", C.c_double),
+        ("residual_confidence", C.c_double),
+        ("measurement_coverage", C.c_double),
+        ("outlier_rejection_ratio", C.c_double),
+        ("phonetic_coverage", C.c_double),
+        ("effective_measurement_blocks", C.c_double),
+        ("voiced", C.c_int32),
+        ("independent", C.c_int32),
+        ("blocks", C.c_int32),
+        ("inliers", C.c_int32),
+        ("used_closest_windows", C.c_int32),
+        ("reserved", C.c_int32),
+    ]
+
+
+class VoiceSpectrumReliabilityOutputs(C.Structure):
+    _fields_ = [
+        ("rows", C.POINTER(VoiceSpectrumReliabilityRow)),
+        ("median_spectrum_db", C.POINTER(C.c_double)),
+        ("spectral_repeatability", C.POINTER(C.c_double)),
+        ("measurement_uncertainty_db", C.POINTER(C.c_double)),
+        ("spectral_snr_db", C.POINTER(C.c_double)),
+        ("window_distance", C.POINTER(C.c_double)),
+        ("inlier_mask", C.POINTER(C.c_uint8)),
+    ]
+
+
 # every symbol include/audioforge_mi.h declares: name -> (restype, argtypes)
 _vp, _i32, _i64, _d, _f, _sz = C.c_void_p, C.c_int32, C.c_int64, C.c_double, C.c_float, C.c_size_t
 _fp, _dp = C.POINTER(C.c_float), C.POINTER(C.c_double)
@@ -289,6 +319,9 @@ SIGNATURES = {
     "af_voice_spectrum_analyze_device": (C.c_int, [_vp, _vp, _i64, _i32, _i64, _dp, _i64, _vp, _i64, _i64, C.POINTER(VoiceSpectrumOutputs)]),
     "af_voice_spectrum_read_windows": (C.c_int, [_vp, _i32, _dp, _dp, _dp, _i32, C.POINTER(_i32)]),
     "af_voice_spectrum_last_kernel_ms": (C.c_int, [_vp, _dp]),
+    "af_voice_spectrum_set_reliability": (C.c_int, [_vp, _i32]),
+    "af_voice_spectrum_last_reliability_kernel_ms": (C.c_int, [_vp, _dp, _i32]),
+    "af_voice_spectrum_read_reliability": (C.c_int, [_vp, C.POINTER(VoiceSpectrumReliabilityOutputs)]),
     "af_gate_process_host": (C.c_int, [_fp, _fp, _i64, _i32, _i64, _d, _d, _d, _d, _i32, _i32, _fp, C.POINTER(C.c_uint64), _i32]),
     "af_measure_integrated_loudness_device": (C.c_int, [_vp, _i64, _i32, _i64, C.c_uint32, _i32, _dp, C.POINTER(_i32)]),
     "af_measure_integrated_loudness_host": (C.c_int, [_fp, _i64, _i32, _i64, C.c_uint32, _i32, _dp, C.POINTER(_i32)]),

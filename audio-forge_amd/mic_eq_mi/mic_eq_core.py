@@ -10,6 +10,7 @@ engine and (b) folds the per-block rows the kernels emit into the dict statistic
 from __future__ import annotations
 
 import ctypes as C
+import dataclasses
 import time
 from typing import Any, Mapping, Sequence
 
@@ -1652,10 +1653,12 @@ class VoiceSpectrum:
     def frames(self, n_samples: int) -> int:
         return int(self._lib.af_voice_spectrum_frames(self._h, int(n_samples)))
 
-    def analyze(self, audio, vad_probabilities=None, noise_audio=None, keep_windows: bool = False, device_pointers=None) -> dict:
+    def analyze(self, audio, vad_probabilities=None, noise_audio=None, keep_windows: bool = False, device_pointers=None,
+                reliability: bool = False) -> dict:
         """audio [n_streams, n] float32 (host), or with `device_pointers=(d_audio, n, n_streams, stride[, d_noise, n_noise,
         noise_stride])` device memory.  Returns arrays by field: the scalars of af_voice_spectrum_row as [n_streams] arrays,
-        spectra [n_streams, bins] (NaN rows where the reference returns None), frame levels and masks [n_streams, frames]."""
+        spectra [n_streams, bins] (NaN rows where the reference returns None), frame levels and masks [n_streams, frames].
+        `reliability` also computes the second half of analyze_voice_spectrum (spectrum.py:647-742) for reliability()."""
         dp, fp = C.POINTER(C.c_double), C.POINTER(C.c_float)
         vad = None if vad_probabilities is None else np.ascontiguousarray(vad_probabilities, dtype=np.float64)
         if device_pointers is None:
@@ -1673,6 +1676,8 @@ class VoiceSpectrum:
         if n < self.nperseg:
             raise ValueError(f"Audio too short for FFT: need {self.nperseg} samples, got {n} ({n / self.sample_rate:.2f} seconds)")
         F, K = self.frames(n), self.bins
+        _lib.check(self._lib.af_voice_spectrum_set_reliability(self._h, int(bool(reliability))))
+        self._last_shape = (B, F)
         rows = (_lib.VoiceSpectrumRow * B)()
         out = {name: np.empty((B, K)) for name in ("speech_db", "noise_db", "spectral_snr_db", "welch_db", "welch_sum")}
         out.update(frame_power=np.empty((B, F)), frame_rms_db=np.empty((B, F)), voiced_mask=np.empty((B, F), dtype=np.uint8))
@@ -1693,6 +1698,33 @@ class VoiceSpectrum:
         for name, _ in _lib.VoiceSpectrumRow._fields_:
             out[name] = np.array([getattr(r, name) for r in rows])
         return out
+
+    def reliability(self) -> dict:
+        """The reliability statistics of the last analyze(reliability=True): the scalars of af_voice_spectrum_reliability_row
+        as [n_streams] arrays, median_spectrum_db, spectral_repeatability, measurement_uncertainty_db and spectral_snr_db
+        [n_streams, bins] (NaN rows where the reference returns None), window_distance [n_streams, frames] (NaN off the voiced
+        frames) and inlier_mask [n_streams, frames]."""
+        B, F = getattr(self, "_last_shape", (0, 0))
+        dp, K = C.POINTER(C.c_double), self.bins
+        rows = (_lib.VoiceSpectrumReliabilityRow * max(B, 1))()
+        out = {name: np.empty((B, K)) for name in ("median_spectrum_db", "spectral_repeatability", "measurement_uncertainty_db",
+                                                    "spectral_snr_db")}
+        out.update(window_distance=np.empty((B, F)), inlier_mask=np.empty((B, F), dtype=np.uint8))
+        o = _lib.VoiceSpectrumReliabilityOutputs(rows=rows, inlier_mask=out["inlier_mask"].ctypes.data_as(C.POINTER(C.c_uint8)),
+                                                 **{k: v.ctypes.data_as(dp) for k, v in out.items() if k != "inlier_mask"})
+        _lib.check(self._lib.af_voice_spectrum_read_reliability(self._h, C.byref(o)))
+        for name, _ in _lib.VoiceSpectrumReliabilityRow._fields_:
+            if name != "reserved":
+                out[name] = np.array([getattr(r, name) for r in rows[:B]])
+        return out
+
+    RELIABILITY_KERNELS = ("row_levels", "block_and_centre_medians", "shape_distances", "block_statistics", "robust_median")
+
+    def last_reliability_kernel_ms(self) -> dict:
+        """GPU ms of each reliability kernel in the last call, summed over its tiles (zeros with the option off)."""
+        ms = (C.c_double * 5)()
+        _lib.check(self._lib.af_voice_spectrum_last_reliability_kernel_ms(self._h, ms, 5))
+        return dict(zip(self.RELIABILITY_KERNELS, (float(v) for v in ms)))
 
     def windows(self, stream: int) -> tuple[np.ndarray, np.ndarray, np.ndarray]:
         """(raw dB, smoothed dB, linear PSD), each [voiced frames, bins], of one stream of the last analyze(keep_windows=True)."""
@@ -1763,9 +1795,9 @@ def measure_voice_spectra(audio, fs: int = 48_000, nperseg: int = 4096, vad_prob
                           return_windows: bool = False, device: int = 0) -> list[dict[str, Any]]:
     """analyze_voice_spectrum (spectrum.py:498-645) of every row of audio [n_streams, n], one dict per stream under the field
     names of VoiceSpectrumResult.  A stream that takes the single-spectrum fallback (:605-645) carries the complete result;
-    the others carry what precedes the robust median (the reliability statistics behind it are not built): the speech and
-    noise references, the per-bin SNR of :603, the frame levels and mask, and with `return_windows` the voiced frames' raw
-    and perceptually smoothed spectra."""
+    the others carry what precedes the robust median (analyze_voice_spectrum_batch returns the complete result for every
+    stream): the speech and noise references, the per-bin SNR of :603, the frame levels and mask, and with `return_windows`
+    the voiced frames' raw and perceptually smoothed spectra."""
     vs = VoiceSpectrum(fs, nperseg, device)
     try:
         r = vs.analyze(audio, vad_probabilities, noise_audio, keep_windows=return_windows)
@@ -1804,3 +1836,80 @@ def measure_voice_spectra(audio, fs: int = 48_000, nperseg: int = 4096, vad_prob
         return results
     finally:
         vs.close()
+
+
+@dataclasses.dataclass(frozen=True)
+class VoiceSpectrumResult:
+    """spectrum.py:33-55, field for field."""
+
+    freqs: np.ndarray
+    median_spectrum_db: np.ndarray
+    window_spectra_db: np.ndarray
+    voiced_window_ratio: float
+    snr_db: float
+    spectral_repeatability: np.ndarray
+    spectral_tilt_db_per_octave: float
+    residual_confidence: float
+    used_single_spectrum_fallback: bool
+    measurement_coverage: float = 1.0
+    outlier_rejection_ratio: float = 0.0
+    vad_probability_used: bool = False
+    vad_active_window_ratio: float = 0.0
+    spectral_snr_db: np.ndarray | None = None
+    noise_spectrum_db: np.ndarray | None = None
+    noise_reference_source: str = "unavailable"
+    measurement_uncertainty_db: np.ndarray | None = None
+    phonetic_coverage: float = 0.0
+    effective_measurement_blocks: float = 0.0
+
+
+def analyze_voice_spectrum_batch(audio, fs: int = 48_000, nperseg: int = 4096, *, vad_probabilities=None, noise_audio=None,
+                                 device: int = 0) -> list[VoiceSpectrumResult]:
+    """analyze_voice_spectrum (spectrum.py:498-742) of every row of audio [n_streams, n]: both of its returns, the robust median
+    and the reliability statistics computed on the device.  window_spectra_db holds the raw voiced windows on the main branch."""
+    a = np.asarray(audio)
+    if a.ndim != 2:
+        raise ValueError("audio must be [n_streams, n]")
+    if a.shape[1] < nperseg:
+        raise ValueError(f"Audio too short for FFT: need {nperseg} samples, got {a.shape[1]} ({a.shape[1] / fs:.2f} seconds)")
+    vs = VoiceSpectrum(fs, nperseg, device)
+    try:
+        r = vs.analyze(a, vad_probabilities, noise_audio, keep_windows=True, reliability=True)
+        q = vs.reliability()
+        results = []
+        for s in range(a.shape[0]):
+            have_noise = not np.isnan(r["noise_db"][s, 0])
+            fallback = bool(r["used_single_spectrum_fallback"][s])
+            median = q["median_spectrum_db"][s]
+            results.append(VoiceSpectrumResult(
+                freqs=vs.freqs, median_spectrum_db=median,
+                window_spectra_db=np.asarray([median]) if fallback else vs.windows(s)[0],
+                voiced_window_ratio=float(r["voiced_window_ratio"][s]), snr_db=float(q["snr_db"][s]),
+                spectral_repeatability=q["spectral_repeatability"][s],
+                spectral_tilt_db_per_octave=float(q["spectral_tilt_db_per_octave"][s]),
+                residual_confidence=float(q["residual_confidence"][s]), used_single_spectrum_fallback=fallback,
+                measurement_coverage=float(q["measurement_coverage"][s]),
+                outlier_rejection_ratio=float(q["outlier_rejection_ratio"][s]),
+                vad_probability_used=bool(r["vad_probability_used"][s]),
+                vad_active_window_ratio=float(r["vad_active_window_ratio"][s]),
+                spectral_snr_db=q["spectral_snr_db"][s] if have_noise else None,
+                noise_spectrum_db=r["noise_db"][s] if have_noise else None,
+                noise_reference_source=NOISE_REFERENCE_SOURCES[int(r["noise_reference_source"][s])],
+                measurement_uncertainty_db=q["measurement_uncertainty_db"][s],
+                phonetic_coverage=float(q["phonetic_coverage"][s]),
+                effective_measurement_blocks=float(q["effective_measurement_blocks"][s])))
+        return results
+    finally:
+        vs.close()
+
+
+def analyze_voice_spectrum(audio, fs=48000, nperseg=4096, *, vad_probabilities=None, noise_audio=None,
+                           noise_spectrum_override=None, noise_reference_source_override=None) -> VoiceSpectrumResult:
+    """Drop-in for spectrum.py:498-742 (samples are taken as float32).  The noise-spectrum override is not built."""
+    if noise_spectrum_override is not None or noise_reference_source_override is not None:
+        raise NotImplementedError("noise_spectrum_override / noise_reference_source_override are not built")
+    if len(audio) < nperseg:
+        raise ValueError(f"Audio too short for FFT: need {nperseg} samples, got {len(audio)} ({len(audio) / fs:.2f} seconds)")
+    row = lambda x: None if x is None else np.asarray(x).reshape(1, -1)  # noqa: E731
+    return analyze_voice_spectrum_batch(np.asarray(audio, dtype=np.float32).reshape(1, -1), fs, nperseg,
+                                        vad_probabilities=row(vad_probabilities), noise_audio=row(noise_audio))[0]

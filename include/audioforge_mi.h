@@ -714,6 +714,43 @@ int af_voice_spectrum_read_windows(af_voice_spectrum *h, int32_t stream, double 
                                    int32_t max_frames, int32_t *n_frames);
 /* GPU time of the kernels of the last call (events around them; copies and host decisions are not in it) */
 int af_voice_spectrum_last_kernel_ms(af_voice_spectrum *h, double *ms);
+/* The second half of analyze_voice_spectrum, spectrum.py:647-742 with _robust_median_spectrum (:250-290) and
+ * _measurement_reliability (:381-495): opt-in and off by default; with it off no call changes by a bit.  With it on, an
+ * analyze call also smooths the voiced windows of every stream that does not take the fallback (keep_windows or not; the
+ * rows stay on the device) and keeps the results below for af_voice_spectrum_read_reliability. */
+int af_voice_spectrum_set_reliability(af_voice_spectrum *h, int32_t enabled);
+/* one stream's scalars of the main branch's return, :722-742; on the fallback branch the constants of :620-644 */
+typedef struct af_voice_spectrum_reliability_row {
+  double snr_db;                        /* _estimate_snr_from_spectrum of the robust median, :673 (:626 of Welch on the fallback) */
+  double spectral_tilt_db_per_octave;   /* _estimate_tilt_db_per_octave, :729 (:632) */
+  double residual_confidence;           /* :701-721 (0, :633) */
+  double measurement_coverage;          /* :692-700 (0.45, :635) */
+  double outlier_rejection_ratio;       /* 1 - inlier ratio, :733 (0, :636) */
+  double phonetic_coverage;             /* :480-488, :740 (0, :643) */
+  double effective_measurement_blocks;  /* _effective_block_count, :411-424, :741 (0, :644) */
+  int32_t voiced;                       /* windows the statistics saw (0 on the fallback) */
+  int32_t independent;                  /* non-overlapping windows kept by :446-454 */
+  int32_t blocks;                       /* block rows of :456-463 */
+  int32_t inliers;                      /* windows behind the robust median, :279-285 */
+  int32_t used_closest_windows;         /* the argsort branch of :281-285 was taken */
+  int32_t reserved;
+} af_voice_spectrum_reliability_row;
+/* Where af_voice_spectrum_read_reliability writes; host memory, every pointer may be null.  Spectra are [n_streams][bins]. */
+typedef struct af_voice_spectrum_reliability_outputs {
+  af_voice_spectrum_reliability_row *rows;  /* [n_streams] */
+  double *median_spectrum_db;          /* _robust_median_spectrum, :669, :724 (the Welch spectrum on the fallback, :623) */
+  double *spectral_repeatability;      /* :478, :490, :728 (zeros, :620) */
+  double *measurement_uncertainty_db;  /* :475-477, :739; +inf below two blocks (:467) and on the fallback (:642) */
+  double *spectral_snr_db;             /* _spectral_snr_db of the robust median, :672 (:616 on the fallback); NaN row where None */
+  double *window_distance;             /* [n_streams][frames] the shape distances of :275 at the voiced frames, NaN elsewhere */
+  uint8_t *inlier_mask;                /* [n_streams][frames] 1 at the voiced frames :279-285 kept */
+} af_voice_spectrum_reliability_outputs;
+/* The reliability results of the last analyze call.  AF_ERR_STATE when that call ran with the option off or no call was made. */
+int af_voice_spectrum_read_reliability(af_voice_spectrum *h, const af_voice_spectrum_reliability_outputs *out);
+/* GPU time of the reliability kernels of the last call, summed over its tiles (they are part of
+ * af_voice_spectrum_last_kernel_ms): ms[0 .. 5) = row levels, block and centre medians, shape distances, block statistics,
+ * robust median.  Zeros when the option was off.  capacity: the doubles ms holds, at least 5. */
+int af_voice_spectrum_last_reliability_kernel_ms(af_voice_spectrum *h, double *ms, int32_t capacity);
 
 /* ---- NoiseSuppressor: rust-core/src/dsp/noise_suppressor.rs:18-194 ----------------------------------------
  * The runtime-selected suppressor interface (`NoiseModel`, trait `NoiseSuppressor`, `new_noise_suppression_engine`) for a
