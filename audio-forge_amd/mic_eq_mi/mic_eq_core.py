@@ -254,6 +254,21 @@ class Engine:
             _lib.check(self._lib.af_suppressor_read_trace(self._h, out.ctypes.data_as(C.POINTER(C.c_int32)), frames))
         return out
 
+    def suppressor_debug_read(self, frame: int, stream: int) -> dict:
+        """The suppressor's test tap for one (frame, stream) cell of the LAST window of the last call (cells of earlier
+        windows, and frames beyond that window's, are stale): Ex Ep Exp [22], feat [44] (42 features + the two pad words the
+        network's K padding reads), gains_raw gains [22], silence, pitch_index, and the spectra X P [481] complex64."""
+        rec = np.zeros(160, dtype=np.float32)  # af::SuppFrameRec
+        X = np.zeros(481, dtype=np.complex64)
+        P = np.zeros(481, dtype=np.complex64)
+        fp = C.POINTER(C.c_float)
+        _lib.check(self._lib.af_suppressor_debug_read(self._h, int(frame), int(stream), rec.ctypes.data_as(fp),
+                                                      X.ctypes.data_as(fp), P.ctypes.data_as(fp)))
+        silence, pitch = (int(v) for v in rec[154:156].view(np.int32))
+        return {"Ex": rec[0:22].copy(), "Ep": rec[22:44].copy(), "Exp": rec[44:66].copy(), "feat": rec[66:110].copy(),
+                "gains_raw": rec[110:132].copy(), "gains": rec[132:154].copy(), "silence": silence, "pitch_index": pitch,
+                "X": X, "P": P}
+
     def process_device(self, in_ptr: int, out_ptr: int, n_samples: int, stream_stride: int,
                        layout: int = _lib.LAYOUT_STREAM_MAJOR, hip_stream: int = 0) -> None:
         """Device pointers (e.g. ``tensor.data_ptr()``); asynchronous on ``hip_stream``."""

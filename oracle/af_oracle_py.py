@@ -443,6 +443,90 @@ def suppressor_pitch_filter_margins(audio, strength: float = 1.0, weight_seed: i
     return margin
 
 
+class RnnDebug(C.Structure):
+    """afo_rnn_debug (af_rnnoise.h): the restatement's tap of the last processed frame.  The one definition of that struct
+    on the Python side."""
+    _fields_ = [("Ex", C.c_float * 22), ("Ep", C.c_float * 22), ("Exp", C.c_float * 22), ("features", C.c_float * 42),
+                ("gains", C.c_float * 22), ("X", C.c_float * 962), ("P", C.c_float * 962), ("pitch_index", C.c_int),
+                ("silence", C.c_int), ("pitch_gain", C.c_float), ("pf_margin", C.c_float), ("gains_raw", C.c_float * 22)]
+
+
+RNN_WEIGHT_BYTES = 87_503  # the fifteen int8 arrays of afo_rnn_weights, no padding between them
+
+
+def rnn_synthetic_weights(seed: int = 0x5EED) -> bytes:
+    """afo_rnn_weights_synthetic as the int8 blob af_suppressor_load_weights takes."""
+    L = lib()
+    L.afo_rnn_weights_synthetic.argtypes = [C.c_void_p, C.c_uint64]
+    w = C.create_string_buffer(RNN_WEIGHT_BYTES)
+    L.afo_rnn_weights_synthetic(w, C.c_uint64(seed))
+    return w.raw
+
+
+class RnnoiseTap:
+    """The restatement frame by frame with its per-frame tap, state kept across `run` calls.
+
+    `weights`: a seed (synthetic weights) or an int8 blob of RNN_WEIGHT_BYTES.  `strength` None: the raw protocol of
+    bin/rnnoise_benchmark.rs (clamp(+-1) x 32768 in, / 32768 out, no mix); a number: RNNoiseProcessor's wrapper
+    (soft clip, smoothed wet/dry mix).  `eval_order` as set_rnn_eval_order."""
+
+    def __init__(self, weights=0x5EED, strength: float | None = None, eval_order: int = 0):
+        L = lib()
+        fp = C.POINTER(C.c_float)
+        L.afo_rnn_state_init.argtypes = [C.c_void_p]
+        L.afo_rnn_process_frame.restype = C.c_float
+        L.afo_rnn_process_frame.argtypes = [C.c_void_p, C.c_void_p, fp, fp]
+        L.afo_suppressor_process_frame.argtypes = [C.c_void_p, fp, fp]
+        L.afo_rnn_debug_last.restype = C.POINTER(RnnDebug)
+        L.afo_rnn_debug_last.argtypes = []
+        blob = rnn_synthetic_weights(weights) if isinstance(weights, int) else bytes(weights)
+        if len(blob) != RNN_WEIGHT_BYTES:
+            raise ValueError(f"weight blob must be {RNN_WEIGHT_BYTES} bytes")
+        self._L, self.raw, self.eval_order = L, strength is None, int(eval_order)
+        if self.raw:
+            self._w = C.create_string_buffer(blob, RNN_WEIGHT_BYTES)
+            self._st = C.create_string_buffer(1 << 15)  # afo_rnn_state is ~12 KB
+            L.afo_rnn_state_init(self._st)
+        else:
+            self._s = C.create_string_buffer(1 << 18)
+            L.afo_suppressor_init(self._s, float(strength), C.c_uint64(0))
+            C.memmove(self._s, blob, RNN_WEIGHT_BYTES)  # afo_suppressor starts with its afo_rnn_weights
+
+    def run(self, audio) -> dict:
+        """Whole frames of `audio` (+-1 full scale).  Returns arrays with a leading frame axis: Ex Ep Exp [22], features [42],
+        gains_raw gains [22], X P [481] complex64, silence pitch_index (int32), out [480] (+-1 full scale)."""
+        x = np.ascontiguousarray(audio, dtype=np.float32)
+        frames = x.size // 480
+        keys = ("Ex", "Ep", "Exp", "features", "gains_raw", "gains")
+        res = {k: np.zeros((frames, 42 if k == "features" else 22), dtype=np.float32) for k in keys}
+        res.update(X=np.zeros((frames, 481), dtype=np.complex64), P=np.zeros((frames, 481), dtype=np.complex64),
+                   silence=np.zeros(frames, dtype=np.int32), pitch_index=np.zeros(frames, dtype=np.int32),
+                   out=np.zeros((frames, 480), dtype=np.float32))
+        L = self._L
+        fout = np.zeros(480, dtype=np.float32)
+        set_rnn_eval_order(self.eval_order)
+        try:
+            for f in range(frames):
+                fin = x[f * 480:(f + 1) * 480]
+                if self.raw:
+                    fin = (np.clip(fin, -1.0, 1.0) * np.float32(32768.0)).astype(np.float32)
+                    L.afo_rnn_process_frame(self._w, self._st, _fptr(fout), _fptr(fin))
+                    res["out"][f] = fout / np.float32(32768.0)
+                else:
+                    fin = np.ascontiguousarray(fin)
+                    L.afo_suppressor_process_frame(self._s, _fptr(fout), _fptr(fin))
+                    res["out"][f] = fout
+                d = L.afo_rnn_debug_last().contents
+                for k in keys:
+                    res[k][f] = np.ctypeslib.as_array(getattr(d, k))
+                res["X"][f] = np.ctypeslib.as_array(d.X).view(np.complex64)
+                res["P"][f] = np.ctypeslib.as_array(d.P).view(np.complex64)
+                res["silence"][f], res["pitch_index"][f] = d.silence, d.pitch_index
+        finally:
+            set_rnn_eval_order(0)
+        return res
+
+
 def scale_sample_for_model(sample: float) -> float:
     """RNNoiseProcessor::scale_sample_for_model (rnnoise.rs:89-111)."""
     L = lib()

@@ -655,6 +655,7 @@ static void compute_rnn(const afo_rnn_weights *w, afo_rnn_state *st, float *gain
 
 /* debug tap of the last processed frame (tests compare GPU intermediates against it) */
 __thread afo_rnn_debug afo_rnn_last; /* per thread: the all-cores baseline leg runs one stream per thread */
+const afo_rnn_debug *afo_rnn_debug_last(void) { return &afo_rnn_last; }
 
 /* --------------------------------------------------------- DenoiseState */
 void afo_rnn_state_init(afo_rnn_state *st) {
@@ -700,6 +701,8 @@ float afo_rnn_process_frame(const afo_rnn_weights *w, afo_rnn_state *st, float *
   cpx X[FREQ], P[FREQ];
   float Ex[NB], Ep[NB], Exp[NB], features[NFEAT], g[NB], gf[FREQ], Ly[NB], tmp[NB];
   float vad_prob = 0;
+  memset(g, 0, sizeof g); /* a silent frame has no gains: the tap reads zeros */
+  memset(afo_rnn_last.gains_raw, 0, sizeof afo_rnn_last.gains_raw);
   biquad_hp(x, st->mem_hp_x, in, FRAME);
   /* frame_analysis */
   memcpy(buf, st->analysis_mem, sizeof(float) * FRAME);
@@ -777,6 +780,7 @@ float afo_rnn_process_frame(const afo_rnn_weights *w, afo_rnn_state *st, float *
   }
   if (!silence) {
     compute_rnn(w, st, g, &vad_prob, features);
+    memcpy(afo_rnn_last.gains_raw, g, sizeof g);
     afo_rnn_last.pf_margin = 1e30f;
     for (int i = 0; i < NB; ++i) afo_rnn_last.pf_margin = fminf(afo_rnn_last.pf_margin, fabsf(Exp[i] - g[i]));
     pitch_filter(X, P, Ex, Ep, Exp, g);

@@ -41,8 +41,10 @@ typedef struct {
   int pitch_index, silence;
   float pitch_gain;
   float pf_margin; /* min over bands of |Exp - g| where pitch_filter branches (Exp > g); 1e30 on a silent frame */
+  float gains_raw[22]; /* the network's output, before g = max(g, 0.6 lastg); `gains` is after it.  Both 0 on a silent frame */
 } afo_rnn_debug;
 extern __thread afo_rnn_debug afo_rnn_last;
+const afo_rnn_debug *afo_rnn_debug_last(void); /* the calling thread's tap */
 
 void afo_rnn_weights_synthetic(afo_rnn_weights *w, uint64_t seed);
 void afo_rnn_state_init(afo_rnn_state *st);
