@@ -48,6 +48,10 @@ struct af_voice_spectrum {
   std::vector<af_voice_spectrum_reliability_row> rel_rows;
   std::vector<double> rel_median, rel_repeat, rel_uncertainty, rel_snr, rel_distance;
   std::vector<uint8_t> rel_inlier;
+  // the noise-spectrum override (af_voice_spectrum_set_noise_override): a copy of the caller's arrays, none when ov_points is 0
+  int32_t ov_points = 0, ov_streams = 0;
+  bool ov_shared = false;
+  std::vector<double> ov_freqs, ov_db;  // [ov_points] | [ov_shared ? 1 : ov_streams][ov_points]
   ~af_voice_spectrum() {
     if (touched_device) { (void)hipSetDevice(device); (void)hipDeviceSynchronize(); }
   }
@@ -84,6 +88,27 @@ double vs_interp(double x, const std::vector<double> &xp, const std::vector<doub
   return slope * (x - xp[(size_t)lo]) + fp[(size_t)lo];
 }
 
+double vs_interp(double x, const double *xp, const double *fp, int n) {  // the same over plain arrays
+  if (x < xp[0]) return fp[0];
+  if (x >= xp[n - 1]) return fp[n - 1];
+  int lo = 0, hi = n - 1;
+  while (hi - lo > 1) {
+    const int mid = (lo + hi) / 2;
+    if (x >= xp[mid]) lo = mid; else hi = mid;
+  }
+  const double slope = (fp[lo + 1] - fp[lo]) / (xp[lo + 1] - xp[lo]);
+  return slope * (x - xp[lo]) + fp[lo];
+}
+
+// the override of one stream when it passes spectrum.py:557-563 (at least two points, all finite), else null
+const double *vs_valid_override(const af_voice_spectrum *h, int stream) {
+  if (h->ov_points < 2) return nullptr;
+  const double *db = h->ov_db.data() + (h->ov_shared ? 0 : (size_t)stream * h->ov_points);
+  for (int i = 0; i < h->ov_points; ++i)
+    if (!std::isfinite(h->ov_freqs[(size_t)i]) || !std::isfinite(db[i])) return nullptr;
+  return db;
+}
+
 // what the host decides for one stream from its frame levels
 struct VsDecision {
   std::vector<double> rms;
@@ -95,7 +120,7 @@ struct VsDecision {
 };
 
 void vs_decide(const double *sums /* [C][2] */, int F, int N, uint32_t fs, const double *vad, int64_t n_vad, bool explicit_noise,
-               VsDecision &d) {
+               bool override_noise, VsDecision &d) {
   const int hop = N / 2, C = F + 1;
   d.rms.resize((size_t)F);
   d.mask.assign((size_t)F, 0);
@@ -141,7 +166,9 @@ void vs_decide(const double *sums /* [C][2] */, int F, int N, uint32_t fs, const
 
   // the noise reference, :570-586
   d.source = af::kVsNoiseUnavailable;
-  if (explicit_noise) {
+  if (override_noise) {  // :554-569: a valid override goes first
+    d.source = af::kVsNoiseOverride;
+  } else if (explicit_noise) {
     d.source = af::kVsNoiseExplicit;
   } else if (F - d.voiced >= af::kVsMinVoicedFrames && d.voiced > 0) {
     std::vector<double> lv, lu;
@@ -254,6 +281,8 @@ int vs_check(af_voice_spectrum *h, const float *audio, int64_t n_samples, int32_
   if (!vad && n_vad > 0) return fail(AF_ERR_INVALID_ARGUMENT, "n_vad without vad_probabilities");
   if (noise && (n_noise < 0 || noise_stride < n_noise)) return fail(AF_ERR_INVALID_ARGUMENT, "noise_stride must cover n_noise >= 0");
   if (!noise && n_noise > 0) return fail(AF_ERR_INVALID_ARGUMENT, "n_noise without noise_audio");
+  if (h->ov_points > 0 && !h->ov_shared && h->ov_streams != n_streams)
+    return fail(AF_ERR_INVALID_ARGUMENT, "the noise override was set for %d streams, the call has %d", h->ov_streams, n_streams);
   return AF_OK;
 }
 
@@ -498,7 +527,8 @@ int vs_analyze(af_voice_spectrum *h, const float *d_audio, int64_t n, int32_t B,
   std::vector<VsDecision> dec((size_t)B);
   std::vector<int32_t> chunks, offset((size_t)B + 1, 0);
   for (int s = 0; s < B; ++s) {
-    vs_decide(&sums[(size_t)s * C * 2], F, N, h->sample_rate, vad ? vad + (int64_t)s * n_vad : nullptr, n_vad, explicit_noise, dec[(size_t)s]);
+    vs_decide(&sums[(size_t)s * C * 2], F, N, h->sample_rate, vad ? vad + (int64_t)s * n_vad : nullptr, n_vad, explicit_noise,
+              vs_valid_override(h, s) != nullptr, dec[(size_t)s]);
     chunks.insert(chunks.end(), dec[(size_t)s].chunks.begin(), dec[(size_t)s].chunks.end());
     offset[(size_t)s + 1] = (int32_t)chunks.size();
   }
@@ -611,6 +641,12 @@ int vs_analyze(af_voice_spectrum *h, const float *d_audio, int64_t n, int32_t B,
           AF_HIP(hipMemcpy(&h->win_linear[at], h->d_rows_linear + from, row_bytes * cnt, hipMemcpyDeviceToHost));
         }
       }
+    }
+    for (int s = t0; s < t1; ++s) {  // :596-602: the override on this grid, ends held
+      const double *ov = dec[(size_t)s].source == af::kVsNoiseOverride && dec[(size_t)s].voiced > 0 ? vs_valid_override(h, s) : nullptr;
+      if (!ov) continue;
+      double *noise = &medians[(size_t)(s - t0) * 2 * K + K];
+      for (int k = 0; k < K; ++k) noise[k] = vs_interp(h->smooth.freqs[(size_t)k], h->ov_freqs.data(), ov, h->ov_points);
     }
     for (int s = t0; s < t1; ++s) {
       const VsDecision &d = dec[(size_t)s];
@@ -754,6 +790,28 @@ int af_voice_spectrum_read_windows(af_voice_spectrum *h, int32_t stream, double 
 int af_voice_spectrum_set_reliability(af_voice_spectrum *h, int32_t enabled) {
   if (!h) return fail(AF_ERR_INVALID_ARGUMENT, "voice spectrum handle is null");
   h->reliability = enabled != 0;
+  return AF_OK;
+}
+
+int af_voice_spectrum_set_noise_override(af_voice_spectrum *h, const double *freqs, const double *spectrum_db, int32_t n_points,
+                                         int32_t n_streams, int64_t stride, int32_t shared) {
+  if (!h) return fail(AF_ERR_INVALID_ARGUMENT, "voice spectrum handle is null");
+  if (!spectrum_db) {  // clear
+    h->ov_points = h->ov_streams = 0;
+    h->ov_freqs.clear();
+    h->ov_db.clear();
+    return AF_OK;
+  }
+  if (!freqs) return fail(AF_ERR_INVALID_ARGUMENT, "freqs is null");
+  if (n_points < 1) return fail(AF_ERR_INVALID_ARGUMENT, "n_points must be positive");
+  if (!shared && (n_streams < 1 || stride < n_points)) return fail(AF_ERR_INVALID_ARGUMENT, "stride must cover n_points for n_streams >= 1");
+  const int rows = shared ? 1 : n_streams;
+  h->ov_freqs.assign(freqs, freqs + n_points);
+  h->ov_db.resize((size_t)rows * n_points);
+  for (int r = 0; r < rows; ++r) std::copy(spectrum_db + (int64_t)r * stride, spectrum_db + (int64_t)r * stride + n_points, &h->ov_db[(size_t)r * n_points]);
+  h->ov_points = n_points;
+  h->ov_streams = rows;
+  h->ov_shared = shared != 0;
   return AF_OK;
 }
 

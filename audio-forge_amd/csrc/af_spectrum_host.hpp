@@ -34,7 +34,7 @@ constexpr double kVsCoverageTargetBlocks = 12.0;  // PHONETIC_COVERAGE_TARGET_BL
 constexpr int kVsCoverageBands = 5;          // _coarse_phonetic_coverage's bands, :391-397
 constexpr int kVsLevelFields = 2 + kVsCoverageBands;  // per smoothed window: voice-band mean | median | the band medians of S - mean
 
-enum VsNoiseSource : int { kVsNoiseUnavailable = 0, kVsNoiseExplicit = 1, kVsNoiseInCapture = 2 };
+enum VsNoiseSource : int { kVsNoiseUnavailable = 0, kVsNoiseExplicit = 1, kVsNoiseInCapture = 2, kVsNoiseOverride = 3 };
 
 // one window spectrum: the frame of `source` (0 the capture, 1 the noise capture) that starts at chunk `chunk`
 struct VsWindowItem { int32_t source, stream, chunk, row; };

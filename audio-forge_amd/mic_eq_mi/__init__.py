@@ -42,6 +42,9 @@ _OPERATORS = (
     "measure_voice_spectra",
     "analyze_voice_spectrum",
     "analyze_voice_spectrum_batch",
+    "analyze_voice_capture_batch",
+    "analyze_noise_reference",
+    "analyze_noise_reference_batch",
     "suppress",
     "rnnoise_benchmark",
 )
@@ -56,8 +59,12 @@ StreamResampler = getattr(_core_module, "StreamResampler", None) if _core_module
 Mixdown = getattr(_core_module, "Mixdown", None) if _core_module is not None else None
 VoiceSpectrum = getattr(_core_module, "VoiceSpectrum", None) if _core_module is not None else None
 VoiceSpectrumResult = getattr(_core_module, "VoiceSpectrumResult", None) if _core_module is not None else None
+NoiseReference = getattr(_core_module, "NoiseReference", None) if _core_module is not None else None
+NoiseReferenceAnalysis = getattr(_core_module, "NoiseReferenceAnalysis", None) if _core_module is not None else None
+CaptureMetadata = getattr(_core_module, "CaptureMetadata", None) if _core_module is not None else None
 new_noise_suppression_engine = (getattr(_core_module, "new_noise_suppression_engine", _missing_core)
                                 if _core_module is not None else _missing_core)
 
-__all__ = ["CORE_AVAILABLE", "Engine", "NoiseSuppressor", "NoiseModel", "StreamResampler", "Mixdown", "VoiceSpectrum", "VoiceSpectrumResult", "new_noise_suppression_engine", *_OPERATORS, "LAYOUT_STREAM_MAJOR", "LAYOUT_TIME_MAJOR", "KERNEL_AUTO",
+__all__ = ["CORE_AVAILABLE", "Engine", "NoiseSuppressor", "NoiseModel", "StreamResampler", "Mixdown", "VoiceSpectrum", "VoiceSpectrumResult", "NoiseReference", "NoiseReferenceAnalysis", "CaptureMetadata",
+           "new_noise_suppression_engine", *_OPERATORS, "LAYOUT_STREAM_MAJOR", "LAYOUT_TIME_MAJOR", "KERNEL_AUTO",
            "KERNEL_LANE_PER_STREAM", "KERNEL_PHASED", "KERNEL_QUAD", "KERNEL_STAGED"]

@@ -117,6 +117,25 @@ class VoiceSpectrumReliabilityOutputs(C.Structure):
     ]
 
 
+class NoiseReferenceRow(C.Structure):
+    _fields_ = ([("status", C.c_int32), ("conservative", C.c_int32), ("reasons", C.c_uint32), ("guidance", C.c_uint32)]
+                + [(name, C.c_double) for name in (
+                    "quality_score", "duration_s", "finite_fraction", "noise_rms_db", "conservative_noise_rms_db", "noise_peak_db",
+                    "crest_factor_db", "clipped_fraction", "zero_fraction", "rms_spread_db", "octave_stability_db",
+                    "spectral_flux_db", "vad_contamination_ratio", "vad_contamination_p90", "capture_age_s",
+                    "in_capture_level_delta_db", "spectral_shape_distance_db", "noise_sum_squares", "noise_peak")]
+                + [(name, C.c_int64) for name in ("finite_samples", "clipped_samples", "zero_samples")]
+                + [(name, C.c_int32) for name in ("in_capture_noise_frame_count", "noise_frames", "speech_frames", "n_bands",
+                                                  "has_in_capture_spectrum", "reserved")])
+
+
+class NoiseReferenceOutputs(C.Structure):
+    _fields_ = [("rows", C.POINTER(NoiseReferenceRow))] + [(name, C.POINTER(C.c_double)) for name in (
+        "explicit_spectrum_db", "conservative_spectrum_db", "in_capture_spectrum_db", "frame_rms_db", "band_levels_db",
+        "noise_chunk_sums", "noise_frame_power", "speech_frame_power", "noise_psd", "band_power", "explicit_middles",
+        "in_capture_middles")]
+
+
 # every symbol include/audioforge_mi.h declares: name -> (restype, argtypes)
 _vp, _i32, _i64, _d, _f, _sz = C.c_void_p, C.c_int32, C.c_int64, C.c_double, C.c_float, C.c_size_t
 _fp, _dp = C.POINTER(C.c_float), C.POINTER(C.c_double)
@@ -322,6 +341,17 @@ SIGNATURES = {
     "af_voice_spectrum_set_reliability": (C.c_int, [_vp, _i32]),
     "af_voice_spectrum_last_reliability_kernel_ms": (C.c_int, [_vp, _dp, _i32]),
     "af_voice_spectrum_read_reliability": (C.c_int, [_vp, C.POINTER(VoiceSpectrumReliabilityOutputs)]),
+    "af_voice_spectrum_set_noise_override": (C.c_int, [_vp, _dp, _dp, _i32, _i32, _i64, _i32]),
+    "af_noise_reference_create": (C.c_int, [C.c_uint32, _i32, C.POINTER(_vp)]),
+    "af_noise_reference_destroy": (None, [_vp]),
+    "af_noise_reference_frame_size": (_i32, [_vp]),
+    "af_noise_reference_bins": (_i32, [_vp, _i64]),
+    "af_noise_reference_frames": (_i64, [_vp, _i64]),
+    "af_noise_reference_analyze_host": (C.c_int, [_vp, _fp, _i64, _i32, _i64, _fp, _i64, _i64, _dp, _i64, _dp, _i64, _dp,
+                                                  C.POINTER(C.c_uint32), C.POINTER(NoiseReferenceOutputs)]),
+    "af_noise_reference_analyze_device": (C.c_int, [_vp, _vp, _i64, _i32, _i64, _vp, _i64, _i64, _dp, _i64, _dp, _i64, _dp,
+                                                    C.POINTER(C.c_uint32), C.POINTER(NoiseReferenceOutputs)]),
+    "af_noise_reference_last_kernel_ms": (C.c_int, [_vp, _dp, _i32]),
     "af_gate_process_host": (C.c_int, [_fp, _fp, _i64, _i32, _i64, _d, _d, _d, _d, _i32, _i32, _fp, C.POINTER(C.c_uint64), _i32]),
     "af_measure_integrated_loudness_device": (C.c_int, [_vp, _i64, _i32, _i64, C.c_uint32, _i32, _dp, C.POINTER(_i32)]),
     "af_measure_integrated_loudness_host": (C.c_int, [_fp, _i64, _i32, _i64, C.c_uint32, _i32, _dp, C.POINTER(_i32)]),
@@ -348,6 +378,7 @@ VALUE_FUNCTIONS = {
     "af_mixdown_destroy", "af_mixdown_mode", "af_mixdown_channels",
     "af_output_writer_destroy", "af_output_writer_max_output_frames",
     "af_voice_spectrum_destroy", "af_voice_spectrum_bins", "af_voice_spectrum_frames",
+    "af_noise_reference_destroy", "af_noise_reference_frame_size", "af_noise_reference_bins", "af_noise_reference_frames",
 }
 
 _lib = None

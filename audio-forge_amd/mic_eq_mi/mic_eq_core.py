@@ -1641,7 +1641,7 @@ def simulate_gate_suppressor_order(audio, vad_probabilities: Sequence[float], su
 
 
 # ------------------------------------------------------------------ voice spectrum measurement
-NOISE_REFERENCE_SOURCES = ("unavailable", "explicit_capture", "in_capture_non_speech")  # spectrum.py:553, 577, 586
+NOISE_REFERENCE_SOURCES = ("unavailable", "explicit_capture", "in_capture_non_speech", "validated_conservative")  # spectrum.py:553-586
 
 
 class VoiceSpectrum:
@@ -1668,13 +1668,30 @@ class VoiceSpectrum:
     def frames(self, n_samples: int) -> int:
         return int(self._lib.af_voice_spectrum_frames(self._h, int(n_samples)))
 
+    def set_noise_override(self, noise_override=None) -> None:
+        """noise_spectrum_override of spectrum.py:554-569 for the calls that follow: (freqs [n], spectrum_db [n] for every stream
+        or [n_streams, n]), or None to clear it.  A stream whose override is not at least two finite points falls through."""
+        dp = C.POINTER(C.c_double)
+        if noise_override is None:
+            _lib.check(self._lib.af_voice_spectrum_set_noise_override(self._h, None, None, 0, 0, 0, 0))
+            return
+        freqs = np.ascontiguousarray(noise_override[0], dtype=np.float64)
+        spectrum = np.ascontiguousarray(noise_override[1], dtype=np.float64)
+        if freqs.ndim != 1 or spectrum.ndim not in (1, 2) or spectrum.shape[-1] != freqs.size or freqs.size == 0:
+            raise ValueError("noise_override must be (freqs [n], spectrum_db [n] or [n_streams, n]) with n >= 1")
+        shared = spectrum.ndim == 1
+        _lib.check(self._lib.af_voice_spectrum_set_noise_override(self._h, freqs.ctypes.data_as(dp), spectrum.ctypes.data_as(dp), freqs.size,
+                                                                  1 if shared else spectrum.shape[0], freqs.size, int(shared)))
+
     def analyze(self, audio, vad_probabilities=None, noise_audio=None, keep_windows: bool = False, device_pointers=None,
-                reliability: bool = False) -> dict:
+                reliability: bool = False, noise_override=None) -> dict:
         """audio [n_streams, n] float32 (host), or with `device_pointers=(d_audio, n, n_streams, stride[, d_noise, n_noise,
         noise_stride])` device memory.  Returns arrays by field: the scalars of af_voice_spectrum_row as [n_streams] arrays,
         spectra [n_streams, bins] (NaN rows where the reference returns None), frame levels and masks [n_streams, frames].
-        `reliability` also computes the second half of analyze_voice_spectrum (spectrum.py:647-742) for reliability()."""
+        `reliability` also computes the second half of analyze_voice_spectrum (spectrum.py:647-742) for reliability().
+        `noise_override`: see set_noise_override; it holds for this call only (None leaves none set)."""
         dp, fp = C.POINTER(C.c_double), C.POINTER(C.c_float)
+        self.set_noise_override(noise_override)
         vad = None if vad_probabilities is None else np.ascontiguousarray(vad_probabilities, dtype=np.float64)
         if device_pointers is None:
             a = np.ascontiguousarray(audio, dtype=np.float32)
@@ -1879,9 +1896,12 @@ class VoiceSpectrumResult:
 
 
 def analyze_voice_spectrum_batch(audio, fs: int = 48_000, nperseg: int = 4096, *, vad_probabilities=None, noise_audio=None,
+                                 noise_spectrum_override=None, noise_reference_source_override=None,
                                  device: int = 0) -> list[VoiceSpectrumResult]:
     """analyze_voice_spectrum (spectrum.py:498-742) of every row of audio [n_streams, n]: both of its returns, the robust median
-    and the reliability statistics computed on the device.  window_spectra_db holds the raw voiced windows on the main branch."""
+    and the reliability statistics computed on the device.  window_spectra_db holds the raw voiced windows on the main branch.
+    noise_spectrum_override: (freqs [n], spectrum_db [n] or [n_streams, n]), spectrum.py:554-569; a stream whose override is
+    accepted reports noise_reference_source_override, or "validated_conservative" without one."""
     a = np.asarray(audio)
     if a.ndim != 2:
         raise ValueError("audio must be [n_streams, n]")
@@ -1889,8 +1909,11 @@ def analyze_voice_spectrum_batch(audio, fs: int = 48_000, nperseg: int = 4096, *
         raise ValueError(f"Audio too short for FFT: need {nperseg} samples, got {a.shape[1]} ({a.shape[1] / fs:.2f} seconds)")
     vs = VoiceSpectrum(fs, nperseg, device)
     try:
-        r = vs.analyze(a, vad_probabilities, noise_audio, keep_windows=True, reliability=True)
+        r = vs.analyze(a, vad_probabilities, noise_audio, keep_windows=True, reliability=True, noise_override=noise_spectrum_override)
         q = vs.reliability()
+        sources = list(NOISE_REFERENCE_SOURCES)
+        if noise_reference_source_override:
+            sources[3] = str(noise_reference_source_override)
         results = []
         for s in range(a.shape[0]):
             have_noise = not np.isnan(r["noise_db"][s, 0])
@@ -1909,7 +1932,7 @@ def analyze_voice_spectrum_batch(audio, fs: int = 48_000, nperseg: int = 4096, *
                 vad_active_window_ratio=float(r["vad_active_window_ratio"][s]),
                 spectral_snr_db=q["spectral_snr_db"][s] if have_noise else None,
                 noise_spectrum_db=r["noise_db"][s] if have_noise else None,
-                noise_reference_source=NOISE_REFERENCE_SOURCES[int(r["noise_reference_source"][s])],
+                noise_reference_source=sources[int(r["noise_reference_source"][s])],
                 measurement_uncertainty_db=q["measurement_uncertainty_db"][s],
                 phonetic_coverage=float(q["phonetic_coverage"][s]),
                 effective_measurement_blocks=float(q["effective_measurement_blocks"][s])))
@@ -1920,7 +1943,8 @@ def analyze_voice_spectrum_batch(audio, fs: int = 48_000, nperseg: int = 4096, *
 
 def analyze_voice_spectrum(audio, fs=48000, nperseg=4096, *, vad_probabilities=None, noise_audio=None,
                            noise_spectrum_override=None, noise_reference_source_override=None) -> VoiceSpectrumResult:
-    """Drop-in for spectrum.py:498-742 (samples are taken as float32).  The noise-spectrum override is not built."""
+    """Drop-in for spectrum.py:498-742 (samples are taken as float32).  This single-capture form still refuses the noise-spectrum
+    override (a pinned contract of the ABI tests); analyze_voice_spectrum_batch takes it for one stream or many."""
     if noise_spectrum_override is not None or noise_reference_source_override is not None:
         raise NotImplementedError("noise_spectrum_override / noise_reference_source_override are not built")
     if len(audio) < nperseg:
@@ -1928,3 +1952,319 @@ def analyze_voice_spectrum(audio, fs=48000, nperseg=4096, *, vad_probabilities=N
     row = lambda x: None if x is None else np.asarray(x).reshape(1, -1)  # noqa: E731
     return analyze_voice_spectrum_batch(np.asarray(audio, dtype=np.float32).reshape(1, -1), fs, nperseg,
                                         vad_probabilities=row(vad_probabilities), noise_audio=row(noise_audio))[0]
+
+
+# ------------------------------------------------------------------ room-noise reference analysis
+NOISE_REFERENCE_STATUS = ("usable", "questionable", "invalid")
+# one text per bit of af_noise_reference_row.reasons / .guidance, in the order noise_reference.py:315-470 appends them
+NOISE_REFERENCE_REASONS = (
+    "room-noise capture is too short",
+    "room-noise capture contains non-finite samples",
+    "room-noise capture is suspiciously silent",
+    "room-noise capture is clipped",
+    "room-noise capture contains isolated clipped samples",
+    "room-noise capture has too few analysis windows",
+    "room-noise capture is dominated by changing events",
+    "room-noise capture is not stationary",
+    "room-noise capture contains dominant transient events",
+    "room-noise capture contains strong transients",
+    "speech is present in the room-noise capture",
+    "possible speech contamination in room-noise capture",
+    "input device changed between noise and voice captures",
+    "input channel mode changed between noise and voice captures",
+    "channel count changed between noise and voice captures",
+    "noise capture sample rate does not match analysis",
+    "voice capture sample rate does not match analysis",
+    "sample rate changed between noise and voice captures",
+    "room-noise reference is stale",
+    "room-noise reference may be stale",
+    "room noise does not match conditions during the voice capture",
+    "room-noise reference only partly matches the voice capture",
+    "room-noise level changed substantially before the voice capture",
+    "room-noise reference is much louder than in-capture quiet frames",
+)
+NOISE_REFERENCE_GUIDANCE = (
+    "Record at least 1.5 seconds of room tone.",
+    "Restart the audio stream and record the room tone again.",
+    "Check the selected microphone and record normal room tone again.",
+    "Lower input gain or remove the transient source, then recapture.",
+    "Recapture without taps or handling noise for a cleaner reference.",
+    "Wait for the room to settle and record a new reference.",
+    "Avoid movement, speech, and intermittent sounds while recapturing.",
+    "Recapture without keyboard, handling, or impact sounds.",
+    "Remain silent and record the room noise again.",
+    "Record another room-noise sample without voices.",
+    "Use the same microphone, channel mode, and sample rate for both captures.",
+    "Record room noise immediately before the voice sample.",
+    "Recapture room noise under the current conditions.",
+    "Recapture room noise and voice without changing the environment.",
+    "Recapture both samples for a more reliable correction.",
+    "Record room noise and voice under the same conditions.",
+    "Check whether the noise source changed between captures.",
+)
+NOISE_REFERENCE_METRICS = ("duration_s", "finite_fraction", "noise_rms_db", "conservative_noise_rms_db", "noise_peak_db",
+                           "crest_factor_db", "clipped_fraction", "zero_fraction", "rms_spread_db", "octave_stability_db",
+                           "spectral_flux_db", "vad_contamination_ratio", "vad_contamination_p90")
+NOISE_REFERENCE_KERNELS = ("statistics_and_chunk_sums", "frame_powers", "frame_spectra", "column_medians")
+
+
+def _clean_optional_text(value):
+    if value is None:
+        return None
+    text = str(value).strip()
+    return text or None
+
+
+@dataclasses.dataclass(frozen=True)
+class CaptureMetadata:
+    """noise_reference.py:21-56, field for field: identity and timing attached to one calibration capture."""
+
+    captured_at_unix_s: float | None = None
+    input_device: str | None = None
+    sample_rate: int | None = None
+    channel_mode: str | None = None
+    channel_count: int | None = None
+
+    @classmethod
+    def coerce(cls, value) -> "CaptureMetadata":
+        if value is None:
+            return cls()
+        if isinstance(value, cls):
+            return value
+        if not isinstance(value, Mapping):
+            raise TypeError("capture metadata must be a mapping or CaptureMetadata")
+        timestamp, sample_rate, channel_count = value.get("captured_at_unix_s"), value.get("sample_rate"), value.get("channel_count")
+        return cls(
+            captured_at_unix_s=float(timestamp) if timestamp is not None and np.isfinite(float(timestamp)) else None,
+            input_device=_clean_optional_text(value.get("input_device")),
+            sample_rate=int(sample_rate) if sample_rate is not None else None,
+            channel_mode=_clean_optional_text(value.get("channel_mode")),
+            channel_count=int(channel_count) if channel_count is not None else None,
+        )
+
+
+@dataclasses.dataclass
+class NoiseReferenceAnalysis:
+    """noise_reference.py:59-86, field for field."""
+
+    status: str
+    quality_score: float
+    usable: bool
+    conservative: bool
+    reasons: list
+    guidance: list
+    metrics: dict
+    frequencies: np.ndarray
+    explicit_spectrum_db: np.ndarray
+    conservative_spectrum_db: np.ndarray
+    in_capture_spectrum_db: np.ndarray | None = None
+    conservative_noise_rms_db: float = -120.0
+
+    def diagnostics(self) -> dict:
+        return {"status": self.status, "quality_score": self.quality_score, "usable": self.usable, "conservative": self.conservative,
+                "reasons": list(self.reasons), "guidance": list(self.guidance), "metrics": dict(self.metrics)}
+
+
+def _metadata_arguments(noise_metadata, speech_metadata, sample_rate: int) -> tuple[float, int, bool]:
+    """_metadata_mismatches, :223-249, as the library takes it: (capture age in s, NaN when unknown and not yet clamped at 0;
+    AF_NOISE_MISMATCH_* bits; identity_metadata_available of :526-528)."""
+    noise, speech = CaptureMetadata.coerce(noise_metadata), CaptureMetadata.coerce(speech_metadata)
+    mask = 0
+    for bit, (left, right) in enumerate(((noise.input_device, speech.input_device), (noise.channel_mode, speech.channel_mode),
+                                         (noise.channel_count, speech.channel_count))):
+        if left is not None and right is not None and left != right:
+            mask |= 1 << bit
+    for bit, metadata in ((3, noise), (4, speech)):
+        if metadata.sample_rate is not None and metadata.sample_rate != sample_rate:
+            mask |= 1 << bit
+    if noise.sample_rate is not None and speech.sample_rate is not None and noise.sample_rate != speech.sample_rate:
+        mask |= 1 << 5
+    age = float("nan")
+    if noise.captured_at_unix_s is not None and speech.captured_at_unix_s is not None:
+        age = speech.captured_at_unix_s - noise.captured_at_unix_s
+    return age, mask, noise.input_device is not None and speech.input_device is not None
+
+
+class NoiseReference:
+    """python/mic_eq/analysis/noise_reference.py for a batch of capture pairs on the device.  One object per sample rate;
+    scratch is kept between calls.  A sample rate whose analysis frame the transform does not take raises NotImplementedError."""
+
+    def __init__(self, sample_rate: int = 48_000, device: int = 0):
+        self._lib = _lib.load()
+        handle = C.c_void_p()
+        _lib.check(self._lib.af_noise_reference_create(int(sample_rate), int(device), C.byref(handle)))
+        self._h = handle
+        self.sample_rate = int(sample_rate)
+        self.frame_size = int(self._lib.af_noise_reference_frame_size(handle))
+
+    def close(self) -> None:
+        if getattr(self, "_h", None):
+            self._lib.af_noise_reference_destroy(self._h)
+            self._h = None
+
+    __del__ = close
+
+    def frames(self, n_samples: int) -> int:
+        return int(self._lib.af_noise_reference_frames(self._h, int(n_samples)))
+
+    def bins(self, n_noise: int) -> int:
+        return int(self._lib.af_noise_reference_bins(self._h, int(n_noise)))
+
+    def frequencies(self, n_noise: int) -> np.ndarray:
+        """The grid of the spectra: the frames', or np.fft.rfftfreq(max(2, n_noise)) below one frame (:339)."""
+        n = self.frame_size if n_noise >= self.frame_size else max(2, int(n_noise))
+        return np.arange(n // 2 + 1) * (1.0 / (n * (1.0 / self.sample_rate)))
+
+    def analyze(self, noise_audio, speech_audio=None, noise_vad_probabilities=None, speech_vad_probabilities=None, capture_age_s=None,
+                metadata_mismatch=None, device_pointers=None, internals: bool = False) -> dict:
+        """noise_audio [n_streams, n_noise] and speech_audio [n_streams, n_speech] | None, float32 (host), or with
+        `device_pointers=(d_noise, n_noise, n_streams, noise_stride, d_speech | None, n_speech, speech_stride)` device memory.
+        Returns arrays by field: the scalars of af_noise_reference_row as [n_streams] arrays, the three spectra
+        [n_streams, bins] (in_capture_spectrum_db: NaN rows where the reference returns None), frame_rms_db [n_streams, frames]
+        and band_levels_db [n_streams, frames, 7] of the noise capture.  `internals` adds what the kernels left: chunk sums,
+        frame powers, PSD rows, band sums and the middles of both medians."""
+        dp, fp = C.POINTER(C.c_double), C.POINTER(C.c_float)
+        if device_pointers is None:
+            z = np.ascontiguousarray(noise_audio, dtype=np.float32)
+            if z.ndim != 2:
+                raise ValueError("noise_audio must be [n_streams, n_noise]")
+            B, n = z.shape
+            v = None if speech_audio is None else np.ascontiguousarray(speech_audio, dtype=np.float32)
+            if v is not None and (v.ndim != 2 or v.shape[0] != B):
+                raise ValueError("speech_audio must be [n_streams, n_speech]")
+            m = 0 if v is None else v.shape[1]
+        else:
+            n, B, m = int(device_pointers[1]), int(device_pointers[2]), int(device_pointers[5]) if device_pointers[4] is not None else 0
+
+        def per_stream(x, dtype, what):
+            if x is None:
+                return None
+            x = np.ascontiguousarray(x, dtype=dtype)
+            if x.ndim == 0 or x.shape[0] != B:
+                raise ValueError(f"{what} must have one entry per stream")
+            return x
+
+        nv = per_stream(noise_vad_probabilities, np.float64, "noise_vad_probabilities")
+        sv = per_stream(speech_vad_probabilities, np.float64, "speech_vad_probabilities")
+        for x, what in ((nv, "noise_vad_probabilities"), (sv, "speech_vad_probabilities")):
+            if x is not None and (x.ndim != 2 or x.shape[1] == 0):
+                raise ValueError(f"{what} must be [n_streams, n] with n >= 1")
+        age = per_stream(capture_age_s, np.float64, "capture_age_s")
+        mismatch = per_stream(metadata_mismatch, np.uint32, "metadata_mismatch")
+        F, Fv, K, Ko = self.frames(n), self.frames(m), self.frame_size // 2 + 1, self.bins(n)
+        rows = (_lib.NoiseReferenceRow * B)()
+        out = {name: np.empty((B, Ko)) for name in ("explicit_spectrum_db", "conservative_spectrum_db", "in_capture_spectrum_db")}
+        out.update(frame_rms_db=np.empty((B, F)), band_levels_db=np.empty((B, F, 7)))
+        if internals:
+            out.update(noise_chunk_sums=np.empty((B, F + 1 if F else 0, 2)), noise_frame_power=np.empty((B, F)),
+                       speech_frame_power=np.empty((B, Fv)), noise_psd=np.empty((B, F, K)), band_power=np.empty((B, F, 7)),
+                       explicit_middles=np.empty((B, 2, K)), in_capture_middles=np.empty((B, 2, K)))
+        o = _lib.NoiseReferenceOutputs(rows=rows, **{k: a.ctypes.data_as(dp) for k, a in out.items()})
+        vad_args = (None if nv is None else nv.ctypes.data_as(dp), 0 if nv is None else nv.shape[1],
+                    None if sv is None else sv.ctypes.data_as(dp), 0 if sv is None else sv.shape[1],
+                    None if age is None else age.ctypes.data_as(dp),
+                    None if mismatch is None else mismatch.ctypes.data_as(C.POINTER(C.c_uint32)), C.byref(o))
+        if device_pointers is None:
+            rc = self._lib.af_noise_reference_analyze_host(self._h, z.ctypes.data_as(fp), n, B, n, None if v is None else v.ctypes.data_as(fp),
+                                                           m, m, *vad_args)
+        else:
+            d_noise, _, _, noise_stride, d_speech, _, speech_stride = device_pointers
+            rc = self._lib.af_noise_reference_analyze_device(self._h, C.c_void_p(int(d_noise)), n, B, int(noise_stride),
+                                                             None if d_speech is None else C.c_void_p(int(d_speech)), m,
+                                                             int(speech_stride), *vad_args)
+        _lib.check(rc)
+        for name, _ in _lib.NoiseReferenceRow._fields_:
+            if name != "reserved":
+                out[name] = np.array([getattr(r, name) for r in rows])
+        out["frequencies"] = self.frequencies(n)
+        return out
+
+    def last_kernel_ms(self) -> dict:
+        """GPU ms of each stage of the last call, summed over its tiles."""
+        ms = (C.c_double * 4)()
+        _lib.check(self._lib.af_noise_reference_last_kernel_ms(self._h, ms, 4))
+        return dict(zip(NOISE_REFERENCE_KERNELS, (float(x) for x in ms)))
+
+
+def _bit_texts(mask: int, table) -> list:
+    return [text for bit, text in enumerate(table) if mask >> bit & 1]
+
+
+def _noise_reference_results(r: dict, identity: Sequence[bool]) -> list:
+    results = []
+    none = lambda x: None if np.isnan(x) else float(x)  # noqa: E731
+    for s in range(len(r["status"])):
+        metrics = {name: float(r[name][s]) for name in NOISE_REFERENCE_METRICS}
+        metrics.update(capture_age_s=none(r["capture_age_s"][s]), identity_metadata_available=bool(identity[s]),
+                       in_capture_noise_frame_count=int(r["in_capture_noise_frame_count"][s]),
+                       in_capture_level_delta_db=none(r["in_capture_level_delta_db"][s]),
+                       spectral_shape_distance_db=none(r["spectral_shape_distance_db"][s]))
+        status = NOISE_REFERENCE_STATUS[int(r["status"][s])]
+        results.append(NoiseReferenceAnalysis(
+            status=status, quality_score=float(r["quality_score"][s]), usable=status != "invalid",
+            conservative=bool(r["conservative"][s]), reasons=_bit_texts(int(r["reasons"][s]), NOISE_REFERENCE_REASONS),
+            guidance=_bit_texts(int(r["guidance"][s]), NOISE_REFERENCE_GUIDANCE), metrics=metrics, frequencies=r["frequencies"],
+            explicit_spectrum_db=r["explicit_spectrum_db"][s], conservative_spectrum_db=r["conservative_spectrum_db"][s],
+            in_capture_spectrum_db=r["in_capture_spectrum_db"][s] if r["has_in_capture_spectrum"][s] else None,
+            conservative_noise_rms_db=float(r["conservative_noise_rms_db"][s])))
+    return results
+
+
+def _per_stream_metadata(value, n_streams: int) -> list:
+    if value is None or isinstance(value, (CaptureMetadata, Mapping)):
+        return [value] * n_streams
+    value = list(value)
+    if len(value) != n_streams:
+        raise ValueError("metadata must be one value or one per stream")
+    return value
+
+
+def analyze_noise_reference_batch(noise_audio, speech_audio, sample_rate: int, *, noise_metadata=None, speech_metadata=None,
+                                  noise_vad_probabilities=None, speech_vad_probabilities=None, device: int = 0) -> list:
+    """analyze_noise_reference (noise_reference.py:280-546) of every row of noise_audio [n_streams, n] against the same row of
+    speech_audio [n_streams, m] (or None).  Metadata: one value (CaptureMetadata, mapping or None) or one per stream."""
+    if sample_rate <= 0:
+        raise ValueError("sample_rate must be positive")
+    z = np.asarray(noise_audio)
+    if z.ndim != 2:
+        raise ValueError("noise_audio must be [n_streams, n_noise]")
+    B = z.shape[0]
+    pairs = [_metadata_arguments(a, b, int(sample_rate))
+             for a, b in zip(_per_stream_metadata(noise_metadata, B), _per_stream_metadata(speech_metadata, B))]
+    nr = NoiseReference(sample_rate, device)
+    try:
+        r = nr.analyze(z, speech_audio, noise_vad_probabilities, speech_vad_probabilities, capture_age_s=[p[0] for p in pairs],
+                       metadata_mismatch=[p[1] for p in pairs])
+        return _noise_reference_results(r, [p[2] for p in pairs])
+    finally:
+        nr.close()
+
+
+def analyze_noise_reference(noise_audio, speech_audio, sample_rate: int, *, noise_metadata=None, speech_metadata=None,
+                            noise_vad_probabilities=None, speech_vad_probabilities=None) -> NoiseReferenceAnalysis:
+    """Drop-in for noise_reference.py:280-546 (samples are taken as float32)."""
+    row = lambda x, dtype: None if x is None else np.asarray(x, dtype=dtype).reshape(1, -1)  # noqa: E731
+    speech = row(speech_audio, np.float32)
+    vad = lambda x: None if x is None or np.asarray(x).size == 0 else row(x, np.float64)  # noqa: E731
+    return analyze_noise_reference_batch(row(noise_audio, np.float32), None if speech is None or speech.shape[1] == 0 else speech,
+                                         sample_rate, noise_metadata=noise_metadata, speech_metadata=speech_metadata,
+                                         noise_vad_probabilities=vad(noise_vad_probabilities),
+                                         speech_vad_probabilities=vad(speech_vad_probabilities))[0]
+
+
+def analyze_voice_capture_batch(noise_audio, speech_audio, fs: int = 48_000, nperseg: int = 4096, *, noise_metadata=None,
+                                speech_metadata=None, noise_vad_probabilities=None, speech_vad_probabilities=None,
+                                vad_probabilities=None, device: int = 0) -> tuple[list, list]:
+    """The two steps of the reference's voice setup (voice_setup.py:1122-1162) for every capture pair: analyze_noise_reference on
+    the room tone and the voice capture, then analyze_voice_spectrum of the voice capture with the conservative spectrum as its
+    noise-spectrum override ("validated_conservative") and the room tone as noise_audio behind it.  speech_vad_probabilities
+    are the posteriors spread evenly over the voice capture (step one), vad_probabilities the ones per 32 ms model window (step
+    two).  Returns (noise reference analyses, voice spectrum results)."""
+    references = analyze_noise_reference_batch(noise_audio, speech_audio, fs, noise_metadata=noise_metadata, speech_metadata=speech_metadata,
+                                               noise_vad_probabilities=noise_vad_probabilities,
+                                               speech_vad_probabilities=speech_vad_probabilities, device=device)
+    override = (references[0].frequencies, np.stack([r.conservative_spectrum_db for r in references]))
+    spectra = analyze_voice_spectrum_batch(speech_audio, fs, nperseg, vad_probabilities=vad_probabilities, noise_audio=noise_audio,
+                                           noise_spectrum_override=override, noise_reference_source_override="validated_conservative",
+                                           device=device)
+    return references, spectra

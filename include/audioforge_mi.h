@@ -664,7 +664,8 @@ int af_measure_integrated_loudness_host(const float *audio, int64_t n_samples, i
  * two from 256 to 8192 (anything else: AF_ERR_UNSUPPORTED); non-finite audio is refused with AF_ERR_NON_FINITE.
  * Frames are nperseg samples at hop nperseg / 2; bins = nperseg / 2 + 1 at k * sample_rate / nperseg Hz. */
 typedef struct af_voice_spectrum af_voice_spectrum;
-enum { AF_NOISE_REFERENCE_UNAVAILABLE = 0, AF_NOISE_REFERENCE_EXPLICIT_CAPTURE = 1, AF_NOISE_REFERENCE_IN_CAPTURE_NON_SPEECH = 2 };
+enum { AF_NOISE_REFERENCE_UNAVAILABLE = 0, AF_NOISE_REFERENCE_EXPLICIT_CAPTURE = 1, AF_NOISE_REFERENCE_IN_CAPTURE_NON_SPEECH = 2,
+       AF_NOISE_REFERENCE_VALIDATED_CONSERVATIVE = 3 };
 /* one stream's scalars of analyze_voice_spectrum, spectrum.py:527-550, 570-586, 605, 625 */
 typedef struct af_voice_spectrum_row {
   int32_t frames;                        /* (n_samples - nperseg) / hop + 1 */
@@ -751,6 +752,110 @@ int af_voice_spectrum_read_reliability(af_voice_spectrum *h, const af_voice_spec
  * af_voice_spectrum_last_kernel_ms): ms[0 .. 5) = row levels, block and centre medians, shape distances, block statistics,
  * robust median.  Zeros when the option was off.  capacity: the doubles ms holds, at least 5. */
 int af_voice_spectrum_last_reliability_kernel_ms(af_voice_spectrum *h, double *ms, int32_t capacity);
+/* noise_spectrum_override of analyze_voice_spectrum, spectrum.py:554-569: a prevalidated noise spectrum (the conservative
+ * spectrum of af_noise_reference_analyze_*) on its own grid freqs[n_points] (increasing), spectrum_db[n_streams][stride] dB,
+ * or with shared != 0 one spectrum_db[n_points] for every stream; the arrays are copied.  spectrum_db null clears it.  While
+ * it is set, an analyze call validates each stream's override as :557-563 does (at least 2 points, all finite): a valid one
+ * takes precedence over noise_audio and the in-capture fallback, is interpolated onto the handle's grid with held ends
+ * (:596-602) and reports AF_NOISE_REFERENCE_VALIDATED_CONSERVATIVE; an invalid one falls through silently.  A per-stream
+ * override whose n_streams differs from the call's is AF_ERR_INVALID_ARGUMENT.  With none set no call changes by a bit. */
+int af_voice_spectrum_set_noise_override(af_voice_spectrum *h, const double *freqs, const double *spectrum_db, int32_t n_points,
+                                         int32_t n_streams, int64_t stride, int32_t shared);
+
+/* ---- room-noise reference analysis: python/mic_eq/analysis/noise_reference.py:118-546 ------------------------------
+ * analyze_noise_reference for a batch of capture pairs: the quality verdict on a room-tone capture (duration, finiteness,
+ * silence, clipping, stationarity, transients, speech contamination, metadata, age, consistency with the quiet frames of the
+ * voice capture) and the explicit, in-capture and conservative noise spectra.  Frames are max(512, round(0.2 sample_rate))
+ * samples at half that hop, Hann-windowed.  The frame must be even, its half free of prime factors above 7 and at most 10240
+ * (8, 12, 16, 22.05, 24, 32, 44.1, 48, 64, 88.2, 96 kHz and everything up to 2.56 kHz qualify; anything else:
+ * AF_ERR_UNSUPPORTED at create).  A non-finite sample reads as 0 and makes its capture invalid, as in the reference. */
+typedef struct af_noise_reference af_noise_reference;
+enum { AF_NOISE_STATUS_USABLE = 0, AF_NOISE_STATUS_QUESTIONABLE = 1, AF_NOISE_STATUS_INVALID = 2 };
+/* bits of af_noise_reference_row.reasons, one per distinct text of :315-470, in the order the reference appends them */
+enum {
+  AF_NOISE_REASON_TOO_SHORT = 1u << 0,            /* "room-noise capture is too short" */
+  AF_NOISE_REASON_NON_FINITE = 1u << 1,           /* "... contains non-finite samples" */
+  AF_NOISE_REASON_SILENT = 1u << 2,               /* "... is suspiciously silent" */
+  AF_NOISE_REASON_CLIPPED = 1u << 3,              /* "... is clipped" */
+  AF_NOISE_REASON_ISOLATED_CLIPS = 1u << 4,       /* "... contains isolated clipped samples" */
+  AF_NOISE_REASON_TOO_FEW_WINDOWS = 1u << 5,      /* "... has too few analysis windows" */
+  AF_NOISE_REASON_CHANGING_EVENTS = 1u << 6,      /* "... is dominated by changing events" */
+  AF_NOISE_REASON_NOT_STATIONARY = 1u << 7,       /* "... is not stationary" */
+  AF_NOISE_REASON_DOMINANT_TRANSIENTS = 1u << 8,  /* "... contains dominant transient events" */
+  AF_NOISE_REASON_STRONG_TRANSIENTS = 1u << 9,    /* "... contains strong transients" */
+  AF_NOISE_REASON_SPEECH_PRESENT = 1u << 10,      /* "speech is present in the room-noise capture" */
+  AF_NOISE_REASON_POSSIBLE_SPEECH = 1u << 11,     /* "possible speech contamination in room-noise capture" */
+  AF_NOISE_REASON_METADATA = 1u << 12,            /* bits 12 .. 17: AF_NOISE_MISMATCH_* << 12 */
+  AF_NOISE_REASON_STALE = 1u << 18,               /* "room-noise reference is stale" */
+  AF_NOISE_REASON_MAY_BE_STALE = 1u << 19,        /* "room-noise reference may be stale" */
+  AF_NOISE_REASON_MISMATCH = 1u << 20,            /* "room noise does not match conditions during the voice capture" */
+  AF_NOISE_REASON_PARTIAL_MATCH = 1u << 21,       /* "room-noise reference only partly matches the voice capture" */
+  AF_NOISE_REASON_LEVEL_CHANGED = 1u << 22,       /* "room-noise level changed substantially before the voice capture" */
+  AF_NOISE_REASON_MUCH_LOUDER = 1u << 23          /* "room-noise reference is much louder than in-capture quiet frames" */
+};
+/* the checks of _metadata_mismatches, :223-244, in the order of their reason texts */
+enum {
+  AF_NOISE_MISMATCH_INPUT_DEVICE = 1u << 0, AF_NOISE_MISMATCH_CHANNEL_MODE = 1u << 1, AF_NOISE_MISMATCH_CHANNEL_COUNT = 1u << 2,
+  AF_NOISE_MISMATCH_NOISE_RATE = 1u << 3, AF_NOISE_MISMATCH_VOICE_RATE = 1u << 4, AF_NOISE_MISMATCH_RATE_CHANGED = 1u << 5
+};
+/* one stream's verdict and the scalars of `metrics`, :511-532; a value the reference leaves None is NaN */
+typedef struct af_noise_reference_row {
+  int32_t status;          /* AF_NOISE_STATUS_* */
+  int32_t conservative;    /* :537 */
+  uint32_t reasons;        /* AF_NOISE_REASON_* */
+  uint32_t guidance;       /* bit i: the i-th distinct guidance text of :315-470 in source order */
+  double quality_score;
+  double duration_s, finite_fraction, noise_rms_db, conservative_noise_rms_db, noise_peak_db, crest_factor_db;
+  double clipped_fraction, zero_fraction, rms_spread_db, octave_stability_db, spectral_flux_db;
+  double vad_contamination_ratio, vad_contamination_p90, capture_age_s, in_capture_level_delta_db, spectral_shape_distance_db;
+  double noise_sum_squares, noise_peak;                 /* what the sample-statistics kernel left */
+  int64_t finite_samples, clipped_samples, zero_samples;
+  int32_t in_capture_noise_frame_count;
+  int32_t noise_frames, speech_frames;  /* analysis frames of the two captures (0 below one frame) */
+  int32_t n_bands;                      /* octave bands that hold a bin */
+  int32_t has_in_capture_spectrum;
+  int32_t reserved;
+} af_noise_reference_row;
+/* Where a call writes; every pointer is host memory and may be null.  bins = af_noise_reference_bins(h, n_noise), F and Fv the
+ * frames of the noise and the voice capture, K = frame / 2 + 1.  Spectra are dB. */
+typedef struct af_noise_reference_outputs {
+  af_noise_reference_row *rows;      /* [n_streams] */
+  double *explicit_spectrum_db;      /* [n_streams][bins] the median over the noise frames, :179 (-120 below one frame, :340) */
+  double *conservative_spectrum_db;  /* [n_streams][bins] :424, :453 */
+  double *in_capture_spectrum_db;    /* [n_streams][bins] :274 on the noise grid (:431-437); a NaN row where it is None */
+  double *frame_rms_db;              /* [n_streams][F] :129 */
+  double *band_levels_db;            /* [n_streams][F][7] :145, the first n_bands of a row; NaN behind them */
+  /* what the kernels left, for tests: */
+  double *noise_chunk_sums;          /* [n_streams][F + 1][2] sums of x and x^2 over hop-sized chunks */
+  double *noise_frame_power;         /* [n_streams][F] :128 */
+  double *speech_frame_power;        /* [n_streams][Fv] */
+  double *noise_psd;                 /* [n_streams][F][K] :133-134 */
+  double *band_power;                /* [n_streams][F][7] :144 */
+  double *explicit_middles;          /* [n_streams][2][K] lower and upper middle of the PSD over the noise frames */
+  double *in_capture_middles;        /* [n_streams][2][K] the same over the quiet voice frames; NaN where none were selected */
+} af_noise_reference_outputs;
+int af_noise_reference_create(uint32_t sample_rate, int32_t device, af_noise_reference **out);
+void af_noise_reference_destroy(af_noise_reference *h);
+int32_t af_noise_reference_frame_size(const af_noise_reference *h);                /* VALUE */
+int32_t af_noise_reference_bins(const af_noise_reference *h, int64_t n_noise);     /* VALUE: frame / 2 + 1; below one frame
+                                                                                      max(2, n_noise) / 2 + 1, the grid of :339 */
+int64_t af_noise_reference_frames(const af_noise_reference *h, int64_t n_samples); /* VALUE: 0 below one frame */
+/* noise: [n_streams][noise_stride] captures of n_noise >= 0 samples.  speech: null, or [n_streams][speech_stride] voice captures
+ * of n_speech samples.  noise_vad / speech_vad: null, or [n_streams][n] speech posteriors spread evenly over the capture
+ * (_interpolate_vad, :188-205).  capture_age_s: null, or per stream the voice capture's time minus the noise capture's (NaN:
+ * unknown; negative counts as 0, :248).  metadata_mismatch: null, or per stream AF_NOISE_MISMATCH_* bits.  _host takes host
+ * audio, _device device audio (on the null stream); the other arrays are host memory.  Both return after the outputs are written. */
+int af_noise_reference_analyze_host(af_noise_reference *h, const float *noise, int64_t n_noise, int32_t n_streams, int64_t noise_stride,
+                                    const float *speech, int64_t n_speech, int64_t speech_stride, const double *noise_vad,
+                                    int64_t n_noise_vad, const double *speech_vad, int64_t n_speech_vad, const double *capture_age_s,
+                                    const uint32_t *metadata_mismatch, const af_noise_reference_outputs *out);
+int af_noise_reference_analyze_device(af_noise_reference *h, const float *d_noise, int64_t n_noise, int32_t n_streams, int64_t noise_stride,
+                                      const float *d_speech, int64_t n_speech, int64_t speech_stride, const double *noise_vad,
+                                      int64_t n_noise_vad, const double *speech_vad, int64_t n_speech_vad, const double *capture_age_s,
+                                      const uint32_t *metadata_mismatch, const af_noise_reference_outputs *out);
+/* GPU time of the kernels of the last call: ms[0 .. 4) = sample statistics and chunk sums, frame powers, frame spectra with
+ * the band sums, column medians (events around them; copies and host decisions are not in it).  capacity: at least 4. */
+int af_noise_reference_last_kernel_ms(af_noise_reference *h, double *ms, int32_t capacity);
 
 /* ---- NoiseSuppressor: rust-core/src/dsp/noise_suppressor.rs:18-194 ----------------------------------------
  * The runtime-selected suppressor interface (`NoiseModel`, trait `NoiseSuppressor`, `new_noise_suppression_engine`) for a
