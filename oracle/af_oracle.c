@@ -1563,6 +1563,9 @@ void afo_deesser_reset(afo_deesser *d) {
   d->detector_confidence = 0.0;
   for (int i = 0; i < 3; ++i) deesser_band_reset(&d->bands[i]);
 }
+size_t afo_deesser_sizeof(void) { return sizeof(afo_deesser); }
+size_t afo_deesser_band_sizeof(void) { return sizeof(afo_deesser_band); }
+size_t afo_biquad_sizeof(void) { return sizeof(afo_biquad); }
 
 /* ------------------------------------------------------------- prefilter */
 /* audio/processor.rs:74-76 */

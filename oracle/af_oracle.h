@@ -275,6 +275,10 @@ void afo_deesser_set_max_reduction_db(afo_deesser *d, double v);
 float afo_deesser_process_sample(afo_deesser *d, float input);
 void afo_deesser_process_block(afo_deesser *d, float *buf, size_t n);
 void afo_deesser_reset(afo_deesser *d);
+/* sizes of the three structs above, for bindings that mirror them field by field */
+size_t afo_deesser_sizeof(void);
+size_t afo_deesser_band_sizeof(void);
+size_t afo_biquad_sizeof(void);
 
 /* ------------------------------------------------------------- prefilter */
 /* audio/processor/routing.rs:9-12,826-843; processor.rs:74-76 */

@@ -148,6 +148,54 @@ class BlockStats(C.Structure):
     ]
 
 
+class Biquad(C.Structure):
+    """afo_biquad (af_oracle.h), field for field."""
+    _fields_ = [(name, C.c_double) for name in ("b0", "b1", "b2", "a1", "a2", "pb0", "pb1", "pb2", "pa1", "pa2", "pz1", "pz2")] + [
+        ("xf_total", C.c_size_t),
+        ("xf_remaining", C.c_size_t),
+        ("z1", C.c_double),
+        ("z2", C.c_double),
+        ("type", C.c_int),
+        ("frequency", C.c_double),
+        ("gain_db", C.c_double),
+        ("q", C.c_double),
+        ("sample_rate", C.c_double),
+        ("enabled", C.c_int),
+    ]
+
+
+class DeEsserBand(C.Structure):
+    """afo_deesser_band."""
+    _fields_ = [(name, C.c_double) for name in ("low_hz", "high_hz", "env", "confidence", "baseline_excess_db", "reduction_db")] + [
+        ("detector_hp", Biquad),
+        ("detector_lp", Biquad),
+        ("dynamic_eq", Biquad),
+    ]
+
+
+class DeEsser(C.Structure):
+    """afo_deesser: a test may own one (`DeEsser()` + `afo_deesser_init`), step it with `afo_deesser_process_sample` and read
+    the envelopes, confidences, baselines, reductions and the dynamic EQs' `gain_db` after every sample."""
+    _fields_ = [("enabled", C.c_int), ("auto_enabled", C.c_int)] + [
+        (name, C.c_double)
+        for name in ("auto_amount", "threshold_db", "ratio", "attack_coeff", "release_coeff", "detector_attack_coeff",
+                     "detector_release_coeff", "max_reduction_db", "current_reduction_db", "broadband_env", "detector_confidence",
+                     "low_cut_hz", "high_cut_hz", "sample_rate")
+    ] + [("bands", DeEsserBand * 3)]
+
+
+DEESSER_SETTERS = ("auto_enabled", "auto_amount", "low_cut_hz", "high_cut_hz", "threshold_db", "ratio", "attack_ms", "release_ms",
+                   "max_reduction_db")  # afo_simulate_auto_eq_chain's order (af_oracle.c)
+
+
+def deesser_apply(deesser, settings: "SimSettings") -> None:
+    """The `deesser_*` settings onto an afo_deesser (a pointer, or `byref` of a mirror), in afo_simulate_auto_eq_chain's order."""
+    L = lib()
+    for name in DEESSER_SETTERS:
+        value = getattr(settings, "deesser_" + name)
+        getattr(L, "afo_deesser_set_" + name)(deesser, int(value) if name == "auto_enabled" else float(value))
+
+
 _lib = None
 
 
@@ -189,6 +237,14 @@ def lib() -> C.CDLL:
             getattr(L, f"afo_deesser_set_{name}").argtypes = [vp, d]
         for name in ("enabled", "auto_enabled"):
             getattr(L, f"afo_deesser_set_{name}").argtypes = [vp, i]
+        L.afo_deesser_init.argtypes = [vp, d]
+        L.afo_deesser_reset.argtypes = [vp]
+        L.afo_deesser_process_sample.restype = f
+        L.afo_deesser_process_sample.argtypes = [vp, f]
+        L.afo_deesser_process_block.argtypes = [vp, fp, sz]
+        for name in ("deesser", "deesser_band", "biquad"):
+            getattr(L, f"afo_{name}_sizeof").restype = sz
+            getattr(L, f"afo_{name}_sizeof").argtypes = []
         L.afo_sim_settings_default.argtypes = [C.POINTER(SimSettings)]
         L.afo_simulate_auto_eq_chain.restype = i
         L.afo_simulate_auto_eq_chain.argtypes = [fp, sz, d, dp, C.POINTER(SimSettings), C.POINTER(SimResult), fp]

@@ -1,7 +1,9 @@
 """The oracle's block processor (`af_oracle_py.Chain`) configured as `simulate_auto_eq_chain` configures it, driven over
 the same calls as an engine: every call starts a new control block, so a call whose length is not a multiple of the
 control block ends in a short block -- as on the GPU.  `simulate_auto_eq_chain` runs one call; this runs any call
-pattern and also returns the per-block rows.  Used by the tests only (CPU side of a comparison)."""
+pattern and also returns the per-block rows, the de-esser's reduction among them.  The de-esser is set up as the simulation sets
+it up, in either stage order; with the EQ, compressor and limiter switched off it runs alone.  Used by the tests only (CPU side
+of a comparison)."""
 from __future__ import annotations
 
 import ctypes as C
@@ -14,7 +16,9 @@ import af_oracle_py as O
 ROW_FIELDS = ("input_sample_peak", "output_sample_peak", "true_peak_limiter_input_peak", "output_true_peak",
               "limiter_peak_gain_reduction_db", "true_peak_limiter_gain_reduction_db", "true_peak_limited_events",
               "compressor_gain_reduction_db")
-ROW_DTYPE = np.dtype([(name, "<u8" if name == "true_peak_limited_events" else "<f4") for name in ROW_FIELDS])
+# the rows also carry the de-esser's per-block reduction (0 with the de-esser off); ROW_FIELDS stays what the chain tests walk over
+ALL_ROW_FIELDS = ROW_FIELDS + ("deesser_gain_reduction_db",)
+ROW_DTYPE = np.dtype([(name, "<u8" if name == "true_peak_limited_events" else "<f4") for name in ALL_ROW_FIELDS])
 
 
 def _lib() -> C.CDLL:
@@ -29,11 +33,11 @@ def control_block(sample_rate: float) -> int:
     return int(min(max(round(sample_rate * 0.020), 1), 8192))  # python_api.rs:512-514
 
 
-def make_chain(sample_rate: float, bands, settings: dict | None) -> O.Chain:
-    """afo_simulate_auto_eq_chain's set-up (af_oracle.c), step for step, on a fresh chain."""
+def make_chain(sample_rate: float, bands, settings: dict | None, eq_enabled: bool = True) -> O.Chain:
+    """afo_simulate_auto_eq_chain's set-up (af_oracle.c), step for step, on a fresh chain.  `eq_enabled=False` switches the EQ
+    off afterwards (the simulation itself has no such setting; the compressor and the limiter have theirs), so that with
+    `compressor_enabled` and `limiter_enabled` false a stage such as the de-esser runs alone."""
     s = O.settings_from_dict(settings)
-    if s.deesser_enabled:
-        raise NotImplementedError("the de-esser is not replayed here")
     chain = O.Chain(float(sample_rate))
     L = chain.L
     chain.set("eq_enabled", 1)
@@ -47,7 +51,9 @@ def make_chain(sample_rate: float, bands, settings: dict | None) -> O.Chain:
             L.afo_eq_set_band_gain(chain.eq, i, float(gain))
             L.afo_eq_set_band_q(chain.eq, i, float(q))
     chain.set("eq_before_deesser", s.eq_before_deesser)
-    chain.set("deesser_enabled", 0)
+    chain.set("deesser_enabled", s.deesser_enabled)
+    if s.deesser_enabled:
+        O.deesser_apply(chain.deesser, s)
     chain.set("compressor_enabled", s.compressor_enabled)
     if s.compressor_enabled:
         c = chain.compressor
@@ -68,6 +74,8 @@ def make_chain(sample_rate: float, bands, settings: dict | None) -> O.Chain:
         L.afo_limiter_set_ceiling(chain.limiter, effective)
         L.afo_limiter_set_release_time(chain.limiter, s.limiter_release_ms)
         L.afo_tp_limiter_set_release_ms(chain.tp_limiter, float(np.float32(s.limiter_release_ms)))
+    if not eq_enabled:
+        chain.set("eq_enabled", 0)
     return chain
 
 
@@ -82,9 +90,10 @@ def sanitize(x: np.ndarray, clamp: bool) -> np.ndarray:
     return y
 
 
-def run_calls(x: np.ndarray, sample_rate: float, bands, settings: dict | None, calls, clamp: bool = False):
+def run_calls(x: np.ndarray, sample_rate: float, bands, settings: dict | None, calls, clamp: bool = False,
+              eq_enabled: bool = True):
     """One stream through the chain in calls of the given lengths: (output float32, rows [blocks] of ROW_DTYPE)."""
-    chain = make_chain(sample_rate, bands, settings)
+    chain = make_chain(sample_rate, bands, settings, eq_enabled)
     y = sanitize(x, clamp)
     cb = control_block(sample_rate)
     rows = []
@@ -93,13 +102,13 @@ def run_calls(x: np.ndarray, sample_rate: float, bands, settings: dict | None, c
         for b0 in range(at, at + length, cb):
             block = y[b0 : min(b0 + cb, at + length)]
             st = chain.process_block(block)
-            rows.append(tuple(getattr(st, name) for name in ROW_FIELDS))
+            rows.append(tuple(getattr(st, name) for name in ALL_ROW_FIELDS))
         at += length
     return y[:at], np.array(rows, dtype=ROW_DTYPE)
 
 
 def run_batch(audio: np.ndarray, sample_rate: float, bands, settings: dict | None, calls, clamp: bool = False,
-              workers: int = 16):
+              workers: int = 16, eq_enabled: bool = True):
     """run_calls over every stream of [n_streams, n] on up to `workers` threads (the oracle keeps no global state:
     every chain is its own allocation, and ctypes releases the GIL inside each call).
     Returns (output [n_streams, sum(calls)], rows [blocks, n_streams])."""
@@ -109,7 +118,7 @@ def run_batch(audio: np.ndarray, sample_rate: float, bands, settings: dict | Non
     rows = [None] * n_streams
 
     def one(s):
-        out[s], rows[s] = run_calls(audio[s], sample_rate, bands, settings, calls, clamp)
+        out[s], rows[s] = run_calls(audio[s], sample_rate, bands, settings, calls, clamp, eq_enabled)
 
     with ThreadPoolExecutor(max_workers=max(1, min(workers, n_streams))) as pool:
         list(pool.map(one, range(n_streams)))
