@@ -1936,6 +1936,63 @@ int af_suppressor_debug_read(af_engine *e, int32_t frame, int32_t stream, float 
   if (p_out) AF_HIP(hipMemcpy(p_out, e->supp.d_P + cell * af::kRnnFreq, sizeof(float2) * af::kRnnFreq, hipMemcpyDeviceToHost));
   return AF_OK;
 }
+// test tap of the pitch path: the whitened pitch buffer of one (frame, stream) cell of the LAST window (`d_ds` is a single set),
+// and the stream's tracker state (last period, last gain) as the last call left it
+int af_suppressor_debug_read_pitch(af_engine *e, int32_t frame, int32_t stream, float *whitened, int32_t *last_period, float *last_gain) {
+  if (!e || !e->supp.d_ds || !e->supp.d_state) return fail(AF_ERR_STATE, "no suppressor window has run");
+  if (stream < 0 || stream >= e->n_streams || (whitened && (frame < 0 || frame >= e->supp.ws_frames)))
+    return fail(AF_ERR_INVALID_ARGUMENT, "frame/stream out of range");
+  AF_HIP(e->use_device());
+  AF_HIP(hipDeviceSynchronize());
+  float ds[af::kPitchBuf / 2], state[2];
+  static_assert(af::SuppState::kLastGain == af::SuppState::kLastPeriod + 1, "last period and gain are neighbours");
+  if (whitened) {
+    const size_t cell = (size_t)frame * e->n_streams + stream;
+    AF_HIP(hipMemcpy(ds, e->supp.d_ds + cell * (af::kPitchBuf / 2), sizeof ds, hipMemcpyDeviceToHost));
+  }
+  AF_HIP(hipMemcpy(state, e->supp.d_state + (size_t)stream * af::SuppState::kCount + af::SuppState::kLastPeriod, sizeof state,
+                   hipMemcpyDeviceToHost));
+  if (whitened) std::memcpy(whitened, ds, sizeof ds);  // (outputs are written only once every copy has succeeded)
+  if (last_period) *last_period = (int32_t)state[0];
+  if (last_gain) *last_gain = state[1];
+  return AF_OK;
+}
+// test tap: ONLY the pitch search kernel, through the launcher the engine uses, on caller-supplied model-input spans
+// [stream][1728 + 480 n_frames] (host pointers): its whitened buffers [frame][stream][864] and its own pitch index
+// [frame][stream] -- the one the tracker overwrites in an engine run.  No engine, no state.
+int af_suppressor_debug_pitch_search(const float *spans, int32_t n_streams, int32_t n_frames, float *whitened, int32_t *pitch_index,
+                                     int32_t device) {
+  if (!spans || !whitened || !pitch_index) return fail(AF_ERR_INVALID_ARGUMENT, "null argument");
+  if (n_streams < 1 || n_streams > 4096 || n_frames < 1 || n_frames > 64)
+    return fail(AF_ERR_INVALID_ARGUMENT, "n_streams must be in [1, 4096] and n_frames in [1, 64]");
+  AF_HIP(hipSetDevice(device));
+  const size_t cells = (size_t)n_frames * n_streams;
+  const size_t span_floats = (size_t)n_streams * (af::kPitchBuf + (size_t)n_frames * af::kRnnFrame);
+  af::DeviceBuffer<float> d_xh, d_ds;
+  af::DeviceBuffer<af::SuppFrameRec> d_rec;
+  AF_HIP(d_xh.reserve_exact(sizeof(float) * span_floats));
+  AF_HIP(d_ds.reserve_exact(sizeof(float) * cells * (af::kPitchBuf / 2)));
+  AF_HIP(d_rec.reserve_exact(sizeof(af::SuppFrameRec) * cells));
+  std::vector<float> ds(cells * (af::kPitchBuf / 2));
+  std::vector<af::SuppFrameRec> rec(cells);
+  af::SuppArgs sa{};
+  sa.xh = d_xh;
+  sa.ds = d_ds;
+  sa.rec = d_rec;
+  sa.n_streams = n_streams;
+  sa.n_frames = n_frames;
+  hipError_t err = hipMemcpy(d_xh, spans, sizeof(float) * span_floats, hipMemcpyHostToDevice);
+  if (err == hipSuccess) err = hipMemset(d_ds, 0xFF, sizeof(float) * ds.size());  // (a cell the kernel leaves out reads as NaN)
+  if (err == hipSuccess) err = hipMemset(d_rec, 0xFF, sizeof(af::SuppFrameRec) * cells);
+  if (err == hipSuccess) err = af::launch_suppressor_pitch_search(sa, af::SuppTables{}, nullptr);  // (the search reads no table)
+  if (err == hipSuccess) err = hipDeviceSynchronize();
+  if (err == hipSuccess) err = hipMemcpy(ds.data(), d_ds, sizeof(float) * ds.size(), hipMemcpyDeviceToHost);
+  if (err == hipSuccess) err = hipMemcpy(rec.data(), d_rec, sizeof(af::SuppFrameRec) * cells, hipMemcpyDeviceToHost);
+  if (err != hipSuccess) return fail(AF_ERR_BACKEND, "pitch search probe failed: %s", hipGetErrorString(err));
+  std::memcpy(whitened, ds.data(), sizeof(float) * ds.size());
+  for (size_t c = 0; c < cells; ++c) pitch_index[c] = rec[c].pitch_index;
+  return AF_OK;
+}
 
 // ---- presets: several chain configurations in one engine, one per 64-stream group
 int af_engine_set_preset_count(af_engine *e, int32_t n) {

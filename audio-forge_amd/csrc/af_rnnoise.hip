@@ -2792,15 +2792,28 @@ hipError_t launch_suppressor_prefilter(const SuppArgs &a, hipStream_t stream) {
   }
 }
 
-// Analysis of one window: spectra, then pitch + cepstral features (frames in order per stream).
-hipError_t launch_suppressor_analysis(const SuppArgs &a, const SuppTables &tb, hipStream_t stream) {
+// Analysis of one window, its three launches: spectra; the pitch search (four frames of a stream per workgroup); the pitch
+// tracker + cepstral features (frames in order per stream).  The search alone is also what af_suppressor_debug_pitch_search runs.
+hipError_t launch_suppressor_spectrum(const SuppArgs &a, const SuppTables &tb, hipStream_t stream) {
   const int64_t units = (int64_t)a.n_streams * ((a.n_frames + kFramesPerWave - 1) / kFramesPerWave);
   const unsigned cells = (unsigned)((units + kFftWaves - 1) / kFftWaves);  // four units (waves) per transform workgroup
   hipLaunchKernelGGL(supp_spectrum_kernel, dim3(cells), dim3(64 * kFftWaves), 0, stream, a, tb);
+  return hipGetLastError();
+}
+hipError_t launch_suppressor_pitch_search(const SuppArgs &a, const SuppTables &tb, hipStream_t stream) {
   const unsigned groups = (unsigned)((a.n_frames + kPsFrames - 1) / kPsFrames);
   hipLaunchKernelGGL(supp_pitchsearch4_kernel, dim3((unsigned)a.n_streams * groups), dim3(64 * kPsFrames), 0, stream, a, tb);
+  return hipGetLastError();
+}
+hipError_t launch_suppressor_pitch_tracker(const SuppArgs &a, const SuppTables &tb, hipStream_t stream) {
   hipLaunchKernelGGL(supp_pitch_kernel, dim3(a.n_streams), dim3(64), 0, stream, a, tb);
   return hipGetLastError();
+}
+hipError_t launch_suppressor_analysis(const SuppArgs &a, const SuppTables &tb, hipStream_t stream) {
+  hipError_t err = launch_suppressor_spectrum(a, tb, stream);
+  if (err == hipSuccess) err = launch_suppressor_pitch_search(a, tb, stream);
+  if (err == hipSuccess) err = launch_suppressor_pitch_tracker(a, tb, stream);
+  return err;
 }
 
 // The rest of the window: pitch-aligned spectra, the network, resynthesis, overlap-add.

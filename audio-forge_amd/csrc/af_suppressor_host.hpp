@@ -13,6 +13,10 @@
 namespace af {
 
 hipError_t launch_suppressor_analysis(const SuppArgs &a, const SuppTables &tb, hipStream_t stream);
+// its three launches, in order (launch_suppressor_analysis calls exactly these)
+hipError_t launch_suppressor_spectrum(const SuppArgs &a, const SuppTables &tb, hipStream_t stream);
+hipError_t launch_suppressor_pitch_search(const SuppArgs &a, const SuppTables &tb, hipStream_t stream);
+hipError_t launch_suppressor_pitch_tracker(const SuppArgs &a, const SuppTables &tb, hipStream_t stream);
 hipError_t launch_suppressor_synthesis(const SuppArgs &a, const SuppTables &tb, const RnnDeviceWeights &w, hipStream_t stream,
                                        hipEvent_t after_network, hipStream_t finish_stream);
 hipError_t launch_suppressor_prefilter(const SuppArgs &a, hipStream_t stream);

@@ -166,6 +166,8 @@ SIGNATURES = {
     "af_suppressor_set_raw_protocol": (C.c_int, [_vp, _i32]),
     "af_suppressor_latency_samples": (_i32, [_vp]),
     "af_suppressor_debug_read": (C.c_int, [_vp, _i32, _i32, _fp, _fp, _fp]),
+    "af_suppressor_debug_read_pitch": (C.c_int, [_vp, _i32, _i32, _fp, C.POINTER(_i32), _fp]),
+    "af_suppressor_debug_pitch_search": (C.c_int, [_fp, _i32, _i32, _fp, C.POINTER(_i32), _i32]),
     "af_eq_set_band_frequency": (C.c_int, [_vp, _i32, _d]),
     "af_eq_set_band_gain": (C.c_int, [_vp, _i32, _d]),
     "af_eq_set_band_q": (C.c_int, [_vp, _i32, _d]),

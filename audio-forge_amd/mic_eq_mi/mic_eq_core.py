@@ -269,6 +269,34 @@ class Engine:
                 "gains_raw": rec[110:132].copy(), "gains": rec[132:154].copy(), "silence": silence, "pitch_index": pitch,
                 "X": X, "P": P}
 
+    def suppressor_debug_read_pitch(self, frame: int | None, stream: int) -> dict:
+        """The pitch path's test tap: ``whitened`` [864] float32, the LPC-whitened 2x-decimated pitch buffer of one
+        (frame, stream) cell of the LAST window (``frame`` None: left out), and the stream's tracker state as the last call
+        left it, ``last_period`` (int) and ``last_gain`` (float32)."""
+        ds = None if frame is None else np.zeros(864, dtype=np.float32)
+        period, gain = C.c_int32(0), C.c_float(0.0)
+        fp = C.POINTER(C.c_float)
+        _lib.check(self._lib.af_suppressor_debug_read_pitch(self._h, 0 if frame is None else int(frame), int(stream),
+                                                            None if ds is None else ds.ctypes.data_as(fp), C.byref(period),
+                                                            C.byref(gain)))
+        return {"whitened": ds, "last_period": int(period.value), "last_gain": np.float32(gain.value)}
+
+    @staticmethod
+    def suppressor_debug_pitch_search(spans, device: int = 0) -> tuple[np.ndarray, np.ndarray]:
+        """The pitch search kernel alone (no engine state), launched as the engine launches it, on model-input ``spans``
+        [streams, 1728 + 480 n_frames] float32: (whitened buffers [n_frames, streams, 864] float32, the search's own pitch
+        index [n_frames, streams] int32 -- the one the tracker overwrites in an engine run)."""
+        x = np.ascontiguousarray(spans, dtype=np.float32)
+        if x.ndim != 2 or x.shape[1] <= 1728 or (x.shape[1] - 1728) % 480:
+            raise ValueError("spans must be [streams, 1728 + 480 n_frames]")
+        n_streams, n_frames = x.shape[0], (x.shape[1] - 1728) // 480
+        ds = np.zeros((n_frames, n_streams, 864), dtype=np.float32)
+        pitch = np.zeros((n_frames, n_streams), dtype=np.int32)
+        fp = C.POINTER(C.c_float)
+        _lib.check(_lib.load().af_suppressor_debug_pitch_search(x.ctypes.data_as(fp), n_streams, n_frames, ds.ctypes.data_as(fp),
+                                                                pitch.ctypes.data_as(C.POINTER(C.c_int32)), int(device)))
+        return ds, pitch
+
     def process_device(self, in_ptr: int, out_ptr: int, n_samples: int, stream_stride: int,
                        layout: int = _lib.LAYOUT_STREAM_MAJOR, hip_stream: int = 0) -> None:
         """Device pointers (e.g. ``tensor.data_ptr()``); asynchronous on ``hip_stream``."""

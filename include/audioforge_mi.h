@@ -244,6 +244,18 @@ int af_suppressor_read_trace(af_engine *e, int32_t *out, int64_t capacity_frames
  * (frame, stream) cell of the last suppressor window */
 int af_suppressor_debug_read(af_engine *e, int32_t frame, int32_t stream, float *record, float *x_spectrum,
                              float *p_spectrum);
+/* test tap of the pitch path (synchronises): the LPC-whitened, 2x-decimated pitch buffer (864 floats) of one (frame, stream)
+ * cell of the last suppressor window (`whitened` null: skipped, `frame` ignored), and the stream's tracker state as the last
+ * call left it: last_period, last_gain (null pointers are skipped).  AF_ERR_STATE before the first window,
+ * AF_ERR_INVALID_ARGUMENT out of range; nothing is written then. */
+int af_suppressor_debug_read_pitch(af_engine *e, int32_t frame, int32_t stream, float *whitened, int32_t *last_period,
+                                   float *last_gain);
+/* test tap: the pitch search kernel ALONE (decimation, whitening, coarse + fine search, interpolation offset), launched as the
+ * engine launches it, on caller-supplied model-input spans [stream][1728 + 480 n_frames] (host pointers; frame f's pitch buffer
+ * is span[480 (f + 1) .. 480 (f + 1) + 1728)).  Returns the whitened buffers [frame][stream][864] and the search's own pitch
+ * index [frame][stream], which the tracker overwrites in an engine run.  n_streams in [1, 4096], n_frames in [1, 64]. */
+int af_suppressor_debug_pitch_search(const float *spans, int32_t n_streams, int32_t n_frames, float *whitened,
+                                     int32_t *pitch_index, int32_t device);
 
 /* ---- ParametricEQ: rust-core/src/dsp/eq.rs --------------------------------------- */
 int af_eq_set_band_frequency(af_engine *e, int32_t band, double frequency_hz); /* eq.rs:419-425 */

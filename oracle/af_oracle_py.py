@@ -504,7 +504,8 @@ class RnnDebug(C.Structure):
     on the Python side."""
     _fields_ = [("Ex", C.c_float * 22), ("Ep", C.c_float * 22), ("Exp", C.c_float * 22), ("features", C.c_float * 42),
                 ("gains", C.c_float * 22), ("X", C.c_float * 962), ("P", C.c_float * 962), ("pitch_index", C.c_int),
-                ("silence", C.c_int), ("pitch_gain", C.c_float), ("pf_margin", C.c_float), ("gains_raw", C.c_float * 22)]
+                ("silence", C.c_int), ("pitch_gain", C.c_float), ("pf_margin", C.c_float), ("gains_raw", C.c_float * 22),
+                ("pitch_ds", C.c_float * 864), ("search_index", C.c_int), ("pitch_ops", C.c_float * 13)]
 
 
 RNN_WEIGHT_BYTES = 87_503  # the fifteen int8 arrays of afo_rnn_weights, no padding between them
@@ -550,14 +551,18 @@ class RnnoiseTap:
 
     def run(self, audio) -> dict:
         """Whole frames of `audio` (+-1 full scale).  Returns arrays with a leading frame axis: Ex Ep Exp [22], features [42],
-        gains_raw gains [22], X P [481] complex64, silence pitch_index (int32), out [480] (+-1 full scale)."""
+        gains_raw gains [22], X P [481] complex64, silence pitch_index (int32), out [480] (+-1 full scale); of the pitch path
+        pitch_ds [864] (the whitened buffer), search_index (int32, the search's own index), pitch_gain, pitch_ops [13] (the
+        f32 operands of its comparisons, af_rnnoise.h)."""
         x = np.ascontiguousarray(audio, dtype=np.float32)
         frames = x.size // 480
         keys = ("Ex", "Ep", "Exp", "features", "gains_raw", "gains")
         res = {k: np.zeros((frames, 42 if k == "features" else 22), dtype=np.float32) for k in keys}
         res.update(X=np.zeros((frames, 481), dtype=np.complex64), P=np.zeros((frames, 481), dtype=np.complex64),
                    silence=np.zeros(frames, dtype=np.int32), pitch_index=np.zeros(frames, dtype=np.int32),
-                   out=np.zeros((frames, 480), dtype=np.float32))
+                   out=np.zeros((frames, 480), dtype=np.float32), pitch_ds=np.zeros((frames, 864), dtype=np.float32),
+                   search_index=np.zeros(frames, dtype=np.int32), pitch_gain=np.zeros(frames, dtype=np.float32),
+                   pitch_ops=np.zeros((frames, 13), dtype=np.float32))
         L = self._L
         fout = np.zeros(480, dtype=np.float32)
         set_rnn_eval_order(self.eval_order)
@@ -578,9 +583,34 @@ class RnnoiseTap:
                 res["X"][f] = np.ctypeslib.as_array(d.X).view(np.complex64)
                 res["P"][f] = np.ctypeslib.as_array(d.P).view(np.complex64)
                 res["silence"][f], res["pitch_index"][f] = d.silence, d.pitch_index
+                res["pitch_ds"][f] = np.ctypeslib.as_array(d.pitch_ds)
+                res["pitch_ops"][f] = np.ctypeslib.as_array(d.pitch_ops)
+                res["search_index"][f], res["pitch_gain"][f] = d.search_index, d.pitch_gain
         finally:
             set_rnn_eval_order(0)
         return res
+
+
+def rnn_pitch_search(pitch_buf, eval_order: int = 0) -> dict:
+    """afo_rnn_debug_pitch_search: the restatement's search alone on one pitch buffer [1728] of model-input samples:
+    pitch_ds [864], search_index, and the search's comparison operands a b c (pitch_ops[0:3])."""
+    L = lib()
+    fp = C.POINTER(C.c_float)
+    L.afo_rnn_debug_pitch_search.restype = C.c_int
+    L.afo_rnn_debug_pitch_search.argtypes = [fp, fp]
+    L.afo_rnn_debug_last.restype = C.POINTER(RnnDebug)
+    L.afo_rnn_debug_last.argtypes = []
+    x = np.ascontiguousarray(pitch_buf, dtype=np.float32)
+    if x.shape != (1728,):
+        raise ValueError("pitch buffer must be [1728]")
+    ds = np.zeros(864, dtype=np.float32)
+    set_rnn_eval_order(int(eval_order))
+    try:
+        index = int(L.afo_rnn_debug_pitch_search(_fptr(x), _fptr(ds)))
+        ops = np.ctypeslib.as_array(L.afo_rnn_debug_last().contents.pitch_ops)[:3].copy()
+    finally:
+        set_rnn_eval_order(0)
+    return {"pitch_ds": ds, "search_index": index, "pitch_ops": ops}
 
 
 def scale_sample_for_model(sample: float) -> float:

@@ -460,12 +460,27 @@ static void pitch_search(const float *x_lp, const float *y, int len, int max_pit
   }
   find_best_pitch(xcorr, y, len >> 1, max_pitch >> 1, best_pitch);
   int offset = 0;
+  afo_rnn_last.pitch_ops[0] = afo_rnn_last.pitch_ops[1] = afo_rnn_last.pitch_ops[2] = 0;
   if (best_pitch[0] > 0 && best_pitch[0] < (max_pitch >> 1) - 1) {
     float a = xcorr[best_pitch[0] - 1], b = xcorr[best_pitch[0]], c = xcorr[best_pitch[0] + 1];
+    afo_rnn_last.pitch_ops[0] = a; afo_rnn_last.pitch_ops[1] = b; afo_rnn_last.pitch_ops[2] = c;
     if ((c - a) > .7f * (b - a)) offset = 1;
     else if ((a - c) > .7f * (b - c)) offset = -1;
   }
   *pitch = 2 * best_pitch[0] - offset;
+}
+
+/* test tap: the search alone on one pitch buffer of 1728 model-input samples: writes the whitened buffer (864), returns the
+ * search's index (what remove_doubling is given); the calling thread's tap holds the search's pitch_ops[0..2] */
+int afo_rnn_debug_pitch_search(const float *pitch_buf, float *ds_out) {
+  float ds[PBUF >> 1];
+  int pitch;
+  pitch_downsample(pitch_buf, ds, PBUF);
+  pitch_search(ds + (PMAX >> 1), ds, PFRAME, PMAX - 3 * PMIN, &pitch);
+  memcpy(ds_out, ds, sizeof ds);
+  memcpy(afo_rnn_last.pitch_ds, ds, sizeof ds);
+  afo_rnn_last.search_index = PMAX - pitch;
+  return PMAX - pitch;
 }
 
 static float compute_pitch_gain(float xy, float xx, float yy) { return xy / sqrtf(1 + xx * yy); }
@@ -501,6 +516,7 @@ static float remove_doubling(const float *x, int maxperiod, int minperiod, int N
   float best_xy = xy, best_yy = yy;
   float g, g0;
   g = g0 = compute_pitch_gain(xy, xx, yy);
+  { float *ops = afo_rnn_last.pitch_ops; ops[3] = xx; ops[4] = xy; ops[5] = yy; ops[6] = g0; }
   for (int k = 2; k <= 15; ++k) {
     int T1 = (2 * T0 + k) / (2 * k);
     if (T1 < minperiod) break;
@@ -528,6 +544,7 @@ static float remove_doubling(const float *x, int maxperiod, int minperiod, int N
   if ((xc[2] - xc[0]) > .7f * (xc[1] - xc[0])) offset = 1;
   else if ((xc[0] - xc[2]) > .7f * (xc[1] - xc[2])) offset = -1;
   if (pg > g) pg = g;
+  { float *ops = afo_rnn_last.pitch_ops; ops[7] = best_xy; ops[8] = best_yy; ops[9] = xc[0]; ops[10] = xc[1]; ops[11] = xc[2]; ops[12] = pg; }
   *T0_ = 2 * T + offset;
   if (*T0_ < minperiod0) *T0_ = minperiod0;
   return pg;
@@ -720,6 +737,8 @@ float afo_rnn_process_frame(const afo_rnn_weights *w, afo_rnn_state *st, float *
   int pitch_index;
   pitch_search(pitch_ds + (PMAX >> 1), pitch_ds, PFRAME, PMAX - 3 * PMIN, &pitch_index);
   pitch_index = PMAX - pitch_index;
+  memcpy(afo_rnn_last.pitch_ds, pitch_ds, sizeof pitch_ds);
+  afo_rnn_last.search_index = pitch_index;
   float gain = remove_doubling(pitch_ds, PMAX, PMIN, PFRAME, &pitch_index, st->last_period, st->last_gain);
   st->last_period = pitch_index;
   st->last_gain = gain;

@@ -42,9 +42,19 @@ typedef struct {
   float pitch_gain;
   float pf_margin; /* min over bands of |Exp - g| where pitch_filter branches (Exp > g); 1e30 on a silent frame */
   float gains_raw[22]; /* the network's output, before g = max(g, 0.6 lastg); `gains` is after it.  Both 0 on a silent frame */
+  /* the pitch path: the LPC-whitened 2x-decimated buffer, the search's own index (768 - pitch_search's result, what
+   * remove_doubling is given), and the f32 operands of the path's comparisons (tests measure their distance from f64):
+   * search a b c = fine xcorr[best - 1 .. best + 1] (0 where no offset applies); tracker xx, xy(T0), yy(T0), g0, best_xy,
+   * best_yy, xc[0..2] at the chosen T, the returned gain */
+  float pitch_ds[864];
+  int search_index;
+  float pitch_ops[13];
 } afo_rnn_debug;
 extern __thread afo_rnn_debug afo_rnn_last;
 const afo_rnn_debug *afo_rnn_debug_last(void); /* the calling thread's tap */
+/* the pitch search alone (pitch_downsample + pitch_search) on one pitch buffer of 1728 model-input samples: writes the
+ * whitened buffer (864 floats), returns the search's index; pitch_ops[0..2] of the calling thread's tap are the search's */
+int afo_rnn_debug_pitch_search(const float *pitch_buf, float *ds_out);
 
 void afo_rnn_weights_synthetic(afo_rnn_weights *w, uint64_t seed);
 void afo_rnn_state_init(afo_rnn_state *st);
