@@ -12,6 +12,7 @@
 #include <vector>
 
 #include "af_api_internal.hpp"
+#include "af_numpy_rules.h"
 #include "af_noise_reference_host.hpp"
 #include "af_spectrum_host.hpp"
 
@@ -43,11 +44,7 @@ const double kNan = std::numeric_limits<double>::quiet_NaN();
 
 double nr_percentile(std::vector<double> v, double q) {  // np.percentile, method "linear", with its two-sided lerp
   std::sort(v.begin(), v.end());
-  const int n = (int)v.size();
-  const double idx = (q / 100.0) * (double)(n - 1);
-  const int lo = std::min(std::max((int)std::floor(idx), 0), n - 1), hi = std::min(lo + 1, n - 1);
-  const double t = idx - (double)lo, a = v[(size_t)lo], b = v[(size_t)hi], diff = b - a;
-  return t >= 0.5 ? b - diff * (1.0 - t) : a + diff * t;
+  return af_percentile_sorted(v.data(), (int)v.size(), q);  // the one restatement of the rule, af_numpy_rules.h
 }
 
 double nr_median(std::vector<double> v) {  // np.median

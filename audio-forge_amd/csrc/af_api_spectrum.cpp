@@ -11,6 +11,7 @@
 #include <vector>
 
 #include "af_api_internal.hpp"
+#include "af_numpy_rules.h"
 #include "af_spectrum_host.hpp"
 
 struct af_voice_spectrum {
@@ -60,13 +61,7 @@ struct af_voice_spectrum {
 namespace {
 
 double vs_percentile_sorted(const std::vector<double> &s, double q) {  // np.percentile, method "linear"
-  const int n = (int)s.size();
-  const double idx = (q / 100.0) * (double)(n - 1);
-  const int lo = std::min(std::max((int)std::floor(idx), 0), n - 1), hi = std::min(lo + 1, n - 1);
-  const double t = idx - (double)lo, a = s[(size_t)lo], b = s[(size_t)hi], diff = b - a;
-  double r = a + diff * t;
-  if (t >= 0.5) r = b - diff * (1.0 - t);
-  return r;
+  return af_percentile_sorted(s.data(), (int)s.size(), q);  // the one restatement of the rule, af_numpy_rules.h
 }
 
 double vs_median(std::vector<double> v) {  // np.median
@@ -75,20 +70,7 @@ double vs_median(std::vector<double> v) {  // np.median
   return n % 2 ? v[n / 2] : (v[n / 2 - 1] + v[n / 2]) / 2.0;
 }
 
-double vs_interp(double x, const std::vector<double> &xp, const std::vector<double> &fp) {  // np.interp, ends held
-  const int n = (int)xp.size();
-  if (x < xp[0]) return fp[0];
-  if (x >= xp[(size_t)n - 1]) return fp[(size_t)n - 1];
-  int lo = 0, hi = n - 1;
-  while (hi - lo > 1) {
-    const int mid = (lo + hi) / 2;
-    if (x >= xp[(size_t)mid]) lo = mid; else hi = mid;
-  }
-  const double slope = (fp[(size_t)lo + 1] - fp[(size_t)lo]) / (xp[(size_t)lo + 1] - xp[(size_t)lo]);
-  return slope * (x - xp[(size_t)lo]) + fp[(size_t)lo];
-}
-
-double vs_interp(double x, const double *xp, const double *fp, int n) {  // the same over plain arrays
+double vs_interp(double x, const double *xp, const double *fp, int n) {  // np.interp, ends held
   if (x < xp[0]) return fp[0];
   if (x >= xp[n - 1]) return fp[n - 1];
   int lo = 0, hi = n - 1;
@@ -140,18 +122,14 @@ void vs_decide(const double *sums /* [C][2] */, int F, int N, uint32_t fs, const
   d.vad_used = false;
   d.vad_active = 0.0;
   if (vad && n_vad > 0) {  // _interpolate_vad_probabilities, :172-197
-    std::vector<double> xp((size_t)n_vad), fp((size_t)n_vad);
+    std::vector<double> xp((size_t)n_vad), fp((size_t)n_vad), posts((size_t)F);
     const int64_t win = std::max<int64_t>(1, (int64_t)std::ceil((double)fs * (double)af::kVsSileroWindow / (double)af::kVsSileroRate));
-    for (int64_t i = 0; i < n_vad; ++i) {
-      xp[(size_t)i] = ((double)i + 0.5) * (double)win;
-      fp[(size_t)i] = std::min(std::max(vad[i], 0.0), 1.0);
-    }
+    af_interpolate_vad_probabilities(vad, n_vad, win, F, hop, N, xp.data(), fp.data(), posts.data());  // shared with the speech features
     const double support = std::max(af::kVsRmsGateDb, floor_db + 0.25 * wide);
     std::vector<uint8_t> combined((size_t)F);
     int count = 0, active = 0;
     for (int f = 0; f < F; ++f) {
-      const double centre = (double)((int64_t)f * hop) + (double)N * 0.5;
-      const double post = vs_interp(centre, xp, fp);
+      const double post = posts[(size_t)f];
       active += post >= af::kVsVadEvidence;
       combined[(size_t)f] = (post >= af::kVsVadEvidence && d.rms[(size_t)f] >= support) || post >= af::kVsVadStrong;
       count += combined[(size_t)f];
@@ -858,6 +836,27 @@ int af_voice_spectrum_last_kernel_ms(af_voice_spectrum *h, double *ms) {
     AF_HIP(h->events.elapsed(i, i + 1, &span));
     *ms += span;
   }
+  return AF_OK;
+}
+
+int af_voice_spectrum_smooth_rows(af_voice_spectrum *h, const double *rows_db, int32_t n_rows, double *out) {
+  if (!h || !rows_db || !out) return fail(AF_ERR_INVALID_ARGUMENT, "null argument");
+  if (n_rows <= 0) return fail(AF_ERR_INVALID_ARGUMENT, "n_rows must be positive");
+  AF_HIP(hipSetDevice(h->device));
+  h->touched_device = true;
+  if (int rc = vs_upload_tables(h)) return rc;
+  const size_t K = (size_t)h->bins, P = af::kVsSmoothPasses, MB = af::kVsMaxBands, bytes = sizeof(double) * K * (size_t)n_rows;
+  const int32_t *tb = h->d_bands;
+  std::vector<int32_t> index((size_t)n_rows);
+  for (int32_t i = 0; i < n_rows; ++i) index[(size_t)i] = i;
+  AF_HIP(h->d_rows_db.reserve_exact(bytes));  // (every call synchronises before it returns: the per-tile scratch is free)
+  AF_HIP(h->d_rows_smooth.reserve_exact(bytes));
+  AF_HIP(h->d_smooth_rows.reserve_exact(sizeof(int32_t) * (size_t)n_rows));
+  AF_HIP(hipMemcpy(h->d_rows_db, rows_db, bytes, hipMemcpyHostToDevice));
+  AF_HIP(hipMemcpy(h->d_smooth_rows, index.data(), sizeof(int32_t) * (size_t)n_rows, hipMemcpyHostToDevice));
+  AF_HIP(af::launch_vs_smooth(h->d_rows_db, h->d_smooth_rows, n_rows, (int32_t)K, tb, h->d_centre, tb + P, tb + P + P * MB,
+                              tb + P + 2 * P * MB, tb + P + 2 * P * MB + K, h->d_freqs, h->d_rows_smooth, nullptr));
+  AF_HIP(hipMemcpy(out, h->d_rows_smooth, bytes, hipMemcpyDeviceToHost));
   return AF_OK;
 }
 

@@ -6,6 +6,7 @@
 // same order.  The column medians over the PSD rows are af_spectrum.hip's launch_vs_median.
 #include <hip/hip_runtime.h>
 
+#include "af_mixed_radix_fft.h"
 #include "af_noise_reference_host.hpp"
 
 namespace af {
@@ -91,47 +92,6 @@ __global__ void __launch_bounds__(kNrThreads) nr_frame_power_kernel(const float 
   if (lane == 0) power[id] = q / (double)N;
 }
 
-__device__ inline double2 nr_cmul(double2 a, double2 t) { return make_double2(a.x * t.x - a.y * t.y, a.x * t.y + a.y * t.x); }
-
-// One decimation-in-frequency stage of radix P over sub-transforms of length L = P * Ls: the butterfly at offset j of a block
-// takes a[q] = buf[base + j + q Ls] and leaves (sum over q, in index order, of a[q] W_P^(q r)) W_L^(j r) at buf[base + j + r Ls].
-// Output 0 needs no product; the others start from a[0] and multiply from q = 1 on.  tw[2 e] = exp(-2 pi i e / M).
-template <int P>
-__device__ void nr_stage(double2 *buf, int M, int L, const double2 *__restrict__ tw) {
-  const int Ls = L / P, root = M / P, scale = M / L;
-  for (int b = threadIdx.x; b < M / P; b += blockDim.x) {
-    const int j = b % Ls, base = (b / Ls) * L + j;
-    double2 a[P], y[P];
-#pragma unroll
-    for (int q = 0; q < P; ++q) a[q] = buf[base + q * Ls];
-#pragma unroll
-    for (int r = 0; r < P; ++r) {
-      double2 acc = a[0];
-#pragma unroll
-      for (int q = 1; q < P; ++q) {
-        const double2 t = r == 0 ? a[q] : nr_cmul(a[q], tw[2 * (((q * r) % P) * root)]);
-        acc = make_double2(acc.x + t.x, acc.y + t.y);
-      }
-      y[r] = r == 0 ? acc : nr_cmul(acc, tw[2 * (j * r * scale)]);
-    }
-#pragma unroll
-    for (int r = 0; r < P; ++r) buf[base + r * Ls] = y[r];
-  }
-  __syncthreads();
-}
-
-// where Z[k] of the M-point transform ends: k = r1 + p1 (r2 + p2 (...)) sits at r1 M / p1 + r2 M / (p1 p2) + ...
-__device__ inline int nr_digit_reverse(int k, int M, const NrPlan &plan) {
-  int pos = 0, stride = M;
-  for (int i = 0; i < plan.n_factors; ++i) {
-    const int p = plan.factor[i];
-    stride /= p;
-    pos += (k % p) * stride;
-    k /= p;
-  }
-  return pos;
-}
-
 __global__ void __launch_bounds__(kNrThreads) nr_frame_kernel(const float *__restrict__ noise, int64_t noise_stride,
                                                                const double *__restrict__ noise_sums, int32_t noise_chunks,
                                                                const float *__restrict__ voice, int64_t voice_stride,
@@ -150,23 +110,10 @@ __global__ void __launch_bounds__(kNrThreads) nr_frame_kernel(const float *__res
   for (int m = tid; m < M; m += T)
     nr_buf[m] = make_double2((nr_sample(x, 2 * m) - mean) * window[2 * m], (nr_sample(x, 2 * m + 1) - mean) * window[2 * m + 1]);
   __syncthreads();
-  for (int i = 0, L = M; i < plan.n_factors; ++i) {
-    const int p = plan.factor[i];
-    if (p == 2) nr_stage<2>(nr_buf, M, L, tw);
-    else if (p == 3) nr_stage<3>(nr_buf, M, L, tw);
-    else if (p == 5) nr_stage<5>(nr_buf, M, L, tw);
-    else nr_stage<7>(nr_buf, M, L, tw);
-    L /= p;
-  }
+  nr_transform(nr_buf, M, plan, tw);
   // the real transform from the half-length one, as vs_bin_power: tw[k] = exp(-2 pi i k / N)
   double *row = psd + (int64_t)it.row * (M + 1);
-  for (int k = tid; k <= M; k += T) {
-    const double2 a = nr_buf[nr_digit_reverse(k % M, M, plan)], b = nr_buf[nr_digit_reverse((M - k) % M, M, plan)], t = tw[k];
-    const double er = 0.5 * (a.x + b.x), ei = 0.5 * (a.y - b.y);
-    const double orr = 0.5 * (a.y + b.y), oi = -0.5 * (a.x - b.x);
-    const double xr = er + (orr * t.x - oi * t.y), xi = ei + (orr * t.y + oi * t.x);
-    row[k] = (xr * xr + xi * xi) / sumw2;
-  }
+  for (int k = tid; k <= M; k += T) row[k] = nr_real_bin_power(nr_buf, k, M, plan, tw) / sumw2;
   __syncthreads();  // every read of the transform is done: the buffer now takes the row, for the band sums
   double *pw = reinterpret_cast<double *>(nr_buf);
   for (int k = tid; k <= M; k += T) pw[k] = row[k];  // each thread reads back what it wrote

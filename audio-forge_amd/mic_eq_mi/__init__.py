@@ -45,6 +45,10 @@ _OPERATORS = (
     "analyze_voice_capture_batch",
     "analyze_noise_reference",
     "analyze_noise_reference_batch",
+    "measure_speech_features_batch",
+    "recommend_voice_chain",
+    "recommend_voice_chain_batch",
+    "configure_voice_chain",
     "suppress",
     "rnnoise_benchmark",
 )
@@ -61,10 +65,11 @@ VoiceSpectrum = getattr(_core_module, "VoiceSpectrum", None) if _core_module is 
 VoiceSpectrumResult = getattr(_core_module, "VoiceSpectrumResult", None) if _core_module is not None else None
 NoiseReference = getattr(_core_module, "NoiseReference", None) if _core_module is not None else None
 NoiseReferenceAnalysis = getattr(_core_module, "NoiseReferenceAnalysis", None) if _core_module is not None else None
+SpeechFeatures = getattr(_core_module, "SpeechFeatures", None) if _core_module is not None else None
 CaptureMetadata = getattr(_core_module, "CaptureMetadata", None) if _core_module is not None else None
 new_noise_suppression_engine = (getattr(_core_module, "new_noise_suppression_engine", _missing_core)
                                 if _core_module is not None else _missing_core)
 
-__all__ = ["CORE_AVAILABLE", "Engine", "NoiseSuppressor", "NoiseModel", "StreamResampler", "Mixdown", "VoiceSpectrum", "VoiceSpectrumResult", "NoiseReference", "NoiseReferenceAnalysis", "CaptureMetadata",
+__all__ = ["CORE_AVAILABLE", "Engine", "NoiseSuppressor", "NoiseModel", "StreamResampler", "Mixdown", "VoiceSpectrum", "VoiceSpectrumResult", "NoiseReference", "NoiseReferenceAnalysis", "SpeechFeatures", "CaptureMetadata",
            "new_noise_suppression_engine", *_OPERATORS, "LAYOUT_STREAM_MAJOR", "LAYOUT_TIME_MAJOR", "KERNEL_AUTO",
            "KERNEL_LANE_PER_STREAM", "KERNEL_PHASED", "KERNEL_QUAD", "KERNEL_STAGED"]

@@ -136,6 +136,56 @@ class NoiseReferenceOutputs(C.Structure):
         "in_capture_middles")]
 
 
+class SpeechFeaturesRow(C.Structure):
+    _fields_ = ([(name, C.c_int32) for name in (
+                    "non_finite", "frames", "active_frames", "spectral_frames", "noise_frames", "vad_probability_used",
+                    "short_term_window_count", "loudness_window_count", "evidence_available", "reserved")]
+                + [(name, C.c_double) for name in (
+                    "active_duration_s", "active_ratio", "vad_active_frame_ratio", "short_term_lufs", "momentary_lufs",
+                    "active_loudness_spread_db", "loudness_range_db", "band_low_db", "band_body_db", "band_presence_db",
+                    "band_sibilance_db", "sibilance_excess_db", "confidence", "frame_probability_p90", "frame_probability_top_mean",
+                    "temporal_score", "absolute_hf_strength_p90", "noise_reliability_p90", "excess_p90_db", "temporal_contrast_db",
+                    "candidate_frame_ratio", "candidate_snr_db", "peak_hz", "adaptive_floor_db")])
+
+
+class SpeechFeaturesOutputs(C.Structure):
+    _fields_ = [("rows", C.POINTER(SpeechFeaturesRow)), ("frame_db", C.POINTER(C.c_double)), ("active_frame_mask", C.POINTER(C.c_uint8)),
+                ("frame_indices", C.POINTER(C.c_int32)), ("frame_probabilities", C.POINTER(C.c_double)),
+                ("frame_feature_rows", C.POINTER(C.c_double)), ("frame_power", C.POINTER(C.c_double)),
+                ("chunk_energy", C.POINTER(C.c_double)), ("band_sums", C.POINTER(C.c_double)),
+                ("sibilance_middles", C.POINTER(C.c_double)), ("sibilance_argmax", C.POINTER(C.c_int32)),
+                ("sibilance_rows", C.POINTER(C.c_double)), ("noise_band_sums", C.POINTER(C.c_double)),
+                ("weighted_sums", C.POINTER(C.c_double)), ("weighted_argmax", C.POINTER(C.c_int32))]
+
+
+class VoiceSetupInputs(C.Structure):
+    _fields_ = [("features", C.POINTER(SpeechFeaturesRow)), ("frame_db", C.POINTER(C.c_double)),
+                ("active_frame_mask", C.POINTER(C.c_uint8)), ("freqs", C.POINTER(C.c_double)), ("spectrum_db", C.POINTER(C.c_double)),
+                ("bins", C.c_int32), ("used_single_spectrum_fallback", C.c_int32), ("residual_confidence", C.c_double),
+                ("snr_db", C.c_double), ("noise_quality_score", C.c_double), ("conservative_noise_rms_db", C.c_double),
+                ("noise_status", C.c_int32), ("vad_available", C.c_int32), ("target_lufs", C.c_double),
+                ("dynamics_intensity", C.c_int32), ("reserved", C.c_int32), ("custom_target_p95_db", C.c_double),
+                ("custom_peak_cap_db", C.c_double), ("enable_probability_threshold", C.c_double)]
+
+
+class VoiceSetupRecommendation(C.Structure):
+    _fields_ = ([(name, C.c_double) for name in (
+                    "speech_floor_db", "speech_body_db", "speech_frame_peak_db", "speech_snr_db", "snr_confidence", "capture_confidence",
+                    "gate_threshold_db", "gate_vad_threshold", "gate_vad_hold_time_ms", "gate_vad_pre_gain", "gate_margin_db")]
+                + [(name, C.c_int32) for name in ("gate_mode", "gate_auto_threshold_enabled", "deesser_enabled",
+                                                  "deesser_frame_evidence_available", "deesser_invalid_evidence", "reserved")]
+                + [(name, C.c_double) for name in (
+                    "deesser_auto_amount", "deesser_low_cut_hz", "deesser_high_cut_hz", "deesser_ratio", "deesser_max_reduction_db",
+                    "deesser_sibilance_excess_db", "deesser_peak_hz", "deesser_frame_evidence_confidence",
+                    "deesser_detection_probability")]
+                + [("deesser_clip_features", C.c_double * 6)]
+                + [(name, C.c_int32) for name in ("compressor_auto_makeup_enabled", "compressor_profile")]
+                + [(name, C.c_double) for name in (
+                    "compressor_threshold_db", "compressor_ratio", "compressor_attack_ms", "compressor_release_ms",
+                    "compressor_makeup_gain_db", "compressor_base_release_ms", "compressor_target_lufs", "compressor_target_p95_db",
+                    "compressor_target_median_db", "compressor_peak_cap_db", "compressor_noise_reference_reliability")])
+
+
 # every symbol include/audioforge_mi.h declares: name -> (restype, argtypes)
 _vp, _i32, _i64, _d, _f, _sz = C.c_void_p, C.c_int32, C.c_int64, C.c_double, C.c_float, C.c_size_t
 _fp, _dp = C.POINTER(C.c_float), C.POINTER(C.c_double)
@@ -344,6 +394,7 @@ SIGNATURES = {
     "af_voice_spectrum_last_reliability_kernel_ms": (C.c_int, [_vp, _dp, _i32]),
     "af_voice_spectrum_read_reliability": (C.c_int, [_vp, C.POINTER(VoiceSpectrumReliabilityOutputs)]),
     "af_voice_spectrum_set_noise_override": (C.c_int, [_vp, _dp, _dp, _i32, _i32, _i64, _i32]),
+    "af_voice_spectrum_smooth_rows": (C.c_int, [_vp, _dp, _i32, _dp]),
     "af_noise_reference_create": (C.c_int, [C.c_uint32, _i32, C.POINTER(_vp)]),
     "af_noise_reference_destroy": (None, [_vp]),
     "af_noise_reference_frame_size": (_i32, [_vp]),
@@ -354,6 +405,20 @@ SIGNATURES = {
     "af_noise_reference_analyze_device": (C.c_int, [_vp, _vp, _i64, _i32, _i64, _vp, _i64, _i64, _dp, _i64, _dp, _i64, _dp,
                                                     C.POINTER(C.c_uint32), C.POINTER(NoiseReferenceOutputs)]),
     "af_noise_reference_last_kernel_ms": (C.c_int, [_vp, _dp, _i32]),
+    "af_speech_features_create": (C.c_int, [C.c_uint32, _i32, _i64, _i64, _i32, C.POINTER(_vp)]),
+    "af_speech_features_destroy": (None, [_vp]),
+    "af_speech_features_frames": (_i64, [_i64]),
+    "af_speech_features_chunks": (_i64, [_i64]),
+    "af_speech_features_sibilance_bins": (_i32, [_vp]),
+    "af_speech_features_set_frame_model": (C.c_int, [_vp, _d, _dp]),
+    "af_speech_features_get_frame_model": (C.c_int, [_vp, _dp, _dp]),
+    "af_speech_features_analyze_host": (C.c_int, [_vp, _fp, _i64, _i32, _i64, _dp, _dp, _i64, _fp, _i64, _i64,
+                                                  C.POINTER(SpeechFeaturesOutputs)]),
+    "af_speech_features_analyze_device": (C.c_int, [_vp, _vp, _i64, _i32, _i64, _dp, _dp, _i64, _vp, _i64, _i64,
+                                                    C.POINTER(SpeechFeaturesOutputs)]),
+    "af_speech_features_last_kernel_ms": (C.c_int, [_vp, _dp, _i32]),
+    "af_voice_setup_default_inputs": (None, [C.POINTER(VoiceSetupInputs)]),
+    "af_voice_setup_recommend": (C.c_int, [C.POINTER(VoiceSetupInputs), C.POINTER(VoiceSetupRecommendation)]),
     "af_gate_process_host": (C.c_int, [_fp, _fp, _i64, _i32, _i64, _d, _d, _d, _d, _i32, _i32, _fp, C.POINTER(C.c_uint64), _i32]),
     "af_measure_integrated_loudness_device": (C.c_int, [_vp, _i64, _i32, _i64, C.c_uint32, _i32, _dp, C.POINTER(_i32)]),
     "af_measure_integrated_loudness_host": (C.c_int, [_fp, _i64, _i32, _i64, C.c_uint32, _i32, _dp, C.POINTER(_i32)]),
@@ -381,6 +446,8 @@ VALUE_FUNCTIONS = {
     "af_output_writer_destroy", "af_output_writer_max_output_frames",
     "af_voice_spectrum_destroy", "af_voice_spectrum_bins", "af_voice_spectrum_frames",
     "af_noise_reference_destroy", "af_noise_reference_frame_size", "af_noise_reference_bins", "af_noise_reference_frames",
+    "af_speech_features_destroy", "af_speech_features_frames", "af_speech_features_chunks", "af_speech_features_sibilance_bins",
+    "af_voice_setup_default_inputs",
 }
 
 _lib = None

@@ -1696,6 +1696,17 @@ class VoiceSpectrum:
     def frames(self, n_samples: int) -> int:
         return int(self._lib.af_voice_spectrum_frames(self._h, int(n_samples)))
 
+    def smooth(self, spectra_db) -> np.ndarray:
+        """smooth_spectrum_perceptual "balanced" (spectrum.py:949-967) of spectra_db [n, bins] (or one [bins]) on this
+        object's grid, on the device: the pass every voiced window goes through."""
+        rows = np.ascontiguousarray(np.atleast_2d(spectra_db), dtype=np.float64)
+        if rows.ndim != 2 or rows.shape[1] != self.bins or rows.shape[0] == 0:
+            raise ValueError(f"spectra_db must be [n, {self.bins}]")
+        out = np.empty_like(rows)
+        dp = C.POINTER(C.c_double)
+        _lib.check(self._lib.af_voice_spectrum_smooth_rows(self._h, rows.ctypes.data_as(dp), rows.shape[0], out.ctypes.data_as(dp)))
+        return out if np.ndim(spectra_db) == 2 else out[0]
+
     def set_noise_override(self, noise_override=None) -> None:
         """noise_spectrum_override of spectrum.py:554-569 for the calls that follow: (freqs [n], spectrum_db [n] for every stream
         or [n_streams, n]), or None to clear it.  A stream whose override is not at least two finite points falls through."""
@@ -2296,3 +2307,331 @@ def analyze_voice_capture_batch(noise_audio, speech_audio, fs: int = 48_000, npe
                                            noise_spectrum_override=override, noise_reference_source_override="validated_conservative",
                                            device=device)
     return references, spectra
+
+
+SPEECH_FEATURES_KERNELS = ("frame_powers", "k_weighting", "frame_spectra", "frame_medians", "weighted_peak")
+_SPEECH_FEATURES_EVIDENCE = ("frame_probability_p90", "frame_probability_top_mean", "temporal_score", "absolute_hf_strength_p90",
+                             "noise_reliability_p90")
+
+
+class SpeechFeatures:
+    """_vad_masked_speech_features (voice_setup.py:161-458) for a batch of voice captures on the device.  48 kHz only (any other
+    rate raises NotImplementedError: the reference resamples to 48 kHz before it K-weights, which is not built); scratch is
+    kept between calls."""
+
+    def __init__(self, sample_rate: int = 48_000, max_streams: int = 4096, max_speech_samples: int = 48_000 * 60,
+                 max_noise_samples: int = 48_000 * 60, device: int = 0):
+        self._lib = _lib.load()
+        handle = C.c_void_p()
+        _lib.check(self._lib.af_speech_features_create(int(sample_rate), int(max_streams), int(max_speech_samples),
+                                                       int(max_noise_samples), int(device), C.byref(handle)))
+        self._h = handle
+        self.sample_rate = int(sample_rate)
+        self.sibilance_bins = int(self._lib.af_speech_features_sibilance_bins(handle))
+
+    def close(self) -> None:
+        if getattr(self, "_h", None):
+            self._lib.af_speech_features_destroy(self._h)
+            self._h = None
+
+    __del__ = close
+
+    def frames(self, n_samples: int) -> int:
+        return int(self._lib.af_speech_features_frames(int(n_samples)))
+
+    def chunks(self, n_samples: int) -> int:
+        return int(self._lib.af_speech_features_chunks(int(n_samples)))
+
+    def set_frame_model(self, intercept: float, coefficients) -> None:
+        """FRAME_INTERCEPT and FRAME_COEFFICIENTS of deesser_fusion.py:30-41 (the defaults)."""
+        w = np.ascontiguousarray(coefficients, dtype=np.float64)
+        if w.shape != (6,):
+            raise ValueError("coefficients must be six values")
+        _lib.check(self._lib.af_speech_features_set_frame_model(self._h, float(intercept), w.ctypes.data_as(C.POINTER(C.c_double))))
+
+    def frame_model(self) -> tuple:
+        intercept, w = C.c_double(), np.zeros(6)
+        _lib.check(self._lib.af_speech_features_get_frame_model(self._h, C.byref(intercept), w.ctypes.data_as(C.POINTER(C.c_double))))
+        return float(intercept.value), w
+
+    def analyze(self, speech, noise_rms_db, vad_probabilities=None, noise_audio=None, device_pointers=None, internals: bool = False) -> dict:
+        """speech [n_streams, n] and noise_audio [n_streams, m] | None, float32 (host), or with `device_pointers=(d_speech, n,
+        n_streams, speech_stride, d_noise | None, m, noise_stride)` device memory.  Returns arrays by field: the scalars of
+        af_speech_features_row as [n_streams] arrays, frame_db and active_frame_mask [n_streams, frames], and frame_indices,
+        frame_probabilities, frame_feature_rows whose first spectral_frames entries per stream are filled.  `internals` adds
+        what the kernels left."""
+        dp, fp = C.POINTER(C.c_double), C.POINTER(C.c_float)
+        if device_pointers is None:
+            x = np.ascontiguousarray(speech, dtype=np.float32)
+            if x.ndim != 2:
+                raise ValueError("speech must be [n_streams, n]")
+            B, n = x.shape
+            z = None if noise_audio is None else np.ascontiguousarray(noise_audio, dtype=np.float32)
+            if z is not None and (z.ndim != 2 or z.shape[0] != B):
+                raise ValueError("noise_audio must be [n_streams, n_noise]")
+            m = 0 if z is None else z.shape[1]
+        else:
+            n, B, m = int(device_pointers[1]), int(device_pointers[2]), int(device_pointers[5]) if device_pointers[4] is not None else 0
+        level = np.ascontiguousarray(noise_rms_db, dtype=np.float64).reshape(-1)
+        if level.size != B:
+            raise ValueError("noise_rms_db must have one entry per stream")
+        vad = None if vad_probabilities is None else np.ascontiguousarray(vad_probabilities, dtype=np.float64)
+        if vad is not None and (vad.ndim != 2 or vad.shape[0] != B or vad.shape[1] == 0):
+            raise ValueError("vad_probabilities must be [n_streams, n_vad] with n_vad >= 1")
+        F, Cn, Fn, S = max(self.frames(n), 0), self.chunks(n), self.frames(m), self.sibilance_bins
+        rows = (_lib.SpeechFeaturesRow * B)()
+        out = dict(frame_db=np.zeros((B, F)), active_frame_mask=np.zeros((B, F), dtype=np.uint8),
+                   frame_indices=np.zeros((B, F), dtype=np.int32), frame_probabilities=np.zeros((B, F)),
+                   frame_feature_rows=np.zeros((B, F, 6)))
+        if internals:
+            out.update(frame_power=np.zeros((B, F)), chunk_energy=np.zeros((B, Cn)), band_sums=np.zeros((B, F, 8)),
+                       sibilance_middles=np.zeros((B, F, 2)), sibilance_argmax=np.zeros((B, F), dtype=np.int32),
+                       sibilance_rows=np.zeros((B, F, S)), noise_band_sums=np.zeros((B, Fn)), weighted_sums=np.zeros((B, S)),
+                       weighted_argmax=np.zeros(B, dtype=np.int32))
+        kinds = {np.dtype(np.float64): C.c_double, np.dtype(np.uint8): C.c_uint8, np.dtype(np.int32): C.c_int32}
+        o = _lib.SpeechFeaturesOutputs(rows=rows, **{k: a.ctypes.data_as(C.POINTER(kinds[a.dtype])) for k, a in out.items()})
+        tail = (level.ctypes.data_as(dp), None if vad is None else vad.ctypes.data_as(dp), 0 if vad is None else vad.shape[1])
+        if device_pointers is None:
+            rc = self._lib.af_speech_features_analyze_host(self._h, x.ctypes.data_as(fp), n, B, n, *tail,
+                                                           None if z is None else z.ctypes.data_as(fp), m, m, C.byref(o))
+        else:
+            d_speech, _, _, stride, d_noise, _, noise_stride = device_pointers
+            rc = self._lib.af_speech_features_analyze_device(self._h, C.c_void_p(int(d_speech)), n, B, int(stride), *tail,
+                                                             None if d_noise is None else C.c_void_p(int(d_noise)), m, int(noise_stride),
+                                                             C.byref(o))
+        _lib.check(rc)
+        for name, _ in _lib.SpeechFeaturesRow._fields_:
+            if name != "reserved":
+                out[name] = np.array([getattr(r, name) for r in rows])
+        return out
+
+    def last_kernel_ms(self) -> dict:
+        """GPU ms of each stage of the last call, summed over its tiles."""
+        ms = (C.c_double * 5)()
+        _lib.check(self._lib.af_speech_features_last_kernel_ms(self._h, ms, 5))
+        return dict(zip(SPEECH_FEATURES_KERNELS, (float(x) for x in ms)))
+
+
+def _speech_features_dicts(r: dict) -> list:
+    """One dict per stream with the keys of voice_setup.py:432-458; None for a stream with a non-finite sample."""
+    results = []
+    for s in range(len(r["frames"])):
+        if r["non_finite"][s]:
+            results.append(None)
+            continue
+        A = int(r["spectral_frames"][s])
+        value = lambda name: float(r[name][s])  # noqa: E731
+        evidence = {"available": bool(r["evidence_available"][s]), "confidence": value("confidence"),
+                    "frame_probabilities": r["frame_probabilities"][s, :A].copy(), "frame_feature_rows": r["frame_feature_rows"][s, :A].copy(),
+                    "frame_indices": r["frame_indices"][s, :A].astype(np.int64)}
+        if evidence["available"]:
+            evidence.update({name: value(name) for name in _SPEECH_FEATURES_EVIDENCE})
+        evidence.update({name: value(name) for name in ("excess_p90_db", "temporal_contrast_db", "candidate_frame_ratio",
+                                                        "candidate_snr_db", "peak_hz")})
+        results.append({
+            "frame_db": r["frame_db"][s].copy(), "active_frame_mask": r["active_frame_mask"][s].astype(bool),
+            "active_duration_s": value("active_duration_s"), "active_ratio": value("active_ratio"),
+            "vad_probability_used": bool(r["vad_probability_used"][s]), "vad_active_frame_ratio": value("vad_active_frame_ratio"),
+            "short_term_lufs": value("short_term_lufs"), "short_term_window_count": int(r["short_term_window_count"][s]),
+            "momentary_lufs": value("momentary_lufs"), "active_loudness_spread_db": value("active_loudness_spread_db"),
+            "loudness_range_db": value("loudness_range_db"), "loudness_window_count": int(r["loudness_window_count"][s]),
+            "band_energy_db": {"low": value("band_low_db"), "body": value("band_body_db"), "presence": value("band_presence_db"),
+                               "sibilance": value("band_sibilance_db")},
+            "sibilance_excess_db": value("sibilance_excess_db"), "deesser_frame_evidence": evidence})
+    return results
+
+
+def measure_speech_features_batch(speech, fs: int, noise_rms_db, *, vad_probabilities=None, noise_audio=None, device: int = 0) -> list:
+    """_vad_masked_speech_features (voice_setup.py:161-458) of every row of speech [n_streams, n]: a list of dicts with the
+    reference's keys (samples are taken as float32).  noise_rms_db: one level per stream; vad_probabilities [n_streams, n_vad] or
+    None; noise_audio [n_streams, m] or None.  A stream with a non-finite sample yields None."""
+    x = np.asarray(speech)
+    if x.ndim != 2:
+        raise ValueError("speech must be [n_streams, n]")
+    m = 0 if noise_audio is None else np.asarray(noise_audio).shape[-1]
+    sf = SpeechFeatures(fs, x.shape[0], max(x.shape[1], 1920), m, device)
+    try:
+        return _speech_features_dicts(sf.analyze(x, noise_rms_db, vad_probabilities, noise_audio))
+    finally:
+        sf.close()
+
+
+TARGET_LUFS_BY_CURVE = {"broadcast": -16.0, "streaming": -16.0, "podcast": -17.0, "flat": -18.0}  # voice_setup.py:53-58
+DYNAMICS_INTENSITIES = ("gentle", "balanced", "dense", "custom")  # AF_DYNAMICS_*
+DEESSER_MODEL_VERSION = "deesser-soft-fusion-v1"  # deesser_fusion.py:7
+DEESSER_CLIP_FEATURE_NAMES = ("frame_probability_p90", "frame_probability_top_mean", "candidate_support", "temporal_contrast",
+                              "absolute_hf_strength_p90", "noise_reliability_p90")  # deesser_fusion.py:19-26
+DEESSER_ENABLE_PROBABILITY_THRESHOLD = 0.4935253581578833  # deesser_fusion.py:57
+
+
+def recommend_voice_chain(features: dict, stream: int, freqs, smoothed_spectrum_db, *, residual_confidence: float, snr_db: float,
+                          used_single_spectrum_fallback: bool, noise_quality_score: float, noise_status: str,
+                          conservative_noise_rms_db: float, target_preset: str = "broadcast", vad_available: bool = True,
+                          dynamics_intensity: str = "balanced", custom_target_p95_db: float = 3.5, custom_peak_cap_db: float = 8.0,
+                          enable_probability_threshold: float = DEESSER_ENABLE_PROBABILITY_THRESHOLD) -> dict:
+    """The rules of voice_setup.py:1143-1223 for one stream of a SpeechFeatures.analyze result: ``gate``, ``deesser`` and
+    ``compressor`` with the key names and value types of _recommend_gate_settings, _recommend_deesser_settings and
+    _recommend_compressor_settings (plus noise_reference_reliability, :1220), ``deesser_diagnostics``,
+    ``compressor_diagnostics``, ``capture_confidence`` and the level percentiles behind them.  What the other analyses measured
+    is taken as arguments: the perceptually smoothed median spectrum on its grid, residual_confidence, snr_db and
+    used_single_spectrum_fallback of the voice spectrum, and quality_score, status and conservative_noise_rms_db of the noise
+    reference.  It returns no EQ bands, no calibrated compressor threshold and no offline validation."""
+    lib = _lib.load()
+    dp = C.POINTER(C.c_double)
+    row = _lib.SpeechFeaturesRow(**{name: kind(features[name][stream]) for name, kind in
+                                    ((n, int if t is C.c_int32 else float) for n, t in _lib.SpeechFeaturesRow._fields_ if n != "reserved")})
+    frame_db = np.ascontiguousarray(features["frame_db"][stream], dtype=np.float64)
+    mask = np.ascontiguousarray(features["active_frame_mask"][stream], dtype=np.uint8)
+    f = np.ascontiguousarray(freqs, dtype=np.float64)
+    db = np.ascontiguousarray(smoothed_spectrum_db, dtype=np.float64)
+    if f.ndim != 1 or f.shape != db.shape or f.size == 0:
+        raise ValueError("freqs and smoothed_spectrum_db must be equal-length vectors")
+    if noise_status not in NOISE_REFERENCE_STATUS:
+        raise ValueError(f"noise_status must be one of {NOISE_REFERENCE_STATUS}")
+    profile = str(dynamics_intensity).lower()
+    inputs = _lib.VoiceSetupInputs()
+    lib.af_voice_setup_default_inputs(C.byref(inputs))
+    inputs.features = C.pointer(row)
+    inputs.frame_db, inputs.active_frame_mask = frame_db.ctypes.data_as(dp), mask.ctypes.data_as(C.POINTER(C.c_uint8))
+    inputs.freqs, inputs.spectrum_db, inputs.bins = f.ctypes.data_as(dp), db.ctypes.data_as(dp), f.size
+    inputs.used_single_spectrum_fallback = int(bool(used_single_spectrum_fallback))
+    inputs.residual_confidence, inputs.snr_db = float(residual_confidence), float(snr_db)
+    inputs.noise_quality_score, inputs.conservative_noise_rms_db = float(noise_quality_score), float(conservative_noise_rms_db)
+    inputs.noise_status, inputs.vad_available = NOISE_REFERENCE_STATUS.index(noise_status), int(bool(vad_available))
+    inputs.target_lufs = TARGET_LUFS_BY_CURVE.get(target_preset, -18.0)
+    inputs.dynamics_intensity = DYNAMICS_INTENSITIES.index(profile) if profile in DYNAMICS_INTENSITIES else 1
+    inputs.custom_target_p95_db, inputs.custom_peak_cap_db = float(custom_target_p95_db), float(custom_peak_cap_db)
+    inputs.enable_probability_threshold = float(enable_probability_threshold)
+    r = _lib.VoiceSetupRecommendation()
+    _lib.check(lib.af_voice_setup_recommend(C.byref(inputs), C.byref(r)))
+    name = DYNAMICS_INTENSITIES[r.compressor_profile]
+    gate = {"enabled": True, "threshold_db": r.gate_threshold_db, "attack_ms": 5.0, "release_ms": 120.0, "gate_mode": int(r.gate_mode),
+            "vad_threshold": r.gate_vad_threshold, "vad_hold_time_ms": r.gate_vad_hold_time_ms, "vad_pre_gain": r.gate_vad_pre_gain,
+            "auto_threshold_enabled": bool(r.gate_auto_threshold_enabled), "gate_margin_db": r.gate_margin_db}
+    deesser = {"enabled": bool(r.deesser_enabled), "auto_enabled": True, "auto_amount": r.deesser_auto_amount,
+               "low_cut_hz": r.deesser_low_cut_hz, "high_cut_hz": r.deesser_high_cut_hz, "threshold_db": -28.0, "ratio": r.deesser_ratio,
+               "attack_ms": 2.0, "release_ms": 80.0, "max_reduction_db": r.deesser_max_reduction_db}
+    value = lambda key: float(features[key][stream])  # noqa: E731
+    deesser_diagnostics = {
+        "enabled": bool(r.deesser_enabled), "sibilance_excess_db": r.deesser_sibilance_excess_db, "peak_hz": r.deesser_peak_hz,
+        "frame_evidence_available": bool(r.deesser_frame_evidence_available),
+        "frame_evidence_confidence": r.deesser_frame_evidence_confidence, "detection_probability": r.deesser_detection_probability,
+        "enable_probability_threshold": float(enable_probability_threshold), "model_version": DEESSER_MODEL_VERSION,
+        "clip_features": dict(zip(DEESSER_CLIP_FEATURE_NAMES, (float(x) for x in r.deesser_clip_features))),
+        "invalid_evidence": bool(r.deesser_invalid_evidence), "temporal_contrast_db": value("temporal_contrast_db"),
+        "candidate_frame_ratio": value("candidate_frame_ratio"), "candidate_snr_db": value("candidate_snr_db")}
+    compressor = {"enabled": True, "threshold_db": r.compressor_threshold_db, "ratio": r.compressor_ratio,
+                  "attack_ms": r.compressor_attack_ms, "release_ms": r.compressor_release_ms,
+                  "makeup_gain_db": r.compressor_makeup_gain_db, "adaptive_release": True,
+                  "base_release_ms": r.compressor_base_release_ms, "auto_makeup_enabled": bool(r.compressor_auto_makeup_enabled),
+                  "target_lufs": r.compressor_target_lufs, "sidechain_highpass_enabled": True,
+                  "measured_short_term_lufs": value("short_term_lufs"), "measured_loudness_range_db": value("loudness_range_db"),
+                  "dynamics_intensity": name, "target_p95_reduction_db": r.compressor_target_p95_db,
+                  "peak_reduction_cap_db": r.compressor_peak_cap_db,
+                  "noise_reference_reliability": r.compressor_noise_reference_reliability}
+    compressor_diagnostics = {"auto_makeup_enabled": bool(r.compressor_auto_makeup_enabled), "target_lufs": r.compressor_target_lufs,
+                              "dynamics_intensity": name, "target_p95_reduction_db": r.compressor_target_p95_db,
+                              "target_median_reduction_db": r.compressor_target_median_db,
+                              "peak_reduction_cap_db": r.compressor_peak_cap_db}
+    return {"gate": gate, "deesser": deesser, "compressor": compressor, "deesser_diagnostics": deesser_diagnostics,
+            "compressor_diagnostics": compressor_diagnostics, "capture_confidence": r.capture_confidence,
+            "snr_confidence": r.snr_confidence, "speech_floor_db": r.speech_floor_db, "speech_body_db": r.speech_body_db,
+            "speech_frame_peak_db": r.speech_frame_peak_db, "speech_snr_db": r.speech_snr_db}
+
+
+def configure_voice_chain(engine: Engine, recommendation: Mapping[str, Any]) -> None:
+    """Hand the gate, de-esser and compressor dicts of recommend_voice_chain to an engine's setters, unchanged.  vad_pre_gain
+    has no setter (it only reaches a Silero instance, which this engine does not have) and is not applied."""
+    gate, deesser, compressor = recommendation["gate"], recommendation["deesser"], recommendation["compressor"]
+    engine.set_gate_enabled(int(gate["enabled"]))
+    engine.gate_set_threshold(gate["threshold_db"])
+    engine.gate_set_attack_time(gate["attack_ms"])
+    engine.gate_set_release_time(gate["release_ms"])
+    engine.gate_set_mode(int(gate["gate_mode"]))
+    engine.gate_set_vad_threshold(gate["vad_threshold"])
+    engine.gate_set_hold_time(gate["vad_hold_time_ms"])
+    engine.gate_set_margin(gate["gate_margin_db"])
+    engine.gate_set_auto_threshold(int(gate["auto_threshold_enabled"]))
+    engine.set_deesser_enabled(int(deesser["enabled"]))
+    engine.deesser_set_auto_enabled(int(deesser["auto_enabled"]))
+    engine.deesser_set_auto_amount(deesser["auto_amount"])
+    engine.deesser_set_low_cut_hz(deesser["low_cut_hz"])
+    engine.deesser_set_high_cut_hz(deesser["high_cut_hz"])
+    engine.deesser_set_threshold_db(deesser["threshold_db"])
+    engine.deesser_set_ratio(deesser["ratio"])
+    engine.deesser_set_attack_ms(deesser["attack_ms"])
+    engine.deesser_set_release_ms(deesser["release_ms"])
+    engine.deesser_set_max_reduction_db(deesser["max_reduction_db"])
+    engine.set_compressor_enabled(int(compressor["enabled"]))
+    engine.compressor_set_threshold(compressor["threshold_db"])
+    engine.compressor_set_ratio(compressor["ratio"])
+    engine.compressor_set_attack_time(compressor["attack_ms"])
+    engine.compressor_set_release_time(compressor["release_ms"])
+    engine.compressor_set_makeup_gain(compressor["makeup_gain_db"])
+    engine.compressor_set_adaptive_release(int(compressor["adaptive_release"]))
+    engine.compressor_set_base_release_time(compressor["base_release_ms"])
+    engine.compressor_set_auto_makeup_enabled(int(compressor["auto_makeup_enabled"]))
+    engine.compressor_set_target_lufs(compressor["target_lufs"])
+    engine.compressor_set_sidechain_highpass_enabled(int(compressor["sidechain_highpass_enabled"]))
+    engine.compressor_set_noise_reference_reliability(compressor["noise_reference_reliability"])
+
+
+NOISE_MIN_DURATION_S, SPEECH_MIN_DURATION_S = 1.5, 3.0  # voice_setup.py:42-43
+
+
+def recommend_voice_chain_batch(noise_audio, speech_audio, fs: int, target_preset: str = "broadcast", *, vad_probabilities=None,
+                                noise_vad_probabilities=None, vad_available: bool = True, dynamics_intensity: str = "balanced",
+                                custom_target_p95_db: float = 3.5, custom_peak_cap_db: float = 8.0, noise_metadata=None,
+                                speech_metadata=None, device: int = 0) -> list:
+    """analyze_voice_setup (voice_setup.py:1082-1223) for every pair of noise_audio [n_streams, m] and speech_audio
+    [n_streams, n] up to its three rule-based recommendations: analyze_voice_capture_batch (the noise reference, then the voice
+    spectrum with the conservative spectrum as its override), the "balanced" smoothing of the median spectrum, the speech
+    features against the conservative noise level, and the rules.  Per pair a dict with ``gate``, ``deesser``, ``compressor``
+    (the reference's keys and value types), ``deesser_diagnostics``, ``compressor_diagnostics``, ``capture_confidence`` and
+    ``features`` (the dict of measure_speech_features_batch), plus the level percentiles, the noise reference's status and
+    conservative level and the spectrum's noise-referenced SNR behind them.
+
+    vad_probabilities [n_streams, n_vad] are the voice capture's posteriors per 32 ms model window and
+    noise_vad_probabilities [n_streams, k] the room tone's; the reference gets both from its native VAD helper.
+    ``vad_available=True`` with no probabilities behaves as the reference does without that helper: the energy fallback, with
+    gate_mode still 1.  ``vad_available=False`` ignores any probabilities, as the reference never asks for them then.  Captures
+    below 1.5 s of room tone or 3 s of voice are refused with the reference's messages (:1099-1102).
+
+    It does NOT return EQ bands (the Auto-EQ optimiser is not built), a calibrated compressor threshold (the calibration
+    search is not built: threshold_db is the rule's starting value) or the offline validation and setup confidences."""
+    noise, speech = np.asarray(noise_audio), np.asarray(speech_audio)
+    if noise.ndim != 2 or speech.ndim != 2 or noise.shape[0] != speech.shape[0]:
+        raise ValueError("noise_audio and speech_audio must be [n_streams, m] and [n_streams, n]")
+    if noise.shape[1] < int(fs * NOISE_MIN_DURATION_S):
+        raise ValueError("Room-noise capture was too short for setup.")
+    if speech.shape[1] < int(fs * SPEECH_MIN_DURATION_S):
+        raise ValueError("Voice capture was too short for setup.")
+    if not vad_available:
+        vad_probabilities = noise_vad_probabilities = None
+    sf = SpeechFeatures(fs, speech.shape[0], speech.shape[1], noise.shape[1], device)  # first: it refuses every rate but 48 kHz
+    try:
+        references, spectra = analyze_voice_capture_batch(noise, speech, fs, noise_metadata=noise_metadata, speech_metadata=speech_metadata,
+                                                          noise_vad_probabilities=noise_vad_probabilities,
+                                                          speech_vad_probabilities=vad_probabilities, vad_probabilities=vad_probabilities,
+                                                          device=device)
+        vs = VoiceSpectrum(fs, 4096, device)
+        try:
+            smoothed = vs.smooth(np.stack([r.median_spectrum_db for r in spectra]))
+        finally:
+            vs.close()
+        raw = sf.analyze(speech, [r.conservative_noise_rms_db for r in references], vad_probabilities, noise)
+    finally:
+        sf.close()
+    features = _speech_features_dicts(raw)
+    results = []
+    for s, (reference, spectrum) in enumerate(zip(references, spectra)):
+        rec = recommend_voice_chain(raw, s, spectrum.freqs, smoothed[s], residual_confidence=spectrum.residual_confidence,
+                                    snr_db=spectrum.snr_db, used_single_spectrum_fallback=spectrum.used_single_spectrum_fallback,
+                                    noise_quality_score=reference.quality_score, noise_status=reference.status,
+                                    conservative_noise_rms_db=reference.conservative_noise_rms_db, target_preset=target_preset,
+                                    vad_available=vad_available, dynamics_intensity=dynamics_intensity,
+                                    custom_target_p95_db=custom_target_p95_db, custom_peak_cap_db=custom_peak_cap_db)
+        rec.update(features=features[s], noise_reference_status=reference.status, noise_referenced_snr_db=float(spectrum.snr_db),
+                   conservative_noise_rms_db=float(reference.conservative_noise_rms_db))
+        results.append(rec)
+    return results

@@ -774,6 +774,11 @@ int af_voice_spectrum_last_reliability_kernel_ms(af_voice_spectrum *h, double *m
 int af_voice_spectrum_set_noise_override(af_voice_spectrum *h, const double *freqs, const double *spectrum_db, int32_t n_points,
                                          int32_t n_streams, int64_t stride, int32_t shared);
 
+/* smooth_spectrum_perceptual "balanced" (spectrum.py:949-967) of n_rows host spectra rows_db[n_rows][bins] (dB, on the handle's
+ * grid) into out[n_rows][bins] (host): the pass every voiced window goes through, for spectra of the caller's -- the median
+ * spectrum that the voice-chain recommendation reads (voice_setup.py:1163-1166).  Returns after out is written. */
+int af_voice_spectrum_smooth_rows(af_voice_spectrum *h, const double *rows_db, int32_t n_rows, double *out);
+
 /* ---- room-noise reference analysis: python/mic_eq/analysis/noise_reference.py:118-546 ------------------------------
  * analyze_noise_reference for a batch of capture pairs: the quality verdict on a room-tone capture (duration, finiteness,
  * silence, clipping, stationarity, transients, speech contamination, metadata, age, consistency with the quiet frames of the
@@ -868,6 +873,125 @@ int af_noise_reference_analyze_device(af_noise_reference *h, const float *d_nois
 /* GPU time of the kernels of the last call: ms[0 .. 4) = sample statistics and chunk sums, frame powers, frame spectra with
  * the band sums, column medians (events around them; copies and host decisions are not in it).  capacity: at least 4. */
 int af_noise_reference_last_kernel_ms(af_noise_reference *h, double *ms, int32_t capacity);
+
+/* ---- speech features: python/mic_eq/analysis/voice_setup.py:161-458 ---------------------------------------------
+ * _vad_masked_speech_features for a batch of voice captures: frame levels and the VAD-fused active-speech mask (:178-205),
+ * momentary and short-term loudness of the active speech (:127-158, :214-261), four robust band levels (:263-289) and the
+ * per-frame sibilance evidence with the frame model of deesser_fusion.py:60-78 (:291-430).  Frames are 1920 samples at hop 960.
+ * 48000 Hz only: the reference K-weights at 48 kHz behind scipy's resample_poly (:130-132), which is not restated here, so any
+ * other rate is AF_ERR_UNSUPPORTED at create.  A capture below one frame is AF_ERR_INVALID_ARGUMENT (the reference raises:
+ * its window and frame shapes disagree, :173, :281).  A non-finite sample in a stream's speech capture, or in a whole analysis
+ * frame of its noise capture (what the reference reads of it: samples behind the last whole frame are not examined), sets that
+ * stream's `non_finite`; none of its other fields is defined then, and the other streams are not affected. */
+typedef struct af_speech_features af_speech_features;
+/* one stream: every scalar of the dict at :432-458 and of its deesser_frame_evidence, :291-302 / :410-430 */
+typedef struct af_speech_features_row {
+  int32_t non_finite;
+  int32_t frames;                   /* len(frame_db) */
+  int32_t active_frames;            /* count of active_frame_mask */
+  int32_t spectral_frames;          /* len(frame_indices): active | energy_active, :269 */
+  int32_t noise_frames;             /* analysis frames of the noise capture (0: the percentile-10 fallback of :317 holds) */
+  int32_t vad_probability_used;
+  int32_t short_term_window_count, loudness_window_count;
+  int32_t evidence_available;       /* deesser_frame_evidence["available"] */
+  int32_t reserved;
+  double active_duration_s, active_ratio, vad_active_frame_ratio;
+  double short_term_lufs, momentary_lufs, active_loudness_spread_db, loudness_range_db;
+  double band_low_db, band_body_db, band_presence_db, band_sibilance_db; /* band_energy_db */
+  double sibilance_excess_db;
+  double confidence, frame_probability_p90, frame_probability_top_mean, temporal_score, absolute_hf_strength_p90;
+  double noise_reliability_p90, excess_p90_db, temporal_contrast_db, candidate_frame_ratio, candidate_snr_db, peak_hz;
+  double adaptive_floor_db;         /* :180 */
+} af_speech_features_row;
+/* Where a call writes; every pointer is host memory and may be null.  F = af_speech_features_frames(n), C =
+ * af_speech_features_chunks(n), Fn the same of the noise capture, S = af_speech_features_sibilance_bins(h).  Per-frame rows of
+ * the spectrally active frames fill the first spectral_frames entries of a stream's F; the rest is left as it was. */
+typedef struct af_speech_features_outputs {
+  af_speech_features_row *rows;   /* [n_streams] */
+  double *frame_db;               /* [n_streams][F] :179 */
+  uint8_t *active_frame_mask;     /* [n_streams][F] :189-205 */
+  int32_t *frame_indices;         /* [n_streams][F] :270 */
+  double *frame_probabilities;    /* [n_streams][F] :387 */
+  double *frame_feature_rows;     /* [n_streams][F][6] :373-386 */
+  /* what the kernels left, for tests: */
+  double *frame_power;            /* [n_streams][F] :178 */
+  double *chunk_energy;           /* [n_streams][C] sums of the squared K-weighted samples over hop-sized chunks */
+  double *band_sums;              /* [n_streams][F][8] 80-250 | 250-2000 | 2000-5000 | 5000-10000 | 250-4500 | 5000-9500 Hz | max | 0 */
+  double *sibilance_middles;      /* [n_streams][F][2] lower and upper middle of a frame's 5000-9500 Hz bins */
+  int32_t *sibilance_argmax;      /* [n_streams][F] :352 */
+  double *sibilance_rows;         /* [n_streams][F][S] :347 */
+  double *noise_band_sums;        /* [n_streams][Fn] :337 before its logarithm */
+  double *weighted_sums;          /* [n_streams][S] :393-397 before the division by the weights' sum */
+  int32_t *weighted_argmax;       /* [n_streams] :400 */
+} af_speech_features_outputs;
+int af_speech_features_create(uint32_t sample_rate, int32_t max_streams, int64_t max_speech_samples, int64_t max_noise_samples,
+                              int32_t device, af_speech_features **out);
+void af_speech_features_destroy(af_speech_features *h);
+int64_t af_speech_features_frames(int64_t n_samples);             /* VALUE: 0 below one frame */
+int64_t af_speech_features_chunks(int64_t n_samples);             /* VALUE: hop-sized chunks, the partial tail included */
+int32_t af_speech_features_sibilance_bins(const af_speech_features *h); /* VALUE: bins of 5000-9500 Hz (181) */
+/* deesser_fusion.py:30-41, FRAME_INTERCEPT and FRAME_COEFFICIENTS (the defaults); non-finite values are refused */
+int af_speech_features_set_frame_model(af_speech_features *h, double intercept, const double coefficients[6]);
+int af_speech_features_get_frame_model(const af_speech_features *h, double *intercept, double coefficients[6]);
+/* speech: [n_streams][speech_stride] captures of n_speech >= 1920 samples.  noise_rms_db: [n_streams].  vad_probabilities:
+ * null, or [n_streams][n_vad] posteriors of 1536 samples each (_interpolate_vad_probabilities, spectrum.py:172-197).  noise:
+ * null, or [n_streams][noise_stride] captures of n_noise samples.  _host takes host audio, _device device audio (on the null
+ * stream); the other arrays are host memory.  Both return after the outputs are written. */
+int af_speech_features_analyze_host(af_speech_features *h, const float *speech, int64_t n_speech, int32_t n_streams, int64_t speech_stride,
+                                    const double *noise_rms_db, const double *vad_probabilities, int64_t n_vad, const float *noise,
+                                    int64_t n_noise, int64_t noise_stride, const af_speech_features_outputs *out);
+int af_speech_features_analyze_device(af_speech_features *h, const float *d_speech, int64_t n_speech, int32_t n_streams,
+                                      int64_t speech_stride, const double *noise_rms_db, const double *vad_probabilities, int64_t n_vad,
+                                      const float *d_noise, int64_t n_noise, int64_t noise_stride, const af_speech_features_outputs *out);
+/* GPU time of the kernels of the last call: ms[0 .. 5) = frame powers, K-weighting, frame spectra, medians over frames,
+ * weighted peak (events around them; copies and host decisions are not in it).  capacity: at least 5. */
+int af_speech_features_last_kernel_ms(af_speech_features *h, double *ms, int32_t capacity);
+
+/* ---- voice-chain recommendation: python/mic_eq/analysis/voice_setup.py:1143-1223, 468-696 ------------------------------
+ * The rules that turn one capture pair's measurements into gate, de-esser and compressor settings: the level percentiles of
+ * the active frames (:1143-1153), snr_confidence and capture_confidence with its five caps (:1169-1190),
+ * _recommend_gate_settings (:468-502), _recommend_deesser_settings with predict_clip_probability (:505-624,
+ * deesser_fusion.py:81-87) and _recommend_compressor_settings (:627-696, :1220-1222).  Host only, f64, no HIP call.  What the
+ * other analyses measured comes in as arguments: the speech features, the smoothed median spectrum with residual_confidence,
+ * snr_db and used_single_spectrum_fallback of the voice spectrum, and quality_score, status and conservative_noise_rms_db of
+ * the noise reference. */
+enum { AF_DYNAMICS_GENTLE = 0, AF_DYNAMICS_BALANCED = 1, AF_DYNAMICS_DENSE = 2, AF_DYNAMICS_CUSTOM = 3 };
+typedef struct af_voice_setup_inputs {
+  const af_speech_features_row *features;  /* of this stream; non_finite must be 0 */
+  const double *frame_db;                  /* [features->frames] */
+  const uint8_t *active_frame_mask;        /* [features->frames] */
+  const double *freqs, *spectrum_db;       /* [bins] the smoothed median spectrum on its grid */
+  int32_t bins;
+  int32_t used_single_spectrum_fallback;
+  double residual_confidence, snr_db;      /* of the voice spectrum */
+  double noise_quality_score, conservative_noise_rms_db;
+  int32_t noise_status;                    /* AF_NOISE_STATUS_* */
+  int32_t vad_available;
+  double target_lufs;                      /* TARGET_LUFS_BY_CURVE[target_preset], -18 for an unknown preset (:655) */
+  int32_t dynamics_intensity;              /* AF_DYNAMICS_*; anything else counts as balanced (:653) */
+  int32_t reserved;
+  double custom_target_p95_db, custom_peak_cap_db;
+  double enable_probability_threshold;     /* ENABLE_PROBABILITY_THRESHOLD, deesser_fusion.py:57 */
+} af_voice_setup_inputs;
+typedef struct af_voice_setup_recommendation {
+  double speech_floor_db, speech_body_db, speech_frame_peak_db, speech_snr_db, snr_confidence, capture_confidence;
+  /* gate, :491-502 (enabled, attack_ms 5 and release_ms 120 are constants) */
+  double gate_threshold_db, gate_vad_threshold, gate_vad_hold_time_ms, gate_vad_pre_gain, gate_margin_db;
+  int32_t gate_mode, gate_auto_threshold_enabled;
+  /* de-esser, :584-623 (auto_enabled, threshold_db -28, attack_ms 2 and release_ms 80 are constants) */
+  int32_t deesser_enabled, deesser_frame_evidence_available, deesser_invalid_evidence, reserved;
+  double deesser_auto_amount, deesser_low_cut_hz, deesser_high_cut_hz, deesser_ratio, deesser_max_reduction_db;
+  double deesser_sibilance_excess_db, deesser_peak_hz, deesser_frame_evidence_confidence, deesser_detection_probability;
+  double deesser_clip_features[6];
+  /* compressor, :670-695 */
+  int32_t compressor_auto_makeup_enabled, compressor_profile; /* AF_DYNAMICS_* actually used */
+  double compressor_threshold_db, compressor_ratio, compressor_attack_ms, compressor_release_ms, compressor_makeup_gain_db;
+  double compressor_base_release_ms, compressor_target_lufs, compressor_target_p95_db, compressor_target_median_db;
+  double compressor_peak_cap_db, compressor_noise_reference_reliability;
+} af_voice_setup_recommendation;
+/* the defaults of analyze_voice_setup's arguments: broadcast, balanced, 3.5 / 8.0, VAD available, the published threshold */
+void af_voice_setup_default_inputs(af_voice_setup_inputs *in);
+int af_voice_setup_recommend(const af_voice_setup_inputs *in, af_voice_setup_recommendation *out);
 
 /* ---- NoiseSuppressor: rust-core/src/dsp/noise_suppressor.rs:18-194 ----------------------------------------
  * The runtime-selected suppressor interface (`NoiseModel`, trait `NoiseSuppressor`, `new_noise_suppression_engine`) for a
