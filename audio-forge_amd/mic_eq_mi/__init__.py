@@ -69,7 +69,15 @@ SpeechFeatures = getattr(_core_module, "SpeechFeatures", None) if _core_module i
 CaptureMetadata = getattr(_core_module, "CaptureMetadata", None) if _core_module is not None else None
 new_noise_suppression_engine = (getattr(_core_module, "new_noise_suppression_engine", _missing_core)
                                 if _core_module is not None else _missing_core)
+# the compressor candidate sweep lives in a module of its own
+if _core_module is not None:
+    from .compressor_search import (CompressorSearch, calibrate_compressor, calibrate_compressor_batch, compressor_input_batch,
+                                    simulate_compressor_candidates_batch)
+else:
+    CompressorSearch = None
+    compressor_input_batch = simulate_compressor_candidates_batch = calibrate_compressor = calibrate_compressor_batch = _missing_core
 
 __all__ = ["CORE_AVAILABLE", "Engine", "NoiseSuppressor", "NoiseModel", "StreamResampler", "Mixdown", "VoiceSpectrum", "VoiceSpectrumResult", "NoiseReference", "NoiseReferenceAnalysis", "SpeechFeatures", "CaptureMetadata",
-           "new_noise_suppression_engine", *_OPERATORS, "LAYOUT_STREAM_MAJOR", "LAYOUT_TIME_MAJOR", "KERNEL_AUTO",
+           "new_noise_suppression_engine", *_OPERATORS, "CompressorSearch", "compressor_input_batch", "simulate_compressor_candidates_batch", "calibrate_compressor",
+           "calibrate_compressor_batch", "LAYOUT_STREAM_MAJOR", "LAYOUT_TIME_MAJOR", "KERNEL_AUTO",
            "KERNEL_LANE_PER_STREAM", "KERNEL_PHASED", "KERNEL_QUAD", "KERNEL_STAGED"]

@@ -186,6 +186,51 @@ class VoiceSetupRecommendation(C.Structure):
                     "compressor_target_median_db", "compressor_peak_cap_db", "compressor_noise_reference_reliability")])
 
 
+class CompressorCandidate(C.Structure):
+    _fields_ = [("capture", C.c_int32), ("reserved", C.c_int32), ("threshold_db", C.c_double), ("ratio", C.c_double),
+                ("attack_ms", C.c_double), ("release_ms", C.c_double)]
+
+
+class CompressorBase(C.Structure):
+    _fields_ = [("makeup_gain_db", C.c_double), ("base_release_ms", C.c_double), ("adaptive_release", C.c_int32),
+                ("sidechain_highpass_enabled", C.c_int32)]
+
+
+class ChainSimulation(C.Structure):
+    _fields_ = ([(name, C.c_float) for name in (
+                    "input_sample_peak_db", "input_rms_db", "output_sample_peak_db", "pre_limiter_true_peak_db", "output_true_peak_db",
+                    "output_rms_db", "limiter_effective_ceiling_db", "sample_headroom_db", "pre_limiter_true_peak_headroom_db",
+                    "true_peak_headroom_db", "limiter_gain_reduction_db", "true_peak_limiter_gain_reduction_db")]
+                + [("true_peak_limited_events", C.c_uint64)]
+                + [(name, C.c_float) for name in (
+                    "compressor_gain_reduction_db", "deesser_gain_reduction_db", "compressor_gain_reduction_median_db",
+                    "compressor_gain_reduction_p95_db", "compressor_gain_reduction_active_ratio", "active_output_gain_db",
+                    "silence_output_gain_db", "silence_level_delta_db", "compressor_pumping_score_db")]
+                + [("non_finite_output", C.c_int32)]
+                + [(name, C.c_float) for name in ("deesser_gain_reduction_median_db", "deesser_gain_reduction_p95_db", "analysis_block_ms",
+                                                  "active_analysis_threshold_db")]
+                + [("active_analysis_block_count", C.c_uint64), ("processed_samples", C.c_uint64)]
+                + [(name, C.c_float) for name in ("output_sample_peak", "pre_limiter_true_peak", "output_true_peak", "output_rms")])
+
+
+class CompressorSearchSettings(C.Structure):
+    _fields_ = ([(name, C.c_double) for name in ("threshold_db", "ratio", "attack_ms", "release_ms", "makeup_gain_db", "base_release_ms")]
+                + [(name, C.c_int32) for name in ("adaptive_release", "sidechain_highpass_enabled", "auto_makeup_enabled", "reserved")]
+                + [(name, C.c_double) for name in ("target_lufs", "measured_short_term_lufs", "target_p95_db", "target_median_db",
+                                                   "peak_cap_db")])
+
+
+class CompressorSearchResult(C.Structure):
+    _fields_ = ([(name, C.c_int32) for name in ("backend_available", "expanded_search_selected", "peak_cap_passed", "iterations",
+                                                  "candidate_count", "evaluated_count", "winner", "verification_equals_evaluation")]
+                + [(name, C.c_double) for name in (
+                    "threshold_db", "ratio", "attack_ms", "release_ms", "measured_median_gain_reduction_db",
+                    "measured_p95_gain_reduction_db", "measured_peak_gain_reduction_db", "active_reduction_ratio", "total_objective",
+                    "incumbent_objective", "threshold_only_objective", "expanded_candidate_objective", "active_output_gain_db",
+                    "silence_output_gain_db", "compressor_pumping_score_db", "output_true_peak_db", "pre_limiter_true_peak_headroom_db")]
+                + [("evaluated", (C.c_double * 4) * 67), ("scores", C.c_double * 67)])
+
+
 # every symbol include/audioforge_mi.h declares: name -> (restype, argtypes)
 _vp, _i32, _i64, _d, _f, _sz = C.c_void_p, C.c_int32, C.c_int64, C.c_double, C.c_float, C.c_size_t
 _fp, _dp = C.POINTER(C.c_float), C.POINTER(C.c_double)
@@ -419,6 +464,21 @@ SIGNATURES = {
     "af_speech_features_last_kernel_ms": (C.c_int, [_vp, _dp, _i32]),
     "af_voice_setup_default_inputs": (None, [C.POINTER(VoiceSetupInputs)]),
     "af_voice_setup_recommend": (C.c_int, [C.POINTER(VoiceSetupInputs), C.POINTER(VoiceSetupRecommendation)]),
+    # compressor candidate sweep
+    "af_compressor_search_create": (C.c_int, [_d, _i32, C.POINTER(_vp)]),
+    "af_compressor_search_destroy": (None, [_vp]),
+    "af_compressor_search_set_limiter": (C.c_int, [_vp, _d, _d, _d, _i32]),
+    "af_compressor_search_load_host": (C.c_int, [_vp, _fp, _i64, _i32, _i64, C.POINTER(BlockStats)]),
+    "af_compressor_search_load_device": (C.c_int, [_vp, _vp, _i64, _i32, _i64, C.POINTER(BlockStats)]),
+    "af_compressor_search_sweep": (C.c_int, [_vp, C.POINTER(CompressorCandidate), _i32, C.POINTER(CompressorBase), _i32,
+                                             C.POINTER(ChainSimulation)]),
+    "af_compressor_search_blocks": (_i64, [_vp]),
+    "af_compressor_search_run": (C.c_int, [_vp, C.POINTER(CompressorSearchSettings), C.POINTER(CompressorSearchResult)]),
+    "af_compressor_search_last_run_ms": (C.c_int, [_vp, _dp]),
+    "af_compressor_search_read_masks": (C.c_int, [_vp, _fp, C.POINTER(C.c_uint8), _fp]),
+    "af_compressor_search_read_rows":(C.c_int, [_vp, C.POINTER(BlockStats), _i64]),
+    "af_compressor_search_read_audio": (C.c_int, [_vp, _fp, _i64]),
+    "af_compressor_search_last_kernel_ms": (C.c_int, [_vp, _dp, _dp]),
     "af_gate_process_host": (C.c_int, [_fp, _fp, _i64, _i32, _i64, _d, _d, _d, _d, _i32, _i32, _fp, C.POINTER(C.c_uint64), _i32]),
     "af_measure_integrated_loudness_device": (C.c_int, [_vp, _i64, _i32, _i64, C.c_uint32, _i32, _dp, C.POINTER(_i32)]),
     "af_measure_integrated_loudness_host": (C.c_int, [_fp, _i64, _i32, _i64, C.c_uint32, _i32, _dp, C.POINTER(_i32)]),
@@ -448,6 +508,7 @@ VALUE_FUNCTIONS = {
     "af_noise_reference_destroy", "af_noise_reference_frame_size", "af_noise_reference_bins", "af_noise_reference_frames",
     "af_speech_features_destroy", "af_speech_features_frames", "af_speech_features_chunks", "af_speech_features_sibilance_bins",
     "af_voice_setup_default_inputs",
+    "af_compressor_search_destroy", "af_compressor_search_blocks",
 }
 
 _lib = None

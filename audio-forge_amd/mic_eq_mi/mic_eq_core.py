@@ -2582,7 +2582,7 @@ NOISE_MIN_DURATION_S, SPEECH_MIN_DURATION_S = 1.5, 3.0  # voice_setup.py:42-43
 def recommend_voice_chain_batch(noise_audio, speech_audio, fs: int, target_preset: str = "broadcast", *, vad_probabilities=None,
                                 noise_vad_probabilities=None, vad_available: bool = True, dynamics_intensity: str = "balanced",
                                 custom_target_p95_db: float = 3.5, custom_peak_cap_db: float = 8.0, noise_metadata=None,
-                                speech_metadata=None, device: int = 0) -> list:
+                                speech_metadata=None, device: int = 0, calibrate_compressor: bool = False, eq_settings=None) -> list:
     """analyze_voice_setup (voice_setup.py:1082-1223) for every pair of noise_audio [n_streams, m] and speech_audio
     [n_streams, n] up to its three rule-based recommendations: analyze_voice_capture_batch (the noise reference, then the voice
     spectrum with the conservative spectrum as its override), the "balanced" smoothing of the median spectrum, the speech
@@ -2597,8 +2597,14 @@ def recommend_voice_chain_batch(noise_audio, speech_audio, fs: int, target_prese
     gate_mode still 1.  ``vad_available=False`` ignores any probabilities, as the reference never asks for them then.  Captures
     below 1.5 s of room tone or 3 s of voice are refused with the reference's messages (:1099-1102).
 
-    It does NOT return EQ bands (the Auto-EQ optimiser is not built), a calibrated compressor threshold (the calibration
-    search is not built: threshold_db is the rule's starting value) or the offline validation and setup confidences."""
+    ``calibrate_compressor=True`` runs the reference's calibration search (voice_setup.py:742-1079; compressor_search.py) on
+    every voice capture behind the EQ of ``eq_settings`` (band_freqs / band_gains / band_qs, one dict or one per stream: the
+    Auto-EQ optimiser that makes them in the reference is not built) and the recommended de-esser: ``compressor`` is then the
+    calibrated dict and ``compressor_calibration`` the search's diagnostics, as voice_setup.py:1241-1263 returns them; without
+    ``eq_settings`` the calibration reads "unavailable" and the compressor stays, as in the reference when its EQ analysis
+    failed.  With the default (False) the return is what it was: threshold_db is the rule's starting value.
+
+    It does NOT return EQ bands (the Auto-EQ optimiser is not built) or the offline validation and setup confidences."""
     noise, speech = np.asarray(noise_audio), np.asarray(speech_audio)
     if noise.ndim != 2 or speech.ndim != 2 or noise.shape[0] != speech.shape[0]:
         raise ValueError("noise_audio and speech_audio must be [n_streams, m] and [n_streams, n]")
@@ -2634,4 +2640,20 @@ def recommend_voice_chain_batch(noise_audio, speech_audio, fs: int, target_prese
         rec.update(features=features[s], noise_reference_status=reference.status, noise_referenced_snr_db=float(spectrum.snr_db),
                    conservative_noise_rms_db=float(reference.conservative_noise_rms_db))
         results.append(rec)
+    if calibrate_compressor:
+        calibrations = [{"backend": "unavailable", "target_gain_reduction_db": 0.0, "measured_gain_reduction_db": 0.0, "iterations": 0}
+                        for _ in results]  # voice_setup.py:1241-1246
+        if eq_settings is not None:
+            from .compressor_search import calibrate_compressor_batch
+
+            pairs = calibrate_compressor_batch(
+                speech, fs, eq_settings, [rec["deesser"] for rec in results], [rec["compressor"] for rec in results],
+                [rec["compressor_diagnostics"]["target_p95_reduction_db"] for rec in results],
+                [rec["compressor_diagnostics"]["target_median_reduction_db"] for rec in results],
+                [rec["compressor_diagnostics"]["peak_reduction_cap_db"] for rec in results], device=device)
+            for rec, (calibrated, _) in zip(results, pairs):
+                rec["compressor"] = calibrated
+            calibrations = [diagnostics for _, diagnostics in pairs]
+        for rec, calibration in zip(results, calibrations):
+            rec["compressor_calibration"] = calibration
     return results

@@ -993,6 +993,105 @@ typedef struct af_voice_setup_recommendation {
 void af_voice_setup_default_inputs(af_voice_setup_inputs *in);
 int af_voice_setup_recommend(const af_voice_setup_inputs *in, af_voice_setup_recommendation *out);
 
+/* ---- compressor candidate sweep: the simulations behind python/mic_eq/analysis/voice_setup.py:699-1079 --------------------
+ * _calibrate_compressor_threshold pushes one capture through simulate_auto_eq_chain (python_api.rs:378-714) once per candidate
+ * (threshold, ratio, attack, release).  Every candidate of a capture shares the capture's de-esser and EQ output, so here that
+ * output (the COMPRESSOR INPUT, an engine run with compressor and limiter disabled) is loaded once with its per-block input
+ * rows, and a LANE = one (capture, candidate) pair runs compressor -> limiter -> true-peak limiter from zero state with its own
+ * compressor parameters.  The lane's per-block rows equal those of an engine whose uniform preset is that candidate, bit for
+ * bit; its af_chain_simulation holds the numeric keys of the reference's result dict (python_api.rs:649-712).
+ * The compressor of a lane is Compressor::new plus the setters of python_api.rs:446-470 in that order: threshold, ratio, attack
+ * and release from the candidate, makeup gain, adaptive release, base release and the side-chain high-pass from the capture's
+ * af_compressor_base; auto-makeup is off (the search simulates with it forced off, voice_setup.py:798-801). */
+typedef struct af_compressor_search af_compressor_search;
+typedef struct af_compressor_candidate {
+  int32_t capture;
+  int32_t reserved;
+  double threshold_db, ratio, attack_ms, release_ms;
+} af_compressor_candidate;
+typedef struct af_compressor_base { /* python_api.rs:454-470 */
+  double makeup_gain_db, base_release_ms;
+  int32_t adaptive_release, sidechain_highpass_enabled;
+} af_compressor_base;
+typedef struct af_chain_simulation { /* python_api.rs:649-712, the numeric keys */
+  float input_sample_peak_db, input_rms_db, output_sample_peak_db, pre_limiter_true_peak_db;
+  float output_true_peak_db, output_rms_db, limiter_effective_ceiling_db, sample_headroom_db;
+  float pre_limiter_true_peak_headroom_db, true_peak_headroom_db, limiter_gain_reduction_db;
+  float true_peak_limiter_gain_reduction_db;
+  uint64_t true_peak_limited_events;
+  float compressor_gain_reduction_db, deesser_gain_reduction_db;
+  float compressor_gain_reduction_median_db, compressor_gain_reduction_p95_db;
+  float compressor_gain_reduction_active_ratio, active_output_gain_db, silence_output_gain_db;
+  float silence_level_delta_db, compressor_pumping_score_db;
+  int32_t non_finite_output;
+  float deesser_gain_reduction_median_db, deesser_gain_reduction_p95_db, analysis_block_ms;
+  float active_analysis_threshold_db;
+  uint64_t active_analysis_block_count, processed_samples;
+  /* the linear maxima and the f32 RMS the dB values above are taken from */
+  float output_sample_peak, pre_limiter_true_peak, output_true_peak, output_rms;
+} af_chain_simulation;
+/* Host work only.  The limiter starts as the search's fixed one (voice_setup.py:748-753): ceiling -1.5 dB, release 80 ms,
+ * careful output, lookahead 2 ms.  AF_ERR_INVALID_ARGUMENT for a non-finite or non-positive sample rate. */
+int af_compressor_search_create(double sample_rate, int32_t device, af_compressor_search **out);
+void af_compressor_search_destroy(af_compressor_search *h);
+/* python_api.rs:472-487 with control.rs:904-910: the effective ceiling is min(ceiling_db, -1.5) under careful output. */
+int af_compressor_search_set_limiter(af_compressor_search *h, double ceiling_db, double release_ms, double lookahead_ms,
+                                     int32_t careful_output);
+/* The captures: audio [n_captures][stride] (host or device memory) and the engine's rows of the run that produced it,
+ * [blocks][n_captures] (host), of which input_sample_peak, input_square_sum and deesser_gain_reduction_db are read.  Blocks are
+ * round(0.020 fs) samples, the last one may be partial.  AF_ERR_UNSUPPORTED above 2048 blocks per capture (the fold's LDS).
+ * _load_host refuses non-finite samples (AF_ERR_NON_FINITE); _load_device does not look at the audio: the caller guarantees
+ * finite samples (an engine's output is) and keeps the memory alive and unchanged while it is loaded.  A non-finite sample
+ * cannot fault: the limiter stages zero it, as in the engine. */
+int af_compressor_search_load_host(af_compressor_search *h, const float *audio, int64_t n_samples, int32_t n_captures, int64_t stride,
+                                   const af_block_stats *input_rows);
+int af_compressor_search_load_device(af_compressor_search *h, const float *d_audio, int64_t n_samples, int32_t n_captures,
+                                     int64_t stride, const af_block_stats *input_rows);
+/* n_lanes candidates in any order and mix of captures; bases: [n_captures]; out: [n_lanes].  keep_audio != 0 also stores every
+ * lane's output audio (a test switch: n_lanes x n_samples floats of device memory). */
+int af_compressor_search_sweep(af_compressor_search *h, const af_compressor_candidate *lanes, int32_t n_lanes,
+                               const af_compressor_base *bases, int32_t keep_audio, af_chain_simulation *out);
+/* The last sweep: its rows as [blocks][n_lanes] af_block_stats (the capture's input fields merged in; capacity in rows), its
+ * audio as [n_lanes][stride] (AF_ERR_STATE when it was not kept), its two kernel times. */
+int64_t af_compressor_search_blocks(const af_compressor_search *h); /* VALUE: control blocks per capture of the loaded batch */
+/* What the host derived per capture at load (python_api.rs:578-617): in_db [n_captures][blocks], mask [n_captures][blocks]
+ * (bit 0: active, bit 1: audible), active_threshold_db [n_captures]; null pointers are skipped. */
+int af_compressor_search_read_masks(const af_compressor_search *h, float *in_db, uint8_t *mask, float *active_threshold_db);
+int af_compressor_search_read_rows(af_compressor_search *h, af_block_stats *rows, int64_t capacity);
+int af_compressor_search_read_audio(af_compressor_search *h, float *audio, int64_t stride);
+int af_compressor_search_last_kernel_ms(af_compressor_search *h, double *sweep_ms, double *fold_ms);
+
+/* _calibrate_compressor_threshold, voice_setup.py:742-1079, for every loaded capture: the incumbent clamped to the bounds
+ * (:770-776), phase 1 = incumbent, 33 thresholds and 16 Halton points (:916-926), the objective of :824-914, two refinement
+ * seeds with +- steps on the four controls (:937-966), the threshold-only / expanded choice (:968-995) and the winner's
+ * verification run (:997-1023): three sweeps per batch (at most 50 and 16 lanes per capture, then one).  The limiter should be
+ * the search's fixed one (the default of af_compressor_search_create).  With auto_makeup_enabled the simulations run with
+ * auto-makeup off and makeup 0 (:798-801).  Without a feasible candidate backend_available is 0, the four controls are the
+ * settings' own and iterations counts the evaluations (:932-935). */
+typedef struct af_compressor_search_settings {
+  double threshold_db, ratio, attack_ms, release_ms; /* the compressor settings to calibrate */
+  double makeup_gain_db, base_release_ms;
+  int32_t adaptive_release, sidechain_highpass_enabled, auto_makeup_enabled, reserved;
+  double target_lufs, measured_short_term_lufs;      /* -18 each when the settings have none (:833-838) */
+  double target_p95_db, target_median_db, peak_cap_db;
+} af_compressor_search_settings;
+typedef struct af_compressor_search_result {
+  int32_t backend_available, expanded_search_selected, peak_cap_passed, iterations, candidate_count;
+  int32_t evaluated_count;      /* candidates simulated and scored, without the verification */
+  int32_t winner;               /* its index in `evaluated`, -1 without a feasible candidate */
+  int32_t verification_equals_evaluation; /* the verification's record equals the winner's first one, byte for byte */
+  double threshold_db, ratio, attack_ms, release_ms; /* calibrated */
+  double measured_median_gain_reduction_db, measured_p95_gain_reduction_db, measured_peak_gain_reduction_db, active_reduction_ratio;
+  double total_objective, incumbent_objective, threshold_only_objective, expanded_candidate_objective;
+  double active_output_gain_db, silence_output_gain_db, compressor_pumping_score_db, output_true_peak_db;
+  double pre_limiter_true_peak_headroom_db;
+  double evaluated[67][4];      /* in evaluation order: threshold_db, ratio, attack_ms, release_ms as simulated */
+  double scores[67];            /* +inf: hard-rejected */
+} af_compressor_search_result;
+int af_compressor_search_run(af_compressor_search *h, const af_compressor_search_settings *settings, af_compressor_search_result *out);
+/* kernel ms of the last run's three sweeps: phase 1 sweep, fold; phase 2 sweep, fold; verification sweep, fold */
+int af_compressor_search_last_run_ms(const af_compressor_search *h, double ms[6]);
+
 /* ---- NoiseSuppressor: rust-core/src/dsp/noise_suppressor.rs:18-194 ----------------------------------------
  * The runtime-selected suppressor interface (`NoiseModel`, trait `NoiseSuppressor`, `new_noise_suppression_engine`) for a
  * batch of streams that advance in lock step: sample counts are per stream, audio is [stream][stride] host memory, the
