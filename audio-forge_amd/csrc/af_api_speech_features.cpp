@@ -2,7 +2,8 @@
 // python/mic_eq/analysis/voice_setup.py:161-458.  The kernels do what is O(samples) and O(frames x bins); what is O(frames) per
 // stream (frame levels, the adaptive floor, the VAD-fused mask, the loudness windows, the frame features and the frame model)
 // is af_speech_features_math.h's, in f64, between the kernels.  Kernels and tables: af_speech_features.hip /
-// af_speech_features_host.hpp; the medians over frames are af_spectrum.hip's.
+// af_speech_features_host.hpp; the medians over frames are af_spectrum.hip's.  The object and its analysis (af::sf_*,
+// af_speech_features_impl.hpp) also serve af_device_rate_features_*, whose rates resample to 48 kHz in front of the K-weighting.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -10,40 +11,16 @@
 #include <cstring>
 #include <vector>
 
-#include "af_api_internal.hpp"
-#include "af_speech_features_host.hpp"
-#include "af_speech_features_math.h"
-#include "af_spectrum_host.hpp"
-
-struct af_speech_features {
-  int device = 0, max_streams = 0, sib_bins = 0;
-  int64_t max_speech = 0, max_noise = 0;
-  bool touched_device = false;
-  double model[1 + SFM_FEATURES];
-  af::NrPlan plan = {};
-  af::SfBandTable bands = {};
-  std::vector<double> window, twiddles, freqs;
-  af::DeviceBuffer<double> d_window, d_twiddles;  // uploaded at the first call
-  af::DeviceBuffer<float> d_speech, d_noise;      // staging of the host entry point
-  af::DeviceBuffer<double> d_power, d_energy;
-  af::DeviceBuffer<double> d_band, d_sib_mid, d_sib_rows, d_noise_band, d_band_mid, d_noise_mid, d_weights, d_sums;  // per tile
-  af::DeviceBuffer<int32_t> d_sib_arg, d_arg;
-  af::DeviceBuffer<af::SfFrameItem> d_items;
-  af::DeviceBuffer<af::VsMedianJob> d_jobs, d_noise_jobs;
-  af::DeviceBuffer<af::SfPeakJob> d_peak_jobs;
-  af::EventChain events;          // pairs of marks around the kernels of the last call
-  std::vector<int8_t> span_kind;  // per pair: which of the five stages it times
-  ~af_speech_features() {
-    if (touched_device) { (void)hipSetDevice(device); (void)hipDeviceSynchronize(); }
-  }
-};
+#include "af_speech_features_impl.hpp"
 
 namespace {
 
-constexpr int kSpans = 5;
-
 int sf_upload_tables(af_speech_features *h) {
   if (h->d_window) return AF_OK;
+  if (!h->phase_table.empty()) {
+    AF_HIP(h->d_phase_table.reserve_exact(sizeof(double) * h->phase_table.size()));
+    AF_HIP(hipMemcpy(h->d_phase_table, h->phase_table.data(), sizeof(double) * h->phase_table.size(), hipMemcpyHostToDevice));
+  }
   AF_HIP(h->d_twiddles.reserve_exact(sizeof(double) * h->twiddles.size()));
   AF_HIP(hipMemcpy(h->d_twiddles, h->twiddles.data(), sizeof(double) * h->twiddles.size(), hipMemcpyHostToDevice));
   AF_HIP(h->d_window.reserve_exact(sizeof(double) * h->window.size()));  // last: its presence means "all tables are up"
@@ -60,8 +37,9 @@ int sf_check(af_speech_features *h, const float *speech, int64_t n, int32_t B, i
   if (!noise_rms_db) return fail(AF_ERR_INVALID_ARGUMENT, "noise_rms_db is null");
   if (B <= 0) return fail(AF_ERR_INVALID_ARGUMENT, "n_streams must be positive");
   if (B > h->max_streams) return fail(AF_ERR_INVALID_ARGUMENT, "n_streams %d is above the handle's max_streams %d", B, h->max_streams);
-  if (n < SFM_FRAME)
-    return fail(AF_ERR_INVALID_ARGUMENT, "speech capture of %lld samples is shorter than one analysis frame of %d", (long long)n, SFM_FRAME);
+  if (n < h->geo.frame)
+    return fail(AF_ERR_INVALID_ARGUMENT, "speech capture of %lld samples is shorter than one analysis frame of %d", (long long)n,
+                h->geo.frame);
   if (n > h->max_speech)
     return fail(AF_ERR_INVALID_ARGUMENT, "n_speech %lld is above the handle's max_speech_samples %lld", (long long)n, (long long)h->max_speech);
   if (stride < n) return fail(AF_ERR_INVALID_ARGUMENT, "speech_stride must cover n_speech");
@@ -71,7 +49,8 @@ int sf_check(af_speech_features *h, const float *speech, int64_t n, int32_t B, i
   if (!noise && m > 0) return fail(AF_ERR_INVALID_ARGUMENT, "n_noise without noise");
   if (m > h->max_noise)
     return fail(AF_ERR_INVALID_ARGUMENT, "n_noise %lld is above the handle's max_noise_samples %lld", (long long)m, (long long)h->max_noise);
-  if (sfm_frames(n) > (1 << 22) || sfm_frames(m) > (1 << 22)) return fail(AF_ERR_UNSUPPORTED, "more than 2^22 frames per stream");
+  if (sfm_frames_at(&h->geo, n) > (1 << 22) || sfm_frames_at(&h->geo, m) > (1 << 22))
+    return fail(AF_ERR_UNSUPPORTED, "more than 2^22 frames per stream");
   return AF_OK;
 }
 
@@ -89,10 +68,51 @@ struct SfStream {
   std::vector<int32_t> listed;
 };
 
+// how many 48 kHz chunks of every stream the scratch (f64 signal and mask bytes) holds at once
+int sf_segment_chunks(const af_speech_features *h, int32_t B) {
+  return (int)std::max<int64_t>(1, h->scratch_bytes / ((int64_t)9 * SFM_CHUNK48 * B));
+}
+
+// resample_poly of every capture and of its sample mask (h->d_active: [B][F] frame flags) and the K-weighting behind it, a
+// segment of whole chunks of all streams at a time -- the recurrence is serial in time and parallel over streams only, so the
+// streams stay together and the filter states are carried in h->d_state: h->d_energy, h->d_masked_energy and h->d_count,
+// [B][chunks of 960] each
+template <typename Span>
+int sf_resample_and_weight(af_speech_features *h, const float *d_speech, int64_t n, int32_t B, int64_t stride, Span &span, hipStream_t q) {
+  const sfm_geometry &geo = h->geo;
+  const int F = (int)sfm_frames_at(&geo, n), C = (int)sfm_chunks48(&geo, n);
+  const int64_t n48 = sfm_resampled_length(&geo, n);
+  const int segment = std::min(C, sf_segment_chunks(h, B));
+  const int64_t row = (int64_t)segment * SFM_CHUNK48;
+  const af::SfResamplePlan plan = {geo.up, geo.down, geo.rem, geo.taps};
+  AF_HIP(h->d_resampled.reserve_exact(sizeof(double) * (size_t)B * row));
+  AF_HIP(h->d_resampled_mask.reserve_exact((size_t)B * row));
+  AF_HIP(h->d_state.reserve_exact(sizeof(double) * 4 * (size_t)B));
+  AF_HIP(h->d_energy.reserve_exact(sizeof(double) * (size_t)B * C));
+  AF_HIP(h->d_masked_energy.reserve_exact(sizeof(double) * (size_t)B * C));
+  AF_HIP(h->d_count.reserve_exact(sizeof(int32_t) * (size_t)B * C));
+  AF_HIP(hipMemsetAsync(h->d_state, 0, sizeof(double) * 4 * (size_t)B, q));
+  for (int c0 = 0; c0 < C; c0 += segment) {
+    const int chunks = std::min(C - c0, segment);
+    const int64_t samples = std::min<int64_t>(n48 - (int64_t)c0 * SFM_CHUNK48, (int64_t)chunks * SFM_CHUNK48);
+    AF_HIP(span(5));
+    AF_HIP(af::launch_sf_resample(d_speech, stride, n, B, h->d_active, F, geo.hop, plan, h->d_phase_table, n48, c0, chunks, row,
+                                  h->d_resampled, h->d_resampled_mask, h->d_count, q));
+    AF_HIP(h->events.mark(q));
+    AF_HIP(span(1));
+    AF_HIP(af::launch_sf_kweight_resampled(h->d_resampled, h->d_resampled_mask, row, samples, B, C, c0, h->d_state, h->d_energy,
+                                           h->d_masked_energy, q));
+    AF_HIP(h->events.mark(q));
+  }
+  return AF_OK;
+}
+
 int sf_analyze(af_speech_features *h, const float *d_speech, int64_t n, int32_t B, int64_t stride, const double *noise_rms_db,
                const double *vad, int64_t n_vad, const float *d_noise, int64_t m, int64_t noise_stride,
                const af_speech_features_outputs *out) {
-  const int F = (int)sfm_frames(n), C = (int)sfm_chunks(n), Fn = d_noise ? (int)sfm_frames(m) : 0, S = h->sib_bins;
+  const sfm_geometry &geo = h->geo;
+  const bool resample = geo.up != geo.down;  // C: chunks of 960 samples at 48 kHz
+  const int F = (int)sfm_frames_at(&geo, n), C = (int)sfm_chunks48(&geo, n), Fn = d_noise ? (int)sfm_frames_at(&geo, m) : 0, S = h->sib_bins;
   const int BF = af::kSfBandFields;
   hipStream_t q = nullptr;
   h->events.restart();
@@ -100,32 +120,57 @@ int sf_analyze(af_speech_features *h, const float *d_speech, int64_t n, int32_t 
   const auto span = [&](int8_t kind) { h->span_kind.push_back(kind); return h->events.mark(q); };
   if (int rc = sf_upload_tables(h)) return rc;
 
-  // 1. frame powers and K-weighted chunk energies
+  // 1. frame powers, then the levels and masks of every stream
   std::vector<double> power((size_t)B * F), energy((size_t)B * C);
   AF_HIP(h->d_power.reserve_exact(sizeof(double) * power.size()));
   AF_HIP(h->d_energy.reserve_exact(sizeof(double) * energy.size()));
   AF_HIP(span(0));
-  AF_HIP(af::launch_sf_frame_power(d_speech, stride, B, F, h->d_power, q));
-  AF_HIP(h->events.mark(q));
-  AF_HIP(span(1));
-  AF_HIP(af::launch_sf_kweight(d_speech, stride, n, B, C, h->d_energy, q));
+  AF_HIP(af::launch_sf_frame_power(d_speech, stride, B, F, geo.frame, geo.hop, h->d_power, q));
   AF_HIP(h->events.mark(q));
   AF_HIP(hipMemcpy(power.data(), h->d_power, sizeof(double) * power.size(), hipMemcpyDeviceToHost));
-  AF_HIP(hipMemcpy(energy.data(), h->d_energy, sizeof(double) * energy.size(), hipMemcpyDeviceToHost));
-
-  // 2. levels, masks and loudness of every stream
   std::vector<SfStream> streams((size_t)B);
-  int64_t max_rows = 1;
   for (int s = 0; s < B; ++s) {
     SfStream &st = streams[(size_t)s];
-    st.row.non_finite = !all_finite(&power[(size_t)s * F], (size_t)F) || !all_finite(&energy[(size_t)s * C], (size_t)C);
+    st.row.non_finite = !all_finite(&power[(size_t)s * F], (size_t)F);
     if (st.row.non_finite) continue;
     st.frame_db.resize((size_t)F); st.post.resize((size_t)F); st.energy_active.resize((size_t)F); st.active.resize((size_t)F);
     st.listed.resize((size_t)F);
-    sfm_masks(&power[(size_t)s * F], F, noise_rms_db[s], vad ? vad + (int64_t)s * n_vad : nullptr, n_vad, st.frame_db.data(),
-              st.energy_active.data(), st.active.data(), st.post.data(), st.listed.data(), &st.row);
+    sfm_masks_at(&geo, &power[(size_t)s * F], F, noise_rms_db[s], vad ? vad + (int64_t)s * n_vad : nullptr, n_vad, st.frame_db.data(),
+                 st.energy_active.data(), st.active.data(), st.post.data(), st.listed.data(), &st.row);
     st.listed.resize((size_t)st.row.spectral_frames);
-    sfm_loudness(&energy[(size_t)s * C], n, st.active.data(), F, &st.row);
+  }
+
+  // 2. K-weighted chunk energies at 48 kHz -- behind the resampling of signal and mask at any other rate -- and the loudness
+  std::vector<double> masked_energy;
+  std::vector<int32_t> count;
+  if (!resample) {
+    AF_HIP(span(1));
+    AF_HIP(af::launch_sf_kweight(d_speech, stride, n, B, C, h->d_energy, q));
+    AF_HIP(h->events.mark(q));
+  } else {
+    std::vector<uint8_t> flags((size_t)B * F, 0);
+    for (int s = 0; s < B; ++s)
+      if (!streams[(size_t)s].row.non_finite) std::memcpy(&flags[(size_t)s * F], streams[(size_t)s].active.data(), (size_t)F);
+    masked_energy.resize((size_t)B * C);
+    count.resize((size_t)B * C);
+    AF_HIP(h->d_active.reserve_exact(flags.size()));
+    AF_HIP(hipMemcpy(h->d_active, flags.data(), flags.size(), hipMemcpyHostToDevice));
+    if (int rc = sf_resample_and_weight(h, d_speech, n, B, stride, span, q)) return rc;
+    AF_HIP(hipMemcpy(masked_energy.data(), h->d_masked_energy, sizeof(double) * masked_energy.size(), hipMemcpyDeviceToHost));
+    AF_HIP(hipMemcpy(count.data(), h->d_count, sizeof(int32_t) * count.size(), hipMemcpyDeviceToHost));
+  }
+  AF_HIP(hipMemcpy(energy.data(), h->d_energy, sizeof(double) * energy.size(), hipMemcpyDeviceToHost));
+  int64_t max_rows = 1;
+  for (int s = 0; s < B; ++s) {
+    SfStream &st = streams[(size_t)s];
+    if (st.row.non_finite) continue;
+    if (!all_finite(&energy[(size_t)s * C], (size_t)C)) {  // a non-finite sample behind the last frame
+      st.row = af_speech_features_row{};
+      st.row.non_finite = 1;
+      continue;
+    }
+    if (!resample) sfm_loudness(&energy[(size_t)s * C], n, st.active.data(), F, &st.row);
+    else sfm_loudness_at(&geo, &energy[(size_t)s * C], &masked_energy[(size_t)s * C], &count[(size_t)s * C], n, st.active.data(), F, &st.row);
     max_rows = std::max<int64_t>(max_rows, st.row.spectral_frames);
   }
 
@@ -183,7 +228,7 @@ int sf_analyze(af_speech_features *h, const float *d_speech, int64_t n, int32_t 
       if (!noise_jobs.empty())
         AF_HIP(hipMemcpy(h->d_noise_jobs, noise_jobs.data(), sizeof(af::VsMedianJob) * noise_jobs.size(), hipMemcpyHostToDevice));
       AF_HIP(span(2));
-      AF_HIP(af::launch_sf_frames(d_speech, stride, d_noise, noise_stride, h->d_items, (int32_t)items.size(), h->plan, h->bands, h->d_window,
+      AF_HIP(af::launch_sf_frames(d_speech, stride, d_noise, noise_stride, h->d_items, (int32_t)items.size(), geo.hop, h->plan, h->bands, h->d_window,
                                   h->d_twiddles, h->d_band, h->d_sib_mid, h->d_sib_arg, h->d_sib_rows, h->d_noise_band, q));
       AF_HIP(h->events.mark(q));
       AF_HIP(span(3));
@@ -261,50 +306,44 @@ int sf_analyze(af_speech_features *h, const float *d_speech, int64_t n, int32_t 
 
 }  // namespace
 
-extern "C" {
+namespace af {
 
-int af_speech_features_create(uint32_t sample_rate, int32_t max_streams, int64_t max_speech_samples, int64_t max_noise_samples,
-                              int32_t device, af_speech_features **out) {
-  if (!out) return fail(AF_ERR_INVALID_ARGUMENT, "out is null");
-  *out = nullptr;
-  if (sample_rate == 0) return fail(AF_ERR_INVALID_ARGUMENT, "sample_rate must be positive");
-  if (sample_rate != SFM_RATE)
-    return fail(AF_ERR_UNSUPPORTED,
-                "sample rate %u Hz: the speech features K-weight at 48000 Hz and the polyphase resampling the reference puts in "
-                "front of that for any other rate is not built",
-                sample_rate);
+int sf_create(const sfm_geometry &geo, int32_t max_streams, int64_t max_speech_samples, int64_t max_noise_samples, int32_t device,
+              af_speech_features **out) {
   if (max_streams <= 0) return fail(AF_ERR_INVALID_ARGUMENT, "max_streams must be positive");
-  if (max_speech_samples < SFM_FRAME)
-    return fail(AF_ERR_INVALID_ARGUMENT, "max_speech_samples must hold one analysis frame of %d samples", SFM_FRAME);
+  if (max_speech_samples < geo.frame)
+    return fail(AF_ERR_INVALID_ARGUMENT, "max_speech_samples must hold one analysis frame of %d samples", geo.frame);
   if (max_noise_samples < 0) return fail(AF_ERR_INVALID_ARGUMENT, "max_noise_samples must be >= 0");
   if (device < 0) return fail(AF_ERR_INVALID_ARGUMENT, "device must be >= 0");
+  NrPlan plan;
+  const SfResamplePlan resample = {geo.up, geo.down, geo.rem, geo.taps};
+  if (geo.frame != 2 * geo.hop || geo.hop > kSfMaxHop || !nr_make_plan(geo.hop, plan) ||
+      (geo.up != geo.down && sf_resample_span(resample) > kSfResampleSpan))
+    return fail(AF_ERR_UNSUPPORTED, "sample rate %d Hz: its analysis frame of %d samples does not fit the frame transform", geo.rate, geo.frame);
   af_speech_features *h = new af_speech_features();
   h->device = device;
   h->max_streams = max_streams;
   h->max_speech = max_speech_samples;
   h->max_noise = max_noise_samples;
+  h->geo = geo;
+  h->plan = plan;  // 960 = 5 3 2^6 at 48 kHz
   h->model[0] = SFM_FRAME_INTERCEPT;
   std::copy(sfm_frame_coefficients, sfm_frame_coefficients + SFM_FEATURES, h->model + 1);
   double sumw2 = 0.0;
-  (void)af::nr_make_plan(af::kSfHop, h->plan);  // 960 = 5 3 2^6
-  af::nr_make_window(af::kSfFrame, h->window, &sumw2);
-  af::nr_make_twiddles(af::kSfFrame, h->twiddles);
-  af::nr_freqs(sample_rate, af::kSfFrame, h->freqs);
-  af::sf_make_bands(h->freqs, h->bands);
-  h->sib_bins = h->bands.last[af::kSfSibBand] - h->bands.first[af::kSfSibBand] + 1;
+  nr_make_window(geo.frame, h->window, &sumw2);
+  nr_make_twiddles(geo.frame, h->twiddles);
+  nr_freqs((uint32_t)geo.rate, geo.frame, h->freqs);
+  sf_make_bands((uint32_t)geo.rate, h->freqs, h->bands);
+  h->sib_bins = h->bands.last[kSfSibBand] - h->bands.first[kSfSibBand] + 1;
+  if (geo.up != geo.down) {
+    h->phase_table.resize((size_t)geo.up * geo.taps);
+    sfm_polyphase_table(&geo, h->phase_table.data());
+  }
   *out = h;
   return AF_OK;
 }
 
-void af_speech_features_destroy(af_speech_features *h) { delete h; }
-
-int64_t af_speech_features_frames(int64_t n_samples) { return sfm_frames(n_samples); }
-
-int64_t af_speech_features_chunks(int64_t n_samples) { return n_samples > 0 ? sfm_chunks(n_samples) : 0; }
-
-int32_t af_speech_features_sibilance_bins(const af_speech_features *h) { return h ? h->sib_bins : 0; }
-
-int af_speech_features_set_frame_model(af_speech_features *h, double intercept, const double coefficients[6]) {
+int sf_set_frame_model(af_speech_features *h, double intercept, const double *coefficients) {
   if (!h || !coefficients) return fail(AF_ERR_INVALID_ARGUMENT, "null argument");
   if (!std::isfinite(intercept) || !all_finite(coefficients, SFM_FEATURES))
     return fail(AF_ERR_INVALID_ARGUMENT, "frame model parameters must be finite");
@@ -313,16 +352,23 @@ int af_speech_features_set_frame_model(af_speech_features *h, double intercept, 
   return AF_OK;
 }
 
-int af_speech_features_get_frame_model(const af_speech_features *h, double *intercept, double coefficients[6]) {
+int sf_get_frame_model(const af_speech_features *h, double *intercept, double *coefficients) {
   if (!h || !intercept || !coefficients) return fail(AF_ERR_INVALID_ARGUMENT, "null argument");
   *intercept = h->model[0];
   std::copy(h->model + 1, h->model + 1 + SFM_FEATURES, coefficients);
   return AF_OK;
 }
 
-int af_speech_features_analyze_device(af_speech_features *h, const float *d_speech, int64_t n_speech, int32_t n_streams,
-                                      int64_t speech_stride, const double *noise_rms_db, const double *vad_probabilities, int64_t n_vad,
-                                      const float *d_noise, int64_t n_noise, int64_t noise_stride, const af_speech_features_outputs *out) {
+int sf_set_scratch_bytes(af_speech_features *h, int64_t bytes) {
+  if (!h) return fail(AF_ERR_INVALID_ARGUMENT, "null argument");
+  if (bytes < 1 || bytes > ((int64_t)1 << 40)) return fail(AF_ERR_INVALID_ARGUMENT, "scratch bytes must be 1 .. 2^40");
+  h->scratch_bytes = bytes;
+  return AF_OK;
+}
+
+int sf_analyze_device(af_speech_features *h, const float *d_speech, int64_t n_speech, int32_t n_streams, int64_t speech_stride,
+                      const double *noise_rms_db, const double *vad_probabilities, int64_t n_vad, const float *d_noise, int64_t n_noise,
+                      int64_t noise_stride, const af_speech_features_outputs *out) {
   if (int rc = sf_check(h, d_speech, n_speech, n_streams, speech_stride, noise_rms_db, vad_probabilities, n_vad, d_noise, n_noise,
                         noise_stride, out))
     return rc;
@@ -332,9 +378,9 @@ int af_speech_features_analyze_device(af_speech_features *h, const float *d_spee
                     noise_stride, out);
 }
 
-int af_speech_features_analyze_host(af_speech_features *h, const float *speech, int64_t n_speech, int32_t n_streams, int64_t speech_stride,
-                                    const double *noise_rms_db, const double *vad_probabilities, int64_t n_vad, const float *noise,
-                                    int64_t n_noise, int64_t noise_stride, const af_speech_features_outputs *out) {
+int sf_analyze_host(af_speech_features *h, const float *speech, int64_t n_speech, int32_t n_streams, int64_t speech_stride,
+                    const double *noise_rms_db, const double *vad_probabilities, int64_t n_vad, const float *noise, int64_t n_noise,
+                    int64_t noise_stride, const af_speech_features_outputs *out) {
   if (int rc = sf_check(h, speech, n_speech, n_streams, speech_stride, noise_rms_db, vad_probabilities, n_vad, noise, n_noise, noise_stride,
                         out))
     return rc;
@@ -352,19 +398,110 @@ int af_speech_features_analyze_host(af_speech_features *h, const float *speech, 
                     with_noise ? h->d_noise.get() : nullptr, with_noise ? n_noise : 0, n_noise, out);
 }
 
-int af_speech_features_last_kernel_ms(af_speech_features *h, double *ms, int32_t capacity) {
+int sf_last_kernel_ms(af_speech_features *h, double *ms, int32_t capacity, int32_t spans) {
   if (!h || !ms) return fail(AF_ERR_INVALID_ARGUMENT, "null argument");
-  if (capacity < kSpans) return fail(AF_ERR_INVALID_ARGUMENT, "ms must hold %d values", kSpans);
-  std::fill(ms, ms + kSpans, 0.0);
+  if (capacity < spans) return fail(AF_ERR_INVALID_ARGUMENT, "ms must hold %d values", spans);
+  std::fill(ms, ms + spans, 0.0);
   if (h->events.marks() == 0) return AF_OK;
   AF_HIP(hipSetDevice(h->device));
   AF_HIP(h->events.wait_last());
   for (size_t i = 0; i < h->span_kind.size() && 2 * i + 1 < h->events.marks(); ++i) {
     double span = 0.0;
     AF_HIP(h->events.elapsed(2 * i, 2 * i + 1, &span));
-    ms[h->span_kind[i]] += span;
+    if (h->span_kind[i] < spans) ms[h->span_kind[i]] += span;
   }
   return AF_OK;
+}
+
+int sf_debug_resample_host(af_speech_features *h, const float *speech, int64_t n, int32_t B, int64_t stride, const uint8_t *active_frames,
+                           double *signal, uint8_t *mask, int32_t *counts) {
+  if (!h || !speech || !active_frames || !signal || !mask || !counts) return fail(AF_ERR_INVALID_ARGUMENT, "null argument");
+  if (h->geo.up == h->geo.down) return fail(AF_ERR_INVALID_ARGUMENT, "a 48000 Hz handle does not resample");
+  if (B <= 0 || B > h->max_streams) return fail(AF_ERR_INVALID_ARGUMENT, "n_streams %d must be 1 .. max_streams %d", B, h->max_streams);
+  if (n < h->geo.frame || n > h->max_speech || stride < n)
+    return fail(AF_ERR_INVALID_ARGUMENT, "n_speech %lld must be one frame of %d .. max_speech_samples %lld within its stride", (long long)n,
+                h->geo.frame, (long long)h->max_speech);
+  AF_HIP(hipSetDevice(h->device));
+  h->touched_device = true;
+  const sfm_geometry &geo = h->geo;
+  const int F = (int)sfm_frames_at(&geo, n), C = (int)sfm_chunks48(&geo, n);
+  const int64_t n48 = sfm_resampled_length(&geo, n);
+  const int segment = std::min(C, sf_segment_chunks(h, B));
+  const int64_t row = (int64_t)segment * SFM_CHUNK48;
+  const SfResamplePlan plan = {geo.up, geo.down, geo.rem, geo.taps};
+  const size_t f4 = sizeof(float);
+  if (int rc = sf_upload_tables(h)) return rc;
+  AF_HIP(h->d_speech.reserve_exact(f4 * (size_t)B * n));
+  AF_HIP(hipMemcpy2D(h->d_speech, f4 * n, speech, f4 * stride, f4 * n, B, hipMemcpyHostToDevice));
+  AF_HIP(h->d_active.reserve_exact((size_t)B * F));
+  AF_HIP(hipMemcpy(h->d_active, active_frames, (size_t)B * F, hipMemcpyHostToDevice));
+  AF_HIP(h->d_resampled.reserve_exact(sizeof(double) * (size_t)B * row));
+  AF_HIP(h->d_resampled_mask.reserve_exact((size_t)B * row));
+  AF_HIP(h->d_count.reserve_exact(sizeof(int32_t) * (size_t)B * C));
+  for (int c0 = 0; c0 < C; c0 += segment) {
+    const int chunks = std::min(C - c0, segment);
+    const int64_t at = (int64_t)c0 * SFM_CHUNK48, samples = std::min<int64_t>(n48 - at, (int64_t)chunks * SFM_CHUNK48);
+    AF_HIP(launch_sf_resample(h->d_speech, n, n, B, h->d_active, F, geo.hop, plan, h->d_phase_table, n48, c0, chunks, row, h->d_resampled,
+                              h->d_resampled_mask, h->d_count, nullptr));
+    AF_HIP(hipMemcpy2D(signal + at, sizeof(double) * n48, h->d_resampled, sizeof(double) * row, sizeof(double) * samples, B,
+                       hipMemcpyDeviceToHost));
+    AF_HIP(hipMemcpy2D(mask + at, (size_t)n48, h->d_resampled_mask, (size_t)row, (size_t)samples, B, hipMemcpyDeviceToHost));
+  }
+  AF_HIP(hipMemcpy(counts, h->d_count, sizeof(int32_t) * (size_t)B * C, hipMemcpyDeviceToHost));
+  return AF_OK;
+}
+
+}  // namespace af
+
+extern "C" {
+
+int af_speech_features_create(uint32_t sample_rate, int32_t max_streams, int64_t max_speech_samples, int64_t max_noise_samples,
+                              int32_t device, af_speech_features **out) {
+  if (!out) return fail(AF_ERR_INVALID_ARGUMENT, "out is null");
+  *out = nullptr;
+  if (sample_rate == 0) return fail(AF_ERR_INVALID_ARGUMENT, "sample_rate must be positive");
+  if (sample_rate != SFM_RATE)
+    return fail(AF_ERR_UNSUPPORTED,
+                "sample rate %u Hz: these entry points K-weight at 48000 Hz only; the polyphase resampling the reference puts in "
+                "front of that for any other rate is behind af_device_rate_features_create",
+                sample_rate);
+  sfm_geometry geo;
+  (void)sfm_make_geometry(SFM_RATE, &geo);
+  return af::sf_create(geo, max_streams, max_speech_samples, max_noise_samples, device, out);
+}
+
+void af_speech_features_destroy(af_speech_features *h) { delete h; }
+
+int64_t af_speech_features_frames(int64_t n_samples) { return sfm_frames(n_samples); }
+
+int64_t af_speech_features_chunks(int64_t n_samples) { return n_samples > 0 ? sfm_chunks(n_samples) : 0; }
+
+int32_t af_speech_features_sibilance_bins(const af_speech_features *h) { return h ? h->sib_bins : 0; }
+
+int af_speech_features_set_frame_model(af_speech_features *h, double intercept, const double coefficients[6]) {
+  return af::sf_set_frame_model(h, intercept, coefficients);
+}
+
+int af_speech_features_get_frame_model(const af_speech_features *h, double *intercept, double coefficients[6]) {
+  return af::sf_get_frame_model(h, intercept, coefficients);
+}
+
+int af_speech_features_analyze_device(af_speech_features *h, const float *d_speech, int64_t n_speech, int32_t n_streams,
+                                      int64_t speech_stride, const double *noise_rms_db, const double *vad_probabilities, int64_t n_vad,
+                                      const float *d_noise, int64_t n_noise, int64_t noise_stride, const af_speech_features_outputs *out) {
+  return af::sf_analyze_device(h, d_speech, n_speech, n_streams, speech_stride, noise_rms_db, vad_probabilities, n_vad, d_noise, n_noise,
+                               noise_stride, out);
+}
+
+int af_speech_features_analyze_host(af_speech_features *h, const float *speech, int64_t n_speech, int32_t n_streams, int64_t speech_stride,
+                                    const double *noise_rms_db, const double *vad_probabilities, int64_t n_vad, const float *noise,
+                                    int64_t n_noise, int64_t noise_stride, const af_speech_features_outputs *out) {
+  return af::sf_analyze_host(h, speech, n_speech, n_streams, speech_stride, noise_rms_db, vad_probabilities, n_vad, noise, n_noise,
+                             noise_stride, out);
+}
+
+int af_speech_features_last_kernel_ms(af_speech_features *h, double *ms, int32_t capacity) {
+  return af::sf_last_kernel_ms(h, ms, capacity, af::kSfSpans);
 }
 
 }  // extern "C"

@@ -46,51 +46,22 @@ static inline double *sfm_sorted_copy(const double *v, int n) {
 static inline int64_t sfm_frames(int64_t n) { return n < SFM_FRAME ? 0 : (n - SFM_FRAME) / SFM_HOP + 1; }
 static inline int64_t sfm_chunks(int64_t n) { return (n + SFM_HOP - 1) / SFM_HOP; } /* the last one may be partial */
 
+/* the frame geometry of a rate and resample_poly's figures towards 48 kHz (sfm_make_geometry below) */
+typedef struct sfm_geometry {
+  int32_t rate, frame, hop, vad_window; /* int(fs 40 / 1000), int(fs 20 / 1000), ceil(fs 512 / 16000) */
+  int32_t up, down;                     /* 48000 / g, fs / g with g = gcd(fs, 48000); 1, 1 at 48 kHz: no resampling */
+  int32_t half, pre, rem, taps;         /* resample_poly: 10 max(up, down); zeros in front of the filter; first output; taps a phase */
+} sfm_geometry;
+static inline void sfm_masks_at(const sfm_geometry *g, const double *power, int F, double noise_rms_db, const double *vad, int64_t n_vad,
+                                double *frame_db, uint8_t *energy_active, uint8_t *active, double *post, int32_t *listed,
+                                af_speech_features_row *r);
+
 /* :178-205 and :269-270 from the frame powers: frame levels, the adaptive floor, the energy mask, the posterior mask with its
  * six-frame rule, the three-frame dilation, and the list of spectrally active frames.  post: [F], written when vad is given. */
 static inline void sfm_masks(const double *power, int F, double noise_rms_db, const double *vad, int64_t n_vad, double *frame_db,
                              uint8_t *energy_active, uint8_t *active, double *post, int32_t *listed, af_speech_features_row *r) {
-  int f, count = 0, evidence = 0, A = 0, n_active = 0;
-  double *sorted, floor_db, p30;
-  const int with_vad = vad && n_vad > 0 && F > 0;
-  for (f = 0; f < F; ++f) frame_db[f] = 10.0 * log10(power[f] + 1e-12);
-  sorted = sfm_sorted_copy(frame_db, F);
-  p30 = af_percentile_sorted(sorted, F, 30.0) + 2.0;
-  free(sorted);
-  floor_db = noise_rms_db + 6.0 > p30 ? noise_rms_db + 6.0 : p30;
-  for (f = 0; f < F; ++f) active[f] = energy_active[f] = frame_db[f] >= floor_db;
-  if (with_vad) {
-    double *xp = (double *)malloc(sizeof(double) * (size_t)n_vad * 2);
-    uint8_t *posterior = (uint8_t *)malloc((size_t)F);
-    const double low = noise_rms_db + 2.0 > floor_db - 4.0 ? noise_rms_db + 2.0 : floor_db - 4.0;
-    af_interpolate_vad_probabilities(vad, n_vad, SFM_VAD_WINDOW, F, SFM_HOP, SFM_FRAME, xp, xp + n_vad, post);
-    for (f = 0; f < F; ++f) {
-      posterior[f] = (post[f] >= SFM_VAD_EVIDENCE && frame_db[f] >= low) || post[f] >= SFM_VAD_STRONG;
-      count += posterior[f];
-      evidence += post[f] >= SFM_VAD_EVIDENCE;
-    }
-    if (count >= 6) memcpy(active, posterior, (size_t)F);
-    free(posterior);
-    free(xp);
-  }
-  if (F >= 3) { /* np.convolve(., ones(3), "same") > 0 */
-    uint8_t prev = 0;
-    for (f = 0; f < F; ++f) {
-      const uint8_t here = active[f], next = f + 1 < F ? active[f + 1] : 0;
-      active[f] = prev | here | next;
-      prev = here;
-    }
-  }
-  for (f = 0; f < F; ++f) {
-    n_active += active[f];
-    if (active[f] | energy_active[f]) listed[A++] = f;
-  }
-  r->frames = F;
-  r->active_frames = n_active;
-  r->spectral_frames = A;
-  r->adaptive_floor_db = floor_db;
-  r->vad_probability_used = with_vad;
-  r->vad_active_frame_ratio = with_vad ? (double)evidence / (double)F : 0.0;
+  static const sfm_geometry at48 = {SFM_RATE, SFM_FRAME, SFM_HOP, SFM_VAD_WINDOW, 1, 1, 0, 0, 0, 0};
+  sfm_masks_at(&at48, power, F, noise_rms_db, vad, n_vad, frame_db, energy_active, active, post, listed, r);
 }
 
 /* the loudness values of one window size from the chunk energies, :143-158: windows of `W` chunks every `H`, kept when at
@@ -150,6 +121,227 @@ static inline void sfm_loudness(const double *energy /* [sfm_chunks(n)] */, int6
   free(short_term);
   free(momentary);
   free(mask);
+}
+
+/* ---- device rates: the same measurement at 16, 22.05, 24, 32, 44.1, 48, 88.2 and 96 kHz.  Frames and masks live at the capture's
+ * rate; the loudness lives at 48 kHz behind scipy.signal.resample_poly (voice_setup.py:127-140 and :214-230), on chunks of 960
+ * resampled samples.  The 48 kHz forms above keep their names and results; at 48 kHz the forms below give the same bits. */
+#define SFM_CHUNK48 960 /* the loudness grid: 20 ms at 48 kHz, whatever the capture's rate */
+static const int32_t sfm_rates[8] = {16000, 22050, 24000, 32000, 44100, 48000, 88200, 96000};
+
+
+/* 0, or -1 for a rate outside the list */
+static inline int sfm_make_geometry(int64_t rate, sfm_geometry *g) {
+  int i, listed = 0;
+  int64_t a, b;
+  memset(g, 0, sizeof *g);
+  for (i = 0; i < 8; ++i) listed |= rate == sfm_rates[i];
+  if (!listed) return -1;
+  g->rate = (int32_t)rate;
+  g->frame = (int32_t)((double)rate * 40.0 / 1000.0);
+  g->hop = (int32_t)((double)rate * 20.0 / 1000.0);
+  g->vad_window = (int32_t)((rate * 512 + 15999) / 16000);
+  for (a = rate, b = SFM_RATE; b;) { const int64_t t = a % b; a = b; b = t; }
+  g->up = (int32_t)(SFM_RATE / a);
+  g->down = (int32_t)(rate / a);
+  if (g->up == g->down) return 0;
+  g->half = 10 * (g->up > g->down ? g->up : g->down);
+  g->pre = g->down - g->half % g->down;
+  g->rem = (g->half + g->pre) / g->down;
+  g->taps = (g->pre + 2 * g->half + 1 + g->up - 1) / g->up;
+  return 0;
+}
+
+static inline int64_t sfm_frames_at(const sfm_geometry *g, int64_t n) { return n < g->frame ? 0 : (n - g->frame) / g->hop + 1; }
+static inline int64_t sfm_chunks_at(const sfm_geometry *g, int64_t n) { return (n + g->hop - 1) / g->hop; }
+/* the length resample_poly returns: ceil(n up / down) */
+static inline int64_t sfm_resampled_length(const sfm_geometry *g, int64_t n) { return (n * g->up + g->down - 1) / g->down; }
+static inline int64_t sfm_chunks48(const sfm_geometry *g, int64_t n) { return (sfm_resampled_length(g, n) + SFM_CHUNK48 - 1) / SFM_CHUNK48; }
+
+/* scipy.special.i0 by its power series: sum of ((x / 2)^2)^k / (k!)^2 */
+static inline double sfm_i0(double x) {
+  const double q = (x / 2.0) * (x / 2.0);
+  double term = 1.0, sum = 1.0;
+  int k;
+  for (k = 1; k < 200; ++k) {
+    term = term * q / ((double)k * (double)k);
+    sum += term;
+    if (term < sum * 1e-17) break;
+  }
+  return sum;
+}
+
+/* resample_poly's default filter: firwin(2 half + 1, 1 / max(up, down), window=("kaiser", 5.0)) * up behind `pre` zeros, as the
+ * polyphase table table[phase * taps + m] = hz[phase + m up] (0 behind the filter's end) */
+static inline void sfm_polyphase_table(const sfm_geometry *g, double *table /* [up][taps] */) {
+  const double pi = 3.14159265358979323846;
+  const int N = 2 * g->half + 1;
+  const double cutoff = 1.0 / (double)(g->up > g->down ? g->up : g->down), alpha = (double)g->half, i0_beta = sfm_i0(5.0);
+  double *h = (double *)malloc(sizeof(double) * (size_t)N), sum = 0.0;
+  int i, phase, m;
+  for (i = 0; i < N; ++i) {
+    const double t = (double)i - alpha, x = cutoff * t, ratio = t / alpha;
+    const double sinc = x == 0.0 ? 1.0 : sin(pi * x) / (pi * x);
+    h[i] = cutoff * sinc * (sfm_i0(5.0 * sqrt(1.0 - ratio * ratio)) / i0_beta);
+    sum += h[i];
+  }
+  for (i = 0; i < N; ++i) h[i] = h[i] / sum * (double)g->up;
+  for (phase = 0; phase < g->up; ++phase)
+    for (m = 0; m < g->taps; ++m) {
+      const int at = phase + m * g->up - g->pre;
+      table[(size_t)phase * g->taps + m] = at >= 0 && at < N ? h[at] : 0.0;
+    }
+  free(h);
+}
+
+/* output o of resample_poly over x[0 .. n): the products of one phase, the oldest input first, multiplied and added apart */
+#define SFM_POLYPHASE_SUM(g, table, n, o, VALUE, acc)                                       \
+  do {                                                                                      \
+    const int64_t t_ = ((int64_t)(o) + (g)->rem) * (g)->down, xi_ = t_ / (g)->up;           \
+    const double *row_ = (table) + (size_t)(t_ % (g)->up) * (g)->taps;                      \
+    int m_;                                                                                 \
+    (acc) = 0.0;                                                                            \
+    for (m_ = (g)->taps - 1; m_ >= 0; --m_) {                                               \
+      const int64_t j = xi_ - m_;                                                           \
+      if (j >= 0 && j < (n)) (acc) += (VALUE) * row_[m_];                                   \
+    }                                                                                       \
+  } while (0)
+
+/* :178-205 at the capture's rate: sfm_masks with the geometry's hop, frame and posterior window */
+static inline void sfm_masks_at(const sfm_geometry *g, const double *power, int F, double noise_rms_db, const double *vad, int64_t n_vad,
+                                double *frame_db, uint8_t *energy_active, uint8_t *active, double *post, int32_t *listed,
+                                af_speech_features_row *r) {
+  int f, count = 0, evidence = 0, A = 0, n_active = 0;
+  double *sorted, floor_db, p30;
+  const int with_vad = vad && n_vad > 0 && F > 0;
+  for (f = 0; f < F; ++f) frame_db[f] = 10.0 * log10(power[f] + 1e-12);
+  sorted = sfm_sorted_copy(frame_db, F);
+  p30 = af_percentile_sorted(sorted, F, 30.0) + 2.0;
+  free(sorted);
+  floor_db = noise_rms_db + 6.0 > p30 ? noise_rms_db + 6.0 : p30;
+  for (f = 0; f < F; ++f) active[f] = energy_active[f] = frame_db[f] >= floor_db;
+  if (with_vad) {
+    double *xp = (double *)malloc(sizeof(double) * (size_t)n_vad * 2);
+    uint8_t *posterior = (uint8_t *)malloc((size_t)F);
+    const double low = noise_rms_db + 2.0 > floor_db - 4.0 ? noise_rms_db + 2.0 : floor_db - 4.0;
+    af_interpolate_vad_probabilities(vad, n_vad, g->vad_window, F, g->hop, g->frame, xp, xp + n_vad, post);
+    for (f = 0; f < F; ++f) {
+      posterior[f] = (post[f] >= SFM_VAD_EVIDENCE && frame_db[f] >= low) || post[f] >= SFM_VAD_STRONG;
+      count += posterior[f];
+      evidence += post[f] >= SFM_VAD_EVIDENCE;
+    }
+    if (count >= 6) memcpy(active, posterior, (size_t)F);
+    free(posterior);
+    free(xp);
+  }
+  if (F >= 3) {
+    uint8_t prev = 0;
+    for (f = 0; f < F; ++f) {
+      const uint8_t here = active[f], next = f + 1 < F ? active[f + 1] : 0;
+      active[f] = prev | here | next;
+      prev = here;
+    }
+  }
+  for (f = 0; f < F; ++f) {
+    n_active += active[f];
+    if (active[f] | energy_active[f]) listed[A++] = f;
+  }
+  r->frames = F;
+  r->active_frames = n_active;
+  r->spectral_frames = A;
+  r->adaptive_floor_db = floor_db;
+  r->vad_probability_used = with_vad;
+  r->vad_active_frame_ratio = with_vad ? (double)evidence / (double)F : 0.0;
+}
+
+/* the sample mask at the capture's rate: sample j is active when frame j / hop or the one before it is (each covers two hops;
+ * behind the last frame nothing is) */
+static inline int sfm_sample_active(const sfm_geometry *g, const uint8_t *active, int F, int64_t j) {
+  const int64_t f = j / g->hop;
+  return (f < F && active[f]) || (f >= 1 && f - 1 < F && active[f - 1]);
+}
+
+/* one window size over the 48 kHz chunks, :143-158: count[c] of the W 960 samples of a window active, its K-weighted energy */
+static inline int sfm_windows48(const double *energy, const int32_t *count, int64_t n48, int W, int H, double *out) {
+  int n_out = 0;
+  int64_t c0;
+  for (c0 = 0; (c0 + W) * SFM_CHUNK48 <= n48; c0 += H) {
+    int64_t masked = 0;
+    int c;
+    double sum = 0.0;
+    for (c = 0; c < W; ++c) masked += count[c0 + c];
+    if ((double)masked / (double)((int64_t)W * SFM_CHUNK48) < 0.55) continue;
+    for (c = 0; c < W; ++c) sum += energy[c0 + c];
+    out[n_out++] = sfm_lufs(sum / (double)((int64_t)W * SFM_CHUNK48));
+  }
+  return n_out;
+}
+
+/* :207-261 at a device rate.  energy, masked_energy, count: [sfm_chunks48(n)] -- sum(y^2), the same over the samples whose
+ * resampled mask is >= 0.5, and how many those are, per chunk of 960 samples of the K-weighted 48 kHz signal of n48 samples.
+ * At 48 kHz the caller derives the last two from the hop mask (sfm_chunk_mask48) and the results are sfm_loudness's. */
+static inline void sfm_loudness_at(const sfm_geometry *g, const double *energy, const double *masked_energy, const int32_t *count,
+                                   int64_t n, const uint8_t *active, int F, af_speech_features_row *r) {
+  const int64_t n48 = sfm_resampled_length(g, n);
+  const int C = (int)sfm_chunks48(g, n), Cr = (int)sfm_chunks_at(g, n);
+  uint8_t *mask = (uint8_t *)calloc((size_t)Cr + 1, 1);
+  double *momentary = (double *)malloc(sizeof(double) * (size_t)(C + 1)), *short_term = (double *)malloc(sizeof(double) * (size_t)(C + 1));
+  double *sorted;
+  int f, c, n_m, n_s;
+  int64_t masked = 0;
+  for (f = 0; f < F; ++f)
+    if (active[f]) mask[f] = mask[f + 1] = 1;
+  for (c = 0; c < Cr; ++c) masked += mask[c];
+  r->active_duration_s = (double)(masked * g->hop) / (double)g->rate;
+  r->active_ratio = (double)(masked * g->hop) / (double)n;
+  n_m = sfm_windows48(energy, count, n48, 20, 5, momentary);
+  n_s = sfm_windows48(energy, count, n48, 150, 50, short_term);
+  if (n_m == 0) { /* the mean over the samples behind the resampled mask, :243-249 */
+    double sum = 0.0;
+    int64_t total = 0;
+    for (c = 0; c < C; ++c)
+      if (count[c]) { sum += masked_energy[c]; total += count[c]; }
+    momentary[0] = sfm_lufs(total ? sum / (double)total : 0.0);
+    n_m = 1;
+  }
+  if (n_s == 0) {
+    memcpy(short_term, momentary, sizeof(double) * (size_t)n_m);
+    n_s = n_m;
+  }
+  sorted = sfm_sorted_copy(momentary, n_m);
+  r->momentary_lufs = af_median_sorted(sorted, n_m);
+  r->active_loudness_spread_db = n_m >= 4 ? af_percentile_sorted(sorted, n_m, 95.0) - af_percentile_sorted(sorted, n_m, 10.0) : 0.0;
+  r->loudness_range_db = r->active_loudness_spread_db;
+  free(sorted);
+  sorted = sfm_sorted_copy(short_term, n_s);
+  r->short_term_lufs = af_median_sorted(sorted, n_s);
+  free(sorted);
+  r->loudness_window_count = n_m;
+  r->short_term_window_count = n_s;
+  free(short_term);
+  free(momentary);
+  free(mask);
+}
+
+/* at 48 kHz the resampled mask is the hop mask itself: count and masked energy of every chunk from the active frames */
+static inline void sfm_chunk_mask48(const double *energy, int64_t n, const uint8_t *active, int F, int32_t *count, double *masked_energy) {
+  const int C = (int)sfm_chunks(n);
+  int c;
+  for (c = 0; c < C; ++c) {
+    const int on = (c < F && active[c]) || (c >= 1 && c - 1 < F && active[c - 1]);
+    count[c] = on ? SFM_CHUNK48 : 0;
+    masked_energy[c] = on ? energy[c] : 0.0;
+  }
+}
+
+/* the band edges of :271-276 and :305-308 at a rate: low[6], high[6] in the order of SFM_BAND_FIELDS */
+static inline void sfm_band_edges(int64_t rate, double *low, double *high) {
+  static const double lo[6] = {80.0, 250.0, 2000.0, 5000.0, 250.0, 5000.0}, hi[6] = {250.0, 2000.0, 5000.0, 10000.0, 4500.0, 9500.0};
+  const double cap = (double)rate * 0.45;
+  int b;
+  for (b = 0; b < 6; ++b) { low[b] = lo[b]; high[b] = hi[b]; }
+  if (cap < high[3]) high[3] = cap;
+  if (cap < high[5]) high[5] = cap;
 }
 
 /* np.median over decibels of a column from its two selected middles (the decibel is monotone, so the median only selects) */

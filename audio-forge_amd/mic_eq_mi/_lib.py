@@ -462,6 +462,22 @@ SIGNATURES = {
     "af_speech_features_analyze_device": (C.c_int, [_vp, _vp, _i64, _i32, _i64, _dp, _dp, _i64, _vp, _i64, _i64,
                                                     C.POINTER(SpeechFeaturesOutputs)]),
     "af_speech_features_last_kernel_ms": (C.c_int, [_vp, _dp, _i32]),
+    "af_device_rate_features_create": (C.c_int, [C.c_uint32, _i32, _i64, _i64, _i32, C.POINTER(_vp)]),
+    "af_device_rate_features_destroy": (None, [_vp]),
+    "af_device_rate_features_frames": (_i64, [_vp, _i64]),
+    "af_device_rate_features_chunks": (_i64, [_vp, _i64]),
+    "af_device_rate_features_resampled_length": (_i64, [_vp, _i64]),
+    "af_device_rate_features_sibilance_bins": (_i32, [_vp]),
+    "af_device_rate_features_set_frame_model": (C.c_int, [_vp, _d, _dp]),
+    "af_device_rate_features_get_frame_model": (C.c_int, [_vp, _dp, _dp]),
+    "af_device_rate_features_set_scratch_bytes": (C.c_int, [_vp, _i64]),
+    "af_device_rate_features_analyze_host": (C.c_int, [_vp, _fp, _i64, _i32, _i64, _dp, _dp, _i64, _fp, _i64, _i64,
+                                                       C.POINTER(SpeechFeaturesOutputs)]),
+    "af_device_rate_features_analyze_device": (C.c_int, [_vp, _vp, _i64, _i32, _i64, _dp, _dp, _i64, _vp, _i64, _i64,
+                                                         C.POINTER(SpeechFeaturesOutputs)]),
+    "af_device_rate_features_last_kernel_ms": (C.c_int, [_vp, _dp, _i32]),
+    "af_device_rate_features_debug_resample_host": (C.c_int, [_vp, _fp, _i64, _i32, _i64, C.POINTER(C.c_uint8), _dp, C.POINTER(C.c_uint8),
+                                                              C.POINTER(_i32)]),
     "af_voice_setup_default_inputs": (None, [C.POINTER(VoiceSetupInputs)]),
     "af_voice_setup_recommend": (C.c_int, [C.POINTER(VoiceSetupInputs), C.POINTER(VoiceSetupRecommendation)]),
     # compressor candidate sweep
@@ -507,6 +523,8 @@ VALUE_FUNCTIONS = {
     "af_voice_spectrum_destroy", "af_voice_spectrum_bins", "af_voice_spectrum_frames",
     "af_noise_reference_destroy", "af_noise_reference_frame_size", "af_noise_reference_bins", "af_noise_reference_frames",
     "af_speech_features_destroy", "af_speech_features_frames", "af_speech_features_chunks", "af_speech_features_sibilance_bins",
+    "af_device_rate_features_destroy", "af_device_rate_features_frames", "af_device_rate_features_chunks",
+    "af_device_rate_features_resampled_length", "af_device_rate_features_sibilance_bins",
     "af_voice_setup_default_inputs",
     "af_compressor_search_destroy", "af_compressor_search_blocks",
 }

@@ -2310,48 +2310,87 @@ def analyze_voice_capture_batch(noise_audio, speech_audio, fs: int = 48_000, npe
 
 
 SPEECH_FEATURES_KERNELS = ("frame_powers", "k_weighting", "frame_spectra", "frame_medians", "weighted_peak")
+SPEECH_FEATURES_RATES = (16_000, 22_050, 24_000, 32_000, 44_100, 48_000, 88_200, 96_000)  # with device_rate=True
 _SPEECH_FEATURES_EVIDENCE = ("frame_probability_p90", "frame_probability_top_mean", "temporal_score", "absolute_hf_strength_p90",
                              "noise_reliability_p90")
 
 
 class SpeechFeatures:
-    """_vad_masked_speech_features (voice_setup.py:161-458) for a batch of voice captures on the device.  48 kHz only (any other
-    rate raises NotImplementedError: the reference resamples to 48 kHz before it K-weights, which is not built); scratch is
-    kept between calls."""
+    """_vad_masked_speech_features (voice_setup.py:161-458) for a batch of voice captures on the device; scratch is kept
+    between calls.  By default 48 kHz only: any other rate raises NotImplementedError.  ``device_rate=True`` takes the rates of
+    SPEECH_FEATURES_RATES (af_device_rate_features_*): frames and spectra at the capture's rate, the loudness at 48 kHz behind
+    the device's restatement of scipy.signal.resample_poly, as the reference does it; at 48 kHz the results are the same bits."""
 
     def __init__(self, sample_rate: int = 48_000, max_streams: int = 4096, max_speech_samples: int = 48_000 * 60,
-                 max_noise_samples: int = 48_000 * 60, device: int = 0):
+                 max_noise_samples: int = 48_000 * 60, device: int = 0, *, device_rate: bool = False):
         self._lib = _lib.load()
+        self.device_rate = bool(device_rate)
+        self._family = "af_device_rate_features_" if self.device_rate else "af_speech_features_"
         handle = C.c_void_p()
-        _lib.check(self._lib.af_speech_features_create(int(sample_rate), int(max_streams), int(max_speech_samples),
-                                                       int(max_noise_samples), int(device), C.byref(handle)))
+        _lib.check(self._fn("create")(int(sample_rate), int(max_streams), int(max_speech_samples), int(max_noise_samples), int(device),
+                                      C.byref(handle)))
         self._h = handle
         self.sample_rate = int(sample_rate)
-        self.sibilance_bins = int(self._lib.af_speech_features_sibilance_bins(handle))
+        self.sibilance_bins = int(self._fn("sibilance_bins")(handle))
+
+    def _fn(self, name: str):
+        return getattr(self._lib, self._family + name)
 
     def close(self) -> None:
         if getattr(self, "_h", None):
-            self._lib.af_speech_features_destroy(self._h)
+            self._fn("destroy")(self._h)
             self._h = None
 
     __del__ = close
 
     def frames(self, n_samples: int) -> int:
-        return int(self._lib.af_speech_features_frames(int(n_samples)))
+        return int(self._fn("frames")(self._h, int(n_samples)) if self.device_rate else self._fn("frames")(int(n_samples)))
 
     def chunks(self, n_samples: int) -> int:
-        return int(self._lib.af_speech_features_chunks(int(n_samples)))
+        """Chunks of the K-weighted 48 kHz signal: hop-sized at 48 kHz, 960 resampled samples at any other rate."""
+        return int(self._fn("chunks")(self._h, int(n_samples)) if self.device_rate else self._fn("chunks")(int(n_samples)))
+
+    def resampled_length(self, n_samples: int) -> int:
+        """Samples of a capture at 48 kHz: ceil(n 48000 / fs), what resample_poly returns."""
+        if not self.device_rate:
+            return int(n_samples)
+        return int(self._fn("resampled_length")(self._h, int(n_samples)))
+
+    def set_scratch_bytes(self, n_bytes: int) -> None:
+        """Bound the scratch of the resampled captures (device_rate=True; 256 MB by default): they pass through it a segment of
+        whole 48 kHz chunks of every stream at a time.  Results do not depend on it."""
+        if not self.device_rate:
+            raise ValueError("the resampling stage belongs to device_rate=True")
+        _lib.check(self._fn("set_scratch_bytes")(self._h, int(n_bytes)))
+
+    def resample(self, speech, active_frames) -> tuple:
+        """The resampling stage alone, for tests (device_rate=True, not 48 kHz): speech [n_streams, n] float32 and frame flags
+        [n_streams, frames(n)] -> (signal [n_streams, n48] f64, mask bytes [n_streams, n48], set bytes per chunk [n_streams, chunks(n)])."""
+        if not self.device_rate:
+            raise ValueError("the resampling stage belongs to device_rate=True")
+        x = np.ascontiguousarray(speech, dtype=np.float32)
+        flags = np.ascontiguousarray(active_frames, dtype=np.uint8)
+        if x.ndim != 2 or flags.shape != (x.shape[0], max(self.frames(x.shape[1]), 0)):
+            raise ValueError("speech must be [n_streams, n] and active_frames [n_streams, frames(n)]")
+        B, n = x.shape
+        n48 = self.resampled_length(n)
+        signal, mask, counts = np.zeros((B, n48)), np.zeros((B, n48), dtype=np.uint8), np.zeros((B, self.chunks(n)), dtype=np.int32)
+        bp = C.POINTER(C.c_uint8)
+        _lib.check(self._fn("debug_resample_host")(self._h, x.ctypes.data_as(C.POINTER(C.c_float)), n, B, n, flags.ctypes.data_as(bp),
+                                                   signal.ctypes.data_as(C.POINTER(C.c_double)), mask.ctypes.data_as(bp),
+                                                   counts.ctypes.data_as(C.POINTER(C.c_int32))))
+        return signal, mask, counts
 
     def set_frame_model(self, intercept: float, coefficients) -> None:
         """FRAME_INTERCEPT and FRAME_COEFFICIENTS of deesser_fusion.py:30-41 (the defaults)."""
         w = np.ascontiguousarray(coefficients, dtype=np.float64)
         if w.shape != (6,):
             raise ValueError("coefficients must be six values")
-        _lib.check(self._lib.af_speech_features_set_frame_model(self._h, float(intercept), w.ctypes.data_as(C.POINTER(C.c_double))))
+        _lib.check(self._fn("set_frame_model")(self._h, float(intercept), w.ctypes.data_as(C.POINTER(C.c_double))))
 
     def frame_model(self) -> tuple:
         intercept, w = C.c_double(), np.zeros(6)
-        _lib.check(self._lib.af_speech_features_get_frame_model(self._h, C.byref(intercept), w.ctypes.data_as(C.POINTER(C.c_double))))
+        _lib.check(self._fn("get_frame_model")(self._h, C.byref(intercept), w.ctypes.data_as(C.POINTER(C.c_double))))
         return float(intercept.value), w
 
     def analyze(self, speech, noise_rms_db, vad_probabilities=None, noise_audio=None, device_pointers=None, internals: bool = False) -> dict:
@@ -2392,13 +2431,12 @@ class SpeechFeatures:
         o = _lib.SpeechFeaturesOutputs(rows=rows, **{k: a.ctypes.data_as(C.POINTER(kinds[a.dtype])) for k, a in out.items()})
         tail = (level.ctypes.data_as(dp), None if vad is None else vad.ctypes.data_as(dp), 0 if vad is None else vad.shape[1])
         if device_pointers is None:
-            rc = self._lib.af_speech_features_analyze_host(self._h, x.ctypes.data_as(fp), n, B, n, *tail,
-                                                           None if z is None else z.ctypes.data_as(fp), m, m, C.byref(o))
+            rc = self._fn("analyze_host")(self._h, x.ctypes.data_as(fp), n, B, n, *tail, None if z is None else z.ctypes.data_as(fp), m, m,
+                                          C.byref(o))
         else:
             d_speech, _, _, stride, d_noise, _, noise_stride = device_pointers
-            rc = self._lib.af_speech_features_analyze_device(self._h, C.c_void_p(int(d_speech)), n, B, int(stride), *tail,
-                                                             None if d_noise is None else C.c_void_p(int(d_noise)), m, int(noise_stride),
-                                                             C.byref(o))
+            rc = self._fn("analyze_device")(self._h, C.c_void_p(int(d_speech)), n, B, int(stride), *tail,
+                                            None if d_noise is None else C.c_void_p(int(d_noise)), m, int(noise_stride), C.byref(o))
         _lib.check(rc)
         for name, _ in _lib.SpeechFeaturesRow._fields_:
             if name != "reserved":
@@ -2406,10 +2444,11 @@ class SpeechFeatures:
         return out
 
     def last_kernel_ms(self) -> dict:
-        """GPU ms of each stage of the last call, summed over its tiles."""
-        ms = (C.c_double * 5)()
-        _lib.check(self._lib.af_speech_features_last_kernel_ms(self._h, ms, 5))
-        return dict(zip(SPEECH_FEATURES_KERNELS, (float(x) for x in ms)))
+        """GPU ms of each stage of the last call, summed over its tiles (with device_rate=True also "resampling")."""
+        names = SPEECH_FEATURES_KERNELS + (("resampling",) if self.device_rate else ())
+        ms = (C.c_double * len(names))()
+        _lib.check(self._fn("last_kernel_ms")(self._h, ms, len(names)))
+        return dict(zip(names, (float(x) for x in ms)))
 
 
 def _speech_features_dicts(r: dict) -> list:
@@ -2441,15 +2480,17 @@ def _speech_features_dicts(r: dict) -> list:
     return results
 
 
-def measure_speech_features_batch(speech, fs: int, noise_rms_db, *, vad_probabilities=None, noise_audio=None, device: int = 0) -> list:
+def measure_speech_features_batch(speech, fs: int, noise_rms_db, *, vad_probabilities=None, noise_audio=None, device: int = 0,
+                                  device_rate: bool = False) -> list:
     """_vad_masked_speech_features (voice_setup.py:161-458) of every row of speech [n_streams, n]: a list of dicts with the
     reference's keys (samples are taken as float32).  noise_rms_db: one level per stream; vad_probabilities [n_streams, n_vad] or
-    None; noise_audio [n_streams, m] or None.  A stream with a non-finite sample yields None."""
+    None; noise_audio [n_streams, m] or None.  A stream with a non-finite sample yields None.  fs is 48000, or with
+    ``device_rate=True`` any of SPEECH_FEATURES_RATES."""
     x = np.asarray(speech)
     if x.ndim != 2:
         raise ValueError("speech must be [n_streams, n]")
     m = 0 if noise_audio is None else np.asarray(noise_audio).shape[-1]
-    sf = SpeechFeatures(fs, x.shape[0], max(x.shape[1], 1920), m, device)
+    sf = SpeechFeatures(fs, x.shape[0], max(x.shape[1], 2 * int(fs * 0.02), 1), m, device, device_rate=device_rate)
     try:
         return _speech_features_dicts(sf.analyze(x, noise_rms_db, vad_probabilities, noise_audio))
     finally:
@@ -2582,7 +2623,8 @@ NOISE_MIN_DURATION_S, SPEECH_MIN_DURATION_S = 1.5, 3.0  # voice_setup.py:42-43
 def recommend_voice_chain_batch(noise_audio, speech_audio, fs: int, target_preset: str = "broadcast", *, vad_probabilities=None,
                                 noise_vad_probabilities=None, vad_available: bool = True, dynamics_intensity: str = "balanced",
                                 custom_target_p95_db: float = 3.5, custom_peak_cap_db: float = 8.0, noise_metadata=None,
-                                speech_metadata=None, device: int = 0, calibrate_compressor: bool = False, eq_settings=None) -> list:
+                                speech_metadata=None, device: int = 0, calibrate_compressor: bool = False, eq_settings=None,
+                                device_rate: bool = False) -> list:
     """analyze_voice_setup (voice_setup.py:1082-1223) for every pair of noise_audio [n_streams, m] and speech_audio
     [n_streams, n] up to its three rule-based recommendations: analyze_voice_capture_batch (the noise reference, then the voice
     spectrum with the conservative spectrum as its override), the "balanced" smoothing of the median spectrum, the speech
@@ -2604,6 +2646,9 @@ def recommend_voice_chain_batch(noise_audio, speech_audio, fs: int, target_prese
     ``eq_settings`` the calibration reads "unavailable" and the compressor stays, as in the reference when its EQ analysis
     failed.  With the default (False) the return is what it was: threshold_db is the rule's starting value.
 
+    fs is 48000, or with ``device_rate=True`` any of SPEECH_FEATURES_RATES: the noise reference, the voice spectrum and the
+    speech features then run at that rate (the loudness behind the resampling to 48 kHz of voice_setup.py:127-140).
+
     It does NOT return EQ bands (the Auto-EQ optimiser is not built) or the offline validation and setup confidences."""
     noise, speech = np.asarray(noise_audio), np.asarray(speech_audio)
     if noise.ndim != 2 or speech.ndim != 2 or noise.shape[0] != speech.shape[0]:
@@ -2614,7 +2659,7 @@ def recommend_voice_chain_batch(noise_audio, speech_audio, fs: int, target_prese
         raise ValueError("Voice capture was too short for setup.")
     if not vad_available:
         vad_probabilities = noise_vad_probabilities = None
-    sf = SpeechFeatures(fs, speech.shape[0], speech.shape[1], noise.shape[1], device)  # first: it refuses every rate but 48 kHz
+    sf = SpeechFeatures(fs, speech.shape[0], speech.shape[1], noise.shape[1], device, device_rate=device_rate)  # first: it refuses a rate
     try:
         references, spectra = analyze_voice_capture_batch(noise, speech, fs, noise_metadata=noise_metadata, speech_metadata=speech_metadata,
                                                           noise_vad_probabilities=noise_vad_probabilities,

@@ -878,8 +878,8 @@ int af_noise_reference_last_kernel_ms(af_noise_reference *h, double *ms, int32_t
  * _vad_masked_speech_features for a batch of voice captures: frame levels and the VAD-fused active-speech mask (:178-205),
  * momentary and short-term loudness of the active speech (:127-158, :214-261), four robust band levels (:263-289) and the
  * per-frame sibilance evidence with the frame model of deesser_fusion.py:60-78 (:291-430).  Frames are 1920 samples at hop 960.
- * 48000 Hz only: the reference K-weights at 48 kHz behind scipy's resample_poly (:130-132), which is not restated here, so any
- * other rate is AF_ERR_UNSUPPORTED at create.  A capture below one frame is AF_ERR_INVALID_ARGUMENT (the reference raises:
+ * 48000 Hz only: the reference K-weights at 48 kHz behind scipy's resample_poly (:130-132), which af_device_rate_features_*
+ * below restates, so any other rate is AF_ERR_UNSUPPORTED at create here.  A capture below one frame is AF_ERR_INVALID_ARGUMENT (the reference raises:
  * its window and frame shapes disagree, :173, :281).  A non-finite sample in a stream's speech capture, or in a whole analysis
  * frame of its noise capture (what the reference reads of it: samples behind the last whole frame are not examined), sets that
  * stream's `non_finite`; none of its other fields is defined then, and the other streams are not affected. */
@@ -946,6 +946,44 @@ int af_speech_features_analyze_device(af_speech_features *h, const float *d_spee
 /* GPU time of the kernels of the last call: ms[0 .. 5) = frame powers, K-weighting, frame spectra, medians over frames,
  * weighted peak (events around them; copies and host decisions are not in it).  capacity: at least 5. */
 int af_speech_features_last_kernel_ms(af_speech_features *h, double *ms, int32_t capacity);
+
+/* ---- speech features at device rates ------------------------------------------------------------------------------
+ * The same measurement for captures at 16000, 22050, 24000, 32000, 44100, 48000, 88200 or 96000 Hz; any other rate is
+ * AF_ERR_UNSUPPORTED at create, with the rate and the rule it breaks.  Frames are int(0.04 fs) samples at hop int(0.02 fs), the
+ * posteriors cover ceil(fs 512 / 16000) samples each, the sibilance bands end at min(., 0.45 fs).  The loudness K-weights at
+ * 48 kHz: signal and sample mask go through scipy.signal.resample_poly(x, 48000 / g, fs / g) (voice_setup.py:127-140, :214-230),
+ * restated on the device -- the same polyphase sum in the same order, on a filter designed here that agrees with scipy's to a
+ * few ulp of its peak.  Rows, outputs and arguments are af_speech_features_*'s, with F = frames(n), C = chunks(n) = chunks of 960
+ * samples of the resampled_length(n) = ceil(n 48000 / fs) samples at 48 kHz.  At 48000 Hz nothing is resampled and every
+ * result has af_speech_features_*'s bits. */
+typedef struct af_device_rate_features af_device_rate_features;
+int af_device_rate_features_create(uint32_t sample_rate, int32_t max_streams, int64_t max_speech_samples, int64_t max_noise_samples,
+                                   int32_t device, af_device_rate_features **out);
+void af_device_rate_features_destroy(af_device_rate_features *h);
+int64_t af_device_rate_features_frames(const af_device_rate_features *h, int64_t n_samples);           /* VALUE: 0 below one frame */
+int64_t af_device_rate_features_chunks(const af_device_rate_features *h, int64_t n_samples);           /* VALUE: 48 kHz chunks of 960 */
+int64_t af_device_rate_features_resampled_length(const af_device_rate_features *h, int64_t n_samples); /* VALUE */
+int32_t af_device_rate_features_sibilance_bins(const af_device_rate_features *h); /* VALUE: 181; 89 at 16 kHz (5000-7200 Hz) */
+int af_device_rate_features_set_frame_model(af_device_rate_features *h, double intercept, const double coefficients[6]);
+int af_device_rate_features_get_frame_model(const af_device_rate_features *h, double *intercept, double coefficients[6]);
+/* The resampled captures pass through scratch a segment of whole 48 kHz chunks of every stream at a time: 9 bytes a sample, at
+ * most `bytes` of it (256 MB by default; at least one chunk of every stream).  Results do not depend on it. */
+int af_device_rate_features_set_scratch_bytes(af_device_rate_features *h, int64_t bytes);
+int af_device_rate_features_analyze_host(af_device_rate_features *h, const float *speech, int64_t n_speech, int32_t n_streams,
+                                         int64_t speech_stride, const double *noise_rms_db, const double *vad_probabilities, int64_t n_vad,
+                                         const float *noise, int64_t n_noise, int64_t noise_stride, const af_speech_features_outputs *out);
+int af_device_rate_features_analyze_device(af_device_rate_features *h, const float *d_speech, int64_t n_speech, int32_t n_streams,
+                                           int64_t speech_stride, const double *noise_rms_db, const double *vad_probabilities,
+                                           int64_t n_vad, const float *d_noise, int64_t n_noise, int64_t noise_stride,
+                                           const af_speech_features_outputs *out);
+/* ms[0 .. 6) = frame powers, K-weighting, frame spectra, medians over frames, weighted peak, resampling.  capacity: at least 6. */
+int af_device_rate_features_last_kernel_ms(af_device_rate_features *h, double *ms, int32_t capacity);
+/* For tests: the resampling stage alone.  active_frames: [n_streams][F] frame flags (host); signal [n_streams][n48] and mask
+ * [n_streams][n48] (1 where the resampled sample mask is >= 0.5) with n48 = resampled_length(n_speech); counts [n_streams][C]
+ * the set bytes per chunk.  Not for a 48000 Hz handle. */
+int af_device_rate_features_debug_resample_host(af_device_rate_features *h, const float *speech, int64_t n_speech, int32_t n_streams,
+                                                int64_t speech_stride, const uint8_t *active_frames, double *signal, uint8_t *mask,
+                                                int32_t *counts);
 
 /* ---- voice-chain recommendation: python/mic_eq/analysis/voice_setup.py:1143-1223, 468-696 ------------------------------
  * The rules that turn one capture pair's measurements into gate, de-esser and compressor settings: the level percentiles of

@@ -1,5 +1,7 @@
 """Cost of the speech-feature measurement: --pairs capture pairs of --noise-seconds of room tone and --voice-seconds of voice at
-48 kHz resident on the device, measured through af_speech_features_analyze_device.  Reported, not gated.  --processes child
+--fs (48 kHz by default) resident on the device, measured through af_speech_features_analyze_device -- at any other rate through
+af_device_rate_features_analyze_device, whose "resampling" stage (resample_poly of signal and mask to 48 kHz) is reported beside
+the K-weighting it feeds.  Reported, not gated.  --processes child
 processes one after the other, each --steps + 1 calls with the first discarded; one JSON line per process: wall ms per call
 (device events around the call, which include the host's decisions and copies between the kernels), the kernels' ms per stage
 (af_speech_features_last_kernel_ms: frame powers, K-weighting, frame spectra, medians over frames, weighted peak), capture
@@ -9,7 +11,7 @@ sibilance bins), LDS bytes (every stage reads and writes the M points once, 32 M
 bytes (the frame's samples and window once, the sibilance row and the band record written once).  The K-weighting kernel is
 set against it as dependent f64 operations per sample and lane.
 
-    python tools/bench_speech_features.py [--pairs 4096] [--noise-seconds 3] [--voice-seconds 10] [--steps 3] [--processes 3]
+    python tools/bench_speech_features.py [--fs 48000] [--pairs 4096] [--noise-seconds 3] [--voice-seconds 10] [--steps 3] [--processes 3]
 """
 from __future__ import annotations
 
@@ -23,8 +25,18 @@ ROOT = pathlib.Path(__file__).resolve().parents[1]
 for p in (ROOT, ROOT / "audio-forge_amd", ROOT / "tests"):
     sys.path.insert(0, str(p))
 
-FS, N, M = 48_000, 1920, 960
-FACTORS = (5, 3, 2, 2, 2, 2, 2, 2)
+
+
+def factors(m: int) -> tuple:
+    """nr_make_plan's factor list of the half-frame: the largest radix first."""
+    out = []
+    for p in (7, 5, 3, 2):
+        while m % p == 0:
+            out.append(p)
+            m //= p
+    return tuple(out)
+
+
 HBM_BYTES_PER_S = 8.0e12     # MI355X HBM3E peak
 F64_FLOPS_PER_S = 78.6e12    # vector f64 peak
 LDS_BYTES_PER_S = 256 * 128 * 2.4e9  # 256 CUs x 128 B a clock at 2.4 GHz
@@ -44,7 +56,9 @@ def run(args) -> None:
 
     from mic_eq_mi import mic_eq_core as core
 
-    B = args.pairs
+    B, FS = args.pairs, args.fs
+    M = int(FS * 20 / 1000.0)
+    N, FACTORS = 2 * M, factors(M)
     n_noise, n_voice = int(args.noise_seconds * FS), int(args.voice_seconds * FS)
     g = torch.Generator(device="cuda").manual_seed(29)
     t = torch.arange(n_voice, device="cuda", dtype=torch.float32) / FS
@@ -59,7 +73,7 @@ def run(args) -> None:
         voice[s0:s0 + b] = torch.randn(b, n_voice, device="cuda", generator=g) * (0.1 * envelope + 0.003)
     torch.cuda.synchronize()
     level = [-50.0] * B
-    sf = core.SpeechFeatures(FS, B, n_voice, n_noise)
+    sf = core.SpeechFeatures(FS, B, n_voice, n_noise, device_rate=FS != 48_000)
     S = sf.sibilance_bins
     pointers = (voice.data_ptr(), n_voice, B, n_voice, noise.data_ptr(), n_noise, n_noise)
     wall, stages, r = [], [], None
@@ -72,7 +86,7 @@ def run(args) -> None:
         if step:  # the first repetition is discarded
             wall.append(a.elapsed_time(b))
             stages.append(sf.last_kernel_ms())
-    noise_frames = sf.frames(n_noise)
+    noise_frames, sf_n48 = sf.frames(n_noise), sf.resampled_length(n_voice)
     sf.close()
     speech_frames = int(r["spectral_frames"].sum())
     frames = speech_frames + B * noise_frames
@@ -81,7 +95,13 @@ def run(args) -> None:
     lds = frames * 32.0 * M * (len(FACTORS) + 1) + speech_frames * 8.0 * S * S
     hbm = frames * (4.0 * N + 8.0 * N) + speech_frames * 8.0 * (S + 8 + 2)
     fft_s, kw_s = best["frame_spectra"] * 1e-3, best["k_weighting"] * 1e-3
-    print(json.dumps({"bench": "speech_features", "pairs": B, "noise_seconds": args.noise_seconds, "voice_seconds": args.voice_seconds,
+    resampling = {}
+    if "resampling" in best:
+        n48 = sf_n48
+        resampling = {"resampling": {"ms": round(best["resampling"], 3), "samples_out": n48,
+                                     "ns_per_output_sample_and_stream": round(best["resampling"] * 1e6 / (n48 * B), 4),
+                                     "ratio_to_k_weighting": round(best["resampling"] / best["k_weighting"], 3)}}
+    print(json.dumps({"bench": "speech_features", "fs": FS, "pairs": B, "noise_seconds": args.noise_seconds, "voice_seconds": args.voice_seconds,
                       "frame": N, "factors": list(FACTORS), "frames_transformed": frames, "speech_frames_listed": speech_frames,
                       "streams_with_evidence": int(r["evidence_available"].sum()), "non_finite_streams": int(r["non_finite"].sum()),
                       "ms_per_call": [round(v, 2) for v in wall],
@@ -96,11 +116,13 @@ def run(args) -> None:
                       "k_weighting": {"ms": round(best["k_weighting"], 3), "workgroups": -(-B // kweight_streams_per_workgroup(B)),
                                       "ns_per_sample_and_lane": round(kw_s / n_voice * 1e9, 2),
                                       "dependent_f64_ops_per_sample": KWEIGHT_OPS_PER_SAMPLE,
-                                      "ratio_to_frame_spectra": round(best["k_weighting"] / best["frame_spectra"], 3)}}), flush=True)
+                                      "ratio_to_frame_spectra": round(best["k_weighting"] / best["frame_spectra"], 3)}, **resampling}),
+          flush=True)
 
 
 def main() -> None:
     ap = argparse.ArgumentParser()
+    ap.add_argument("--fs", type=int, default=48_000)
     ap.add_argument("--pairs", type=int, default=4096)
     ap.add_argument("--noise-seconds", type=float, default=3.0)
     ap.add_argument("--voice-seconds", type=float, default=10.0)
@@ -112,7 +134,7 @@ def main() -> None:
         run(args)
         return
     for _ in range(args.processes):  # a fresh process each: code-object load and first allocations are in the discarded call
-        forward = [f"--{k.replace('_', '-')}={getattr(args, k)}" for k in ("pairs", "noise_seconds", "voice_seconds", "steps")]
+        forward = [f"--{k.replace('_', '-')}={getattr(args, k)}" for k in ("fs", "pairs", "noise_seconds", "voice_seconds", "steps")]
         subprocess.run([sys.executable, __file__, "--child", *forward], check=True)
 
 
