@@ -1957,6 +1957,22 @@ int af_suppressor_debug_read_pitch(af_engine *e, int32_t frame, int32_t stream, 
   if (last_gain) *last_gain = state[1];
   return AF_OK;
 }
+// test tap of the pre-pass: one stream's row of the LAST window's model-input buffer -- the 1728 history samples the pre-pass
+// copied in front, then the window's samples -- and the row's length
+int af_suppressor_debug_read_model_input(af_engine *e, int32_t stream, float *row, int64_t capacity, int64_t *length) {
+  if (!e || !e->supp.d_xh || e->supp.last_xh_slot < 0) return fail(AF_ERR_STATE, "no suppressor window has run");
+  const int64_t n = af::kPitchBuf + (int64_t)e->supp.last_xh_frames * af::kRnnFrame;
+  if (stream < 0 || stream >= e->n_streams || !length || (row && capacity < n))
+    return fail(AF_ERR_INVALID_ARGUMENT, "stream out of range, no length pointer, or fewer than %lld floats of room", (long long)n);
+  if (row) {
+    AF_HIP(e->use_device());
+    AF_HIP(hipDeviceSynchronize());
+    AF_HIP(hipMemcpy(row, e->supp.d_xh + (size_t)e->supp.last_xh_slot * e->supp.xh_floats + (size_t)stream * (size_t)n, sizeof(float) * (size_t)n,
+                     hipMemcpyDeviceToHost));
+  }
+  *length = n;
+  return AF_OK;
+}
 // test tap: ONLY the pitch search kernel, through the launcher the engine uses, on caller-supplied model-input spans
 // [stream][1728 + 480 n_frames] (host pointers): its whitened buffers [frame][stream][864] and its own pitch index
 // [frame][stream] -- the one the tracker overwrites in an engine run.  No engine, no state.
@@ -2408,6 +2424,8 @@ static int run_suppressor_pipeline(af_engine *e, const CallArgs &c, const float 
       AF_HIP(af::launch_suppressor_prefilter(window_args(w), e->pre_stream));
     }
     AF_HIP(hipEventRecord(pre_done[w], e->pre_stream));
+    e->supp.last_xh_slot = (int)(w % kXh);  // (af_suppressor_debug_read_model_input)
+    e->supp.last_xh_frames = (int)wins[w].nf;
     return AF_OK;
   };
   auto enqueue_ana = [&](int64_t w) -> int {

@@ -10,7 +10,7 @@
 //
 // Seven kernels per window of frames:
 //   supp_prefilter_kernel  lane per stream: model-input scaling + RNNoise's 2nd-order high-pass over
-//                          samples (a recurrence), 64x64 tiles transposed through LDS.
+//                          samples (a recurrence), tiles of 64 streams x 32 samples transposed through LDS.
 //   supp_spectrum_kernel   wave per (frame, stream): 960-point windowed transform, 22 band energies.
 //   supp_pitch_kernel      wave per stream, frames in order: LPC-whitened 2x-decimated buffer, coarse +
 //                          fine cross-correlation, octave-error removal (looks at the previous frame),
@@ -78,19 +78,36 @@ hipError_t launch_scale_probe(const float *in, float *out, int64_t n, hipStream_
 // around a feed-forward soft clip, so its duration is samples x (instructions on the longest recurrence) x ~8 cycles (one
 // wave issues a dependent vector instruction every ~8 cycles: tools/probe/valu_latency.hip) whatever the lane count.  As one
 // wave doing everything that was ~800 cycles per sample (2.4-3.0 ms per 8 880-sample window at ANY batch: what a small batch
-// waited for).  Now a workgroup of six waves takes 64 streams and works as a pipeline over 64-sample tiles, one barrier per
-// tile: wave 0 loads tile i (64 row loads, transposed into LDS), wave 1 runs the front end on tile i-1 (lane = stream), wave 2
-// the soft clip on tile i-2 (lane = TIME: 64 independent samples per instruction), wave 3 the model's high-pass on tile i-3
-// (lane = stream), waves 4 and 5 write the dry signal of tile i-2 and the model input of tile i-4 back as rows.
+// waited for).  Now a workgroup of six waves takes 64 streams and works as a pipeline over kPreT-sample tiles, one barrier per
+// tile: wave 0 loads tile i (transposed into LDS), wave 1 runs the front end on tile i-1 IN PLACE (lane = stream), wave 2
+// the soft clip of tile i-2 into a second ring (lane = TIME), wave 3 the model's high-pass on tile i-3 in place there
+// (lane = stream), waves 4 and 5 write the dry signal of tile i-2 and the model input of tile i-4 back as rows.  A tile of
+// either ring is in flight for three iterations, so each ring holds three.
+// Tile length (AF_PRE_TILE, a power of two up to 64): 32 samples.  The six tiles are then 49 920 bytes and
+// two transform workgroups, or a search workgroup and a transform workgroup, fit on the CU beside this one; eight tiles of
+// 64 samples (133 120 bytes) left room for nothing but the tracker.  The lane = time roles keep all 64 lanes busy: lane l
+// works on sample l % kPreT of row (l / kPreT) * kPreT + r, so a row segment is kPreT x 4 bytes (128: still a whole cache
+// line) and a wave touches 64 / kPreT rows per instruction.
+#ifndef AF_PRE_TILE
+#define AF_PRE_TILE 32
+#endif
 constexpr int kPreGroup = 64;
 constexpr int kPreWaves = 6;
-constexpr int kPreTile = 64 * (kPreGroup + 1);  // floats per LDS tile
+constexpr int kPreT = AF_PRE_TILE;               // samples per tile
+constexpr int kPreRow = kPreGroup + 1;           // floats per LDS row: one sample of the 64 streams + a pad column
+constexpr int kPreTile = kPreT * kPreRow;        // floats per LDS tile
+constexpr int kPreRing = 3;                      // tiles per ring
+constexpr bool kPreRagged = kRnnFrame % kPreT != 0;  // a window is whole frames: at 32 (480 = 15 x 32) no tile is short
+static_assert(kPreT >= 8 && kPreT <= 64 && (kPreT & (kPreT - 1)) == 0, "the tile length divides the wave");
 template <bool kClamp, bool kDcHp, bool kRaw>
 __global__ __launch_bounds__(64 * kPreWaves) void supp_prefilter_kernel(SuppArgs a) {
-  extern __shared__ float pre_lds[];  // in[2], dry[2], sc[2], xh[2]
+  extern __shared__ float pre_lds[];  // in -> dry [3], sc -> xh [3]
   constexpr bool kFront = kClamp || kDcHp;
-  float *t_in = pre_lds, *t_dry = pre_lds + 2 * kPreTile, *t_sc = pre_lds + 4 * kPreTile, *t_xh = pre_lds + 6 * kPreTile;
+  constexpr int T = kPreT;
+  float *t_dry = pre_lds, *t_xh = pre_lds + kPreRing * kPreTile;
+  auto sel = [](int64_t ti) { return (int)(ti % kPreRing) * kPreTile; };  // (ti >= 0)
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int tl = lane & (T - 1), row0 = (lane / T) * T;  // lane = time roles: sample tl of rows row0 + r, r < T
   const int s0 = blockIdx.x * kPreGroup;
   const int s = s0 + lane;
   const bool valid = s < a.n_streams;
@@ -99,9 +116,9 @@ __global__ __launch_bounds__(64 * kPreWaves) void supp_prefilter_kernel(SuppArgs
   const int64_t n = (int64_t)a.n_frames * kRnnFrame;
   const int64_t xh_stride = kPitchBuf + n;
   float *st = a.state + (int64_t)sc * SuppState::kCount;
-  const int64_t ntiles = (n + 63) / 64;
-  auto at = [](float *tile, int t, int col) -> float & { return tile[t * (kPreGroup + 1) + col]; };
-  auto tile_len = [&](int64_t ti) { return (int)((n - ti * 64) < 64 ? (n - ti * 64) : 64); };
+  const int64_t ntiles = (n + T - 1) / T;
+  auto at = [](float *tile, int t, int col) -> float & { return tile[t * kPreRow + col]; };
+  auto tile_len = [&](int64_t ti) { return kPreRagged ? (int)((n - ti * T) < T ? (n - ti * T) : T) : T; };
 
   // history: the previous 1728 model-input samples go in front of the window -- the tail of the previous
   // window's buffer when there is one (its kernels may still be running), else what the last call saved
@@ -129,81 +146,95 @@ __global__ __launch_bounds__(64 * kPreWaves) void supp_prefilter_kernel(SuppArgs
   const float b0 = -2.0f, b1 = 1.0f, a0 = -1.99599f, a1 = 0.99600f;  // RNNoise input high-pass
   const double hb0 = a.hp_b0, hb1 = a.hp_b1, hb2 = a.hp_b2, ha1 = a.hp_a1, ha2 = a.hp_a2;
   const bool hp_on = a.front_hp != 0;
+  // the load wave's rows: first_row + min(r, rows_left) (clamped, not skipped: the T loads stay in flight together)
+  const int first_row = (s0 + row0) < a.n_streams ? (s0 + row0) : a.n_streams - 1;
+  const float *const in_lane = a.in + (int64_t)first_row * a.in_stride + a.frame0 * kRnnFrame;
 
+  // The load wave keeps one tile in flight in registers: tile it + 1 is requested when tile `it` has gone to LDS, so the
+  // loads' latency passes during the iteration before the one that needs them (what a small batch, whose pre-pass has the
+  // chip to itself, waits for: at 32 samples a tile's recurrences are shorter than one load).  The T row addresses are the
+  // same for every tile but for the column: left to itself the compiler keeps all of them in registers for the whole kernel
+  // (64 VGPRs for every wave of it).  So the tile's first address and the row limit pass through an empty asm, and each
+  // row's address is two independent adds from there -- independent: a pointer walked from row to row made the loads one
+  // more recurrence.
+  float v[T];
+  auto request = [&](int64_t ti) {
+    const int len = tile_len(ti);
+    const float *p = in_lane + ti * T + (tl < len ? tl : len - 1);
+    int rows_left = a.n_streams - 1 - first_row;
+    asm volatile("" : "+v"(p), "+v"(rows_left));
+    const float *const p_last = p + (int64_t)rows_left * a.in_stride;
+#pragma unroll
+    for (int r = 0; r < T; ++r) v[r] = *(r <= rows_left ? p + (int64_t)r * a.in_stride : p_last);
+  };
+  if (wave == 0 && ntiles > 0) request(0);
+
+  // (every wave runs every iteration and its barrier: the trip count is uniform and no role returns early)
   for (int64_t it = 0; it < ntiles + 4; ++it) {
-    if (wave == 0) {  // ---- load tile `it` (rows are clamped, not skipped: the 64 loads stay in flight together)
+    if (wave == 0) {  // ---- tile `it` to LDS, transposed; request tile it + 1
       const int64_t ti = it;
       if (ti < ntiles) {
-        const int len = tile_len(ti);
-        const int64_t col = a.frame0 * kRnnFrame + ti * 64 + (lane < len ? lane : len - 1);
-        float v[kPreGroup];
+        float *tile = t_dry + sel(ti);
 #pragma unroll
-        for (int r = 0; r < kPreGroup; ++r) {
-          const int sr = (s0 + r) < a.n_streams ? (s0 + r) : a.n_streams - 1;
-          v[r] = a.in[(int64_t)sr * a.in_stride + col];
-        }
-        float *tile = t_in + (ti & 1) * kPreTile;
-#pragma unroll
-        for (int r = 0; r < kPreGroup; ++r) at(tile, lane, r) = v[r];
+        for (int r = 0; r < T; ++r) at(tile, tl, row0 + r) = v[r];
+        if (ti + 1 < ntiles) request(ti + 1);
       }
-    } else if (wave == 1) {  // ---- front end on tile it - 1 (lane = stream): routing.rs:802-843
+    } else if (wave == 1) {  // ---- front end on tile it - 1, in place (lane = stream): routing.rs:802-843
       const int64_t ti = it - 1;
-      if (ti >= 0 && ti < ntiles) {
+      if (kFront && ti >= 0 && ti < ntiles) {
         const int len = tile_len(ti);
-        float *src = t_in + (ti & 1) * kPreTile, *dst = t_dry + (ti & 1) * kPreTile;
+        float *tile = t_dry + sel(ti);
 #pragma unroll 8
-        for (int t = 0; t < 64; ++t) {
+        for (int t = 0; t < T; ++t) {
           if (t < len) {
-            float v = at(src, t, lane);
-            if (kFront) {
-              if (!finite32(v)) v = 0.0f;                                        // routing.rs:808-811
-              if (kClamp) v = v < -1.0f ? -1.0f : (v > 1.0f ? 1.0f : v);        // routing.rs:822
-              if (kDcHp) {                                                       // routing.rs:832-840
-                const float o = v - dc_x1 + 0.995f * dc_y1;
-                dc_x1 = v;
-                dc_y1 = o;
-                v = o;
-                if (hp_on) {
-                  const double xin = (double)o;
-                  const double y = hb0 * xin + z1;
-                  z1 = hb1 * xin - ha1 * y + z2;
-                  z2 = hb2 * xin - ha2 * y;
-                  v = (float)y;
-                }
+            float v = at(tile, t, lane);
+            if (!finite32(v)) v = 0.0f;                                        // routing.rs:808-811
+            if (kClamp) v = v < -1.0f ? -1.0f : (v > 1.0f ? 1.0f : v);        // routing.rs:822
+            if (kDcHp) {                                                       // routing.rs:832-840
+              const float o = v - dc_x1 + 0.995f * dc_y1;
+              dc_x1 = v;
+              dc_y1 = o;
+              v = o;
+              if (hp_on) {
+                const double xin = (double)o;
+                const double y = hb0 * xin + z1;
+                z1 = hb1 * xin - ha1 * y + z2;
+                z2 = hb2 * xin - ha2 * y;
+                v = (float)y;
               }
             }
-            at(dst, t, lane) = v;
+            at(tile, t, lane) = v;
           }
         }
       }
     } else if (wave == 2) {  // ---- model-input scaling of tile it - 2 (lane = time)
       const int64_t ti = it - 2;
       if (ti >= 0 && ti < ntiles) {
-        float *src = t_dry + (ti & 1) * kPreTile, *dst = t_sc + (ti & 1) * kPreTile;
+        float *src = t_dry + sel(ti), *dst = t_xh + sel(ti);
 #pragma unroll 8
-        for (int r = 0; r < kPreGroup; ++r) {
-          float v = at(src, lane, r);
+        for (int r = 0; r < T; ++r) {
+          float v = at(src, tl, row0 + r);
           if (kRaw) {  // bin/rnnoise_benchmark.rs:75-79
             v = (v < -1.0f ? -1.0f : (v > 1.0f ? 1.0f : v)) * 32768.0f;
           } else {
             v = scale_for_model(v);
           }
-          at(dst, lane, r) = v;
+          at(dst, tl, row0 + r) = v;
         }
       }
-    } else if (wave == 3) {  // ---- the model's own high-pass on tile it - 3 (lane = stream)
+    } else if (wave == 3) {  // ---- the model's own high-pass on tile it - 3, in place (lane = stream)
       const int64_t ti = it - 3;
       if (ti >= 0 && ti < ntiles) {
         const int len = tile_len(ti);
-        float *src = t_sc + (ti & 1) * kPreTile, *dst = t_xh + (ti & 1) * kPreTile;
+        float *tile = t_xh + sel(ti);
 #pragma unroll 8
-        for (int t = 0; t < 64; ++t) {
+        for (int t = 0; t < T; ++t) {
           if (t < len) {
-            const float v = at(src, t, lane);
+            const float v = at(tile, t, lane);
             const float y = v + m0;
             m0 = m1 + (b0 * v - a0 * y);
             m1 = (b1 * v - a1 * y);
-            at(dst, t, lane) = y;
+            at(tile, t, lane) = y;
           }
         }
       }
@@ -211,23 +242,23 @@ __global__ __launch_bounds__(64 * kPreWaves) void supp_prefilter_kernel(SuppArgs
       const int64_t ti = it - 2;
       if (kFront && ti >= 0 && ti < ntiles) {
         const int len = tile_len(ti);
-        float *src = t_dry + (ti & 1) * kPreTile;
+        float *src = t_dry + sel(ti);
 #pragma unroll 8
-        for (int r = 0; r < kPreGroup; ++r) {
-          const int sr = s0 + r;
-          if (sr < a.n_streams && lane < len)
-            a.out[(int64_t)sr * a.stream_stride + a.frame0 * kRnnFrame + ti * 64 + lane] = at(src, lane, r);
+        for (int r = 0; r < T; ++r) {
+          const int sr = s0 + row0 + r;
+          if (sr < a.n_streams && tl < len)
+            a.out[(int64_t)sr * a.stream_stride + a.frame0 * kRnnFrame + ti * T + tl] = at(src, tl, row0 + r);
         }
       }
     } else {  // ---- the model input of tile it - 4
       const int64_t ti = it - 4;
       if (ti >= 0 && ti < ntiles) {
         const int len = tile_len(ti);
-        float *src = t_xh + (ti & 1) * kPreTile;
+        float *src = t_xh + sel(ti);
 #pragma unroll 8
-        for (int r = 0; r < kPreGroup; ++r) {
-          const int sr = s0 + r;
-          if (sr < a.n_streams && lane < len) a.xh[(int64_t)sr * xh_stride + kPitchBuf + ti * 64 + lane] = at(src, lane, r);
+        for (int r = 0; r < T; ++r) {
+          const int sr = s0 + row0 + r;
+          if (sr < a.n_streams && tl < len) a.xh[(int64_t)sr * xh_stride + kPitchBuf + ti * T + tl] = at(src, tl, row0 + r);
         }
       }
     }
@@ -2731,7 +2762,8 @@ extern "C" __global__ __launch_bounds__(64 * kFftWaves, 3) void supp_synth_kerne
 // The sample-serial pre-pass of a window (independent of the other kernels: it may run a window ahead).
 template <bool kClamp, bool kDcHp, bool kRaw>
 static hipError_t launch_prefilter_variant(const SuppArgs &a, hipStream_t stream) {
-  constexpr size_t lds = sizeof(float) * 8 * kPreTile;
+  constexpr size_t lds = sizeof(float) * 2 * kPreRing * kPreTile;  // 49 920 bytes at 32-sample tiles
+  static_assert(lds <= 65536 + sizeof(float) * 2 * kPreRing * kPreT || kPreT > 32, "the pre-pass leaves room for transform workgroups beside it");
   static bool attr_set = false;
   if (!attr_set) {
     hipError_t err = hipFuncSetAttribute(reinterpret_cast<const void *>(supp_prefilter_kernel<kClamp, kDcHp, kRaw>),

@@ -96,6 +96,7 @@ struct SuppressorHost {
   float2 *d_X = nullptr, *d_P = nullptr;
   SuppFrameRec *d_rec = nullptr;
   int ws_frames = 0, ws_streams = 0;
+  int last_xh_slot = -1, last_xh_frames = 0;  // the model-input buffer the last pre-pass wrote and its window's frames (test tap)
 
   SuppressorHost() { synthetic_weights(weights, 0x5EEDULL); }
 
@@ -281,6 +282,8 @@ struct SuppressorHost {
     d_X = d_P = nullptr;
     d_rec = nullptr;
     ws_frames = ws_streams = 0;
+    last_xh_slot = -1;
+    last_xh_frames = 0;
   }
   void release_all() {
     release_workspace();

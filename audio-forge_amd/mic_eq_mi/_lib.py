@@ -263,6 +263,7 @@ SIGNATURES = {
     "af_suppressor_debug_read": (C.c_int, [_vp, _i32, _i32, _fp, _fp, _fp]),
     "af_suppressor_debug_read_pitch": (C.c_int, [_vp, _i32, _i32, _fp, C.POINTER(_i32), _fp]),
     "af_suppressor_debug_pitch_search": (C.c_int, [_fp, _i32, _i32, _fp, C.POINTER(_i32), _i32]),
+    "af_suppressor_debug_read_model_input": (C.c_int, [_vp, _i32, _fp, _i64, C.POINTER(_i64)]),
     "af_eq_set_band_frequency": (C.c_int, [_vp, _i32, _d]),
     "af_eq_set_band_gain": (C.c_int, [_vp, _i32, _d]),
     "af_eq_set_band_q": (C.c_int, [_vp, _i32, _d]),

@@ -281,6 +281,17 @@ class Engine:
                                                             C.byref(gain)))
         return {"whitened": ds, "last_period": int(period.value), "last_gain": np.float32(gain.value)}
 
+    def suppressor_debug_read_model_input(self, stream: int) -> np.ndarray:
+        """The pre-pass's test tap: ``stream``'s row of the LAST window's model-input buffer, float32
+        [1728 + 480 x that window's frames]: the history samples the pre-pass put in front, then the window's."""
+        n = C.c_int64(0)
+        _lib.check(self._lib.af_suppressor_debug_read_model_input(self._h, int(stream), None, 0, C.byref(n)))
+        row = np.zeros(n.value, dtype=np.float32)
+        _lib.check(self._lib.af_suppressor_debug_read_model_input(self._h, int(stream), row.ctypes.data_as(C.POINTER(C.c_float)),
+                                                                  row.size, C.byref(n)))
+        assert n.value == row.size
+        return row
+
     @staticmethod
     def suppressor_debug_pitch_search(spans, device: int = 0) -> tuple[np.ndarray, np.ndarray]:
         """The pitch search kernel alone (no engine state), launched as the engine launches it, on model-input ``spans``

@@ -250,6 +250,11 @@ int af_suppressor_debug_read(af_engine *e, int32_t frame, int32_t stream, float 
  * AF_ERR_INVALID_ARGUMENT out of range; nothing is written then. */
 int af_suppressor_debug_read_pitch(af_engine *e, int32_t frame, int32_t stream, float *whitened, int32_t *last_period,
                                    float *last_gain);
+/* test tap of the pre-pass (synchronises): one stream's row of the last suppressor window's model-input buffer, i.e. the 1728
+ * history samples the pre-pass put in front followed by the window's 480 x frames samples.  `*length` receives the row's
+ * length; `row` (null: only the length is reported) must have room for it (`capacity` floats).  AF_ERR_STATE before the
+ * first window, AF_ERR_INVALID_ARGUMENT out of range or too small; nothing is written then. */
+int af_suppressor_debug_read_model_input(af_engine *e, int32_t stream, float *row, int64_t capacity, int64_t *length);
 /* test tap: the pitch search kernel ALONE (decimation, whitening, coarse + fine search, interpolation offset), launched as the
  * engine launches it, on caller-supplied model-input spans [stream][1728 + 480 n_frames] (host pointers; frame f's pitch buffer
  * is span[480 (f + 1) .. 480 (f + 1) + 1728)).  Returns the whitened buffers [frame][stream][864] and the search's own pitch
