@@ -4,10 +4,13 @@
 // (gate.rs:626-637): 8 ms RMS detector in dB, threshold / 4 dB hysteresis / 50 ms hold, 4:1 expansion capped at
 // 36 dB (24 dB while the chatter auto-relax is active), one-pole attack/release on the linear gain, and the
 // chatter detector (>= 4 open/close flips inside 500 ms, 1 s cool-down).  One recurrence per stream:
-// lane per stream over 64 x 64 LDS tiles, state in registers.
+// lane per stream over 64 x 64 LDS tiles, state in registers.  The decision, the chatter tracking and its timers are
+// GateLogic (af_prepass.h), the code the realtime gate stage steps; the f64 state rows, the detector and the smoothing are
+// this kernel's own.
 #include <hip/hip_runtime.h>
 
 #include "af_dsp.h"
+#include "af_prepass.h"
 
 namespace af {
 
@@ -30,15 +33,13 @@ __global__ __launch_bounds__(kLanes) void gate_lane_kernel(GateArgs a) {
   const int s = s0 + lane;
   const bool valid = s < a.n_streams;
   double rms = 0.0, gain = 0.0;
-  int hold = 0, window = 0, cooldown = 0, relax = 0, transitions = 0;
-  bool open = false, eff_open = false, has_eff = false;
-  uint64_t events = 0;
+  GateLogic gl;  // (events: of this call)
   const int64_t NS = a.n_streams;
   if (a.state && valid) {
     rms = a.state[0 * NS + s]; gain = a.state[1 * NS + s];
-    hold = (int)a.state[2 * NS + s]; window = (int)a.state[3 * NS + s]; cooldown = (int)a.state[4 * NS + s];
-    relax = (int)a.state[5 * NS + s]; transitions = (int)a.state[6 * NS + s];
-    open = a.state[7 * NS + s] != 0.0; eff_open = a.state[8 * NS + s] != 0.0; has_eff = a.state[9 * NS + s] != 0.0;
+    gl.hold = (int)a.state[2 * NS + s]; gl.window = (int)a.state[3 * NS + s]; gl.cooldown = (int)a.state[4 * NS + s];
+    gl.relax = (int)a.state[5 * NS + s]; gl.trans = (int)a.state[6 * NS + s];
+    gl.open = a.state[7 * NS + s] != 0.0; gl.eff = a.state[8 * NS + s] != 0.0; gl.has_eff = a.state[9 * NS + s] != 0.0;
   }
   int in_block = 0;
   int64_t block = 0;
@@ -56,45 +57,13 @@ __global__ __launch_bounds__(kLanes) void gate_lane_kernel(GateArgs a) {
       // update_detector, gate.rs:265-285
       rms = a.rms_coeff * rms + (1.0 - a.rms_coeff) * xin * xin;
       const double level = lin2db(sqrt(rms), 1e-10);
-      if (level >= a.threshold_db) {
-        open = true;
-        hold = a.hold_samples;
-      } else if (hold > 0) {
-        hold -= 1;
-        open = true;
-      } else if (level <= a.threshold_db - 4.0) {
-        open = false;
-      }
-      // detector_gain_reduction_db, gate.rs:288-306
-      const double range = relax > 0 ? 24.0 : 36.0;
-      const double gr = open ? 0.0 : dclamp((a.threshold_db - level) * (1.0 - 1.0 / 4.0), 0.0, range);
-      // track_gate_transition, gate.rs:578-611
-      if (!has_eff) {
-        eff_open = open;
-        has_eff = true;
-      } else if (open != eff_open) {
-        eff_open = open;
-        if (window == 0) {
-          window = a.window_samples;
-          transitions = 1;
-        } else {
-          transitions += 1;
-        }
-        if (transitions >= 4 && cooldown == 0) {
-          events += 1;
-          cooldown = a.cooldown_samples;
-          if (a.vad_mode) relax = a.relax_samples;
-          window = 0;
-          transitions = 0;
-        }
-      }
-      if (relax > 0) relax -= 1;  // advance_chatter_timers, gate.rs:562-575
-      if (window > 0) {
-        window -= 1;
-        if (window == 0) transitions = 0;
-      }
-      if (cooldown > 0) cooldown -= 1;
-      // apply_gain, gate.rs:613-623
+      gl.decide((level >= a.threshold_db ? 1 : 0) | (level <= a.threshold_db - 4.0 ? 2 : 0), a.hold_samples);
+      // detector_gain_reduction_db, gate.rs:288-306: the range is the one in force before this sample's transition is tracked
+      const double range = gl.relax > 0 ? 24.0 : 36.0;
+      const double gr = gl.open ? 0.0 : dclamp((a.threshold_db - level) * (1.0 - 1.0 / 4.0), 0.0, range);
+      gl.track(gl.open, a.vad_mode != 0, a.window_samples, a.cooldown_samples, a.relax_samples);
+      gl.advance_timers();
+      // apply_gain, gate.rs:625-635
       const double target = db2lin(-gr);
       const double coeff = target > gain ? a.attack_coeff : a.release_coeff;
       gain = coeff * gain + (1.0 - coeff) * target;
@@ -114,12 +83,12 @@ __global__ __launch_bounds__(kLanes) void gate_lane_kernel(GateArgs a) {
   }
   if (valid) {
     if (in_block > 0 && a.gain_trace) a.gain_trace[block * NS + s] = (float)gain;
-    if (a.chatter) a.chatter[s] = events;
+    if (a.chatter) a.chatter[s] = (uint64_t)gl.events;
     if (a.state) {
       a.state[0 * NS + s] = rms; a.state[1 * NS + s] = gain;
-      a.state[2 * NS + s] = hold; a.state[3 * NS + s] = window; a.state[4 * NS + s] = cooldown;
-      a.state[5 * NS + s] = relax; a.state[6 * NS + s] = transitions;
-      a.state[7 * NS + s] = open ? 1.0 : 0.0; a.state[8 * NS + s] = eff_open ? 1.0 : 0.0; a.state[9 * NS + s] = has_eff ? 1.0 : 0.0;
+      a.state[2 * NS + s] = gl.hold; a.state[3 * NS + s] = gl.window; a.state[4 * NS + s] = gl.cooldown;
+      a.state[5 * NS + s] = gl.relax; a.state[6 * NS + s] = gl.trans;
+      a.state[7 * NS + s] = gl.open ? 1.0 : 0.0; a.state[8 * NS + s] = gl.eff ? 1.0 : 0.0; a.state[9 * NS + s] = gl.has_eff ? 1.0 : 0.0;
     }
   }
 }

@@ -28,11 +28,15 @@ SILENT = 64
 CALLS = (1, 4, 12, 20)
 FRAMES = sum(CALLS)
 HISTORY = 1728
-VARIANTS = {  # name: (input clamp, DC block + 80 Hz high-pass, raw protocol)
+VARIANTS = {  # name: (input clamp, DC block + 80 Hz high-pass, raw protocol): every instantiation of supp_prefilter_kernel
     "front-end-off": (False, False, False),
+    "raw": (False, False, True),
     "dc-hp": (False, True, False),
-    "clamp-dc-hp": (True, True, False),
     "raw-dc-hp": (False, True, True),
+    "clamp": (True, False, False),
+    "raw-clamp": (True, False, True),
+    "clamp-dc-hp": (True, True, False),
+    "raw-clamp-dc-hp": (True, True, True),
 }
 
 

@@ -89,7 +89,7 @@ def test_read_gate_state_accepts_null_pointers(engine):
 def test_gated_prepass_resources(tmp_path):
     hipcc = HIPCC if os.path.exists(HIPCC) else shutil.which("hipcc")
     res = subprocess.run([hipcc, "--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-x", "hip",
-                          str(CSRC / "af_rnnoise.hip"), "-S", "--cuda-device-only", "-o", str(tmp_path / "rn.s"),
+                          str(CSRC / "af_prepass.hip"), "-S", "--cuda-device-only", "-o", str(tmp_path / "rn.s"),
                           "-Rpass-analysis=kernel-resource-usage"], capture_output=True, text=True, cwd=CSRC, check=True)
     blocks = re.split(r"remark: Function Name: ", res.stderr)
     gate = [b for b in blocks if b.startswith("_ZN2af26supp_prefilter_gate_kernel")]

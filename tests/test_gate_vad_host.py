@@ -86,7 +86,7 @@ def test_bad_evidence_arguments_are_refused(core):
 
 def _resource_remarks():
     cmd = ["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-x", "hip",
-           "--cuda-device-only", "-c", "af_rnnoise.hip", "-o", "/dev/null", "-Rpass-analysis=kernel-resource-usage"]
+           "--cuda-device-only", "-c", "af_prepass.hip", "-o", "/dev/null", "-Rpass-analysis=kernel-resource-usage"]
     text = subprocess.run(cmd, cwd=CSRC, capture_output=True, text=True, check=True).stderr
     res, name = {}, None
     for line in text.splitlines():

@@ -11,8 +11,8 @@ other rows are clamped), rows of streams 0, 63, 64 and 65 read after each of fou
                 happened by the tapped row being shorter than the call
 
 Input (tests/prepass_ref.py): gains up to 2.6 that drive the soft clip far beyond +-1, DC offsets, a silent stream, and on the
-clamped variant one NaN, one +inf and one -inf.  Variants: front end off, DC + high-pass, clamp + DC + high-pass on the
-wrapper protocol; DC + high-pass on the raw protocol.  Expected values come from the oracle alone (afo_sanitize_and_clamp,
+clamped variants one NaN, one +inf and one -inf.  Variants: all eight instantiations of the kernel, i.e. the input clamp, the
+DC block + high-pass and the raw protocol each on and off.  Expected values come from the oracle alone (afo_sanitize_and_clamp,
 oracle.prefilter, oracle.scale_sample_for_model / raw_model_input, the model's high-pass restated in numpy float32), with
 state carried over the whole timeline.  Rows are compared BIT FOR BIT.
 
