@@ -371,3 +371,73 @@ def bound(stage: str, restatement: dict) -> float:
     same stimulus and metric (a different f32 factorisation of the same 960-point transform and a different summation order
     differ by a small constant, not by an order of magnitude), and not under 4 f32 epsilons of the metric's scale."""
     return max(4.0 * worst(restatement["err"][stage])[0], 4.0 * F32_EPS * restatement["scale"][stage])
+
+
+# ------------------------------------------------------------------------------------------------ the free run
+def mix_coefficient() -> np.float32:
+    """The wrapper's wet/dry smoothing coefficient, 1 - exp(-(480 / 48000) / (15 / 1000)), every operation in f32."""
+    coeff = np.float32(1.0) - np.exp(-((np.float32(480.0) / np.float32(48000.0)) / (np.float32(15.0) / np.float32(1000.0))))
+    assert coeff.dtype == np.float32
+    return coeff
+
+
+def free_run(model_input: np.ndarray, pitch_index: np.ndarray, blob: bytes, strength: float | None = None,
+             dry: np.ndarray | None = None) -> dict:
+    """The stage functions above chained WITHOUT teacher forcing: every stage is fed the float64 result of the stage before
+    it, from the f32-restated high-pass (biquad_hp_f32) to the overlap-add, with the cepstral ring, the three GRU states, the
+    `lastg` floor and the overlap carried in f64 over the whole run.  What an exact evaluation of the algorithm gives on this
+    model input -- not what any f32 implementation gives: where the algorithm is ill-conditioned, two correct f32
+    evaluations leave this and each other by more than their rounding.
+
+    `model_input` [streams, frames x 480] float32 as for `evaluate`.  `pitch_index` [frames, streams]: the only decision
+    taken from outside (the pitch path has its own reference, tests/pitch_stage_ref.py).  The silence flag is
+    sum(Ex) < 0.04 of the run's own Ex; `gains = max(gains_raw, 0.6 x previous gains)`, held across silent frames.
+    `strength` / `dry` [streams, frames x 480]: the wrapper's smoothed wet/dry mix as `evaluate` restates it (the smoothed
+    strength in f32, as the wrapper keeps it).
+
+    Returns `out` [streams, frames x 480] float64 in +-1 full scale, and per frame `feat` [frames, streams, 42], `gains_raw`
+    [frames, streams, 22] (zeros on a silent frame, like the taps), `silence` [frames, streams] bool and `Ex_sum`
+    [frames, streams] (the flag's operand); for reports also `gains`, `Ex`, `Ep`, `Exp` [frames, streams, 22]."""
+    pitch_index = np.asarray(pitch_index, dtype=np.int64)
+    n_frames, n_streams = pitch_index.shape
+    assert model_input.shape[0] == n_streams and model_input.shape[1] >= n_frames * FRAME
+    x = biquad_hp_f32(model_input[:, :n_frames * FRAME], np.zeros((n_streams, 2), dtype=np.float32)).astype(np.float64)
+    hist = np.zeros((n_streams, PBUF))
+    features = FeaturesF64(n_streams)
+    net = NetworkF64(blob, n_streams)
+    lastg = np.zeros((n_streams, NB))
+    overlap = np.zeros((n_streams, FRAME))
+    smoothed = np.ones(n_streams, dtype=np.float32)
+    coeff = mix_coefficient()
+    rows = np.arange(n_streams)
+    res = {"out": np.zeros((n_streams, n_frames * FRAME)), "feat": np.zeros((n_frames, n_streams, NFEAT)),
+           "gains_raw": np.zeros((n_frames, n_streams, NB)), "silence": np.zeros((n_frames, n_streams), dtype=bool),
+           "Ex_sum": np.zeros((n_frames, n_streams)), "gains": np.zeros((n_frames, n_streams, NB)),
+           "Ex": np.zeros((n_frames, n_streams, NB)), "Ep": np.zeros((n_frames, n_streams, NB)),
+           "Exp": np.zeros((n_frames, n_streams, NB))}
+    for f in range(n_frames):
+        hist = np.concatenate([hist[:, FRAME:], x[:, f * FRAME:(f + 1) * FRAME]], axis=1)
+        X = spectrum_f64(hist[:, PBUF - WINDOW:])
+        start = PBUF - WINDOW - pitch_index[f]
+        assert np.all((start >= 0) & (start <= PBUF - WINDOW)), "pitch index outside [0, 768]"
+        P = spectrum_f64(hist[rows[:, None], start[:, None] + np.arange(WINDOW)[None, :]])
+        ex, ep, exp = band_values_f64(X, P)
+        total = np.sum(ex, axis=1)
+        silent = total < SILENCE_THRESHOLD
+        live = ~silent
+        feat = features.step(ex, exp, pitch_index[f], silent)
+        graw = np.where(live[:, None], net.step(feat, silent), 0.0)
+        gains = np.where(live[:, None], np.maximum(graw, 0.6 * lastg), 0.0)
+        lastg = np.where(live[:, None], gains, lastg)
+        wet = synthesis_f64(X, P, ex, ep, exp, graw, gains, silent, overlap) / 32768.0
+        if strength is not None:
+            smoothed = np.float32(strength) * coeff + smoothed * (np.float32(1.0) - coeff)
+            assert smoothed.dtype == np.float32
+            mix = smoothed < np.float32(1.0)
+            d = dry[:, f * FRAME:(f + 1) * FRAME].astype(np.float64)
+            mixed = smoothed.astype(np.float64)[:, None] * wet + (np.float32(1.0) - smoothed).astype(np.float64)[:, None] * d
+            wet = np.where(mix[:, None], mixed, wet)
+        res["out"][:, f * FRAME:(f + 1) * FRAME] = wet
+        res["feat"][f], res["gains_raw"][f], res["silence"][f], res["Ex_sum"][f] = feat, graw, silent, total
+        res["gains"][f], res["Ex"][f], res["Ep"][f], res["Exp"][f] = gains, ex, ep, exp
+    return res

@@ -5,12 +5,14 @@ half of the realtime chain composed per stream (tests/gate_oracle.py) over the e
 
 Tolerances: without the suppressor max abs 1e-6 per stream after the chain, 2e-7 on the gated signal itself; behind the
 suppressor the output is bit-identical to the engine's own suppressor fed the oracle's gated signal (gate off), and within
-RMS 1e-5 and worst sample 1e-5 of the oracle on every stream but the named SUPPRESSOR_EXCEPTIONS; gate state: current_gain
+RMS 1e-5 and worst sample 1e-5 of the oracle on every stream but the named SUPPRESSOR_EXCEPTIONS, each of which is capped
+at 5 x the oracle's own distance from a free-running float64 evaluation of the same configuration; gate state: current_gain
 within 1e-6, events, is_open, relax equal."""
 import numpy as np
 import pytest
 
 import gate_oracle as GO
+import lane_free_run_stimulus as LF
 import signals as S
 
 pytestmark = pytest.mark.gpu
@@ -30,11 +32,17 @@ SETTINGS = {
     "thr-20_live": ([GO.DEFAULT_GATE] * 3 + [dict(GO.DEFAULT_GATE, threshold_db=-20.0, **OTHER)] * 3, False),
 }
 # Streams of this stimulus whose suppressor output is off the oracle's by more than 1e-5 in one or two frames (2e-5 .. 6e-5;
-# RMS under 1e-6) WITHOUT the gate as well: the suppressor's own deviation on this input, not the gate stage's -- with the gate
-# on, the engine's output is bit-identical to its suppressor on the oracle's gated signal.  Pitch decisions and silence flags
-# equal the oracle's there, and pitch_filter's Exp > g branch is >= 5e-3 from its edge (test_gate_lane_stimulus.py).
-# Recorded by the strict xfail test_suppressor_alone_on_the_lane_stimulus; the set must match exactly (a stream that leaves
-# or joins it fails).
+# RMS under 1e-6) WITHOUT the gate as well: not the gate stage's doing -- with the gate on, the engine's output is
+# bit-identical to its suppressor on the oracle's gated signal -- and not an error of either side.  The f32 algorithm is
+# ill-conditioned on those frames: a loud, nearly pure tone changes level inside the frame, X is broadband, the pitch-lagged P
+# still holds the tone alone, and pitch_filter scales P by sqrt(Ex / Ep), thousands, in bands where P is only the rounding
+# floor of an f32 transform.  The oracle itself is 1.3e-5 .. 4e-5 from a free-running float64 evaluation there and 6e-8 in the
+# median (tests/test_suppressor_free_run_ref.py, without a GPU), and the device is held to that evaluation stage by stage in
+# tests/test_gpu_suppressor_free_run.py.  Pitch decisions and silence flags equal the oracle's there, and pitch_filter's
+# Exp > g branch is >= 5e-3 from its edge (test_gate_lane_stimulus.py).
+# The set must match exactly (a stream that leaves or joins it fails), and a listed stream is capped (`_exception_caps`):
+# |got - oracle| <= 5 x that stream's worst oracle-to-free-run distance in the same configuration -- the device is held within
+# 4 x of the free run, the oracle is within 1 x.
 SUPPRESSOR_EXCEPTIONS = {N_STREAMS: (29, 68, 82, 93), 4096: (1992,)}
 REPORT = {}
 
@@ -174,10 +182,40 @@ def _gate_free(core, gated, calls, chain=True, raw=False):
         eng.close()
 
 
-def _suppressor_bounds(name, got, want, same, gain_err, exceptions, streams=None, tol=1e-5):
+_CAPS = {}
+
+
+def _exception_caps(key, signal, want, streams, raw=False, chain_calls=None):
+    """{stream: cap} for the listed exceptions `streams`.  `signal` [len(streams), n]: what the suppressor is handed (the
+    oracle's gated signal, or the front end's output); `want` [len(streams), m]: the oracle's output in this configuration.
+    The free-running float64 suppressor (suppressor_stage_ref.free_run, the pitch index its only borrowed decision) runs on
+    `signal` -- behind it, for `chain_calls`, the oracle's dynamics chain over those call lengths, as behind the oracle's
+    own suppressor -- and the cap is 5 x the largest |want - that|.  CPU only; nothing of the device enters."""
+    if key not in _CAPS:
+        import chain_oracle as CO
+
+        free = LF.oracle_and_free_run(signal, raw=raw)["free"]["out"].astype(np.float32)
+        if chain_calls is not None:
+            free = np.stack([CO.run_calls(row, 48_000.0, *CHAIN, [c for c in chain_calls if c > 0])[0] for row in free])
+        assert free.shape == want.shape, (free.shape, want.shape)
+        distance = np.abs(want.astype(np.float64) - free.astype(np.float64)).max(axis=1)
+        _CAPS[key] = {int(s): 5.0 * float(v) for s, v in zip(streams, distance)}
+    return _CAPS[key]
+
+
+def _assert_caps(name, streams, worst, caps):
+    line = []
+    for s, cap in sorted(caps.items()):
+        value = float(worst[list(streams).index(s)])
+        line.append(f"{s}: {value:.3e} <= {cap:.3e}")
+        assert value <= cap, f"{name}: named exception {s} is {value:.3e} from the oracle, cap {cap:.3e} (5 x oracle vs f64 free run)"
+    return ", ".join(line)
+
+
+def _suppressor_bounds(name, got, want, same, gain_err, exceptions, caps, streams=None, tol=1e-5):
     """Behind the suppressor: `got` bit-identical to `same` (_gate_free on the oracle's gated signal: the gate stage adds
     nothing); against the oracle RMS <= tol on every stream and worst sample <= tol on every stream but `exceptions`,
-    which must be exactly the streams over it."""
+    which must be exactly the streams over it, each within its cap (`_exception_caps`)."""
     assert got.shape == want.shape == same.shape, (got.shape, want.shape, same.shape)
     differ = np.flatnonzero((got.view(np.uint32) != same.view(np.uint32)).any(axis=1))
     assert differ.size == 0, f"{name}: streams {differ[:8].tolist()} differ from the suppressor on the oracle's gated signal"
@@ -190,7 +228,10 @@ def _suppressor_bounds(name, got, want, same, gain_err, exceptions, streams=None
                     f"worst sample {inside.max():.3e} (named exceptions {over}: {worst.max():.3e}), worst gain {gain_err:.3e}")
     bad = np.flatnonzero(~(rms <= tol))
     assert bad.size == 0, f"{name}: streams {streams[bad[:8]].tolist()} exceed rms {tol:g} (rms {rms.max():.3e})"
-    assert over == sorted(s for s in exceptions if s in set(streams.tolist())), f"{name}: streams over {tol:g}: {over}"
+    listed = sorted(s for s in exceptions if s in set(streams.tolist()))
+    assert over == listed, f"{name}: streams over {tol:g}: {over}"
+    assert sorted(caps) == listed, (sorted(caps), listed)
+    REPORT[name] += "; caps " + _assert_caps(name, streams.tolist(), worst, caps)
 
 
 def _gate_acted(want_state):
@@ -286,6 +327,13 @@ def _gated(audio, calls, params):
     return _oracle(("gate only", audio.shape[0], calls), audio, 48_000.0, calls, params)[0]
 
 
+def _wrapper_caps(audio, params, want):
+    """The caps of the 130-stream wrapper runs behind the gate and the chain over SUPP_CALLS."""
+    listed = list(SUPPRESSOR_EXCEPTIONS[N_STREAMS])
+    return _exception_caps(("supp",), _gated(audio, SUPP_CALLS, params)[listed], want[listed], listed,
+                           chain_calls=GO.output_calls(SUPP_CALLS, "wrapper"))
+
+
 def _assert_suppressor_ran(forms, traces, lengths):
     for (kernel, chain, launches), trace, n in zip(forms, traces, lengths):
         assert trace.shape[0] == n // GO.FRAME and launches >= 4, (kernel, chain, launches, trace.shape, n)
@@ -308,7 +356,8 @@ def test_behind_the_suppressor_every_stream(core, kernel):
         eng.close()
     _gate_acted(want_st)
     same = _gate_free(core, _gated(audio, SUPP_CALLS, params), SUPP_CALLS)
-    _suppressor_bounds(f"suppressor, kernel {kernel}", got, want, same, gain_err, SUPPRESSOR_EXCEPTIONS[N_STREAMS])
+    _suppressor_bounds(f"suppressor, kernel {kernel}", got, want, same, gain_err, SUPPRESSOR_EXCEPTIONS[N_STREAMS],
+                       _wrapper_caps(audio, params, want))
 
 
 def test_raw_protocol_with_the_gate(core):
@@ -327,7 +376,9 @@ def test_raw_protocol_with_the_gate(core):
     finally:
         eng.close()
     same = _gate_free(core, _gated(audio, SUPP_CALLS, params), SUPP_CALLS, chain=False, raw=True)
-    _suppressor_bounds("raw protocol + gate", got, want, same, gain_err, SUPPRESSOR_EXCEPTIONS[N_STREAMS])
+    listed = list(SUPPRESSOR_EXCEPTIONS[N_STREAMS])
+    caps = _exception_caps(("raw",), _gated(audio, SUPP_CALLS, params)[listed], want[listed], listed, raw=True)
+    _suppressor_bounds("raw protocol + gate", got, want, same, gain_err, SUPPRESSOR_EXCEPTIONS[N_STREAMS], caps)
 
 
 @pytest.mark.parametrize("device", ["stride", "inplace"])
@@ -344,7 +395,8 @@ def test_process_device_behind_the_suppressor(core, device):
     finally:
         eng.close()
     same = _gate_free(core, _gated(audio, SUPP_CALLS, params), SUPP_CALLS)
-    _suppressor_bounds(f"process_device {device}, suppressor", got, want, same, gain_err, SUPPRESSOR_EXCEPTIONS[N_STREAMS])
+    _suppressor_bounds(f"process_device {device}, suppressor", got, want, same, gain_err, SUPPRESSOR_EXCEPTIONS[N_STREAMS],
+                       _wrapper_caps(audio, params, want))
 
 
 def test_4096_streams_behind_the_suppressor(core):
@@ -373,17 +425,22 @@ def test_4096_streams_behind_the_suppressor(core):
     assert np.array_equal(st["is_open"][sample], want_st["is_open"])
     assert np.array_equal(st["auto_relax_active"][sample], want_st["auto_relax_active"])
     assert lengths == GO.output_calls(calls, "wrapper")
-    same = _gate_free(core, _gated(audio, calls, params), calls)
+    gated = _gated(audio, calls, params)
+    same = _gate_free(core, gated, calls)
     differ = np.flatnonzero((got.view(np.uint32) != same.view(np.uint32)).any(axis=1))
     assert differ.size == 0, f"streams {differ[:8].tolist()} differ from the suppressor on the oracle's gated signal"
+    listed = list(SUPPRESSOR_EXCEPTIONS[n_streams])
+    caps = _exception_caps(("4096",), gated[listed], want[[sample.index(s) for s in listed]], listed,
+                           chain_calls=GO.output_calls(calls, "wrapper"))
     _suppressor_bounds("4096 suppressor (sampled)", got[sample], want, same[sample], float(gain.max()),
-                       SUPPRESSOR_EXCEPTIONS[n_streams], streams=sample)
+                       SUPPRESSOR_EXCEPTIONS[n_streams], caps, streams=sample)
 
 
-@pytest.mark.xfail(strict=True, reason="the suppressor alone (no gate) is off the oracle by 2e-5 .. 6e-5 in one or two frames "
-                                       "of streams 29, 68, 82 and 93 of this stimulus (SUPPRESSOR_EXCEPTIONS); cause not found")
 def test_suppressor_alone_on_the_lane_stimulus(core):
-    """Prefilter -> suppressor, no gate, chain off, against the oracle at the suppressor's bound (test_gpu_suppressor.py)."""
+    """Prefilter -> suppressor, no gate, chain off, against the oracle at the suppressor's bound (test_gpu_suppressor.py): RMS
+    <= 1e-5 on every stream, worst sample <= 1e-5 on every stream but exactly the SUPPRESSOR_EXCEPTIONS, each of those within
+    5 x the oracle's own distance from the free-running float64 suppressor on the same input.  Why these streams leave 1e-5
+    at all: the comment at SUPPRESSOR_EXCEPTIONS and tests/test_suppressor_free_run_ref.py."""
     audio = _audio()
     eng = core.Engine(48_000.0, N_STREAMS)
     eng.set_eq_enabled(0)
@@ -398,9 +455,15 @@ def test_suppressor_alone_on_the_lane_stimulus(core):
         eng.close()
     m = got.shape[1]
     want = np.stack([_suppressor_oracle(audio[s, :m]) for s in range(N_STREAMS)])
-    worst = np.abs(got.astype(np.float64) - want).max(axis=1)
-    print(f"suppressor alone on the lane stimulus: worst {worst.max():.3e}, streams over 1e-5 {np.flatnonzero(worst > 1e-5).tolist()}")
-    assert worst.max() <= 1e-5
+    d = got.astype(np.float64) - want
+    rms, worst = np.sqrt(np.mean(d * d, axis=1)), np.abs(d).max(axis=1)
+    listed = list(SUPPRESSOR_EXCEPTIONS[N_STREAMS])
+    over = np.flatnonzero(worst > 1e-5).tolist()
+    print(f"suppressor alone on the lane stimulus: worst rms {rms.max():.3e}, worst sample {worst.max():.3e}, streams over 1e-5 {over}")
+    assert float(rms.max()) <= 1e-5, (int(rms.argmax()), float(rms.max()))
+    assert over == listed, over
+    caps = _exception_caps(("alone",), LF.suppressor_input("A", audio[listed, :m]), want[listed], listed)
+    print("suppressor alone, caps " + _assert_caps("suppressor alone", list(range(N_STREAMS)), worst, caps))
 
 
 def _suppressor_oracle(x):
