@@ -1405,7 +1405,7 @@ int stage_diag_eq_params(af_engine *e, hipStream_t stream, bool *crossfade, int3
 
 extern "C" {
 
-int af_version(void) { return 100; }
+int af_version(void) { return 101; }
 const char *af_last_error(void) { return af_last_error_text.c_str(); }
 
 int af_device_count(void) {

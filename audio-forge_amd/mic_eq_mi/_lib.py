@@ -231,6 +231,75 @@ class CompressorSearchResult(C.Structure):
                 + [("evaluated", (C.c_double * 4) * 67), ("scores", C.c_double * 67)])
 
 
+TARGET_PRESETS = ("broadcast", "podcast", "streaming", "flat")  # AF_TARGET_*
+SETUP_SIGNALS = ("noise", "original", "verification", "rendered", "rendered_noise")  # AF_SETUP_SIGNAL_*
+
+
+class SetupVerificationAudio(C.Structure):
+    _fields_ = [("samples", C.c_void_p), ("stride", C.c_int64), ("length", C.c_int64), ("lengths", C.POINTER(C.c_int64))]
+
+
+class SetupVerificationRow(C.Structure):
+    _fields_ = [("masked_bins", C.c_int32), ("snr_available", C.c_int32), ("band_present", C.c_int32 * 4),
+                ("non_finite", C.c_int32 * 5), ("clipped_0999", C.c_int32 * 5), ("clipped_1", C.c_int32 * 5), ("reserved", C.c_int32),
+                ("spectral_target_error_before_db", C.c_double), ("spectral_target_error_after_db", C.c_double),
+                ("shape_delta_db", C.c_double), ("band_snr_db", C.c_double * 4), ("offsets_before", C.c_double * 5),
+                ("offsets_after", C.c_double * 5), ("sum_squares", C.c_double * 5), ("peak", C.c_double * 5), ("rms_db", C.c_double * 5)]
+
+
+SETUP_DECISIONS = ("accept", "reduce", "rollback", "retry")  # AF_SETUP_*
+SETUP_REASON_NO_RENDERER = 6  # AF_SETUP_REASON_NO_RENDERER: the one early exit that also reports simulation_backend
+# the bits of SetupVerificationEvidence.present, AF_SETUP_HAS_*, in bit order
+SETUP_EVIDENCE_KEYS = ("compressor_gain_reduction_p95_db", "compressor_gain_reduction_db", "output_true_peak_db",
+                       "limiter_effective_ceiling_db", "true_peak_limited_events", "output_rms_db", "input_rms_db",
+                       "deesser_gain_reduction_p95_db", "compressor_gain_reduction_median_db", "deesser_gain_reduction_median_db",
+                       "target_p95_reduction_db", "peak_reduction_cap_db", "deesser_max_reduction_db")
+
+
+class SetupVerificationEvidence(C.Structure):
+    _fields_ = ([("present", C.c_uint32), ("backend_is_rust", C.c_int32), ("verification_samples", C.c_int64),
+                 ("sample_rate", C.c_double), ("true_peak_limited_events", C.c_uint64)]
+                + [(name, C.c_double) for name in (
+                    "compressor_gain_reduction_p95_db", "compressor_gain_reduction_db", "output_true_peak_db",
+                    "limiter_effective_ceiling_db", "output_rms_db", "input_rms_db", "deesser_gain_reduction_p95_db",
+                    "compressor_gain_reduction_median_db", "deesser_gain_reduction_median_db", "target_p95_reduction_db",
+                    "peak_reduction_cap_db", "deesser_max_reduction_db", "before_snr_db", "after_snr_db",
+                    "loudness_variation_before_db", "loudness_variation_after_db")])
+
+
+class SetupVerificationResult(C.Structure):
+    _fields_ = ([(name, C.c_int32) for name in ("decision", "reason", "early_exit", "clipped")]
+                + [("limiter_activity_events", C.c_uint64)]
+                + [(name, C.c_double) for name in (
+                    "spectral_target_error_before_db", "spectral_target_error_after_db", "loudness_variation_before_db",
+                    "loudness_variation_after_db", "noise_floor_change_db", "relative_noise_floor_change_db", "snr_change_db",
+                    "compressor_gain_reduction_median_db", "compressor_gain_reduction_p95_db", "compressor_gain_reduction_peak_db",
+                    "deesser_gain_reduction_median_db", "deesser_gain_reduction_p95_db", "output_true_peak_db",
+                    "level_difference_db", "shape_delta_db")])
+
+
+SETUP_HAS_DEESSER_PEAK = 1 << 13  # AF_SETUP_HAS_DEESSER_PEAK
+
+
+class SetupOfflineInputs(C.Structure):
+    _fields_ = ([(name, C.c_double) for name in (
+                    "capture_confidence", "snr_confidence", "speech_dynamic_range_db", "conservative_noise_rms_db",
+                    "noise_referenced_snr_db", "active_duration_s", "deesser_frame_evidence_confidence", "peak_reduction_cap_db",
+                    "target_p95_reduction_db", "eq_analysis_confidence")]
+                + [(name, C.c_int32) for name in ("deesser_enabled", "noise_status_usable", "has_eq_settings", "eq_has_analysis_confidence",
+                                                  "eq_apply_recommended", "simulation_available", "backend_is_rust")]
+                + [("present", C.c_uint32)]
+                + [(name, C.c_double) for name in ("output_true_peak_db", "limiter_effective_ceiling_db", "compressor_gain_reduction_db",
+                                                   "compressor_gain_reduction_p95_db", "deesser_gain_reduction_db")])
+
+
+class SetupOfflineResult(C.Structure):
+    _fields_ = ([(name, C.c_int32) for name in ("offline_validation_passed", "weak_capture", "apply_recommended")]
+                + [("uncertainty_reasons", C.c_uint32)]
+                + [(name, C.c_double) for name in ("eq_confidence", "gate_confidence", "deesser_confidence", "compressor_confidence",
+                                                   "setup_confidence", "recommendation_uncertainty")])
+
+
 # every symbol include/audioforge_mi.h declares: name -> (restype, argtypes)
 _vp, _i32, _i64, _d, _f, _sz = C.c_void_p, C.c_int32, C.c_int64, C.c_double, C.c_float, C.c_size_t
 _fp, _dp = C.POINTER(C.c_float), C.POINTER(C.c_double)
@@ -496,6 +565,18 @@ SIGNATURES = {
     "af_compressor_search_read_rows":(C.c_int, [_vp, C.POINTER(BlockStats), _i64]),
     "af_compressor_search_read_audio": (C.c_int, [_vp, _fp, _i64]),
     "af_compressor_search_last_kernel_ms": (C.c_int, [_vp, _dp, _dp]),
+    # second-passage verification: the measurements
+    "af_setup_verification_create": (C.c_int, [C.c_uint32, _i32, _i32, _i32, C.POINTER(_vp)]),
+    "af_setup_verification_destroy": (None, [_vp]),
+    "af_setup_verification_measure_host": (C.c_int, [_vp, _i32, _dp, _dp, _dp, _i64, _dp, _i64, C.POINTER(_i32),
+                                                     C.POINTER(SetupVerificationAudio), C.POINTER(SetupVerificationRow)]),
+    "af_setup_verification_measure_device": (C.c_int, [_vp, _i32, _vp, _vp, _vp, _i64, _vp, _i64, C.POINTER(_i32),
+                                                       C.POINTER(SetupVerificationAudio), _vp, _vp]),
+    "af_setup_verification_decide": (C.c_int, [C.POINTER(SetupVerificationRow), C.POINTER(SetupVerificationEvidence),
+                                               C.POINTER(SetupVerificationResult)]),
+    "af_setup_verification_reason_text": (C.c_char_p, [_i32]),
+    "af_setup_offline_validation": (C.c_int, [C.POINTER(SetupOfflineInputs), C.POINTER(SetupOfflineResult)]),
+    "af_setup_offline_reason_text": (C.c_char_p, [_i32]),
     "af_gate_process_host": (C.c_int, [_fp, _fp, _i64, _i32, _i64, _d, _d, _d, _d, _i32, _i32, _fp, C.POINTER(C.c_uint64), _i32]),
     "af_measure_integrated_loudness_device": (C.c_int, [_vp, _i64, _i32, _i64, C.c_uint32, _i32, _dp, C.POINTER(_i32)]),
     "af_measure_integrated_loudness_host": (C.c_int, [_fp, _i64, _i32, _i64, C.c_uint32, _i32, _dp, C.POINTER(_i32)]),
@@ -528,6 +609,7 @@ VALUE_FUNCTIONS = {
     "af_device_rate_features_resampled_length", "af_device_rate_features_sibilance_bins",
     "af_voice_setup_default_inputs",
     "af_compressor_search_destroy", "af_compressor_search_blocks",
+    "af_setup_verification_destroy", "af_setup_verification_reason_text", "af_setup_offline_reason_text",
 }
 
 _lib = None

@@ -2635,7 +2635,7 @@ def recommend_voice_chain_batch(noise_audio, speech_audio, fs: int, target_prese
                                 noise_vad_probabilities=None, vad_available: bool = True, dynamics_intensity: str = "balanced",
                                 custom_target_p95_db: float = 3.5, custom_peak_cap_db: float = 8.0, noise_metadata=None,
                                 speech_metadata=None, device: int = 0, calibrate_compressor: bool = False, eq_settings=None,
-                                device_rate: bool = False) -> list:
+                                device_rate: bool = False, offline_validation: bool = False) -> list:
     """analyze_voice_setup (voice_setup.py:1082-1223) for every pair of noise_audio [n_streams, m] and speech_audio
     [n_streams, n] up to its three rule-based recommendations: analyze_voice_capture_batch (the noise reference, then the voice
     spectrum with the conservative spectrum as its override), the "balanced" smoothing of the median spectrum, the speech
@@ -2660,7 +2660,11 @@ def recommend_voice_chain_batch(noise_audio, speech_audio, fs: int, target_prese
     fs is 48000, or with ``device_rate=True`` any of SPEECH_FEATURES_RATES: the noise reference, the voice spectrum and the
     speech features then run at that rate (the loudness behind the resampling to 48 kHz of voice_setup.py:127-140).
 
-    It does NOT return EQ bands (the Auto-EQ optimiser is not built) or the offline validation and setup confidences."""
+    It does NOT return EQ bands (the Auto-EQ optimiser is not built).  With ``offline_validation=True`` every record gains a
+    ``diagnostics`` dict with the reference's keys of voice_setup.py:1265-1364 (the setup passage through the recommended chain,
+    the offline validation, the stage and setup confidences, uncertainty_reasons, weak_capture, apply_recommended); ``eq_settings``
+    plays the role it plays for the calibration, and without it the flat bands apply and Auto-EQ counts as abstained.  48 kHz only.
+    Without the keyword the return is what it was."""
     noise, speech = np.asarray(noise_audio), np.asarray(speech_audio)
     if noise.ndim != 2 or speech.ndim != 2 or noise.shape[0] != speech.shape[0]:
         raise ValueError("noise_audio and speech_audio must be [n_streams, m] and [n_streams, n]")
@@ -2712,4 +2716,12 @@ def recommend_voice_chain_batch(noise_audio, speech_audio, fs: int, target_prese
             calibrations = [diagnostics for _, diagnostics in pairs]
         for rec, calibration in zip(results, calibrations):
             rec["compressor_calibration"] = calibration
+    if offline_validation:
+        if int(fs) != 48_000:
+            raise NotImplementedError(f"sample rate {fs}: the offline validation is built for 48000 Hz")
+        from .setup_verification import offline_validation_diagnostics
+
+        for rec, diagnostics in zip(results, offline_validation_diagnostics(results, [r.reasons for r in references], speech, fs,
+                                                                            eq_settings, device)):
+            rec["diagnostics"] = diagnostics
     return results

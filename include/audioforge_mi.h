@@ -1135,6 +1135,159 @@ int af_compressor_search_run(af_compressor_search *h, const af_compressor_search
 /* kernel ms of the last run's three sweeps: phase 1 sweep, fold; phase 2 sweep, fold; verification sweep, fold */
 int af_compressor_search_last_run_ms(const af_compressor_search *h, double ms[6]);
 
+/* ---- second-passage verification, the measurements: python/mic_eq/analysis/voice_setup.py:1446-1679 ---------------------
+ * validate_voice_setup_verification renders a second passage and the room tone through the recommended chain and measures both
+ * sides.  This object takes what the other analyses leave (the median spectra of the original, the verification and the
+ * rendered passage from af_voice_spectrum_*, the rendered side's spectral SNR, and the five signals) and returns, per stream,
+ * the numbers the reference's decision reads that no other entry point yields:
+ *   _shape_error_db (:1446-1465) of the before and the after side against the adaptive house curve
+ *     (auto_eq_parts/target.py:15-104 over TARGET_CURVES / EQ_FREQUENCIES), with the five scalars the adaptive offsets were
+ *     derived from (body, presence and sibilance means, tilt in dB/octave, low-mid balance: target.py:24-43);
+ *   the repeatability delta (:1562-1575);
+ *   the medians of the after side's spectral SNR over low 80-250 | body 250-1000 | presence 1000-4500 | sibilance 4500-10000 Hz
+ *     (:1634-1645), lower edge inclusive, upper exclusive, NaN as np.median, a band without bins absent;
+ *   per signal the f64 sum of squares in NumPy's pairwise order and _rms_db of it (:102-106), the peak, whether a sample is not
+ *     finite, and the clipped tests of :1490 (>= 0.999) and :1677 (>= 1.0).
+ * The three spectra share the grid np.fft.rfftfreq(nperseg, 1 / sample_rate), on which the np.interp of :1562-1566 returns the
+ * original's own values.  af_setup_verification_decide below turns a row and the simulation's numbers into accept / reduce /
+ * rollback / retry.  Sum orders: csrc/af_setup_verification_math.h. */
+enum { AF_TARGET_BROADCAST = 0, AF_TARGET_PODCAST = 1, AF_TARGET_STREAMING = 2, AF_TARGET_FLAT = 3, AF_TARGET_PRESET_COUNT = 4 };
+enum { /* the signals of one stream, in the order of every [AF_SETUP_SIGNALS] array */
+  AF_SETUP_SIGNAL_NOISE = 0, AF_SETUP_SIGNAL_ORIGINAL = 1, AF_SETUP_SIGNAL_VERIFICATION = 2, AF_SETUP_SIGNAL_RENDERED = 3,
+  AF_SETUP_SIGNAL_RENDERED_NOISE = 4, AF_SETUP_SIGNALS = 5
+};
+typedef struct af_setup_verification af_setup_verification;
+typedef struct af_setup_verification_audio {
+  const float *samples;   /* [n_streams][stride]; NULL: the signal is absent (zero sums and flags, rms_db -120) */
+  int64_t stride;         /* >= length */
+  int64_t length;         /* samples per stream */
+  const int64_t *lengths; /* HOST memory in both entry points, [n_streams], each in 0..length; NULL: `length` for every stream */
+} af_setup_verification_audio;
+typedef struct af_setup_verification_row {
+  int32_t masked_bins;      /* bins in 80..12000 Hz; below 8 both errors are +inf (:1455-1456) */
+  int32_t snr_available;    /* 0: no spectral SNR was given, frequency_dependent_snr_db is empty (:1636) */
+  int32_t band_present[4];
+  int32_t non_finite[5], clipped_0999[5], clipped_1[5];
+  int32_t reserved;
+  double spectral_target_error_before_db, spectral_target_error_after_db; /* :1552-1561 */
+  double shape_delta_db;                                                  /* :1575; NaN without a masked bin */
+  double band_snr_db[4];                                                  /* 0 where absent */
+  double offsets_before[5], offsets_after[5]; /* body | presence | sibilance means, tilt dB/octave, low-mid balance; 0 below 8 bins */
+  double sum_squares[5], peak[5], rms_db[5];
+} af_setup_verification_row;
+/* Host work only.  AF_ERR_UNSUPPORTED for a rate other than 48000 and for nperseg above 16384 (the kernel's LDS sort holds
+ * 4096 masked bins); AF_ERR_INVALID_ARGUMENT for nperseg odd or below 2, max_streams < 1, device < 0. */
+int af_setup_verification_create(uint32_t sample_rate, int32_t nperseg, int32_t max_streams, int32_t device, af_setup_verification **out);
+void af_setup_verification_destroy(af_setup_verification *v);
+/* original_db, before_db, after_db: [n_streams][spectrum_stride] rows of nperseg / 2 + 1 bins; after_snr_db: the same shape
+ * with its own stride, or NULL; preset_ids: HOST memory in both entry points, [n_streams] AF_TARGET_* (any other id:
+ * AF_ERR_INVALID_ARGUMENT "Unknown target preset", target.py:78-79); audio: AF_SETUP_SIGNALS entries; rows: [n_streams].
+ * Arguments are checked before any GPU work.  _device takes device pointers for spectra, SNR, samples and rows, and enqueues
+ * on hip_stream; a non-finite sample cannot fault and is reported in non_finite.  The first call on a handle allocates its
+ * device buffers and uploads the grid synchronously; later calls only enqueue, and the preset ids and lengths are the caller's
+ * again when the call returns.  A handle holds one copy of the presets and the lengths on the device: calls on one handle go to
+ * one stream, or are separated by a synchronisation; use one handle per stream otherwise. */
+int af_setup_verification_measure_host(af_setup_verification *v, int32_t n_streams, const double *original_db, const double *before_db,
+                                       const double *after_db, int64_t spectrum_stride, const double *after_snr_db, int64_t snr_stride,
+                                       const int32_t *preset_ids, const af_setup_verification_audio *audio,
+                                       af_setup_verification_row *rows);
+int af_setup_verification_measure_device(af_setup_verification *v, int32_t n_streams, const double *d_original_db,
+                                         const double *d_before_db, const double *d_after_db, int64_t spectrum_stride,
+                                         const double *d_after_snr_db, int64_t snr_stride, const int32_t *preset_ids,
+                                         const af_setup_verification_audio *audio, af_setup_verification_row *d_rows, void *hip_stream);
+
+/* The rules of validate_voice_setup_verification for one stream, voice_setup.py:1484-1495 and :1590-1679: host work only.
+ * The early exits (:1484-1495, :1527-1537) return three keys in the reference: early_exit is 1 and only decision and reason
+ * are meaningful.  Otherwise the ladder of :1608-1632 in its order: retry, then rollback, then reduce, then accept.
+ * A key the simulation dict or the settings lack is marked by a cleared bit in `present` and takes the reference's default:
+ * 120 for the two compressor reductions and the output true peak (:1593-1597), -1.5 for the ceiling (:1598), 0 events (:1599),
+ * the measured _rms_db of the rendered / the verification passage for output_rms_db / input_rms_db (:1601-1603), 0 for the
+ * de-esser and median reductions (:1624, :1664-1674), 3.5 / 8.0 / 6.0 for target_p95_reduction_db / peak_reduction_cap_db /
+ * max_reduction_db (:1591-1592, :1625). */
+enum { AF_SETUP_ACCEPT = 0, AF_SETUP_REDUCE = 1, AF_SETUP_ROLLBACK = 2, AF_SETUP_RETRY = 3 };
+enum { /* reasons[0] of the reference's result: af_setup_verification_reason_text */
+  AF_SETUP_REASON_PASSED = 0,       /* :1632 */
+  AF_SETUP_REASON_STRONGER = 1,     /* :1629 */
+  AF_SETUP_REASON_WORSENED = 2,     /* :1619 */
+  AF_SETUP_REASON_DIFFERS = 3,      /* :1610 */
+  AF_SETUP_REASON_TOO_SHORT = 4,    /* :1487 */
+  AF_SETUP_REASON_CLIPPED = 5,      /* :1493 */
+  AF_SETUP_REASON_NO_RENDERER = 6,  /* :1534 */
+  AF_SETUP_REASON_COUNT = 7
+};
+enum { /* bits of af_setup_verification_evidence.present */
+  AF_SETUP_HAS_COMPRESSOR_P95 = 1 << 0, AF_SETUP_HAS_COMPRESSOR_PEAK = 1 << 1, AF_SETUP_HAS_OUTPUT_TRUE_PEAK = 1 << 2,
+  AF_SETUP_HAS_CEILING = 1 << 3, AF_SETUP_HAS_LIMITED_EVENTS = 1 << 4, AF_SETUP_HAS_OUTPUT_RMS = 1 << 5,
+  AF_SETUP_HAS_INPUT_RMS = 1 << 6, AF_SETUP_HAS_DEESSER_P95 = 1 << 7, AF_SETUP_HAS_COMPRESSOR_MEDIAN = 1 << 8,
+  AF_SETUP_HAS_DEESSER_MEDIAN = 1 << 9, AF_SETUP_HAS_TARGET_P95 = 1 << 10, AF_SETUP_HAS_PEAK_CAP = 1 << 11,
+  AF_SETUP_HAS_DEESSER_MAX_REDUCTION = 1 << 12
+};
+typedef struct af_setup_verification_evidence { /* what the rules read beside the measured row */
+  uint32_t present;
+  int32_t backend_is_rust;          /* simulation_backend == "rust" and both renders returned audio (:1527-1531) */
+  int64_t verification_samples;     /* :1484 */
+  double sample_rate;
+  uint64_t true_peak_limited_events;
+  /* the simulation dict of the verification passage (python_api.rs:649-712) */
+  double compressor_gain_reduction_p95_db, compressor_gain_reduction_db, output_true_peak_db, limiter_effective_ceiling_db;
+  double output_rms_db, input_rms_db, deesser_gain_reduction_p95_db, compressor_gain_reduction_median_db;
+  double deesser_gain_reduction_median_db;
+  /* compressor_settings and deesser_settings */
+  double target_p95_reduction_db, peak_reduction_cap_db, deesser_max_reduction_db;
+  /* VoiceSpectrum.snr_db of the two sides (:1605) and active_loudness_spread_db of the two feature runs (:1655-1660) */
+  double before_snr_db, after_snr_db, loudness_variation_before_db, loudness_variation_after_db;
+} af_setup_verification_evidence;
+typedef struct af_setup_verification_result { /* :1647-1679; frequency_dependent_snr_db is the row's band_snr_db */
+  int32_t decision, reason, early_exit, clipped;
+  uint64_t limiter_activity_events;
+  double spectral_target_error_before_db, spectral_target_error_after_db;
+  double loudness_variation_before_db, loudness_variation_after_db;
+  double noise_floor_change_db, relative_noise_floor_change_db, snr_change_db;
+  double compressor_gain_reduction_median_db, compressor_gain_reduction_p95_db, compressor_gain_reduction_peak_db;
+  double deesser_gain_reduction_median_db, deesser_gain_reduction_p95_db, output_true_peak_db;
+  double level_difference_db, shape_delta_db; /* what the retry test read (:1608) */
+} af_setup_verification_result;
+int af_setup_verification_decide(const af_setup_verification_row *row, const af_setup_verification_evidence *evidence,
+                                 af_setup_verification_result *out);
+const char *af_setup_verification_reason_text(int32_t reason); /* VALUE: NULL for an unknown index */
+
+/* The offline validation and the confidences behind apply_recommended, voice_setup.py:1265-1364, for one stream: host work only.
+ * The caller simulates the setup passage through the recommended chain (:1297-1312) and hands over what the rules read.
+ * uncertainty_reasons (:1332-1356) come back as bits in the reference's order, after the noise reference's own reasons (which
+ * the caller holds): af_setup_offline_reason_text. */
+enum {
+  AF_SETUP_UNCERTAIN_LITTLE_SPEECH = 1 << 0,  /* "too little VAD-active speech", :1335 */
+  AF_SETUP_UNCERTAIN_WEAK_SNR = 1 << 1,       /* :1337 */
+  AF_SETUP_UNCERTAIN_UNSTABLE = 1 << 2,       /* :1339 */
+  AF_SETUP_UNCERTAIN_NOT_PASSED = 1 << 3,     /* :1341 */
+  AF_SETUP_UNCERTAIN_ADVISORY = 1 << 4,       /* :1343 */
+  AF_SETUP_UNCERTAIN_EQ_ABSTAINED = 1 << 5,   /* :1356 */
+  AF_SETUP_UNCERTAIN_COUNT = 6
+};
+typedef struct af_setup_offline_inputs {
+  double capture_confidence, snr_confidence;          /* af_voice_setup_recommendation */
+  double speech_dynamic_range_db;                     /* features' loudness_range_db, :1152 */
+  double conservative_noise_rms_db, noise_referenced_snr_db, active_duration_s;
+  double deesser_frame_evidence_confidence;
+  double peak_reduction_cap_db, target_p95_reduction_db; /* compressor diagnostics, :1324-1326 */
+  double eq_analysis_confidence;                      /* read when eq_has_analysis_confidence, :1271 */
+  int32_t deesser_enabled, noise_status_usable;
+  int32_t has_eq_settings, eq_has_analysis_confidence, eq_apply_recommended; /* eq_settings.get("apply_recommended", True) */
+  int32_t simulation_available;                       /* 0: simulate_candidate_chain raised (:1329-1330) */
+  int32_t backend_is_rust;
+  uint32_t present;                                   /* AF_SETUP_HAS_OUTPUT_TRUE_PEAK | _CEILING | _COMPRESSOR_PEAK | _COMPRESSOR_P95 | AF_SETUP_HAS_DEESSER_PEAK */
+  double output_true_peak_db, limiter_effective_ceiling_db, compressor_gain_reduction_db, compressor_gain_reduction_p95_db;
+  double deesser_gain_reduction_db;
+} af_setup_offline_inputs;
+enum { AF_SETUP_HAS_DEESSER_PEAK = 1 << 13 };
+typedef struct af_setup_offline_result {
+  int32_t offline_validation_passed, weak_capture, apply_recommended;
+  uint32_t uncertainty_reasons;
+  double eq_confidence, gate_confidence, deesser_confidence, compressor_confidence, setup_confidence, recommendation_uncertainty;
+} af_setup_offline_result;
+int af_setup_offline_validation(const af_setup_offline_inputs *in, af_setup_offline_result *out);
+const char *af_setup_offline_reason_text(int32_t bit_index); /* VALUE: NULL for an unknown index */
+
 /* ---- NoiseSuppressor: rust-core/src/dsp/noise_suppressor.rs:18-194 ----------------------------------------
  * The runtime-selected suppressor interface (`NoiseModel`, trait `NoiseSuppressor`, `new_noise_suppression_engine`) for a
  * batch of streams that advance in lock step: sample counts are per stream, audio is [stream][stride] host memory, the
