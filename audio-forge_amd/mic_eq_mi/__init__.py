@@ -84,8 +84,16 @@ else:
     SetupVerification = None
     measure_setup_verification_batch = decide_voice_setup_verification = _missing_core
     verify_voice_setup_batch = validate_voice_setup_verification = _missing_core
+# ... and the EQ headroom validation with its per-lane EQ
+if _core_module is not None:
+    from .headroom import (LaneEq, apply_headroom_validation, apply_headroom_validation_batch, simulate_candidate_chain,
+                           simulate_candidate_chain_batch)
+else:
+    LaneEq = None
+    simulate_candidate_chain = simulate_candidate_chain_batch = apply_headroom_validation = apply_headroom_validation_batch = _missing_core
 
 __all__ = ["CORE_AVAILABLE", "Engine", "NoiseSuppressor", "NoiseModel", "StreamResampler", "Mixdown", "VoiceSpectrum", "VoiceSpectrumResult", "NoiseReference", "NoiseReferenceAnalysis", "SpeechFeatures", "CaptureMetadata",
            "new_noise_suppression_engine", *_OPERATORS, "CompressorSearch", "compressor_input_batch", "simulate_compressor_candidates_batch", "calibrate_compressor",
-           "calibrate_compressor_batch", "SetupVerification", "measure_setup_verification_batch", "decide_voice_setup_verification", "verify_voice_setup_batch", "validate_voice_setup_verification", "LAYOUT_STREAM_MAJOR", "LAYOUT_TIME_MAJOR", "KERNEL_AUTO",
+           "calibrate_compressor_batch", "SetupVerification", "measure_setup_verification_batch", "decide_voice_setup_verification", "verify_voice_setup_batch", "validate_voice_setup_verification", "LaneEq",
+           "simulate_candidate_chain", "simulate_candidate_chain_batch", "apply_headroom_validation", "apply_headroom_validation_batch", "LAYOUT_STREAM_MAJOR", "LAYOUT_TIME_MAJOR", "KERNEL_AUTO",
            "KERNEL_LANE_PER_STREAM", "KERNEL_PHASED", "KERNEL_QUAD", "KERNEL_STAGED"]

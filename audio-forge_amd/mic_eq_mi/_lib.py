@@ -565,6 +565,14 @@ SIGNATURES = {
     "af_compressor_search_read_rows":(C.c_int, [_vp, C.POINTER(BlockStats), _i64]),
     "af_compressor_search_read_audio": (C.c_int, [_vp, _fp, _i64]),
     "af_compressor_search_last_kernel_ms": (C.c_int, [_vp, _dp, _dp]),
+    # per-lane EQ
+    "af_lane_eq_create": (C.c_int, [_d, _i32, C.POINTER(_vp)]),
+    "af_lane_eq_destroy": (None, [_vp]),
+    "af_lane_eq_run_host": (C.c_int, [_vp, _fp, _i64, _i32, _i64, C.POINTER(_i32), _i32, _dp]),
+    "af_lane_eq_run_device": (C.c_int, [_vp, _vp, _i64, _i32, _i64, C.POINTER(_i32), _i32, _dp]),
+    "af_lane_eq_output": (C.c_int, [_vp, C.POINTER(_vp), C.POINTER(_i64)]),
+    "af_lane_eq_read_output": (C.c_int, [_vp, _fp, _i64]),
+    "af_lane_eq_last_kernel_ms": (C.c_int, [_vp, _dp]),
     # second-passage verification: the measurements
     "af_setup_verification_create": (C.c_int, [C.c_uint32, _i32, _i32, _i32, C.POINTER(_vp)]),
     "af_setup_verification_destroy": (None, [_vp]),
@@ -608,7 +616,7 @@ VALUE_FUNCTIONS = {
     "af_device_rate_features_destroy", "af_device_rate_features_frames", "af_device_rate_features_chunks",
     "af_device_rate_features_resampled_length", "af_device_rate_features_sibilance_bins",
     "af_voice_setup_default_inputs",
-    "af_compressor_search_destroy", "af_compressor_search_blocks",
+    "af_compressor_search_destroy", "af_compressor_search_blocks", "af_lane_eq_destroy",
     "af_setup_verification_destroy", "af_setup_verification_reason_text", "af_setup_offline_reason_text",
 }
 

@@ -2635,7 +2635,7 @@ def recommend_voice_chain_batch(noise_audio, speech_audio, fs: int, target_prese
                                 noise_vad_probabilities=None, vad_available: bool = True, dynamics_intensity: str = "balanced",
                                 custom_target_p95_db: float = 3.5, custom_peak_cap_db: float = 8.0, noise_metadata=None,
                                 speech_metadata=None, device: int = 0, calibrate_compressor: bool = False, eq_settings=None,
-                                device_rate: bool = False, offline_validation: bool = False) -> list:
+                                device_rate: bool = False, offline_validation: bool = False, validate_eq_headroom: bool = False) -> list:
     """analyze_voice_setup (voice_setup.py:1082-1223) for every pair of noise_audio [n_streams, m] and speech_audio
     [n_streams, n] up to its three rule-based recommendations: analyze_voice_capture_batch (the noise reference, then the voice
     spectrum with the conservative spectrum as its override), the "balanced" smoothing of the median spectrum, the speech
@@ -2664,8 +2664,15 @@ def recommend_voice_chain_batch(noise_audio, speech_audio, fs: int, target_prese
     ``diagnostics`` dict with the reference's keys of voice_setup.py:1265-1364 (the setup passage through the recommended chain,
     the offline validation, the stage and setup confidences, uncertainty_reasons, weak_capture, apply_recommended); ``eq_settings``
     plays the role it plays for the calibration, and without it the flat bands apply and Auto-EQ counts as abstained.  48 kHz only.
-    Without the keyword the return is what it was."""
+    Without the keyword the return is what it was.
+
+    ``validate_eq_headroom=True`` first takes the caller's ``eq_settings`` through apply_headroom_validation_batch (headroom.py) on
+    the voice capture with default chain settings, as voice_setup.py:1227-1237 does with the optimiser's result: every record gains
+    an ``eq`` key with the validated settings, and the calibration and the offline validation use their scaled gains.  Without the
+    keyword the return is what it was."""
     noise, speech = np.asarray(noise_audio), np.asarray(speech_audio)
+    if validate_eq_headroom and eq_settings is None:
+        raise ValueError("validate_eq_headroom needs eq_settings")
     if noise.ndim != 2 or speech.ndim != 2 or noise.shape[0] != speech.shape[0]:
         raise ValueError("noise_audio and speech_audio must be [n_streams, m] and [n_streams, n]")
     if noise.shape[1] < int(fs * NOISE_MIN_DURATION_S):
@@ -2700,6 +2707,12 @@ def recommend_voice_chain_batch(noise_audio, speech_audio, fs: int, target_prese
         rec.update(features=features[s], noise_reference_status=reference.status, noise_referenced_snr_db=float(spectrum.snr_db),
                    conservative_noise_rms_db=float(reference.conservative_noise_rms_db))
         results.append(rec)
+    if validate_eq_headroom:
+        from .headroom import apply_headroom_validation_batch
+
+        eq_settings = apply_headroom_validation_batch(speech, fs, eq_settings, device=device)
+        for rec, validated in zip(results, eq_settings):
+            rec["eq"] = validated
     if calibrate_compressor:
         calibrations = [{"backend": "unavailable", "target_gain_reduction_db": 0.0, "measured_gain_reduction_db": 0.0, "iterations": 0}
                         for _ in results]  # voice_setup.py:1241-1246

@@ -1135,6 +1135,36 @@ int af_compressor_search_run(af_compressor_search *h, const af_compressor_search
 /* kernel ms of the last run's three sweeps: phase 1 sweep, fold; phase 2 sweep, fold; verification sweep, fold */
 int af_compressor_search_last_run_ms(const af_compressor_search *h, double ms[6]);
 
+/* ---- per-lane EQ: the EQ half of the renders behind python/mic_eq/analysis/auto_eq_parts/headroom.py:292-354 -------------
+ * apply_headroom_validation pushes one capture through simulate_auto_eq_chain (python_api.rs:378-714) once per gain scale: the
+ * same audio through ten-band EQs that differ only in their gains.  Here a LANE = one (capture, band set) pair runs the EQ of
+ * that chain over its capture's row, from zero state, with its own coefficients: ParametricEQ::new(sample_rate)
+ * (eq.rs:357-368), then set_band_frequency, set_band_gain, set_band_q per band in that order (python_api.rs:408-412, the legacy
+ * (frequency_hz, gain_db, q) triples), then ParametricEQ::process_block_inplace (eq.rs:371-379) with the coefficient crossfade
+ * the setters scheduled (biquad.rs:249-327).  Non-finite input samples are zeroed first (python_api.rs:517-520).  A lane's output
+ * equals the compressor input of an engine configured with the lane's bands and nothing but the EQ enabled, bit for bit.
+ * The output stays on the device as [n_lanes][stride] float32 and is what af_compressor_search_load_device takes. */
+typedef struct af_lane_eq af_lane_eq;
+/* Host work only.  AF_ERR_INVALID_ARGUMENT for a non-finite or non-positive sample rate and for device < 0. */
+int af_lane_eq_create(double sample_rate, int32_t device, af_lane_eq **out);
+void af_lane_eq_destroy(af_lane_eq *h);
+/* audio: [n_captures][stride] float32 (host memory / device memory); lane_capture: HOST memory, [n_lanes], each in
+ * 0..n_captures-1, in any order and mix; bands: HOST memory, [n_lanes][10][3] doubles (frequency_hz, gain_db, q).
+ * Arguments are checked before any GPU work: AF_ERR_INVALID_ARGUMENT for a null pointer, n_samples <= 0, n_captures <= 0,
+ * n_lanes <= 0, stride < n_samples, a lane_capture out of range, a band value that is not finite.  _run_device does not look at
+ * the audio and keeps no reference to it after the kernel has run; both calls return when the kernel has been enqueued on the
+ * device's null stream (the readers below wait for it). */
+int af_lane_eq_run_host(af_lane_eq *h, const float *audio, int64_t n_samples, int32_t n_captures, int64_t stride,
+                        const int32_t *lane_capture, int32_t n_lanes, const double *bands);
+int af_lane_eq_run_device(af_lane_eq *h, const float *d_audio, int64_t n_samples, int32_t n_captures, int64_t stride,
+                          const int32_t *lane_capture, int32_t n_lanes, const double *bands);
+/* The last run's output on the device: [n_lanes][*stride] float32, *stride >= n_samples (rows start 256 B aligned); valid until
+ * the next run on the handle or its destruction.  AF_ERR_STATE before the first run. */
+int af_lane_eq_output(af_lane_eq *h, float **d_out, int64_t *stride);
+/* The last run's output to host memory as [n_lanes][stride], n_samples per row. */
+int af_lane_eq_read_output(af_lane_eq *h, float *out, int64_t stride);
+int af_lane_eq_last_kernel_ms(af_lane_eq *h, double *ms);
+
 /* ---- second-passage verification, the measurements: python/mic_eq/analysis/voice_setup.py:1446-1679 ---------------------
  * validate_voice_setup_verification renders a second passage and the room tone through the recommended chain and measures both
  * sides.  This object takes what the other analyses leave (the median spectra of the original, the verification and the
