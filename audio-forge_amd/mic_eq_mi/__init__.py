@@ -91,9 +91,17 @@ if _core_module is not None:
 else:
     LaneEq = None
     simulate_candidate_chain = simulate_candidate_chain_batch = apply_headroom_validation = apply_headroom_validation_batch = _missing_core
+# ... and the latency calibration
+if _core_module is not None:
+    from .latency_calibration import (LatencyCalibration, LatencyCalibrationResult, analyze_latency, analyze_latency_batch,
+                                      generate_probe_signal, result_to_profile)
+else:
+    LatencyCalibration = LatencyCalibrationResult = None
+    generate_probe_signal = analyze_latency = analyze_latency_batch = result_to_profile = _missing_core
 
 __all__ = ["CORE_AVAILABLE", "Engine", "NoiseSuppressor", "NoiseModel", "StreamResampler", "Mixdown", "VoiceSpectrum", "VoiceSpectrumResult", "NoiseReference", "NoiseReferenceAnalysis", "SpeechFeatures", "CaptureMetadata",
            "new_noise_suppression_engine", *_OPERATORS, "CompressorSearch", "compressor_input_batch", "simulate_compressor_candidates_batch", "calibrate_compressor",
            "calibrate_compressor_batch", "SetupVerification", "measure_setup_verification_batch", "decide_voice_setup_verification", "verify_voice_setup_batch", "validate_voice_setup_verification", "LaneEq",
-           "simulate_candidate_chain", "simulate_candidate_chain_batch", "apply_headroom_validation", "apply_headroom_validation_batch", "LAYOUT_STREAM_MAJOR", "LAYOUT_TIME_MAJOR", "KERNEL_AUTO",
+           "simulate_candidate_chain", "simulate_candidate_chain_batch", "apply_headroom_validation", "apply_headroom_validation_batch", "LatencyCalibration",
+           "LatencyCalibrationResult", "generate_probe_signal", "analyze_latency", "analyze_latency_batch", "result_to_profile", "LAYOUT_STREAM_MAJOR", "LAYOUT_TIME_MAJOR", "KERNEL_AUTO",
            "KERNEL_LANE_PER_STREAM", "KERNEL_PHASED", "KERNEL_QUAD", "KERNEL_STAGED"]

@@ -585,6 +585,18 @@ SIGNATURES = {
     "af_setup_verification_reason_text": (C.c_char_p, [_i32]),
     "af_setup_offline_validation": (C.c_int, [C.POINTER(SetupOfflineInputs), C.POINTER(SetupOfflineResult)]),
     "af_setup_offline_reason_text": (C.c_char_p, [_i32]),
+    # latency calibration (the structures are latency_calibration.py's)
+    "af_latency_create": (C.c_int, [_d, _dp, _i64, _i32, _i64, _i32, C.POINTER(_vp)]),
+    "af_latency_destroy": (None, [_vp]),
+    "af_latency_layout": (C.c_int, [_vp, C.POINTER(_i32), C.POINTER(_i32), C.POINTER(_i32), C.POINTER(_i32)]),
+    "af_latency_analyze_host": (C.c_int, [_vp, _fp, _i64, _i64, _i32, C.POINTER(_i64), _vp]),
+    "af_latency_analyze_device": (C.c_int, [_vp, _vp, _i64, _i64, _i32, C.POINTER(_i64), _vp]),
+    "af_latency_read_results": (C.c_int, [_vp, _vp, _i32]),
+    "af_latency_read_scores": (C.c_int, [_vp, _i32, _i32, C.POINTER(_i32), C.POINTER(_i32), _dp, _dp, C.POINTER(_i32), C.POINTER(_i32),
+                                         _dp, _i64]),
+    "af_latency_last_kernel_ms": (C.c_int, [_vp, _dp, _dp]),
+    "af_latency_message_text": (C.c_char_p, [_i32, _i32]),
+    "af_latency_debug_rfft": (C.c_int, [_vp, _fp, _i64, _dp]),
     "af_gate_process_host": (C.c_int, [_fp, _fp, _i64, _i32, _i64, _d, _d, _d, _d, _i32, _i32, _fp, C.POINTER(C.c_uint64), _i32]),
     "af_measure_integrated_loudness_device": (C.c_int, [_vp, _i64, _i32, _i64, C.c_uint32, _i32, _dp, C.POINTER(_i32)]),
     "af_measure_integrated_loudness_host": (C.c_int, [_fp, _i64, _i32, _i64, C.c_uint32, _i32, _dp, C.POINTER(_i32)]),
@@ -618,6 +630,7 @@ VALUE_FUNCTIONS = {
     "af_voice_setup_default_inputs",
     "af_compressor_search_destroy", "af_compressor_search_blocks", "af_lane_eq_destroy",
     "af_setup_verification_destroy", "af_setup_verification_reason_text", "af_setup_offline_reason_text",
+    "af_latency_destroy", "af_latency_message_text",
 }
 
 _lib = None

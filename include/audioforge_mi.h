@@ -1318,6 +1318,79 @@ typedef struct af_setup_offline_result {
 int af_setup_offline_validation(const af_setup_offline_inputs *in, af_setup_offline_result *out);
 const char *af_setup_offline_reason_text(int32_t bit_index); /* VALUE: NULL for an unknown index */
 
+/* ---- latency calibration: python/mic_eq/analysis/latency_calibration.py -------------------------------------------------
+ * analyze_latency (:232-515) for a batch of recordings of one probe at one sample rate.  The probe is a repeated Barker-13
+ * burst (generate_probe_signal :45-71, _coded_probe_components :74-115); a recording's route delay is estimated from the
+ * normalised cross-correlation of the whole probe (:137-168, here a direct f64 sum per lag), a local search per burst
+ * (:359-384) and a GCC-PHAT cross-check (:171-198: one forward real transform of the recording, the whitened product with the
+ * burst's transform, one inverse transform, a windowed first-argmax per burst).  The passes run back to back on the device's
+ * null stream with no host wait between them: the burst windows depend on the whole-probe peak and are computed on the device.
+ * The rules of :424-515 (medians, the 75th percentile of the deviations, the confidence, success, the message) run on the host
+ * when the results are read.  Sum orders: csrc/af_latency_math.h.  Recordings are float32; the probe is taken as doubles.
+ * One addition over the reference: a recording with a sample that is not finite is not analysed (AF_LATENCY_EXIT_NON_FINITE);
+ * the reference has no such check and would return NaNs.
+ * The PHAT transform of a stream has n = the next power of two >= recording + burst real points; n above 2^18 (5.4 s at 48 kHz)
+ * is refused. */
+enum { /* why a stream was not analysed: the reference's early exits in their order (:254, :279, :314, :336), then ours */
+  AF_LATENCY_EXIT_NONE = 0, AF_LATENCY_EXIT_ROUTE = 1, AF_LATENCY_EXIT_SHORT = 2, AF_LATENCY_EXIT_WINDOW = 3,
+  AF_LATENCY_EXIT_NO_OVERLAP = 4, AF_LATENCY_EXIT_NON_FINITE = 5, AF_LATENCY_EXIT_COUNT = 6
+};
+enum { /* :487-494 */
+  AF_LATENCY_MESSAGE_OK = 0, AF_LATENCY_MESSAGE_DISAGREE = 1, AF_LATENCY_MESSAGE_ECHO = 2, AF_LATENCY_MESSAGE_LOW_CONFIDENCE = 3,
+  AF_LATENCY_MESSAGE_COUNT = 4
+};
+enum { /* the spans of af_latency_last_kernel_ms */
+  AF_LATENCY_PASS_CONDITION = 0, AF_LATENCY_PASS_PROBE = 1, AF_LATENCY_PASS_BURSTS = 2, AF_LATENCY_PASS_PHAT = 3, AF_LATENCY_PASSES = 4
+};
+enum { AF_LATENCY_MAX_OFFSETS = 4, AF_LATENCY_MAX_TRANSFORM = 1 << 18 };
+typedef struct af_latency af_latency;
+typedef struct af_latency_search { /* the keywords of analyze_latency for one stream; has_*: the keyword is not None */
+  double min_search_ms, max_search_ms;
+  double expected_playback_start_ms, expected_playback_jitter_ms, expected_latency_min_ms, expected_latency_max_ms;
+  int32_t has_playback_start, has_playback_jitter, has_latency_min, has_latency_max;
+  int32_t route_supported; /* route_kind is "output_to_input" after strip().lower(), :253-254 */
+  int32_t reserved;
+} af_latency_search;
+typedef struct af_latency_result {
+  int32_t success, exit_code, message, repetition_count; /* message is read only when exit_code is AF_LATENCY_EXIT_NONE */
+  int64_t peak_sample_offset;
+  double measured_round_trip_ms, applied_compensation_ms, confidence, agreement_ms, ambiguity_score, sub_sample_offset,
+      route_latency_ms;
+} af_latency_result;
+/* Host work only: the burst and its offsets (:325-328), the centred probe and burst with their energies (:276, :160), the
+ * twiddle table.  AF_ERR_INVALID_ARGUMENT for a sample_rate that is not finite and positive, a null or non-finite probe, a
+ * probe_samples below 16, max_streams < 1, max_record_samples < 1, device < 0, and a max_record_samples whose transform
+ * (max_record_samples + burst) would exceed AF_LATENCY_MAX_TRANSFORM real points. */
+int af_latency_create(double sample_rate, const double *probe, int64_t probe_samples, int32_t max_streams, int64_t max_record_samples,
+                      int32_t device, af_latency **out);
+void af_latency_destroy(af_latency *h);
+/* The burst's layout: *n_offsets <= AF_LATENCY_MAX_OFFSETS starts into offsets, the burst's length, the local radius (:351). */
+int af_latency_layout(af_latency *h, int32_t *n_offsets, int32_t *offsets, int32_t *burst_samples, int32_t *local_radius);
+/* recorded: [n_streams][stride] float32 (host memory / device memory), stream s holding lengths[s] samples (NULL: n_samples
+ * each; HOST memory either way); search: HOST memory, one per stream.  Arguments are checked before any GPU work:
+ * AF_ERR_INVALID_ARGUMENT for a null pointer, n_streams outside 1..max_streams, n_samples outside 1..max_record_samples,
+ * stride < n_samples, a length outside 0..n_samples, a search value that is not finite.  Both return when the kernels have been
+ * enqueued; _analyze_device keeps no reference to the recordings after they have run. */
+int af_latency_analyze_host(af_latency *h, const float *recorded, int64_t n_samples, int64_t stride, int32_t n_streams,
+                            const int64_t *lengths, const af_latency_search *search);
+int af_latency_analyze_device(af_latency *h, const float *d_recorded, int64_t n_samples, int64_t stride, int32_t n_streams,
+                              const int64_t *lengths, const af_latency_search *search);
+/* Waits for the last analysis and folds each stream's record into its result.  AF_ERR_STATE before the first analysis. */
+int af_latency_read_results(af_latency *h, af_latency_result *out, int32_t n_streams);
+/* Diagnostics of one stream of the last analysis.  which = 0: the whole-probe search; 1 + k: the window of burst k.
+ * *lag_lo and *count: the lags scored; scores, window_energy: [*count] (NULL: not wanted); phat: the PHAT correlation at the
+ * lags *phat_lo .. *phat_lo + *phat_count - 1 of burst k's window (which >= 1 only).  capacity: what each array holds;
+ * AF_ERR_INVALID_ARGUMENT when it is too small (the counts are still returned). */
+int af_latency_read_scores(af_latency *h, int32_t stream, int32_t which, int32_t *lag_lo, int32_t *count, double *scores,
+                           double *window_energy, int32_t *phat_lo, int32_t *phat_count, double *phat, int64_t capacity);
+/* The span of the last analysis and, when pass_ms is not NULL, its AF_LATENCY_PASSES parts. */
+int af_latency_last_kernel_ms(af_latency *h, double *ms, double *pass_ms);
+const char *af_latency_message_text(int32_t exit_code, int32_t message); /* VALUE: NULL for unknown indices */
+/* Test hook: the forward real transform of the PHAT pass alone.  x: HOST memory, n_real float32, n_real a power of two in
+ * 2^9..AF_LATENCY_MAX_TRANSFORM; out: HOST memory, n_real / 2 + 1 (re, im) pairs.  Up to 2^14 real points it is the
+ * one-workgroup LDS form, above that the four-step form. */
+int af_latency_debug_rfft(af_latency *h, const float *x, int64_t n_real, double *out);
+
 /* ---- NoiseSuppressor: rust-core/src/dsp/noise_suppressor.rs:18-194 ----------------------------------------
  * The runtime-selected suppressor interface (`NoiseModel`, trait `NoiseSuppressor`, `new_noise_suppression_engine`) for a
  * batch of streams that advance in lock step: sample counts are per stream, audio is [stream][stride] host memory, the
