@@ -432,8 +432,8 @@ int ensure_started(af_engine *e) {
     AF_HIP(e->d_params_pre.reserve_exact(sizeof(af::ChainParams)));
     AF_HIP(e->d_params_de.reserve_exact(sizeof(af::ChainParams)));
     if (!e->d_status) {
-      AF_HIP(e->d_status.reserve_exact(sizeof(int32_t)));
-      AF_HIP(e->d_status.keep_if(hipMemset(e->d_status, 0, sizeof(int32_t))));
+      AF_HIP(e->d_status.reserve_exact(sizeof(int32_t) * af::kStatusWords));  // (LaunchArgs::status)
+      AF_HIP(e->d_status.keep_if(hipMemset(e->d_status, 0, sizeof(int32_t) * af::kStatusWords)));
     }
     int rc = upload_initial_state(e);
     if (rc) return rc;
@@ -2063,6 +2063,17 @@ int af_engine_set_ring_variant(af_engine *e, int32_t waves, int32_t chunk) {
   return AF_OK;
 }
 int af_engine_last_kernel(const af_engine *e) { return e ? e->last_kernel_used : 0; }
+int af_engine_debug_detector_reuse_chunks(af_engine *e, uint64_t *chunks) {
+  if (!e || !chunks) return fail(AF_ERR_INVALID_ARGUMENT, "null argument");
+  *chunks = 0;
+  if (!e->d_status) return AF_OK;  // nothing has run yet
+  AF_HIP(e->use_device());
+  AF_HIP(hipDeviceSynchronize());
+  unsigned long long n = 0;
+  AF_HIP(hipMemcpy(&n, e->d_status.get() + af::kStatusReuseWord, sizeof n, hipMemcpyDeviceToHost));
+  *chunks = (uint64_t)n;
+  return AF_OK;
+}
 int af_engine_set_timing_enabled(af_engine *e, int32_t on) {
   if (!e) return fail(AF_ERR_INVALID_ARGUMENT, "engine is null");
   e->timing = on != 0;

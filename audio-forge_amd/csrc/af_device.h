@@ -164,6 +164,7 @@ struct BlockStats {
   float makeup_gain_db, makeup_activity, makeup_reliability, pad;  // compressor metering at block end
 };
 
+constexpr int kStatusWords = 4, kStatusReuseWord = 2;
 struct LaunchArgs {
   const ChainParams *params;  // device; an array when `group_preset` is set
   const int32_t *group_preset;  // device, [ceil(n_streams / 64)]: the parameter block of each 64-stream group, or null (all use [0])
@@ -172,7 +173,10 @@ struct LaunchArgs {
   const float *in;
   float *out;
   BlockStats *stats;          // [blocks][n_streams]
-  int32_t *status;            // device word: non-zero when a kernel gave up on a token (never expected)
+  int32_t *status;            // device words (kStatusWords of them) or null.  [0]: non-zero when a kernel gave up on a token (never
+                              // expected).  [kStatusReuseWord], read as one 64-bit word (test tap): the token ring adds the chunks whose
+                              // output detector took the input observer's maxima instead of running its own FIR.  (One pointer for
+                              // both: a second one, alive to the end of the ring kernel, costs it scalar registers it does not have.)
   const BlockStats *pre_stats;  // rows of the pre-pass launch (compressor-input block power), or null
   const double *pre_power;    // [blocks][n_streams] the same block power as a plain array (af_eq_systolic.hip as the pre-pass); wins over pre_stats
   const double *vad_prob;     // [blocks][n_streams] speech posteriors for auto-makeup, or null

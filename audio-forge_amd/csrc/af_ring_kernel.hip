@@ -33,6 +33,24 @@ namespace af {
 constexpr int kTpRing = 128;  // rows of the shared true-peak input/output rings (power of two)
 constexpr int kEqGroup = 5;   // biquad sections per token
 constexpr int kMaxEqGroups = kMaxEqSections / kEqGroup;
+// The output detector's FIR, skipped where it repeats the input observer's (chunks of 4 only: kTpDelay is then 5 chunks exactly).
+// The detector's ring holds Tpo[n] = clamp(Tpi[n - kTpDelay] * g[n]).  While the true-peak gain is exactly 1 and the clamp idle,
+// Tpo[n] has the bits of Tpi[n - kTpDelay]; once that has held for every sample of the detector's window (kTpTaps samples back
+// from the chunk's last: the chunk and the kDetCleanChunks - 1 before it) the detector would run the same function on the same
+// bits as the observer did kTpDelay samples earlier, so the chunk's output true peak IS the maximum of the observer's values of
+// chunk q - kDetDelayChunks.  -DAF_NO_DETECTOR_REUSE builds without (A/B).
+constexpr int kDetDelayChunks = kTpDelay / 4;
+constexpr int kDetCleanChunks = (kTpTaps - 1 + 3) / 4 + 1;  // 9: chunks q - 8 .. q cover samples n0 - 32 .. n0 + 3
+constexpr float kDetCleanCap = 15.0f;
+// Ring of the observer's chunk maxima, row q % kItpMaxRing.  Chunk q reads row q - kDetDelayChunks after its true-peak
+// token and before its final fold; that row is next written by chunk q - kDetDelayChunks + kItpMaxRing.  The wave of
+// that chunk ran chunk q - kDetDelayChunks + kItpMaxRing - kRingWaves just before, to its end, final fold included; the fold is
+// first come first served, so if that earlier chunk is q or a later one, q has folded -- and read -- already.  Hence
+// kItpMaxRing >= kRingWaves + kDetDelayChunks (21 for 16 waves).  24 rows = 6 KB and not 32: with a 2 ms lookahead and a coefficient
+// crossfade pending on ten EQ sections the layout has 7 424 bytes to spare of a CU's 160 KB, and must go on fitting.
+constexpr int kItpMaxRing = 24;
+static_assert(kTpDelay % 4 == 0 && kDetCleanChunks == 9 && kDetCleanCap >= kDetCleanChunks,
+              "detector reuse: delay in whole chunks, clean run within its cap");
 
 // tokens
 enum : int { kTokIn = 0, kTokCompA, kTokCompC, kTokCompE, kTokMeter, kTokLim, kTokTp, kTokFin, kTokEq0, kNumTokens = kTokEq0 + kMaxEqGroups };
@@ -52,10 +70,13 @@ enum : int {
 // LDS rows, f32 plane (each row = 64 floats)
 enum : int {
   kR32DcX1 = 0, kR32DcY1, kR32TpGain, kR32LimPrefix, kR32InPeak, kR32OutPeak, kR32TpInPeak, kR32OutTp,
-  kR32TpGmin, kR32TpLimited, kR32NonFinite, kR32Pad,
+  kR32TpGmin, kR32TpLimited, kR32NonFinite,
+  kR32TpClean,                 // true-peak unit: chunks in a row (capped) whose output had the bits of its delayed input; 0 at every launch, never saved
+  kR32ReuseCount,              // (test tap, as integers) chunks of this launch that took the detector's reuse path: every lane counts them all
   kR32Tpi,                     // kTpRing rows
   kR32Tpo = kR32Tpi + kTpRing, // kTpRing rows
-  kR32LimRing = kR32Tpo + kTpRing  // 2*W rows
+  kR32ItpMax = kR32Tpo + kTpRing,  // kItpMaxRing rows
+  kR32LimRing = kR32ItpMax + kItpMaxRing  // 2*W rows
 };
 
 __host__ __device__ inline size_t ring_lds_bytes(int n_sections, int lookahead, bool crossfade) {
@@ -267,6 +288,8 @@ __global__ __launch_bounds__(kRingWaves *kLanes) void chain_ring_kernel(LaunchAr
       L32(kR32TpGmin) = 1.0f;
       L32(kR32TpLimited) = 0.0f;
       L32(kR32NonFinite) = 0.0f;
+      L32(kR32TpClean) = 0.0f;
+      L32(kR32ReuseCount) = 0.0f;
     }
     // history rows: state row r holds sample n0-32+r
     for (int r = wave; r < kTpTaps; r += kRingWaves) {
@@ -290,6 +313,15 @@ __global__ __launch_bounds__(kRingWaves *kLanes) void chain_ring_kernel(LaunchAr
 
   constexpr int64_t kAllReady = 0x7fffffffffffffffLL;
   int64_t ready_seen = a.ready ? 0 : kAllReady;  // (wave-uniform)
+#ifdef AF_NO_DETECTOR_REUSE
+  constexpr bool kDetReuse = false;
+#else
+  constexpr bool kDetReuse = kChunk == 4;
+  static_assert(!kDetReuse || kItpMaxRing >= kRingWaves + kDetDelayChunks, "a row of chunk maxima is read before its next writer starts");
+#endif
+  // (a launch reuses only if it runs the observer, i.e. the limiter, and the detector; spelled out at each use: one more
+  // wave-uniform value alive through the chunk loop is one more scalar register spilled)
+#define AF_DET_REUSE (kDetReuse && out_detector && (flags & kFlagLimiter) != 0)
   for (int64_t q64 = wave; q64 < Q; q64 += kRingWaves) {
     const int q = (int)q64;
     const int64_t b = q64 / cpb;
@@ -865,9 +897,18 @@ __global__ __launch_bounds__(kRingWaves *kLanes) void chain_ring_kernel(LaunchAr
             itp[k] = tp_observe_ring(&l32[kR32Tpi * kLanes], nb + k, lane);
             AF_PIN(8, itp[k]);
           }
+        // the chunk's maximum for the detector of chunk q + kDetDelayChunks (folded as the detector folds its own values); the
+        // store precedes this chunk's true-peak token_pass, the read follows the reader's token_wait of the same token
+        if (kFull && AF_DET_REUSE) {
+          float m = 0.0f;
+  #pragma unroll
+          for (int k = 0; k < kChunk; ++k) m = fmaxf(m, itp[k]);
+          L32(kR32ItpMax + q % kItpMaxRing) = m;
+        }
       }
 
       // ---- token: true-peak gain (true_peak.rs:341-374), chain output, block output stats
+      float clean_run = 0.0f;  // chunks up to this one, in a row, that left the true-peak unit with the bits of its delayed input
       if (!comp_only) {
       token_wait(turn, kTokTp, q);
       {
@@ -876,6 +917,7 @@ __global__ __launch_bounds__(kRingWaves *kLanes) void chain_ring_kernel(LaunchAr
         float nonfinite = first_in_block ? 0.0f : L32(kR32NonFinite);
         float tp_in_peak = 0.0f, tp_gmin = 1.0f, tp_limited = 0.0f;
         if (flags & kFlagLimiter) {
+          unsigned changed = kFull ? 0u : 1u;  // bits in which an output differs from its delayed input (a lane mask held as a bool is a scalar pair)
           float g = L32(kR32TpGain);
           tp_in_peak = first_in_block ? 0.0f : L32(kR32TpInPeak);
           tp_gmin = first_in_block ? 1.0f : L32(kR32TpGmin);
@@ -898,7 +940,12 @@ __global__ __launch_bounds__(kRingWaves *kLanes) void chain_ring_kernel(LaunchAr
               float o = fclamp(delayed * g, -tp_ceiling, tp_ceiling);
               if (!finite_f32(o)) o = 0.0f;
               x[k] = o;
+              if (kDetReuse) changed |= __float_as_uint(o) ^ __float_as_uint(delayed);  // (o is finite here, so equal bits mean a finite value)
             }
+          if (kDetReuse) {
+            clean_run = changed == 0u ? fminf(L32(kR32TpClean) + 1.0f, kDetCleanCap) : 0.0f;
+            L32(kR32TpClean) = clean_run;
+          }
           L32(kR32TpGain) = g;
           L32(kR32TpInPeak) = tp_in_peak;
           L32(kR32TpGmin) = tp_gmin;
@@ -955,7 +1002,13 @@ __global__ __launch_bounds__(kRingWaves *kLanes) void chain_ring_kernel(LaunchAr
           }
       }
       float otp = 0.0f;
-      if (out_detector) {
+      if (kFull && AF_DET_REUSE && __builtin_amdgcn_ballot_w64(clean_run < (float)kDetCleanChunks) == 0) {
+        // every stream of the wave: the detector's window has the bits of the observer's window kTpDelay samples earlier
+        // (q >= kDetCleanChunks - 1 here: the clean run starts at 0 in every launch)
+        otp = L32(kR32ItpMax + (q - kDetDelayChunks) % kItpMaxRing);
+        atomicAdd(reinterpret_cast<unsigned *>(&L32(kR32ReuseCount)), 1u);  // (test tap; per lane: no mask, no scalar kept)
+        AF_PIN(16, otp);
+      } else if (out_detector) {
   #pragma unroll
         for (int k = 0; k < kChunk; ++k)
           if (kFull || k < len) otp = fmaxf(otp, tp_observe_ring(&l32[kR32Tpo * kLanes], nb + k, lane));
@@ -979,7 +1032,11 @@ __global__ __launch_bounds__(kRingWaves *kLanes) void chain_ring_kernel(LaunchAr
     else chunk_body(std::false_type{});
   }
   __syncthreads();
-  if (tid == 0 && turn[kAbortSlot] != 0 && a.status) atomicExch(a.status, 1);
+  if (tid == 0 && a.status) {
+    if (turn[kAbortSlot] != 0) atomicExch(a.status, 1);
+    const unsigned reused = *reinterpret_cast<const unsigned *>(&L32(kR32ReuseCount));
+    if (kDetReuse && reused != 0) atomicAdd(reinterpret_cast<unsigned long long *>(a.status + kStatusReuseWord), (unsigned long long)reused);
+  }
 #ifdef AF_TOKEN_PROFILE
   if (tid == 0 && blockIdx.x == 0 && Q > 0) {
     const long long ticks = clock64() - prof_k0, wall = wall_clock64() - prof_w0;  // shader cycles; 100 MHz constant clock
@@ -1073,6 +1130,7 @@ __global__ __launch_bounds__(kRingWaves *kLanes) void chain_ring_kernel(LaunchAr
   }
 #undef L64
 #undef L32
+#undef AF_DET_REUSE
 }
 
 size_t ring_kernel_dynamic_lds(int n_sections, int lookahead_samples, bool crossfade) {

@@ -435,6 +435,7 @@ SIGNATURES = {
     "af_engine_last_chain_launch_ms": (C.c_int, [_vp, _dp, _dp, C.POINTER(_i32)]),
     # product resampler
     "af_engine_last_kernel": (C.c_int, [_vp]),
+    "af_engine_debug_detector_reuse_chunks": (C.c_int, [_vp, C.POINTER(C.c_uint64)]),
     "af_resampler_calculate_cutoff": (C.c_int, [_i32, _i32, C.POINTER(C.c_float)]),
     "af_resampler_create": (C.c_int, [C.c_uint32, C.c_uint32, _i64, _i32, _i32, _i32, C.POINTER(_vp)]),
     "af_resampler_destroy": (None, [_vp]),

@@ -380,6 +380,13 @@ class Engine:
             _lib.check(self._lib.af_engine_read_block_stats(self._h, rows.ctypes.data_as(C.POINTER(BlockStats)), rows.size))
         return rows
 
+    def debug_detector_reuse_chunks(self) -> int:
+        """Test tap: chunks (summed over 64-stream groups and token-ring launches so far) whose output true-peak detector took
+        the input observer's maxima instead of running its own FIR."""
+        n = C.c_uint64(0)
+        _lib.check(self._lib.af_engine_debug_detector_reuse_chunks(self._h, C.byref(n)))
+        return int(n.value)
+
     def last_kernel_ms(self) -> tuple[float, int]:
         ms, launches = C.c_double(0.0), C.c_int32(0)
         _lib.check(self._lib.af_engine_last_kernel_ms(self._h, C.byref(ms), C.byref(launches)))

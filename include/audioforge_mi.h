@@ -362,6 +362,9 @@ int af_engine_assign_presets(af_engine *e, const int32_t *preset_of_group, int32
 int af_engine_set_kernel(af_engine *e, int32_t kernel);
 /* AF_KERNEL_* the most recent chain launch used; VALUE, not a status */
 int af_engine_last_kernel(const af_engine *e);
+/* test tap (synchronises): chunks, summed over the 64-stream groups of every token-ring launch of this engine so far, whose
+ * output true-peak detector reused the maxima of the input observer instead of running its own FIR (same bits either way) */
+int af_engine_debug_detector_reuse_chunks(af_engine *e, uint64_t *chunks);
 /* tuning of the token-ring kernel: wavefronts per 64-stream group and samples per chunk
  * (built: 16x4, 16x2, 12x4, 12x2, 8x4, 8x2; 0,0 = default) */
 int af_engine_set_ring_variant(af_engine *e, int32_t waves, int32_t chunk);
