@@ -20,6 +20,7 @@
 #include "af_resampler_host.hpp"
 #include "af_retune.h"
 #include "af_stages.h"
+#include "af_stream_state_host.hpp"
 #include "af_suppressor_host.hpp"
 #include "af_switches.hpp"
 
@@ -227,6 +228,9 @@ struct af_engine {
   int dyn_pending_row = 0;            // first of the 15 plane rows behind every kernel's own (allocated with live control on), or 0
   af::DeviceBuffer<af::ChainParams> d_retune;  // the op list on the device, in parameter-block units (it travels through stage_upload)
   af::TimedSpan retune_span;          // around the last call's launch of the retune kernel, if it made one with timing on
+  // Per-stream lifecycle (af_engine_set_stream_lifecycle): restart, export and import of single streams between calls
+  // (af_stream_state.h).  With the switch on the engine never runs the stage pipeline, whose rings are the histories.
+  af::sstate::Lifecycle life;
 
   af_engine(double fs, int n, int dev) : proto(fs), n_streams(n), device(dev), sample_rate(fs) {}
   ~af_engine();
@@ -328,25 +332,60 @@ const af::ChainProto &preset_proto(const af_engine *e, int k) { return k == 0 ? 
 af::ChainParams &preset_params(af_engine *e, int k) { return k == 0 ? e->host_params : e->extra_presets[k - 1].host_params; }
 int preset_of_stream(const af_engine *e, int64_t s) { return e->group_preset.empty() ? 0 : e->group_preset[s / 64]; }
 
+// the loudness-meter rows preset k's streams own (0 without auto-makeup)
+int preset_meter_slots(af_engine *e, int k) {
+  const af::ChainProto &p = preset_proto(e, k);
+  return (p.compressor_enabled && p.compressor.auto_makeup_enabled) ? preset_params(e, k).comp.meter_slots : 0;
+}
+
+// The height of the two state planes: the tallest preset's rows, and with live control 3 x 5 more f64 rows for each stream's
+// pending dynamic-EQ coefficients (af_device.h, dyn_pending_row) behind every row a kernel addresses by itself (*first_live,
+// else 0).  Reads the parameter blocks export_params wrote.
+void plane_heights(af_engine *e, int *n64_out, int *n32_out, int *first_live) {
+  const int n_presets = 1 + (int)e->extra_presets.size();
+  int n64 = 0, n32 = 0;
+  for (int k = 0; k < n_presets; ++k) {
+    n64 = std::max(n64, af::f64_field_count(preset_params(e, k).n_eq_sections, preset_meter_slots(e, k)));
+    n32 = std::max(n32, af::f32_field_count(preset_proto(e, k).limiter.lookahead_samples));
+  }
+  *first_live = 0;
+  if (e->live_control) {
+    *first_live = n64;
+    n64 += 15;
+  }
+  *n64_out = n64;
+  *n32_out = n32;
+}
+
+// The column a stream of preset k starts from: its prototype's values in the rows that do not start at zero.  `v64` / `v32`
+// hold at least kF64Fixed / kF32Fixed zeros.  (upload_initial_state for every stream, af_engine_restart_streams for some.)
+void initial_rows(af_engine *e, int k, double *v64, float *v32) {
+  const af::CompressorProto &c = preset_proto(e, k).compressor;
+  v64[af::kCompPeakEnvDb] = -120.0;
+  v64[af::kCompGr] = c.current_gain_reduction_db;
+  v64[af::kCompFastEnv] = c.fast_release_env_db;
+  v64[af::kCompSlowEnv] = c.slow_release_env_db;
+  v64[af::kCompCurReleaseMs] = c.current_release_ms;
+  v64[af::kCompTargetReleaseMs] = c.target_release_ms;
+  // compressor.rs:760-761: release_coeff is tc(current_release_ms) from the first sample on
+  v64[af::kCompReleaseCoeff] = af::time_constant_to_coeff(c.current_release_ms, c.sample_rate);
+  v64[af::kCompSmoothedMakeup] = c.smoothed_makeup_gain;
+  v64[af::kCompCurrentLufs] = -100.0;
+  v64[af::kLimGain] = 1.0;
+  for (int i = 0; i < 3; ++i) {  // the dynamic EQ's coefficients are per-stream state (deesser.rs:536-538)
+    const af::BiquadCoef &bc = preset_params(e, k).deesser.bands[i].dynamic_eq.active;
+    double *d = &v64[af::kDeBand0 + i * af::kDeBandStride + 6];
+    d[0] = bc.b0; d[1] = bc.b1; d[2] = bc.b2; d[3] = bc.a1; d[4] = bc.a2;
+  }
+  v32[af::kTpGain] = 1.0f;
+}
+
 // ... and the initial per-stream state planes.
 int upload_initial_state(af_engine *e) {
   const int64_t B = e->n_streams;
   const int n_presets = 1 + (int)e->extra_presets.size();
   int n64 = 0, n32 = 0;
-  for (int k = 0; k < n_presets; ++k) {
-    const af::ChainProto &p = preset_proto(e, k);
-    const af::ChainParams &hp = preset_params(e, k);
-    const int meter_slots = (p.compressor_enabled && p.compressor.auto_makeup_enabled) ? hp.comp.meter_slots : 0;
-    n64 = std::max(n64, af::f64_field_count(hp.n_eq_sections, meter_slots));
-    n32 = std::max(n32, af::f32_field_count(p.limiter.lookahead_samples));
-  }
-  // live control: 3 x 5 more rows for each stream's pending dynamic-EQ coefficients (af_device.h, dyn_pending_row), behind
-  // every row a kernel addresses by itself
-  e->dyn_pending_row = 0;
-  if (e->live_control) {
-    e->dyn_pending_row = n64;
-    n64 += 15;
-  }
+  plane_heights(e, &n64, &n32, &e->dyn_pending_row);
   if (n64 != e->n_f64 || n32 != e->n_f32) {
     e->d_st64.release();
     e->d_st32.release();
@@ -358,28 +397,7 @@ int upload_initial_state(af_engine *e) {
   // every stream starts from its preset's prototype
   std::vector<std::vector<double>> v64s(n_presets, std::vector<double>(n64, 0.0));
   std::vector<std::vector<float>> v32s(n_presets, std::vector<float>(n32, 0.0f));
-  for (int k = 0; k < n_presets; ++k) {
-    std::vector<double> &v64 = v64s[k];
-    std::vector<float> &v32 = v32s[k];
-    const af::CompressorProto &c = preset_proto(e, k).compressor;
-    v64[af::kCompPeakEnvDb] = -120.0;
-    v64[af::kCompGr] = c.current_gain_reduction_db;
-    v64[af::kCompFastEnv] = c.fast_release_env_db;
-    v64[af::kCompSlowEnv] = c.slow_release_env_db;
-    v64[af::kCompCurReleaseMs] = c.current_release_ms;
-    v64[af::kCompTargetReleaseMs] = c.target_release_ms;
-    // compressor.rs:760-761: release_coeff is tc(current_release_ms) from the first sample on
-    v64[af::kCompReleaseCoeff] = af::time_constant_to_coeff(c.current_release_ms, c.sample_rate);
-    v64[af::kCompSmoothedMakeup] = c.smoothed_makeup_gain;
-    v64[af::kCompCurrentLufs] = -100.0;
-    v64[af::kLimGain] = 1.0;
-    for (int i = 0; i < 3; ++i) {  // the dynamic EQ's coefficients are per-stream state (deesser.rs:536-538)
-      const af::BiquadCoef &bc = preset_params(e, k).deesser.bands[i].dynamic_eq.active;
-      double *d = &v64[af::kDeBand0 + i * af::kDeBandStride + 6];
-      d[0] = bc.b0; d[1] = bc.b1; d[2] = bc.b2; d[3] = bc.a1; d[4] = bc.a2;
-    }
-    v32[af::kTpGain] = 1.0f;
-  }
+  for (int k = 0; k < n_presets; ++k) initial_rows(e, k, v64s[k].data(), v32s[k].data());
   std::vector<double> plane64((size_t)n64 * B);
   std::vector<float> plane32((size_t)n32 * B);
   for (int64_t st = 0; st < B; ++st) {
@@ -393,6 +411,9 @@ int upload_initial_state(af_engine *e) {
 }
 
 int ensure_started(af_engine *e) {
+  if (!e->started && e->life.enabled && e->kernel == AF_KERNEL_STAGED)  // (refused before the device is touched)
+    return fail(AF_ERR_UNSUPPORTED, "the stage pipeline keeps the streams' histories in its hand-over rings, which the per-stream "
+                                    "lifecycle cannot restart, export or import: AF_KERNEL_STAGED with af_engine_set_stream_lifecycle on");
   AF_HIP(e->use_device());
   if (!e->started) {
     export_params(e);
@@ -446,6 +467,7 @@ int ensure_started(af_engine *e) {
     e->started = true;
     e->samples_processed = 0;
     e->pending = 0;
+    e->life.clear();
   }
   return AF_OK;
 }
@@ -1460,6 +1482,7 @@ int af_engine_reset(af_engine *e) {
   }
   e->live_retuned.clear();
   e->live_cuts.clear();
+  e->life.clear();  // every stream restarts with the engine (the switch is kept)
   if (e->d_gate) {  // NoiseGate::reset, gate.rs:759-785: every state field back to its initial value
     AF_HIP(e->use_device());
     AF_HIP(hipMemset(e->d_gate, 0, sizeof(int64_t) * af::kGateFields * e->n_streams));
@@ -2650,7 +2673,8 @@ static int process_device_impl(af_engine *e, const float *in, float *out, int64_
     // (and several presets with auto-makeup: the token-ring kernel's pre-pass pair is a single-preset build)
     const bool deesser_staged = (probe.flags & af::kFlagDeesser) != 0 ||
                                 (!e->extra_presets.empty() && (probe.flags & af::kFlagCompressor) && probe.comp.auto_makeup_enabled);
-    e->pipe.active = serves && (e->kernel == AF_KERNEL_STAGED || (e->kernel == AF_KERNEL_AUTO && env_staged != 0 &&
+    // (the per-stream lifecycle keeps AUTO off the pipeline, whose rings are the histories: the forms above its stream limit serve)
+    e->pipe.active = serves && !e->life.enabled && (e->kernel == AF_KERNEL_STAGED || (e->kernel == AF_KERNEL_AUTO && env_staged != 0 &&
                                  (deesser_staged || e->n_streams <= (e->supp.enabled ? kStagedAutoMaxStreamsBehindSuppressor : kStagedAutoMaxStreams))) ||
                                 (e->kernel == AF_KERNEL_AUTO && env_staged > 0));
     e->pipe.decided = true;
@@ -3175,6 +3199,238 @@ int af_engine_last_chain_launch_ms(af_engine *e, double *first_ms, double *tail_
     AF_HIP(span.elapsed_ms(&ms));
     *first_ms += ms;
   }
+  return AF_OK;
+}
+
+// ---- per-stream lifecycle: restart, export and import of single streams between calls (af_stream_state.h) ----------------
+int af_engine_set_stream_lifecycle(af_engine *e, int32_t enabled) {
+  if (int rc = require_config(e)) return rc;
+  e->life.enabled = enabled != 0;
+  return AF_OK;
+}
+
+namespace {
+namespace ss = af::sstate;
+
+// the shape record of a slot of preset k.  Before streaming started (af_engine_stream_state_size) the planes' heights are
+// what the first call would allocate, and the gate plane exists if the gate is on.
+ss::Shape lifecycle_shape(af_engine *e, int k) {
+  int n64 = e->n_f64, n32 = e->n_f32, first_live = 0;
+  if (!e->started) {
+    export_params(e);
+    plane_heights(e, &n64, &n32, &first_live);
+  }
+  const af::ChainParams &hp = preset_params(e, k);
+  ss::Shape s{};
+  s.sample_rate = e->sample_rate;
+  s.control_block = hp.control_block;
+  s.n_eq_sections = hp.n_eq_sections;
+  s.lookahead = preset_proto(e, k).limiter.lookahead_samples;
+  s.meter_slots = preset_meter_slots(e, k);
+  s.stage_flags = (hp.flags & ss::kStageMask) | (s.meter_slots > 0 ? ss::kStageAutoMakeup : 0u);
+  s.suppressor = e->supp.enabled ? 1 : 0;
+  s.gate_plane = (e->d_gate || (!e->started && e->gate_enabled)) ? 1 : 0;
+  s.live_rows = e->live_control ? 1 : 0;
+  s.rows64 = n64;
+  s.rows32 = af::kF32Fixed + (n32 - af::kF32Fixed) / 2;
+  return s;
+}
+
+// Everything that refuses a lifecycle call, in two halves: the arguments and what the engine's configuration rules out
+// (decided in configuration mode too); then not started, and what the engine's momentary state rules out.  An import checks
+// its blobs' headers between the two.  None of it needs the device, and a refused call has touched nothing.
+int lifecycle_accepts_config(af_engine *e, const char *what, const int32_t *streams, int32_t n) {
+  if (!e) return fail(AF_ERR_INVALID_ARGUMENT, "engine is null");
+  if (!e->life.enabled)
+    return fail(AF_ERR_STATE, "%s needs af_engine_set_stream_lifecycle(e, 1), a configuration setter (off by default)", what);
+  const std::string msg = ss::check_list(streams, n, e->n_streams);
+  if (!msg.empty()) return fail(AF_ERR_INVALID_ARGUMENT, "%s: %s", what, msg.c_str());
+  // objects that keep per-stream state of their own, which a blob does not carry and a restart would not reach
+  if (e->rs_in || e->rs_out)
+    return fail(AF_ERR_UNSUPPORTED, "%s: device-rate I/O is set (af_engine_set_io_sample_rates); the resamplers keep per-stream "
+                                    "histories the stream lifecycle does not cover", what);
+  if (e->mix)
+    return fail(AF_ERR_UNSUPPORTED, "%s: multichannel input is set (af_engine_set_input_channels); the mixdown keeps per-stream "
+                                    "state the stream lifecycle does not cover", what);
+  if (e->ow)
+    return fail(AF_ERR_UNSUPPORTED, "%s: the output writer is set (af_engine_set_output_writer); it keeps per-stream state the "
+                                    "stream lifecycle does not cover", what);
+  if (e->gate_vad_attached)
+    return fail(AF_ERR_UNSUPPORTED, "%s: the VAD-fused gate is attached (af_gate_set_vad_auto_gate_enabled); its controller plane "
+                                    "is not part of a stream's state blob", what);
+  if (e->kernel == AF_KERNEL_STAGED)
+    return fail(AF_ERR_UNSUPPORTED, "%s: the stage pipeline is selected; its hand-over rings hold the streams' histories", what);
+  return AF_OK;
+}
+int lifecycle_accepts_state(af_engine *e, const char *what) {
+  if (!e->started) return fail(AF_ERR_STATE, "%s: streaming has not started; a stream's lifecycle begins with the first process call", what);
+  if (e->pipe.active) return fail(AF_ERR_UNSUPPORTED, "%s: the stage pipeline is active; its hand-over rings hold the streams' histories", what);
+  if (e->pending > 0)
+    return fail(AF_ERR_UNSUPPORTED, "%s: %d samples per stream are pending in the suppressor's frame assembly, which all streams share; "
+                                    "feed whole 480-sample frames first", what, e->pending);
+  const int cb = e->host_params.control_block;
+  if (cb > 0 && e->samples_processed % cb != 0)
+    return fail(AF_ERR_UNSUPPORTED, "%s: the engine's sample count %lld is not a whole number of %d-sample control blocks", what,
+                (long long)e->samples_processed, cb);
+  for (int k = 0; k <= (int)e->extra_presets.size(); ++k) {
+    const af::ChainParams &o = preset_params(e, k);
+    bool xf = false;
+    for (int j = 0; j < o.n_eq_sections; ++j) xf = xf || o.eq[j].xf_remaining > 0;
+    if (o.flags & af::kFlagDeesser)
+      for (const af::DeEsserBandParams &b : o.deesser.bands)
+        xf = xf || b.detector_hp.xf_remaining > 0 || b.detector_lp.xf_remaining > 0 || b.dynamic_eq.xf_remaining > 0;
+    if (xf)
+      return fail(AF_ERR_UNSUPPORTED, "%s: a coefficient crossfade is in flight in preset %d; its counters are shared by the preset's "
+                                      "streams.  Process until it has ended", what, k);
+  }
+  if (!e->retune_ops.empty())
+    return fail(AF_ERR_UNSUPPORTED, "%s: %d live-control state edits are pending; they apply to every stream of their preset at the "
+                                    "next call", what, (int)e->retune_ops.size());
+  return AF_OK;
+}
+int lifecycle_accepts(af_engine *e, const char *what, const int32_t *streams, int32_t n) {
+  if (int rc = lifecycle_accepts_config(e, what, streams, n)) return rc;
+  return lifecycle_accepts_state(e, what);
+}
+
+ss::PlaneView lifecycle_view(const af_engine *e) {
+  ss::PlaneView v{};
+  v.st64 = e->d_st64;
+  v.st32 = e->d_st32;
+  v.gate = e->d_gate;
+  v.supp = e->supp.enabled ? e->supp.d_state : nullptr;
+  v.n_streams = e->n_streams;
+  v.rows64 = e->n_f64;
+  v.rows32_plane = e->n_f32;
+  v.ring_cap = (e->n_f32 - af::kF32Fixed) / 2;
+  return v;
+}
+
+void lifecycle_slots(af_engine *e, const int32_t *streams, int32_t n, std::vector<ss::Slot> &slots) {
+  slots.resize((size_t)n);
+  for (int32_t i = 0; i < n; ++i) {
+    const int k = preset_of_stream(e, streams[i]);
+    const int W = preset_proto(e, k).limiter.lookahead_samples + 1;
+    slots[(size_t)i] = ss::Slot{streams[i], k, W, (int32_t)(e->samples_processed % W)};
+  }
+}
+
+size_t round16(size_t b) { return (b + 15u) & ~(size_t)15u; }
+
+// the staging pointers of a transfer of n streams inside e->life.d_stage, the slot list behind them
+ss::TransferArgs lifecycle_transfer(af_engine *e, const ss::Shape &s, int32_t n) {
+  ss::TransferArgs a{};
+  a.v = lifecycle_view(e);
+  unsigned char *base = e->life.d_stage;
+  a.stage64 = reinterpret_cast<int64_t *>(base);
+  a.stage32 = reinterpret_cast<float *>(base + ss::stage_f32_offset(s, n));
+  a.stage_supp = s.suppressor ? reinterpret_cast<float *>(base + ss::stage_supp_offset(s, n)) : nullptr;
+  a.slots = reinterpret_cast<const ss::Slot *>(base + round16(ss::stage_bytes(s, n)));
+  a.n = n;
+  a.words64 = ss::words64(s);
+  a.rows32 = s.rows32;
+  return a;
+}
+}  // namespace
+
+int af_engine_restart_streams(af_engine *e, const int32_t *streams, int32_t n) {
+  if (int rc = lifecycle_accepts(e, "af_engine_restart_streams", streams, n)) return rc;
+  if (n == 0) return AF_OK;
+  AF_HIP(e->use_device());
+  hipStream_t stream = e->last_stream;
+  // one upload: [prototype f64 columns | slot list | prototype f32 columns], then one launch; the host waits for neither
+  const int n_presets = 1 + (int)e->extra_presets.size();
+  const size_t b64 = sizeof(double) * (size_t)n_presets * e->n_f64, bsl = sizeof(ss::Slot) * (size_t)n;
+  std::vector<unsigned char> host(round16(b64) + round16(bsl) + sizeof(float) * (size_t)n_presets * af::kF32Fixed, 0);
+  double *p64 = reinterpret_cast<double *>(host.data());
+  float *p32 = reinterpret_cast<float *>(host.data() + round16(b64) + round16(bsl));
+  for (int k = 0; k < n_presets; ++k) initial_rows(e, k, p64 + (size_t)k * e->n_f64, p32 + (size_t)k * af::kF32Fixed);
+  std::vector<ss::Slot> slots;
+  lifecycle_slots(e, streams, n, slots);
+  std::memcpy(host.data() + round16(b64), slots.data(), bsl);
+  AF_HIP(e->life.d_stage.reserve_retiring(host.size(), e->retired, stream));
+  AF_HIP(e->life.stager.upload(e->life.d_stage, host.data(), host.size(), stream));
+  ss::RestartArgs a{};
+  a.v = lifecycle_view(e);
+  a.proto64 = reinterpret_cast<const double *>(e->life.d_stage.get());
+  a.slots = reinterpret_cast<const ss::Slot *>(e->life.d_stage + round16(b64));
+  a.proto32 = reinterpret_cast<const float *>(e->life.d_stage + round16(b64) + round16(bsl));
+  a.n = n;
+  a.n_presets = n_presets;
+  AF_HIP(ss::launch_restart(a, stream));
+  for (int32_t i = 0; i < n; ++i) e->life.set_origin(streams[i], e->samples_processed, e->n_streams);
+  return AF_OK;
+}
+
+int af_engine_stream_state_size(af_engine *e, size_t *bytes) {
+  if (!e || !bytes) return fail(AF_ERR_INVALID_ARGUMENT, "null argument");
+  *bytes = ss::blob_bytes(lifecycle_shape(e, 0));  // (the size depends on the engine's planes alone, not on the slot's preset)
+  return AF_OK;
+}
+
+int af_engine_export_stream_state(af_engine *e, const int32_t *streams, int32_t n, void *blobs) {
+  if (int rc = lifecycle_accepts_config(e, "af_engine_export_stream_state", streams, n)) return rc;
+  if (n > 0 && !blobs) return fail(AF_ERR_INVALID_ARGUMENT, "af_engine_export_stream_state: blobs is null");
+  if (int rc = lifecycle_accepts_state(e, "af_engine_export_stream_state")) return rc;
+  if (n == 0) return AF_OK;
+  AF_HIP(e->use_device());
+  hipStream_t stream = e->last_stream;
+  std::vector<ss::Shape> shapes((size_t)n);
+  std::vector<int64_t> samples((size_t)n);
+  for (int32_t i = 0; i < n; ++i) {
+    shapes[(size_t)i] = lifecycle_shape(e, preset_of_stream(e, streams[i]));
+    samples[(size_t)i] = e->samples_processed - e->life.origin_of(streams[i]);
+  }
+  const ss::Shape &s = shapes[0];
+  const size_t stage = ss::stage_bytes(s, n), bsl = sizeof(ss::Slot) * (size_t)n;
+  AF_HIP(e->life.d_stage.reserve_retiring(round16(stage) + bsl, e->retired, stream));
+  std::vector<ss::Slot> slots;
+  lifecycle_slots(e, streams, n, slots);
+  AF_HIP(e->life.stager.upload(e->life.d_stage + round16(stage), slots.data(), bsl, stream));
+  AF_HIP(ss::launch_export(lifecycle_transfer(e, s, n), stream));
+  std::vector<unsigned char> host(stage);
+  AF_HIP(hipMemcpyAsync(host.data(), e->life.d_stage, stage, hipMemcpyDeviceToHost, stream));
+  AF_HIP(hipStreamSynchronize(stream));
+  ss::stage_to_blobs(host.data(), n, shapes, samples, static_cast<unsigned char *>(blobs), ss::blob_bytes(s));
+  return AF_OK;
+}
+
+int af_engine_import_stream_state(af_engine *e, const int32_t *streams, int32_t n, const void *blobs) {
+  if (int rc = lifecycle_accepts_config(e, "af_engine_import_stream_state", streams, n)) return rc;
+  if (n > 0 && !blobs) return fail(AF_ERR_INVALID_ARGUMENT, "af_engine_import_stream_state: blobs is null");
+  if (n == 0) return lifecycle_accepts_state(e, "af_engine_import_stream_state");
+  // every header against its destination slot, before anything is touched
+  const ss::Shape s0 = lifecycle_shape(e, preset_of_stream(e, streams[0]));
+  const size_t stride = ss::blob_bytes(s0);
+  const unsigned char *src = static_cast<const unsigned char *>(blobs);
+  std::vector<int64_t> samples((size_t)n);
+  for (int32_t i = 0; i < n; ++i) {
+    ss::BlobHeader h;
+    std::memcpy(&h, src + (size_t)i * stride, sizeof h);
+    const std::string msg = ss::check_header(h, lifecycle_shape(e, preset_of_stream(e, streams[i])));
+    if (!msg.empty()) return fail(AF_ERR_INVALID_ARGUMENT, "af_engine_import_stream_state: blob %d for stream %d: %s", i, streams[i], msg.c_str());
+    samples[(size_t)i] = h.samples;
+  }
+  if (int rc = lifecycle_accepts_state(e, "af_engine_import_stream_state")) return rc;
+  AF_HIP(e->use_device());
+  hipStream_t stream = e->last_stream;
+  const size_t stage = ss::stage_bytes(s0, n), bsl = sizeof(ss::Slot) * (size_t)n;
+  std::vector<unsigned char> host(round16(stage) + bsl, 0);
+  ss::blobs_to_stage(src, stride, n, s0, host.data());
+  std::vector<ss::Slot> slots;
+  lifecycle_slots(e, streams, n, slots);
+  std::memcpy(host.data() + round16(stage), slots.data(), bsl);
+  AF_HIP(e->life.d_stage.reserve_retiring(host.size(), e->retired, stream));
+  AF_HIP(e->life.stager.upload(e->life.d_stage, host.data(), host.size(), stream));
+  AF_HIP(ss::launch_import(lifecycle_transfer(e, s0, n), stream));
+  for (int32_t i = 0; i < n; ++i) e->life.set_origin(streams[i], e->samples_processed - samples[(size_t)i], e->n_streams);
+  return AF_OK;
+}
+
+int af_engine_stream_samples_processed(const af_engine *e, int32_t stream, int64_t *samples) {
+  if (!e || !samples) return fail(AF_ERR_INVALID_ARGUMENT, "null argument");
+  if (stream < 0 || stream >= e->n_streams) return fail(AF_ERR_INVALID_ARGUMENT, "stream %d out of range for %d streams", stream, e->n_streams);
+  *samples = e->samples_processed - e->life.origin_of(stream);
   return AF_OK;
 }
 

@@ -314,6 +314,12 @@ SIGNATURES = {
     "af_engine_set_live_control": (C.c_int, [_vp, _i32]),
     "af_engine_live_control_pending": (C.c_int, [_vp, C.POINTER(_i32)]),
     "af_engine_last_retune_ms": (C.c_int, [_vp, _dp]),
+    "af_engine_set_stream_lifecycle": (C.c_int, [_vp, _i32]),
+    "af_engine_restart_streams": (C.c_int, [_vp, C.POINTER(_i32), _i32]),
+    "af_engine_stream_state_size": (C.c_int, [_vp, C.POINTER(_sz)]),
+    "af_engine_export_stream_state": (C.c_int, [_vp, C.POINTER(_i32), _i32, _vp]),
+    "af_engine_import_stream_state": (C.c_int, [_vp, C.POINTER(_i32), _i32, _vp]),
+    "af_engine_stream_samples_processed": (C.c_int, [_vp, _i32, C.POINTER(_i64)]),
     "af_engine_set_deesser_enabled": (C.c_int, [_vp, _i32]),
     "af_engine_set_eq_enabled": (C.c_int, [_vp, _i32]),
     "af_engine_set_compressor_enabled": (C.c_int, [_vp, _i32]),

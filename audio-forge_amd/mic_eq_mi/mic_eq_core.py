@@ -137,6 +137,62 @@ class Engine:
         _lib.check(self._lib.af_engine_last_retune_ms(self._h, C.byref(ms)))
         return ms.value
 
+    # -- per-stream lifecycle -----------------------------------------------------
+    def set_stream_lifecycle(self, enabled: bool) -> None:
+        """Accept ``restart_streams`` / ``export_stream_state`` / ``import_stream_state`` between calls once streaming has
+        started.  A configuration setter (RuntimeError after the first call); off by default.  With it on the engine never
+        runs the stage pipeline."""
+        _lib.check(self._lib.af_engine_set_stream_lifecycle(self._h, int(bool(enabled))))
+
+    @staticmethod
+    def _stream_list(indices):
+        idx = [int(i) for i in indices]
+        return (C.c_int32 * max(len(idx), 1))(*idx), len(idx)
+
+    def stream_state_size(self) -> int:
+        """Bytes of one stream-state blob of this engine."""
+        size = C.c_size_t(0)
+        _lib.check(self._lib.af_engine_stream_state_size(self._h, C.byref(size)))
+        return size.value
+
+    def restart_streams(self, indices) -> None:
+        """The listed streams continue from a fresh engine's state (a caller left, another takes the slot); every other
+        stream is untouched.  One launch, no wait.  ValueError: duplicate or out-of-range index; NotImplementedError: the
+        engine is not at a point where single streams can be cut out (pending samples, a crossfade in flight, ...)."""
+        arr, n = self._stream_list(indices)
+        _lib.check(self._lib.af_engine_restart_streams(self._h, arr, n))
+
+    def export_stream_state(self, indices) -> list:
+        """One canonical state blob (``bytes``) per listed stream: a checkpoint, or what ``import_stream_state`` of another
+        engine of the same shape continues from bit for bit."""
+        arr, n = self._stream_list(indices)
+        size = self.stream_state_size()
+        buf = (C.c_ubyte * max(size * n, 1))()
+        _lib.check(self._lib.af_engine_export_stream_state(self._h, arr, n, C.cast(buf, C.c_void_p)))
+        raw = bytes(buf)
+        return [raw[i * size:(i + 1) * size] for i in range(n)]
+
+    def import_stream_state(self, indices, blobs) -> None:
+        """Put exported blobs into the listed slots.  ValueError, nothing touched: a blob that is not one (magic, version)
+        or whose shape record differs from the slot's; the message names the field."""
+        arr, n = self._stream_list(indices)
+        blobs = [bytes(b) for b in blobs]
+        size = self.stream_state_size()
+        if len(blobs) != n:
+            raise ValueError(f"expected {n} blobs, got {len(blobs)}")
+        for i, b in enumerate(blobs):
+            if len(b) != size:
+                raise ValueError(f"blob {i} has {len(b)} bytes, a stream state blob of this engine has {size}")
+        raw = b"".join(blobs)
+        buf = (C.c_ubyte * max(len(raw), 1)).from_buffer_copy(raw or b"\0")
+        _lib.check(self._lib.af_engine_import_stream_state(self._h, arr, n, C.cast(buf, C.c_void_p)))
+
+    def stream_samples_processed(self, stream: int) -> int:
+        """Samples the stream has run since its own (re)start; an import carries the count over."""
+        out = C.c_int64(0)
+        _lib.check(self._lib.af_engine_stream_samples_processed(self._h, int(stream), C.byref(out)))
+        return out.value
+
     # -- processing ---------------------------------------------------------------
     def process(self, audio: np.ndarray, layout: int = _lib.LAYOUT_STREAM_MAJOR) -> np.ndarray:
         """Host arrays: [n_streams, n] (stream-major) or [n, n_streams] (time-major) float32."""

@@ -129,6 +129,45 @@ int af_engine_live_control_pending(const af_engine *e, int32_t *ops);
 /* with af_engine_set_timing_enabled: device time of the last call's state-retune launch, 0 when it launched none (synchronises) */
 int af_engine_last_retune_ms(af_engine *e, double *ms);
 
+/* ---- per-stream lifecycle: restart, export and import single streams of a running engine ----------------------------
+ * In the reference every stream is its own AudioProcessor with its own reset() and lifetime.  With
+ * af_engine_set_stream_lifecycle(e, 1) (a configuration setter, off by default: with it off every call, kernel choice and
+ * bit is as without it) a started engine accepts the calls below BETWEEN process calls.  With the switch on AF_KERNEL_AUTO
+ * never selects the stage pipeline (its hand-over rings hold the histories) and takes the forms it takes above the
+ * pipeline's stream limit; an engine forced to AF_KERNEL_STAGED is refused at its first process call (AF_ERR_UNSUPPORTED).
+ *
+ * `streams` is a host array of n DISTINCT stream indices (a duplicate or an index out of range: AF_ERR_INVALID_ARGUMENT);
+ * n = 0 does nothing.  Every call is one kernel launch on the stream of the last process call; restart and import do not
+ * wait for the device, export waits for its one copy to the host.  Every stream not listed is untouched.
+ *
+ * af_engine_restart_streams: the listed streams continue from the state a fresh engine gives them -- their preset's
+ *   initial chain state, the suppressor's initial row, a zero gate row (Biquad::reset to the configured target,
+ *   NoiseGate::reset, rnnoise.rs:205-210) -- and their own sample count restarts at 0.  (The reference's reset(): where
+ *   configuration setters scheduled a coefficient crossfade -- EQ bands, de-esser cuts -- a fresh engine plays it in its
+ *   first samples; its counters belong to the preset, so a restarted stream starts at the configured target instead.)
+ * af_engine_export_stream_state: n blobs of af_engine_stream_state_size bytes each, back to back.  A blob is CANONICAL: it
+ *   does not depend on the engine's absolute sample count (the limiter's delay ring is stored oldest input first, its
+ *   block maxima are not stored), so the same stream history gives the same bytes in any engine.  It starts with a header
+ *   (magic, version, sizes, sample rate, control block, the shape of the slot's preset and of the engine's state planes,
+ *   the stream's own sample count); layout: DESIGN.md 4.24 and csrc/af_stream_state.h.
+ * af_engine_import_stream_state: each blob's header is checked against its destination slot first: a wrong magic or
+ *   version or a shape that differs gives AF_ERR_INVALID_ARGUMENT, the message names the field, and nothing is touched.
+ *   Parameter VALUES may differ between source and destination; that is the caller's business, as with live control.  The
+ *   ring is placed at this engine's phase and the maxima are recomputed, so the stream continues bit for bit.
+ * af_engine_stream_samples_processed: samples the stream has run since its own (re)start, an import carrying the count over.
+ *
+ * Refused with AF_ERR_UNSUPPORTED, nothing touched, the message naming the rule: samples pending in the suppressor's frame
+ * assembly (af_engine_pending_input), an engine sample count that is not a whole number of control blocks, a coefficient
+ * crossfade in flight in any preset, live-control edits pending, the stage pipeline active or selected, the VAD-fused gate
+ * attached, and device-rate I/O, multichannel input or the output writer set (they keep per-stream state of their own).
+ * AF_ERR_STATE: the switch is off, or streaming has not started.  All of these are decided before any device call. */
+int af_engine_set_stream_lifecycle(af_engine *e, int32_t enabled);
+int af_engine_restart_streams(af_engine *e, const int32_t *streams, int32_t n);
+int af_engine_stream_state_size(af_engine *e, size_t *bytes);  /* one blob of this engine; valid in configuration mode too */
+int af_engine_export_stream_state(af_engine *e, const int32_t *streams, int32_t n, void *blobs /* [n][bytes] host */);
+int af_engine_import_stream_state(af_engine *e, const int32_t *streams, int32_t n, const void *blobs);
+int af_engine_stream_samples_processed(const af_engine *e, int32_t stream, int64_t *samples);
+
 /* ---- chain switches: block_processor.rs:62-84 ----------------------------------- */
 int af_engine_set_deesser_enabled(af_engine *e, int32_t enabled);
 int af_engine_set_eq_enabled(af_engine *e, int32_t enabled);
