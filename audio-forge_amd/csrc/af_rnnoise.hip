@@ -32,6 +32,7 @@
 
 #include "af_dsp.h"
 #include "af_fft_consts.h"
+#include "af_pitch_coarse_map.h"
 #include "af_suppressor.h"
 #include "af_switches.hpp"
 
@@ -457,6 +458,33 @@ __device__ __forceinline__ void best_pitch_scan_wave(const float *numa, const fl
   }
 }
 
+// The same scan where only a few lags hold a correlation (the fine stage: at most ten, within +-2 of the two coarse candidates;
+// every other lag's numerator is -1 and cannot pass `num >= 0`): the lanes 0 .. 9 hold the candidates in ascending lag order --
+// lag, numerator, and the window energy the recurrence had reached AT that lag -- and one round of the selection above runs over
+// them.  Each candidate meets exactly the state the lower ones left, which is all the sequential scan would have shown it.
+__device__ __forceinline__ void best_pitch_scan_candidates(float num, float sy, int lag, int &bp0, int &bp1) {
+  float bn0 = -1, bn1 = -1, bd0 = 0, bd1 = 0;
+  bp0 = 0;
+  bp1 = 1;
+  unsigned long long todo = ~0ull;
+  for (;;) {
+    const bool pass = num >= 0.0f && num * bd1 > bn1 * sy;
+    const unsigned long long m = __ballot(pass) & todo;
+    if (m == 0) break;
+    const int k = __ffsll((long long)m) - 1;
+    const float nk = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(num), k));
+    const float sk = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(sy), k));
+    const int pk = __builtin_amdgcn_readlane(lag, k);
+    if (nk * bd0 > bn0 * sk) {
+      bn1 = bn0; bd1 = bd0; bp1 = bp0;
+      bn0 = nk; bd0 = sk; bp0 = pk;
+    } else {
+      bn1 = nk; bd1 = sk; bp1 = pk;
+    }
+    todo = k == 63 ? 0ull : ~0ull << (k + 1);
+  }
+}
+
 // ---- pitch, part 1 (everything that depends on the frame alone: 2x decimation + LPC-4 whitening, coarse and fine cross-correlation
 // search; leaves the whitened buffer and the candidate period for part 2), round 3: FOUR frames of one stream per workgroup (a wave each).  Consecutive frames' 1728-sample windows
 // overlap by 1248 samples, so the workgroup fetches the span once -- coalesced 16-byte loads, all in flight together --
@@ -465,17 +493,18 @@ __device__ __forceinline__ void best_pitch_scan_wave(const float *numa, const fl
 // span's LDS becomes the waves' scan arrays (one workgroup barrier); from there on a wave only ever synchronises with itself.
 // Arithmetic and evaluation orders are those of that removed kernel: the whitened buffers and pitch indices agreed bit for bit.
 constexpr int kPsFrames = 4;                                   // frames (waves) per workgroup
-constexpr int kPsX0 = 255;                                     // first data word of PsScan::c.x4z (17 x 15 guard words below it)
 constexpr int kPsRaw = kPitchBuf + (kPsFrames - 1) * kRnnFrame;  // samples of the shared span: 3168
-struct PsScan {  // a wave's scan arrays: the coarse stage's (d4, numa, da, syy over 147 lags), then the fine stage's (294 lags)
+struct PsScan {  // a wave's scan arrays: the coarse stage's (its two operands; numa, da, syy over 147 lags), then the fine stage's
   union {
-    // x4z: x[j] at kPsX0 + j + (j >> 4), zeros on both sides: the coarse correlation's B operand reads x[4 s + k - 16 c] for every
-    // step s and column c, 255 words below and 152 above the data for the lags that do not exist -- as zeros in memory they cost
-    // nothing, as a bounds test they were six vector instructions per matrix instruction
-    struct { float d4[kPitchBuf / 4]; float numa[152], da[152], syy[152]; float x4z[672]; } c;
-    struct { float xc[304], numa[304], da[304], syy[304]; } f;
+    // y4p, xz: the coarse correlation's operands as af_pitch_coarse_map.h lays them out -- the 4x-decimated buffer with one pad word
+    // per sixteen (the A operand's rows are 16 samples apart; da and Syy0 read the same copy), and x with its zero guards for the
+    // 15 + 16 indices a step reaches outside the frame (as zeros in memory they cost nothing, as a bounds test they were six vector
+    // instructions per matrix instruction)
+    struct { float y4p[460]; float xz[272]; float numa[152], da[152], syy[152]; } c;
+    struct { float da[304]; } f;  // the energy deltas up to the highest candidate lag; the candidates themselves live in lanes
   };
 };
+static_assert(pitch_coarse::kYWords <= 460 && pitch_coarse::kXWords <= 272 && pitch_coarse::kYLen == kPitchBuf / 4, "coarse operands");
 struct alignas(16) PitchSearch4Lds {
   float ds[kPsFrames][kPitchBuf / 2];
   union {
@@ -624,48 +653,47 @@ extern "C" __global__ __launch_bounds__(64 * kPsFrames, 4) void supp_pitchsearch
   const float *x_lp = ds + (kPitchMax >> 1);
   int best0, best1;
   {
-    // coarse: 4x decimated, 147 lags x 240 products on the matrix cores.
-    // xcorr[lag] = sum_j x[j] y[j + lag].  Write lag = 16 c + i and j = 4 s + k - 16 c: then
-    //   D[i][c] += A[i][k] B[k][c],  A[i][k] = y[4 s + k + i],  B[k][c] = x[4 s + k - 16 c] (0 outside the frame),
-    // summed over the steps s = 0..95, visits every j in ascending order for each (i, c), one fused multiply-add
-    // per term (v_mfma_f32_16x16x4_f32 accumulates its four k in order): exactly inner_prod_fma of the CPU
-    // restatement.  A zero B entry leaves the accumulator unchanged.  ~4 vector instructions per step instead of the
+    // coarse: 4x decimated, 147 lags x 240 products on the matrix cores (the index map: af_pitch_coarse_map.h).
+    // xcorr[lag] = sum_j x[j] y[j + lag].  Write lag = 16 i + c and j = 4 s + k - c: then
+    //   D[i][c] += A[i][k] B[k][c],  A[i][k] = y[4 s + k + 16 i],  B[k][c] = x[4 s + k - c] (0 outside the frame),
+    // summed over the steps s = 0..63, visits every j in ascending order for each (i, c), one fused multiply-add
+    // per term (v_mfma_f32_16x16x4_f32 accumulates its four k in order, whichever slot a j falls into): exactly inner_prod_fma of
+    // the CPU restatement.  A zero B entry leaves the accumulator unchanged.  ~4 vector instructions per step instead of the
     // 16 (and 10 LDS reads) of a lane-per-lag loop.
+    namespace cm = pitch_coarse;
     constexpr int len = kRnnWindow >> 2, mp = (kPitchMax - 3 * kPitchMin) >> 2;
-    static_assert(kPsX0 + (len - 1) + ((len - 1) >> 4) < 672 && 3 + 4 * 95 + 23 + kPsX0 < 672, "x4z holds the data and both guards");
-    for (int i = lane; i < kPsX0; i += 64) S.c.x4z[i] = 0.0f;
-    for (int i = kPsX0 + len + ((len - 1) >> 4) + lane; i < 672; i += 64) S.c.x4z[i] = 0.0f;
+    static_assert(len == cm::kLen && mp == cm::kLags && (kPitchMax >> 2) + len == cm::kYLen, "the map's shape");
+    if (lane < cm::kXGuardLo) S.c.xz[lane] = 0.0f;
+    if (lane < cm::kXGuardHi) S.c.xz[cm::kXGuardLo + len + lane] = 0.0f;
     for (int i = lane; i < kPitchBuf / 4; i += 64) {
       const float v = ds[2 * i];
-      S.c.d4[i] = v;
-      // the B operand reads x[4 s + k - 16 c]: sixteen columns 16 apart -- two banks for a whole half-wave in the plain layout
-      // (most of this kernel's 0.52 conflict / LDS-active ratio); one pad word per sixteen makes the column stride 17
+      // the A operand reads y[4 s + k + 16 i]: sixteen rows 16 apart -- two banks for a whole half-wave in the plain layout;
+      // one pad word per sixteen makes the row stride 17
+      S.c.y4p[cm::y_word(i)] = v;
       const int j = i - (kPitchMax >> 2);
-      if (j >= 0 && j < len) S.c.x4z[kPsX0 + j + (j >> 4)] = v;
+      if (j >= 0) S.c.xz[cm::kXGuardLo + j] = v;
     }
     wave_lds_fence();
     {
       typedef float v4f_ps __attribute__((ext_vector_type(4)));
       v4f_ps acc = {0.0f, 0.0f, 0.0f, 0.0f};
-      const int col = lane & 15, kq = lane >> 4;
-      const float *ap = S.c.d4 + kq + col;          // y[4 s + k + i]
-      // x[j] = x_lp[2 j] sits at kPsX0 + j + (j >> 4); j = 4 s + k - 16 c, k < 4, so j + floor(j / 16) = k - 17 c + 4 s + (s >> 2):
       // a per-lane base and a compile-time offset per step
-      const float *bp = S.c.x4z + kPsX0 + kq - 17 * col;
+      const float *ap = S.c.y4p + cm::a_base(cm::lane_k(lane), cm::lane_row(lane));
+      const float *bp = S.c.xz + cm::b_base(cm::lane_k(lane), cm::lane_row(lane));
 #pragma unroll
-      for (int st = 0; st < 96; ++st) {
-        const float av = ap[4 * st];
-        const float bv = bp[4 * st + (st >> 2)];
+      for (int st = 0; st < cm::kSteps; ++st) {
+        const float av = ap[cm::a_step(st)];
+        const float bv = bp[cm::b_step(st)];
         acc = __builtin_amdgcn_mfma_f32_16x16x4f32(av, bv, acc, 0, 0, 0);
       }
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
-        const int lag = 16 * col + kq * 4 + r;
-        if (lag < mp) {
+        const int lag = cm::out_lag(lane, r);
+        if (cm::out_row(lane, r) < cm::kRows && lag < mp) {
           const float sum = acc[r];
           const float x16 = sum * 1e-12f;
           S.c.numa[lag] = sum > 0 ? x16 * x16 : -1.0f;
-          const float ya = S.c.d4[lag + len], yb = S.c.d4[lag];
+          const float ya = S.c.y4p[cm::y_word(lag + len)], yb = S.c.y4p[cm::y_word(lag)];
           S.c.da[lag] = ya * ya - yb * yb;
         }
       }
@@ -674,7 +702,10 @@ extern "C" __global__ __launch_bounds__(64 * kPsFrames, 4) void supp_pitchsearch
     float Syy0;
     {
       float acc = 0.0f;
-      for (int i = lane; i < len; i += 64) acc = acc + S.c.d4[i] * S.c.d4[i];
+      for (int i = lane; i < len; i += 64) {
+        const float v = S.c.y4p[cm::y_word(i)];
+        acc = acc + v * v;
+      }
       Syy0 = 1.0f + wave_allsum_xor(acc);
     }
     wave_lds_fence();
@@ -683,42 +714,64 @@ extern "C" __global__ __launch_bounds__(64 * kPsFrames, 4) void supp_pitchsearch
   }
   AF_PS_STAMP(5);  // coarse scan
   wave_lds_fence();  // the coarse arrays are dead: the fine stage's take their place
+  // fine: 2x decimated, only within +-2 of the two coarse candidates (at most ten lags).  find_best_pitch over all 294 lags
+  // would find every other numerator -1, which cannot pass: the candidates alone are scanned, in ascending lag order, each with
+  // the window energy the recurrence reaches at its lag -- so the recurrence is walked from lag 0 to the highest candidate and
+  // no further, and kept at the candidates only.  Lane q holds candidate q: its lag (-1: none), correlation, numerator, energy.
+  int lag_l = -1;
+  float xc_l = 0.0f;
   {
-    // fine: 2x decimated, only within +-2 of the two coarse candidates (at most ten lags)
     constexpr int len = kRnnWindow >> 1, mp = (kPitchMax - 3 * kPitchMin) >> 1;
-    for (int i = lane; i < mp; i += 64) {
-      S.f.xc[i] = 0.0f;
-      S.f.numa[i] = -1.0f;
+    const int lo = 2 * (best0 < best1 ? best0 : best1), hi = 2 * (best0 < best1 ? best1 : best0);
+    const int last = hi + 2 < mp ? hi + 2 : mp - 1;  // the highest candidate
+    for (int i = lane; i < last; i += 64) {
       const float ya = ds[i + len], yb = ds[i];
       S.f.da[i] = ya * ya - yb * yb;
     }
-    wave_lds_fence();
-    for (int c = 0; c < 2; ++c) {
-      const int centre = 2 * (c == 0 ? best0 : best1);
-      for (int i = centre - 2; i <= centre + 2; ++i) {
-        if (i < 0 || i >= mp) continue;
-        if (c == 1) {
-          const int d0 = i - 2 * best0;
-          if (d0 <= 2 && d0 >= -2) continue;  // already done for the first candidate
-        }
-        const float v = fmaxf(-1.0f, wave_dot64_n<len>(x_lp, ds + i, lane));
-        if (lane == 0) {
-          S.f.xc[i] = v;
-          const float x16 = v * 1e-12f;
-          S.f.numa[i] = v > 0 ? x16 * x16 : -1.0f;
-        }
+    float num_l = -1.0f, sy_l = 1.0f;
+    for (int q = 0; q < 10; ++q) {
+      // candidates 0 .. 4: lo - 2 .. lo + 2; 5 .. 9: hi - 2 .. hi + 2 without those the first five hold already
+      const int i = q < 5 ? lo - 2 + q : hi - 7 + q;
+      if (i < 0 || i >= mp || (q >= 5 && i <= lo + 2)) continue;
+      const float v = fmaxf(-1.0f, wave_dot64_n<len>(x_lp, ds + i, lane));
+      if (lane == q) {
+        lag_l = i;
+        xc_l = v;
+        const float x16 = v * 1e-12f;
+        num_l = v > 0 ? x16 * x16 : -1.0f;
       }
     }
     AF_PS_STAMP(6);  // fine correlations
-    const float Syy0 = 1.0f + wave_dot64_n<len>(ds, ds, lane);
+    float Syy = 1.0f + wave_dot64_n<len>(ds, ds, lane);
     wave_lds_fence();
-    best_pitch_scan_wave<mp>(S.f.numa, S.f.da, S.f.syy, Syy0, lane, best0, best1);
+    // Syy <- max(1, Syy + da[i]), two dependent operations per lag: plain stretches up to each group of candidates, and inside a
+    // group the candidate's lane keeps the value before the step
+    int i = 0;
+    for (int g = 0; g < 2; ++g) {
+      const int start = (g == 0 ? lo : hi) - 2;
+#pragma unroll 8
+      for (; i < start; ++i) Syy = fmaxf(1.0f, Syy + S.f.da[i]);
+#pragma unroll
+      for (int q = 0; q < 5; ++q) {
+        const int c = start + q;
+        if (c < i || c >= mp) continue;  // below lag 0, or passed already: the first group's
+        if (lag_l == c) sy_l = Syy;      // (c == i: the walk stands at this candidate)
+        if (c < last) Syy = fmaxf(1.0f, Syy + S.f.da[c]);
+        i = c + 1;
+      }
+    }
+    best_pitch_scan_candidates(num_l, sy_l, lag_l, best0, best1);
   }
   int pitch_index;
   {
     int offset = 0;
     if (best0 > 0 && best0 < (max_pitch >> 1) - 1) {
-      const float pa = S.f.xc[best0 - 1], pbv = S.f.xc[best0], pc = S.f.xc[best0 + 1];
+      // xcorr[best0 - 1 .. best0 + 1]: a lag that was no candidate reads as 0
+      auto xc_at = [&](int i) {
+        const unsigned long long m = __ballot(lag_l == i);
+        return m ? __int_as_float(__builtin_amdgcn_readlane(__float_as_int(xc_l), __ffsll((long long)m) - 1)) : 0.0f;
+      };
+      const float pa = xc_at(best0 - 1), pbv = xc_at(best0), pc = xc_at(best0 + 1);
       if ((pc - pa) > .7f * (pbv - pa)) offset = 1;
       else if ((pa - pc) > .7f * (pbv - pc)) offset = -1;
     }
