@@ -63,28 +63,35 @@ static_assert(sizeof(af_block_stats) == 72, "stats row size");
 
 thread_local std::string af_last_error_text;
 
-// one more chain preset of an engine (preset 0 is af_engine::proto / host_params)
+// one chain preset of an engine: the prototype the setters edit and its flattened parameter block (export_params)
 struct af_preset {
   af::ChainProto proto;
-  af::ChainParams host_params{};
+  af::ChainParams params{};
   explicit af_preset(double fs) : proto(fs) {}
 };
 
 struct af_engine {
-  af::ChainProto proto;
-  // Presets.  An engine is N streams in groups of 64 (one chain workgroup each); every group runs one preset.  Preset 0 is
-  // `proto`; af_engine_set_preset_count adds fresh ones, the setters address the selected one, af_engine_assign_presets
-  // maps groups to presets.  The device holds the parameter blocks as an array and a group -> preset table.
-  std::vector<af_preset> extra_presets;
+  // Presets.  An engine is N streams in groups of 64 (one chain workgroup each); every group runs one preset.  The table is
+  // never empty: af_engine_set_preset_count adds fresh ones (and reallocates: base() and selected() are taken fresh at each
+  // use), the setters address the selected one, af_engine_assign_presets maps groups to presets.  The device holds the
+  // parameter blocks as an array and, with more than one preset, a group -> preset table.
+  std::vector<af_preset> presets;
   int current_preset = 0;
+  int n_presets() const { return (int)presets.size(); }
+  af_preset &base() { return presets[0]; }  // preset 0: what decides everything the presets must agree on
+  const af_preset &base() const { return presets[0]; }
+  af_preset &selected() { return presets[(size_t)current_preset]; }
+  const af_preset &selected() const { return presets[(size_t)current_preset]; }
   std::vector<int32_t> group_preset;         // [ceil(n_streams / 64)], empty = every group runs preset 0
   af::DeviceBuffer<int32_t> d_group_preset;
-  af::DeviceBuffer<af::ChainParams> d_params_multi;  // [1 + extra_presets.size()]
-  af::DeviceBuffer<af::ChainParams> d_params_eq;  // [1 + extra_presets.size()]: what the systolic EQ kernel reads (af_eq_systolic.hip)
-  std::vector<af::ChainParams> uploaded_eq;
-  int eq_params_presets = 0;
+  // The parameter blocks on the device, each beside a host copy of what it holds: a launch site hands over the blocks it is
+  // about to run on and only a change is uploaded (first launch; while a coefficient crossfade advances; a live setter).
+  // af_engine_reset invalidates all four.
+  af::Mirrored<af::ChainParams> d_params;      // [n_presets()]: what the chain kernels and the stage kernels read
+  af::Mirrored<af::ChainParams> d_params_pre;  // the pre-pass launch's variant (auto-makeup, EQ-before-de-esser)
+  af::Mirrored<af::ChainParams> d_params_de;   // the de-esser pass reads the unedited parameter block
+  af::Mirrored<af::ChainParams> d_params_eq;   // [kEqParamSlots][n_presets()]: what the systolic EQ kernel reads (af_eq_systolic.hip)
   uint64_t eq_slot_cursor = 0;               // stage pipeline with the de-esser: the next window's parameter slot
-  std::vector<af::ChainParams> uploaded_multi;
   int n_streams;
   int device;
   bool touched_device = false;  // use_device() succeeded once: there may be allocations, and the destructor has a device to wait for
@@ -99,34 +106,25 @@ struct af_engine {
   int last_launches = 0;
   int last_kernel_used = 0;  // AF_KERNEL_* of the most recent chain launch
 
-  af::ChainParams host_params{};
-  af::ChainParams uploaded{};   // what d_params currently holds
-  bool uploaded_valid = false;
-  af::DeviceBuffer<af::ChainParams> d_params;
   af::DeviceBuffer<double> d_st64;
   af::DeviceBuffer<float> d_st32;
   int n_f64 = 0, n_f32 = 0;
   af::DeviceBuffer<af::BlockStats> d_stats;
   af::DeviceBuffer<af::BlockStats> d_stats_pre;  // rows of the pre-pass launch (auto-makeup)
-  af::DeviceBuffer<af::ChainParams> d_params_pre;
-  af::ChainParams uploaded_pre{};          // what d_params_pre currently holds
-  bool uploaded_pre_valid = false;
   af::DeviceBuffer<double> d_block_power;  // [blocks][streams] of the current call: compressor-input block power written by the systolic EQ
-  // Parameter uploads go through engine-owned pinned staging slots (stage_upload): the host never waits for a stream, and
-  // a slot is only reused once the copy that read it has run.
+  // Parameter uploads go through engine-owned pinned staging slots: the host never waits for a stream, and a slot is only
+  // reused once the copy that read it has run.
   af::PinnedSlots<32> stager;  // (the stage pipeline with the de-esser uploads one block per window: the host may run this many windows ahead)
   // Device buffers that had to grow while earlier work may still read them: kept until that work has ended (an event on the
   // stream the call was made on), freed by a later call, a reset or the destructor -- growing never synchronises the device.
   af::RetireList retired;
-  hipStream_t syn_stream = nullptr;        // CU partition: pitch spectra + network + resynthesis (else the caller's stream)
-  hipStream_t fin_stream = nullptr;        // resynthesis + overlap-add of window w beside pitch spectra + network of w+1
-  hipStream_t lim_stream = nullptr;        // AF_ROLES=2: the limiter half of the chain (af_roles.hip) on CUs of its own
-  hipStream_t eq_stream = nullptr;         // the window's systolic EQ (af_eq_systolic.hip), behind its overlap-add, beside the next window's synthesis
+  // The side streams (ensure_side_streams): owned, or under AF_SERIAL_STREAMS aliases of the caller's stream.
+  af::Stream syn_stream;                   // CU partition: pitch spectra + network + resynthesis (else the caller's stream)
+  af::Stream fin_stream;                   // resynthesis + overlap-add of window w beside pitch spectra + network of w+1
+  af::Stream lim_stream;                   // AF_ROLES=2: the limiter half of the chain (af_roles.hip) on CUs of its own
+  af::Stream eq_stream;                    // the window's systolic EQ (af_eq_systolic.hip), behind its overlap-add, beside the next window's synthesis
   int partition_chain_cus = 0;             // CUs reserved for the chain stream (0 = the streams are not masked)
   af::DeviceBuffer<af::BlockStats> d_stats_de;    // rows of the de-esser pass
-  af::DeviceBuffer<af::ChainParams> d_params_de;  // the de-esser pass reads the unedited parameter block
-  af::ChainParams uploaded_de{};
-  bool uploaded_de_valid = false;
   af::DeviceBuffer<double> d_vad;          // [blocks][streams] speech posteriors for the next call
   int64_t vad_blocks = 0;
   double vad_reliability = 0.0, noise_floor_db = 0.0, live_noise_reliability = 0.0;
@@ -136,10 +134,9 @@ struct af_engine {
   af::DeviceBuffer<float> d_io;  // staging for the host entry point
   hipStream_t last_stream = nullptr;
   af::SuppressorHost supp;
-  bool borrowed_streams = false;                         // AF_SERIAL_STREAMS: the side streams alias the caller's
-  hipStream_t aux_stream = nullptr;                      // chain launches while the suppressor fills the chip
-  hipStream_t pre_stream = nullptr;                      // the suppressor's sample-serial pre-pass, two windows ahead
-  hipStream_t ana_stream = nullptr;                      // spectra + pitch, one window ahead
+  af::Stream aux_stream;                                 // chain launches while the suppressor fills the chip
+  af::Stream pre_stream;                                 // the suppressor's sample-serial pre-pass, two windows ahead
+  af::Stream ana_stream;                                 // spectra + pitch, one window ahead
   std::vector<af::Event> sync_events;
   size_t ev_cursor = 0;                                  // next free entry of sync_events within the current call
   std::vector<af::TimedSpan> chain_ms_events;  // timing brackets of the chain launches of the last call
@@ -157,7 +154,7 @@ struct af_engine {
     af::StageRings rings{};
     std::vector<af::DeviceBuffer<>> allocs;
     int64_t tw_max = 0;                    // longest window the rings were sized for
-    hipStream_t stream = nullptr;          // where the launch steps go when the suppressor's pipeline feeds the chain
+    af::Stream stream;                     // where the launch steps go when the suppressor's pipeline feeds the chain
     int64_t windows = 0;                   // windows launched since the rings were last cleared
     static constexpr int kMkSets = 4;
     af::DeviceBuffer<double> d_mk;
@@ -165,7 +162,6 @@ struct af_engine {
     static constexpr int kBpSets = 16;
     af::DeviceBuffer<double> d_bp;         // auto-makeup: block powers, written seven launch steps before they are read
     int64_t call_stride = 0;               // stream stride of the call being scheduled
-    const af::ChainParams *d_chain = nullptr;  // the parameter block(s) the stages read (an array with several presets)
     bool with_deesser = false;             // the rings include the de-esser stages'
     int32_t w_min = 1;                     // smallest lookahead + 1 over the presets
     uint32_t strip = 0;                    // chain flags another kernel has taken over (the suppressor's pre-pass)
@@ -226,13 +222,13 @@ struct af_engine {
   std::vector<char> live_retuned;     // per preset: a live setter was accepted since the last reset (the prototype follows the device)
   std::vector<char> live_cuts;        // per preset: ... one that moved the de-esser's cut frequencies (DeEsserParams::dyn_pending_row is in force)
   int dyn_pending_row = 0;            // first of the 15 plane rows behind every kernel's own (allocated with live control on), or 0
-  af::DeviceBuffer<af::ChainParams> d_retune;  // the op list on the device, in parameter-block units (it travels through stage_upload)
+  af::DeviceBuffer<af::ChainParams> d_retune;  // the op list on the device, in parameter-block units (it travels through the parameter stager)
   af::TimedSpan retune_span;          // around the last call's launch of the retune kernel, if it made one with timing on
   // Per-stream lifecycle (af_engine_set_stream_lifecycle): restart, export and import of single streams between calls
   // (af_stream_state.h).  With the switch on the engine never runs the stage pipeline, whose rings are the histories.
   af::sstate::Lifecycle life;
 
-  af_engine(double fs, int n, int dev) : proto(fs), n_streams(n), device(dev), sample_rate(fs) {}
+  af_engine(double fs, int n, int dev) : presets(1, af_preset(fs)), n_streams(n), device(dev), sample_rate(fs) {}
   ~af_engine();
   hipError_t use_device() {
     const hipError_t err = hipSetDevice(device);
@@ -247,9 +243,7 @@ af_engine::~af_engine() {
   if (touched_device) {
     (void)hipSetDevice(device);
     (void)hipDeviceSynchronize();
-    if (borrowed_streams) aux_stream = pre_stream = ana_stream = fin_stream = eq_stream = nullptr;
-    for (hipStream_t st : {pipe.stream, lim_stream, fin_stream, eq_stream, syn_stream, aux_stream, pre_stream, ana_stream})
-      if (st) (void)hipStreamDestroy(st);
+    for (af::Stream *st : {&pipe.stream, &lim_stream, &fin_stream, &eq_stream, &syn_stream, &aux_stream, &pre_stream, &ana_stream}) st->reset();
     supp.release_all();
   }
   af_stream_resampler_destroy(rs_in);
@@ -271,16 +265,6 @@ int require_config(af_engine *e) {
   e->params_dirty = true;
   return AF_OK;
 }
-
-// Copy `count` parameter blocks to the device behind everything already queued on `stream`, from a pinned engine-owned slot.
-int stage_upload(af_engine *e, af::ChainParams *dst, const af::ChainParams *src, size_t count, hipStream_t stream) {
-  AF_HIP(e->stager.upload(dst, src, sizeof(af::ChainParams) * count, stream));
-  return AF_OK;
-}
-
-// the prototype the setters address
-af::ChainProto &cur(af_engine *e) { return e->current_preset == 0 ? e->proto : e->extra_presets[e->current_preset - 1].proto; }
-const af::ChainProto &cur(const af_engine *e) { return e->current_preset == 0 ? e->proto : e->extra_presets[e->current_preset - 1].proto; }
 
 int check_band(int32_t band) {
   if (band < 0 || band >= af::kNumBands) return fail(AF_ERR_INVALID_ARGUMENT, "band index %d out of range", band);
@@ -325,28 +309,36 @@ void export_params(af_engine *e, const af::ChainProto &p, af::ChainParams &o) {
   o.tp.release_coeff = tp.release_coeff;
 }
 void export_params(af_engine *e) {
-  export_params(e, e->proto, e->host_params);
-  for (af_preset &ps : e->extra_presets) export_params(e, ps.proto, ps.host_params);
+  for (af_preset &ps : e->presets) export_params(e, ps.proto, ps.params);
 }
-const af::ChainProto &preset_proto(const af_engine *e, int k) { return k == 0 ? e->proto : e->extra_presets[k - 1].proto; }
-af::ChainParams &preset_params(af_engine *e, int k) { return k == 0 ? e->host_params : e->extra_presets[k - 1].host_params; }
+// The presets' parameter blocks as a launch runs them: `strip` = flags another kernel has taken care of (a pre-pass's front
+// end), `add` = flags that tell the kernels so.
+std::vector<af::ChainParams> run_params(const af_engine *e, uint32_t strip, uint32_t add = 0) {
+  std::vector<af::ChainParams> runs;
+  runs.reserve(e->presets.size());
+  for (const af_preset &ps : e->presets) {
+    runs.push_back(ps.params);
+    runs.back().flags = (runs.back().flags & ~strip) | add;
+  }
+  return runs;
+}
 int preset_of_stream(const af_engine *e, int64_t s) { return e->group_preset.empty() ? 0 : e->group_preset[s / 64]; }
 
 // the loudness-meter rows preset k's streams own (0 without auto-makeup)
 int preset_meter_slots(af_engine *e, int k) {
-  const af::ChainProto &p = preset_proto(e, k);
-  return (p.compressor_enabled && p.compressor.auto_makeup_enabled) ? preset_params(e, k).comp.meter_slots : 0;
+  const af::ChainProto &p = e->presets[k].proto;
+  return (p.compressor_enabled && p.compressor.auto_makeup_enabled) ? e->presets[k].params.comp.meter_slots : 0;
 }
 
 // The height of the two state planes: the tallest preset's rows, and with live control 3 x 5 more f64 rows for each stream's
 // pending dynamic-EQ coefficients (af_device.h, dyn_pending_row) behind every row a kernel addresses by itself (*first_live,
 // else 0).  Reads the parameter blocks export_params wrote.
 void plane_heights(af_engine *e, int *n64_out, int *n32_out, int *first_live) {
-  const int n_presets = 1 + (int)e->extra_presets.size();
+  const int n_presets = e->n_presets();
   int n64 = 0, n32 = 0;
   for (int k = 0; k < n_presets; ++k) {
-    n64 = std::max(n64, af::f64_field_count(preset_params(e, k).n_eq_sections, preset_meter_slots(e, k)));
-    n32 = std::max(n32, af::f32_field_count(preset_proto(e, k).limiter.lookahead_samples));
+    n64 = std::max(n64, af::f64_field_count(e->presets[k].params.n_eq_sections, preset_meter_slots(e, k)));
+    n32 = std::max(n32, af::f32_field_count(e->presets[k].proto.limiter.lookahead_samples));
   }
   *first_live = 0;
   if (e->live_control) {
@@ -360,7 +352,7 @@ void plane_heights(af_engine *e, int *n64_out, int *n32_out, int *first_live) {
 // The column a stream of preset k starts from: its prototype's values in the rows that do not start at zero.  `v64` / `v32`
 // hold at least kF64Fixed / kF32Fixed zeros.  (upload_initial_state for every stream, af_engine_restart_streams for some.)
 void initial_rows(af_engine *e, int k, double *v64, float *v32) {
-  const af::CompressorProto &c = preset_proto(e, k).compressor;
+  const af::CompressorProto &c = e->presets[k].proto.compressor;
   v64[af::kCompPeakEnvDb] = -120.0;
   v64[af::kCompGr] = c.current_gain_reduction_db;
   v64[af::kCompFastEnv] = c.fast_release_env_db;
@@ -373,7 +365,7 @@ void initial_rows(af_engine *e, int k, double *v64, float *v32) {
   v64[af::kCompCurrentLufs] = -100.0;
   v64[af::kLimGain] = 1.0;
   for (int i = 0; i < 3; ++i) {  // the dynamic EQ's coefficients are per-stream state (deesser.rs:536-538)
-    const af::BiquadCoef &bc = preset_params(e, k).deesser.bands[i].dynamic_eq.active;
+    const af::BiquadCoef &bc = e->presets[k].params.deesser.bands[i].dynamic_eq.active;
     double *d = &v64[af::kDeBand0 + i * af::kDeBandStride + 6];
     d[0] = bc.b0; d[1] = bc.b1; d[2] = bc.b2; d[3] = bc.a1; d[4] = bc.a2;
   }
@@ -383,7 +375,7 @@ void initial_rows(af_engine *e, int k, double *v64, float *v32) {
 // ... and the initial per-stream state planes.
 int upload_initial_state(af_engine *e) {
   const int64_t B = e->n_streams;
-  const int n_presets = 1 + (int)e->extra_presets.size();
+  const int n_presets = e->n_presets();
   int n64 = 0, n32 = 0;
   plane_heights(e, &n64, &n32, &e->dyn_pending_row);
   if (n64 != e->n_f64 || n32 != e->n_f32) {
@@ -419,39 +411,37 @@ int ensure_started(af_engine *e) {
     export_params(e);
     // the limiter's delay ring and suffix maxima live in LDS: kernel 3 (16 streams per workgroup) holds ~1000 samples
     // of lookahead (2 ms at 384 kHz = 768), kernels 1 and 2 (64 streams) ~127 / ~180
-    if (e->proto.limiter_enabled &&
-        af::quad_kernel_dynamic_lds(e->host_params.n_eq_sections, e->proto.limiter.lookahead_samples, true) > af::kMaxLdsBytes)
+    if (e->base().proto.limiter_enabled &&
+        af::quad_kernel_dynamic_lds(e->base().params.n_eq_sections, e->base().proto.limiter.lookahead_samples, true) > af::kMaxLdsBytes)
       return fail(AF_ERR_UNSUPPORTED, "limiter lookahead of %d samples exceeds what the LDS-resident ring holds",
-                  e->proto.limiter.lookahead_samples);
-    if (e->proto.compressor_enabled && e->proto.compressor.auto_makeup_enabled) {
-      if (e->host_params.comp.meter_slots <= 0)
+                  e->base().proto.limiter.lookahead_samples);
+    if (e->base().proto.compressor_enabled && e->base().proto.compressor.auto_makeup_enabled) {
+      if (e->base().params.comp.meter_slots <= 0)
         return fail(AF_ERR_UNSUPPORTED, "auto-makeup needs a control block that divides the 400 ms loudness window "
                                         "(e.g. 480 or 960 samples at 48 kHz) and a sample rate the meter supports");
-      if (e->host_params.control_block < 64)
+      if (e->base().params.control_block < 64)
         return fail(AF_ERR_UNSUPPORTED, "auto-makeup needs control blocks of at least 64 samples");
     }
-    if (!e->extra_presets.empty()) {
+    if (e->n_presets() > 1) {
       // several presets in one engine: the plain one-launch form of the token-ring kernel serves them (the workgroup of a
       // 64-stream group reads its own parameter block); what shapes the launch itself must agree across presets
-      for (const af_preset &ps : e->extra_presets) {
-        if (ps.host_params.control_block != e->host_params.control_block)
+      for (const af_preset &ps : e->presets) {
+        if (ps.params.control_block != e->base().params.control_block)
           return fail(AF_ERR_INVALID_ARGUMENT, "every preset of an engine must use the same control block");
-        if (ps.proto.sample_rate != e->proto.sample_rate) return fail(AF_ERR_INVALID_ARGUMENT, "presets must share the sample rate");
+        if (ps.proto.sample_rate != e->base().proto.sample_rate) return fail(AF_ERR_INVALID_ARGUMENT, "presets must share the sample rate");
       }
       if (e->kernel != AF_KERNEL_AUTO && e->kernel != AF_KERNEL_PHASED && e->kernel != AF_KERNEL_STAGED)
         return fail(AF_ERR_UNSUPPORTED, "multi-preset engines run the token-ring kernel or the stage pipeline");
       const size_t n_groups = (size_t)(e->n_streams + 63) / 64;
       if (e->group_preset.size() != n_groups) e->group_preset.assign(n_groups, 0);
       e->d_group_preset.release();
-      e->d_params_multi.release();
       AF_HIP(e->d_group_preset.reserve_exact(sizeof(int32_t) * n_groups));
       AF_HIP(hipMemcpy(e->d_group_preset, e->group_preset.data(), sizeof(int32_t) * n_groups, hipMemcpyHostToDevice));
-      AF_HIP(e->d_params_multi.reserve_exact(sizeof(af::ChainParams) * (1 + e->extra_presets.size())));
-      e->uploaded_multi.clear();
     }
-    AF_HIP(e->d_params.reserve_exact(sizeof(af::ChainParams)));
-    AF_HIP(e->d_params_pre.reserve_exact(sizeof(af::ChainParams)));
-    AF_HIP(e->d_params_de.reserve_exact(sizeof(af::ChainParams)));
+    AF_HIP(e->d_params.reserve(e->presets.size()));
+    AF_HIP(e->d_params_pre.reserve(1));
+    AF_HIP(e->d_params_de.reserve(1));
+    AF_HIP(e->d_params_eq.reserve(e->presets.size() * kEqParamSlots));  // one set of blocks per window in flight
     if (!e->d_status) {
       AF_HIP(e->d_status.reserve_exact(sizeof(int32_t) * af::kStatusWords));  // (LaunchArgs::status)
       AF_HIP(e->d_status.keep_if(hipMemset(e->d_status, 0, sizeof(int32_t) * af::kStatusWords)));
@@ -459,7 +449,7 @@ int ensure_started(af_engine *e) {
     int rc = upload_initial_state(e);
     if (rc) return rc;
     if (e->supp.enabled) {
-      if (e->proto.sample_rate != 48000.0)
+      if (e->base().proto.sample_rate != 48000.0)
         return fail(AF_ERR_INVALID_ARGUMENT, "the RNNoise suppressor runs at 48 kHz only (rnnoise.rs:3,46)");
       AF_HIP(e->supp.reset_state(e->n_streams));
     }
@@ -484,8 +474,8 @@ int check_device_status(af_engine *e) {
 
 // after a launch of n samples: advance the (stream-uniform) crossfade counters
 void advance_crossfades(af_engine *e, int64_t n) {
- for (int preset = 0; preset <= (int)e->extra_presets.size(); ++preset) {
-  af::ChainParams &o = preset_params(e, preset);
+ for (af_preset &ps : e->presets) {
+  af::ChainParams &o = ps.params;
   std::vector<af::SectionParams *> sections;
   for (int k = 0; k < o.n_eq_sections; ++k) sections.push_back(&o.eq[k]);
   if (o.flags & af::kFlagDeesser)
@@ -529,10 +519,10 @@ int setter_mode(af_engine *e, bool *live) {
 // applied to it afterwards then acts on the running filter: schedule() keeps `active` and restarts the counter.
 void live_sync_proto(af_engine *e) {
   const int k = e->current_preset;
-  e->live_retuned.resize(1 + e->extra_presets.size(), 0);
+  e->live_retuned.resize(e->presets.size(), 0);
   e->live_retuned[(size_t)k] = 1;
-  af::ChainProto &p = cur(e);
-  const af::ChainParams &o = preset_params(e, k);
+  af::ChainProto &p = e->selected().proto;
+  const af::ChainParams &o = e->selected().params;
   auto take = [](af::BiquadProto &b, const af::SectionParams &sp) {
     b.active = sp.active;
     b.pending = sp.pending;
@@ -585,9 +575,9 @@ void live_set_release(af_engine *e, const af::CompressorProto &c) {
 
 // the selected preset's parameter block follows its prototype (the next call uploads it if it changed)
 int live_commit(af_engine *e) {
-  af::ChainParams &o = preset_params(e, e->current_preset);
+  af::ChainParams &o = e->selected().params;
   const int n_before = o.n_eq_sections;
-  export_params(e, cur(e), o);
+  export_params(e, e->selected().proto, o);
   if ((size_t)e->current_preset < e->live_cuts.size() && e->live_cuts[(size_t)e->current_preset]) o.deesser.dyn_pending_row = e->dyn_pending_row;
   if (o.n_eq_sections != n_before) return fail(AF_ERR_BACKEND, "internal: a live setter changed the EQ's section count");
   return AF_OK;
@@ -598,9 +588,9 @@ int live_commit(af_engine *e) {
 int live_eq_set_band(af_engine *e, int band, const af::EqBandConfig &c) {
   if (c.filter_type < 0 || c.filter_type > 5)
     return fail(AF_ERR_INVALID_ARGUMENT, "band %d has unsupported EQ filter type id: %d", band, c.filter_type);
-  const std::string msg = af::eq_validate(c, band, cur(e).sample_rate);
+  const std::string msg = af::eq_validate(c, band, e->selected().proto.sample_rate);
   if (!msg.empty()) return fail(AF_ERR_INVALID_ARGUMENT, "%s", msg.c_str());
-  const af::EqProto &eq = cur(e).eq;
+  const af::EqProto &eq = e->selected().proto.eq;
   if (af::EqBandProto::required_sections(c) > eq.bands[band].processing_sections)
     return fail(AF_ERR_UNSUPPORTED, "band %d would need %d biquad sections and holds %d: the per-stream state planes are sized when "
                                     "streaming starts; call af_engine_reset first",
@@ -608,7 +598,7 @@ int live_eq_set_band(af_engine *e, int band, const af::EqBandConfig &c) {
   live_sync_proto(e);
   int first = 0;
   for (int b = 0; b < band; ++b) first += eq.bands[b].processing_sections;
-  cur(e).eq.set_band_config(band, c);
+  e->selected().proto.eq.set_band_config(band, c);
   for (int sct = 0; sct < eq.bands[band].processing_sections; ++sct) live_restart_section(e, af::kEqBase + 4 * (first + sct));
   return live_commit(e);
 }
@@ -623,10 +613,10 @@ int launch_pending_retune(af_engine *e, hipStream_t stream) {
   AF_HIP(e->d_retune.reserve_retiring(blocks * sizeof(af::ChainParams), e->retired, stream));
   std::vector<af::ChainParams> carrier(blocks);  // (the pinned stager moves parameter blocks: the list rides in as many as it fills)
   std::memcpy(carrier.data(), e->retune_ops.data(), bytes);
-  if (int rc = stage_upload(e, e->d_retune, carrier.data(), blocks, stream)) return rc;
+  AF_HIP(e->stager.upload(e->d_retune, carrier.data(), blocks * sizeof(af::ChainParams), stream));
   af::RetuneArgs ra{};
   ra.ops = reinterpret_cast<const af::RetuneOp *>(e->d_retune.get());
-  ra.group_preset = e->extra_presets.empty() ? nullptr : e->d_group_preset;
+  ra.group_preset = e->n_presets() == 1 ? nullptr : e->d_group_preset;
   ra.st64 = e->d_st64;
   ra.n_ops = (int32_t)e->retune_ops.size();
   ra.n_streams = e->n_streams;
@@ -671,7 +661,7 @@ void vad_gate_args(const af_engine *e, af::VadGateArgs &va) {
   const float fs32 = (float)(uint32_t)fs;  // VadAutoGate::sample_rate is a u32
   va.plane = e->d_gate_vad;
   va.dec = e->d_vad_dec;
-  va.block = e->host_params.control_block;
+  va.block = e->base().params.control_block;
   va.mode = e->gate_mode;
   va.auto_threshold = e->vad_auto_threshold ? 1 : 0;
   va.vad_threshold = e->vad_threshold;
@@ -729,7 +719,28 @@ int vad_gate_prepare(af_engine *e, int64_t blocks, hipStream_t stream, af::VadGa
 // choice holds until a reset, while the gate can be switched off between calls.
 bool front_end_in_gate_prepass(const af_engine *e) {
   if (e->supp.enabled) return false;
-  return e->gate_enabled || (e->pipe.active && (e->host_params.flags & (af::kFlagDcBlock | af::kFlagPreHighpass)));
+  return e->gate_enabled || (e->pipe.active && (e->base().params.flags & (af::kFlagDcBlock | af::kFlagPreHighpass)));
+}
+
+// What the chain launches of a segment share: the engine's planes and parameter blocks (an array beside the group -> preset
+// table exactly when there are several presets) and the segment.  A launch site sets only what its launch differs in.
+af::LaunchArgs segment_args(const af_engine *e, const float *in, float *out, af::BlockStats *stats, int64_t n_samples,
+                            int64_t stream_stride, int64_t samples_before, int32_t layout) {
+  af::LaunchArgs a{};
+  a.params = e->d_params;
+  a.group_preset = e->n_presets() > 1 ? e->d_group_preset.get() : nullptr;
+  a.st64 = e->d_st64;
+  a.st32 = e->d_st32;
+  a.in = in;
+  a.out = out;
+  a.stats = stats;
+  a.status = e->d_status;
+  a.n_samples = n_samples;
+  a.stream_stride = stream_stride;
+  a.samples_before = samples_before;
+  a.n_streams = e->n_streams;
+  a.layout = layout;
+  return a;
 }
 
 // Several presets in one engine: one launch of the token-ring kernel, the workgroup of every 64-stream group reading its
@@ -737,47 +748,27 @@ bool front_end_in_gate_prepass(const af_engine *e) {
 int launch_chain_multi(af_engine *e, uint32_t strip, uint32_t add, const float *in, float *out, int64_t n_samples,
                        int64_t stream_stride, int32_t layout, int64_t samples_before, af::BlockStats *stats, hipStream_t stream,
                        bool stats_cleared) {
-  const int n_presets = 1 + (int)e->extra_presets.size();
-  for (int k = 0; k < n_presets; ++k) {
+  for (const af_preset &ps : e->presets) {
     // (the stage pipeline runs both for several presets, when the presets agree on which stages there are: stage_pipe_serves)
-    const af::ChainParams &hp = preset_params(e, k);
+    const af::ChainParams &hp = ps.params;
     if ((hp.flags & af::kFlagDeesser) || ((hp.flags & af::kFlagCompressor) && hp.comp.auto_makeup_enabled))
       return fail(AF_ERR_UNSUPPORTED, "several presets with the de-esser or auto-makeup run on the stage pipeline only, and there every "
                                       "preset must enable the same stages (de-esser ahead of the EQ, compressor, auto-makeup, limiter)");
   }
-  std::vector<af::ChainParams> runs((size_t)n_presets);
+  const std::vector<af::ChainParams> runs = run_params(e, strip, add);
   size_t dyn = 0;  // every workgroup lays out its own preset: the launch needs the largest of the layouts
-  for (int k = 0; k < n_presets; ++k) {
-    runs[k] = preset_params(e, k);
-    runs[k].flags = (runs[k].flags & ~strip) | add;
+  for (const af::ChainParams &run : runs) {
     bool xf = false;
-    for (int j = 0; j < runs[k].n_eq_sections; ++j) xf |= runs[k].eq[j].xf_remaining > 0;
-    dyn = std::max(dyn, af::ring_kernel_dynamic_lds(runs[k].n_eq_sections, runs[k].lim.lookahead_samples, xf));
+    for (int j = 0; j < run.n_eq_sections; ++j) xf |= run.eq[j].xf_remaining > 0;
+    dyn = std::max(dyn, af::ring_kernel_dynamic_lds(run.n_eq_sections, run.lim.lookahead_samples, xf));
   }
   if (dyn > af::kMaxLdsBytes)
     return fail(AF_ERR_UNSUPPORTED, "the token-ring kernel needs more LDS than a CU has for one of the presets");
   e->last_kernel_used = AF_KERNEL_PHASED;
   const int cb = runs[0].control_block;
   const int64_t rows = ((n_samples + cb - 1) / cb) * e->n_streams;
-  if (e->uploaded_multi.size() != runs.size() ||
-      std::memcmp(e->uploaded_multi.data(), runs.data(), sizeof(af::ChainParams) * runs.size()) != 0) {
-    e->uploaded_multi = runs;  // (what the device holds; the copy itself reads a pinned slot)
-    if (int rc = stage_upload(e, e->d_params_multi, runs.data(), runs.size(), stream)) return rc;
-  }
-  af::LaunchArgs a{};
-  a.st64 = e->d_st64;
-  a.st32 = e->d_st32;
-  a.in = in;
-  a.out = out;
-  a.stats = stats;
-  a.status = e->d_status;
-  a.params = e->d_params_multi;
-  a.group_preset = e->d_group_preset;
-  a.n_samples = n_samples;
-  a.stream_stride = stream_stride;
-  a.samples_before = samples_before;
-  a.n_streams = e->n_streams;
-  a.layout = layout;
+  AF_HIP(e->d_params.sync(runs.data(), runs.size(), e->stager, stream));
+  const af::LaunchArgs a = segment_args(e, in, out, stats, n_samples, stream_stride, samples_before, layout);
   af::TimedSpan span;
   if (e->timing) AF_HIP(span.begin(stream));
   if (!stats_cleared) AF_HIP(hipMemsetAsync(stats, 0, sizeof(af::BlockStats) * rows, stream));  // fields are written by their tokens
@@ -806,10 +797,10 @@ int launch_chain_segment(af_engine *e, const af::ChainParams &run_in, bool run_m
   // `ready`: the segment is a whole call whose input arrives window by window (LaunchArgs::ready); only the plain one-launch form
   // of the token-ring kernel follows such a counter -- the caller has checked that this is what the configuration takes
   const bool followed_counter = ready != nullptr;
-  if (ready && (!e->extra_presets.empty() || e->kernel == AF_KERNEL_ROLES || af::switches().roles != 0))
+  if (ready && (e->n_presets() > 1 || e->kernel == AF_KERNEL_ROLES || af::switches().roles != 0))
     return fail(AF_ERR_BACKEND, "internal: only the plain token-ring launch follows a ready counter");
-  if (!e->extra_presets.empty())
-    return launch_chain_multi(e, e->host_params.flags & ~run_in.flags, run_in.flags & af::kFlagInputDone, in, out, n_samples,
+  if (e->n_presets() > 1)
+    return launch_chain_multi(e, e->base().params.flags & ~run_in.flags, run_in.flags & af::kFlagInputDone, in, out, n_samples,
                               stream_stride, layout, samples_before, stats, stream, stats_cleared);
   af::ChainParams run = run_in;
   const int cb = run.control_block;
@@ -865,27 +856,11 @@ int launch_chain_segment(af_engine *e, const af::ChainParams &run_in, bool run_m
       const bool ring_comp = comp_on && roles_env == 2 && ring_fits;
       af::ChainParams up = run;
       if (ring_comp) up.flags = (up.flags & ~af::kFlagLimiter) | af::kFlagCompOnly;
-      if (!e->uploaded_valid || std::memcmp(&e->uploaded, &up, sizeof up) != 0) {
-        e->uploaded = up;
-        if (int rc = stage_upload(e, e->d_params, &e->uploaded, 1, stream)) return rc;
-        e->uploaded_valid = true;
-      }
+      AF_HIP(e->d_params.sync(&up, 1, e->stager, stream));
       af::TimedSpan span;
       if (e->timing) AF_HIP(span.begin(stream));
       if (!stats_cleared) AF_HIP(hipMemsetAsync(stats, 0, sizeof(af::BlockStats) * rows, stream));
-      af::LaunchArgs ra{};
-      ra.st64 = e->d_st64;
-      ra.st32 = e->d_st32;
-      ra.in = in;
-      ra.out = out;
-      ra.stats = stats;
-      ra.status = e->d_status;
-      ra.params = e->d_params;
-      ra.n_samples = n_samples;
-      ra.stream_stride = stream_stride;
-      ra.samples_before = samples_before;
-      ra.n_streams = e->n_streams;
-      ra.layout = layout;
+      af::LaunchArgs ra = segment_args(e, in, out, stats, n_samples, stream_stride, samples_before, layout);
       if (!input_done) {  // EQ (or a plain pass when it is off) + block input statistics
         AF_HIP(af::launch_eq_systolic(e->d_params, nullptr, e->d_st64, in, out, nullptr, nullptr, 0, 0, stats, any_xf, n_samples,
                                       stream_stride, e->n_streams, stream));
@@ -895,10 +870,7 @@ int launch_chain_segment(af_engine *e, const af::ChainParams &run_in, bool run_m
       if (ring_comp) {
         af::ChainParams shape = up;
         shape.flags = (shape.flags & ~af::kFlagEq) | af::kFlagInputDone;  // (the systolic EQ kernel above did both)
-        if (std::memcmp(&e->uploaded, &shape, sizeof shape) != 0) {
-          e->uploaded = shape;
-          if (int rc = stage_upload(e, e->d_params, &e->uploaded, 1, stream)) return rc;
-        }
+        AF_HIP(e->d_params.sync(&shape, 1, e->stager, stream));  // (behind the EQ launch, which read `up`)
         AF_HIP(af::launch_chain_ring(ra, shape.n_eq_sections, shape.lim.lookahead_samples, any_xf, e->ring_variant, false, stream));
         ra.in = out;
         e->last_launches += 1;
@@ -924,19 +896,7 @@ int launch_chain_segment(af_engine *e, const af::ChainParams &run_in, bool run_m
     }
     if (e->kernel == AF_KERNEL_ROLES) kernel = ring_fits ? AF_KERNEL_PHASED : (quad_ok ? AF_KERNEL_QUAD : AF_KERNEL_LANE_PER_STREAM);  // not served: as AUTO
   }
-  af::LaunchArgs a{};
-  a.st64 = e->d_st64;
-  a.st32 = e->d_st32;
-  a.in = in;
-  a.out = out;
-  a.stats = stats;
-  a.status = e->d_status;
-  a.params = e->d_params;
-  a.n_samples = n_samples;
-  a.stream_stride = stream_stride;
-  a.samples_before = samples_before;
-  a.n_streams = e->n_streams;
-  a.layout = layout;
+  af::LaunchArgs a = segment_args(e, in, out, stats, n_samples, stream_stride, samples_before, layout);
   af::TimedSpan span;
   if (e->timing) AF_HIP(span.begin(stream));
   if (two_pass || deesser) {  // (per-call scratch: the old rows are retired, not freed)
@@ -946,11 +906,7 @@ int launch_chain_segment(af_engine *e, const af::ChainParams &run_in, bool run_m
   const af::BlockStats *input_rows = nullptr;  // where the block input statistics end up when a side pass saw the input
   if (deesser) {
     // the de-esser pass reads the unmodified parameter block (its own copy: the chain kernels get edited flags)
-    if (!e->uploaded_de_valid || std::memcmp(&e->uploaded_de, &run_in, sizeof run_in) != 0) {
-      e->uploaded_de = run_in;
-      if (int rc = stage_upload(e, e->d_params_de, &e->uploaded_de, 1, stream)) return rc;
-      e->uploaded_de_valid = true;
-    }
+    AF_HIP(e->d_params_de.sync(&run_in, 1, e->stager, stream));
     AF_HIP(hipMemsetAsync(e->d_stats_de, 0, sizeof(af::BlockStats) * rows, stream));
     if (!eq_first) {
       // routing.rs: pre-filter -> de-esser -> EQ ...: this pass takes the front end with it
@@ -972,16 +928,8 @@ int launch_chain_segment(af_engine *e, const af::ChainParams &run_in, bool run_m
       post.flags &= ~(af::kFlagEq | front_flags);
       // both variants are uploaded only when they change (first launch; while a coefficient crossfade advances), through
       // pinned slots: no host wait inside a window loop
-      if (!e->uploaded_pre_valid || std::memcmp(&e->uploaded_pre, &pre, sizeof pre) != 0) {
-        e->uploaded_pre = pre;
-        if (int rc = stage_upload(e, e->d_params_pre, &e->uploaded_pre, 1, stream)) return rc;
-        e->uploaded_pre_valid = true;
-      }
-      if (!e->uploaded_valid || std::memcmp(&e->uploaded, &post, sizeof post) != 0) {
-        e->uploaded = post;
-        if (int rc = stage_upload(e, e->d_params, &e->uploaded, 1, stream)) return rc;
-        e->uploaded_valid = true;
-      }
+      AF_HIP(e->d_params_pre.sync(&pre, 1, e->stager, stream));
+      AF_HIP(e->d_params.sync(&post, 1, e->stager, stream));
       AF_HIP(hipMemsetAsync(e->d_stats_pre, 0, sizeof(af::BlockStats) * rows, stream));
       af::LaunchArgs a1 = a;
       a1.params = e->d_params_pre;
@@ -1005,11 +953,7 @@ int launch_chain_segment(af_engine *e, const af::ChainParams &run_in, bool run_m
       AF_HIP(af::launch_chain_ring(a2, post.n_eq_sections, post.lim.lookahead_samples, any_xf, e->ring_variant, auto_makeup, stream));
       e->last_launches += 2;
     } else {
-      if (!e->uploaded_valid || std::memcmp(&e->uploaded, &run, sizeof run) != 0) {
-        e->uploaded = run;
-        if (int rc = stage_upload(e, e->d_params, &e->uploaded, 1, stream)) return rc;
-        e->uploaded_valid = true;
-      }
+      AF_HIP(e->d_params.sync(&run, 1, e->stager, stream));
       if (auto_makeup) {  // the systolic EQ kernel was this segment's pre-pass
         a.pre_power = pre_power;
         a.vad_prob = vad;
@@ -1020,11 +964,7 @@ int launch_chain_segment(af_engine *e, const af::ChainParams &run_in, bool run_m
       e->last_launches += 1;
     }
   } else {
-    if (!e->uploaded_valid || std::memcmp(&e->uploaded, &run, sizeof run) != 0) {
-      e->uploaded = run;
-      if (int rc = stage_upload(e, e->d_params, &e->uploaded, 1, stream)) return rc;
-      e->uploaded_valid = true;
-    }
+    AF_HIP(e->d_params.sync(&run, 1, e->stager, stream));
     if (kernel == AF_KERNEL_QUAD) {
       AF_HIP(hipMemsetAsync(stats, 0, sizeof(af::BlockStats) * rows, stream));  // fields are written by their tokens
       AF_HIP(af::launch_chain_quad(a, run.n_eq_sections, run.lim.lookahead_samples, any_xf, e->ring_variant ? e->ring_variant / 100 : 12, stream));
@@ -1071,11 +1011,11 @@ bool stage_pipe_serves_one(const af::ChainParams &run) {
 // `run`: preset 0 as the chain will see it (the front end's flags stripped when the suppressor's pre-pass owns them)
 bool stage_pipe_serves(af_engine *e, const af::ChainParams &run, int32_t layout) {
   if (layout != AF_LAYOUT_STREAM_MAJOR || !stage_pipe_serves_one(run)) return false;
-  const uint32_t strip = e->host_params.flags & ~run.flags;
-  for (int k = 1; k <= (int)e->extra_presets.size(); ++k) {
+  const uint32_t strip = e->base().params.flags & ~run.flags;
+  for (int k = 1; k < e->n_presets(); ++k) {
     // several presets: every group's stages run as roles of the same dispatches, so the presets must agree on which stages
     // there are and which code paths they take (what differs freely: every coefficient, the EQ, the limiter's lookahead)
-    af::ChainParams other = preset_params(e, k);
+    af::ChainParams other = e->presets[k].params;
     other.flags &= ~strip;
     const uint32_t shape = af::kFlagCompressor | af::kFlagLimiter | af::kFlagDeesser;
     if (!stage_pipe_serves_one(other) || (other.flags & shape) != (run.flags & shape) ||
@@ -1097,7 +1037,7 @@ size_t pow2_at_least(int64_t n) {
 int stage_pipe_prepare(af_engine *e, int64_t tw_max) {
   auto &sp = e->pipe;
   {  // the per-block arrays (makeup gains, block powers): a reset may have brought a shorter control block, i.e. more blocks
-    const int cb = e->host_params.control_block;
+    const int cb = e->base().params.control_block;
     const int64_t rows = ((std::max(tw_max, sp.tw_max) + cb - 1) / cb + 1) * e->n_streams;
     if (rows > sp.mk_rows) {
       if (sp.d_mk || sp.d_bp) AF_HIP(hipDeviceSynchronize());
@@ -1107,7 +1047,7 @@ int stage_pipe_prepare(af_engine *e, int64_t tw_max) {
       sp.mk_rows = rows;
     }
   }
-  if (sp.rings.xe && tw_max <= sp.tw_max && sp.with_deesser == ((e->host_params.flags & af::kFlagDeesser) != 0)) return AF_OK;
+  if (sp.rings.xe && tw_max <= sp.tw_max && sp.with_deesser == ((e->base().params.flags & af::kFlagDeesser) != 0)) return AF_OK;
   if (sp.rings.xe) {  // grow: only between calls of a fresh engine (the rings hold the histories)
     if (sp.windows > 0 && tw_max > sp.tw_max)
       return fail(AF_ERR_UNSUPPORTED, "a call of %lld samples per window after smaller ones: the stage pipeline's rings were sized for %lld",
@@ -1120,7 +1060,7 @@ int stage_pipe_prepare(af_engine *e, int64_t tw_max) {
   const int64_t hist = 2 * (af::kMaxLookahead + 1) + 64;
   // a ring holds the windows between its producer and its last consumer, one more, and the history: the stages advance in lock
   // step, an f64 ring's reader two windows behind its writer at most, the EQ output's last reader seven
-  const bool deesser = (e->host_params.flags & af::kFlagDeesser) != 0;
+  const bool deesser = (e->base().params.flags & af::kFlagDeesser) != 0;
   // (with the de-esser: a band's coefficients wait three launch steps for the third dynamic EQ of the cascade, and the chain
   // input nine for nothing -- the EQ now reads the de-esser's output ring)
   const size_t r64 = pow2_at_least((deesser ? 6 : 4) * tw_max + hist), r32 = pow2_at_least(10 * tw_max + hist);
@@ -1155,9 +1095,9 @@ int stage_pipe_prepare(af_engine *e, int64_t tw_max) {
     AF_HIP(hipGetDeviceProperties(&prop, e->device));
     std::vector<uint32_t> mask((size_t)(prop.multiProcessorCount + 31) / 32, 0u);
     for (int bit = 0; bit < prop.multiProcessorCount; ++bit) mask[bit >> 5] |= 1u << (bit & 31);
-    if (hipExtStreamCreateWithCUMask(&sp.stream, (uint32_t)mask.size(), mask.data()) != hipSuccess) {
+    if (sp.stream.create_with_cu_mask((uint32_t)mask.size(), mask.data()) != hipSuccess) {
       (void)hipGetLastError();
-      AF_HIP(hipStreamCreateWithFlags(&sp.stream, hipStreamNonBlocking));
+      AF_HIP(sp.stream.create());
     }
   }
   return AF_OK;
@@ -1187,29 +1127,10 @@ int stage_pipe_clear(af_engine *e) {  // a fresh engine: the histories are zeros
 // The parameter block(s) the stage kernels read: preset 0 alone, or all presets as an array beside the group -> preset table.
 int stage_chain_params(af_engine *e, hipStream_t stream) {
   auto &sp = e->pipe;
-  const int n_presets = 1 + (int)e->extra_presets.size();
-  std::vector<af::ChainParams> runs((size_t)n_presets);
+  const std::vector<af::ChainParams> runs = run_params(e, sp.strip);
   sp.w_min = 1 << 30;
-  for (int k = 0; k < n_presets; ++k) {
-    runs[k] = preset_params(e, k);
-    runs[k].flags &= ~sp.strip;
-    sp.w_min = std::min<int32_t>(sp.w_min, runs[k].lim.lookahead_samples + 1);
-  }
-  if (n_presets == 1) {
-    if (!e->uploaded_valid || std::memcmp(&e->uploaded, &runs[0], sizeof runs[0]) != 0) {
-      e->uploaded = runs[0];
-      if (int rc = stage_upload(e, e->d_params, &e->uploaded, 1, stream)) return rc;
-      e->uploaded_valid = true;
-    }
-    sp.d_chain = e->d_params;
-  } else {
-    if (e->uploaded_multi.size() != runs.size() ||
-        std::memcmp(e->uploaded_multi.data(), runs.data(), sizeof(af::ChainParams) * runs.size()) != 0) {
-      e->uploaded_multi = runs;
-      if (int rc = stage_upload(e, e->d_params_multi, runs.data(), runs.size(), stream)) return rc;
-    }
-    sp.d_chain = e->d_params_multi;
-  }
+  for (const af::ChainParams &run : runs) sp.w_min = std::min<int32_t>(sp.w_min, run.lim.lookahead_samples + 1);
+  AF_HIP(e->d_params.sync(runs.data(), runs.size(), e->stager, stream));
   return AF_OK;
 }
 
@@ -1271,8 +1192,8 @@ int stage_diag_step(af_engine *e, const af::ChainParams &run, const StagePlan &p
                     hipStream_t stream) {
   auto &sp = e->pipe;
   af::DiagArgs d{};
-  d.base.params = sp.d_chain;
-  d.base.group_preset = e->extra_presets.empty() ? nullptr : e->d_group_preset;
+  d.base.params = e->d_params;
+  d.base.group_preset = e->n_presets() == 1 ? nullptr : e->d_group_preset;
   d.base.st64 = e->d_st64;
   d.base.st32 = e->d_st32;
   d.base.n_streams = e->n_streams;
@@ -1322,8 +1243,7 @@ int stage_diag_step(af_engine *e, const af::ChainParams &run, const StagePlan &p
 // every other stream on the rest.
 int ensure_side_streams(af_engine *e, hipStream_t stream) {
   if (af::switches().serial_streams) {  // AF_SERIAL_STREAMS, diagnostic: every stage on the caller's stream (per-kernel times without overlap)
-    e->aux_stream = e->pre_stream = e->ana_stream = e->fin_stream = e->eq_stream = stream;
-    e->borrowed_streams = true;
+    for (af::Stream *side : {&e->aux_stream, &e->pre_stream, &e->ana_stream, &e->fin_stream, &e->eq_stream}) side->borrow(stream);
   }
 
   if (!e->aux_stream) {
@@ -1358,68 +1278,45 @@ int ensure_side_streams(af_engine *e, hipStream_t stream) {
       // the chain takes mask bits 0.. (CU indices 0.. of every XCD), the limiter half the next ones
       for (int bit = 0; bit < total_cus; ++bit)
         (bit < chain_cus ? chain_mask : (bit < chain_cus + lim_cus ? lim_mask : rest_mask))[bit >> 5] |= 1u << (bit & 31);
-      hipError_t err = hipExtStreamCreateWithCUMask(&e->aux_stream, (uint32_t)chain_mask.size(), chain_mask.data());
-      if (err == hipSuccess && lim_cus > 0) err = hipExtStreamCreateWithCUMask(&e->lim_stream, (uint32_t)lim_mask.size(), lim_mask.data());
-      if (err == hipSuccess) err = hipExtStreamCreateWithCUMask(&e->pre_stream, (uint32_t)rest_mask.size(), rest_mask.data());
-      if (err == hipSuccess) err = hipExtStreamCreateWithCUMask(&e->ana_stream, (uint32_t)rest_mask.size(), rest_mask.data());
-      if (err == hipSuccess) err = hipExtStreamCreateWithCUMask(&e->syn_stream, (uint32_t)rest_mask.size(), rest_mask.data());
-      if (err == hipSuccess) err = hipExtStreamCreateWithCUMask(&e->fin_stream, (uint32_t)rest_mask.size(), rest_mask.data());
-      if (err == hipSuccess) err = hipExtStreamCreateWithCUMask(&e->eq_stream, (uint32_t)rest_mask.size(), rest_mask.data());
+      hipError_t err = e->aux_stream.create_with_cu_mask((uint32_t)chain_mask.size(), chain_mask.data());
+      if (err == hipSuccess && lim_cus > 0) err = e->lim_stream.create_with_cu_mask((uint32_t)lim_mask.size(), lim_mask.data());
+      for (af::Stream *rest : {&e->pre_stream, &e->ana_stream, &e->syn_stream, &e->fin_stream, &e->eq_stream})
+        if (err == hipSuccess) err = rest->create_with_cu_mask((uint32_t)rest_mask.size(), rest_mask.data());
       if (err != hipSuccess) {  // platform without queue CU masks: plain streams
         (void)hipGetLastError();
-        for (hipStream_t *sp : {&e->aux_stream, &e->pre_stream, &e->ana_stream, &e->syn_stream, &e->fin_stream, &e->eq_stream, &e->lim_stream}) {
-          if (*sp) (void)hipStreamDestroy(*sp);
-          *sp = nullptr;
-        }
+        for (af::Stream *st : {&e->aux_stream, &e->pre_stream, &e->ana_stream, &e->syn_stream, &e->fin_stream, &e->eq_stream, &e->lim_stream}) st->reset();
         chain_cus = 0;
       }
     }
     e->partition_chain_cus = chain_cus;
   }
-  if (!e->aux_stream) AF_HIP(hipStreamCreateWithFlags(&e->aux_stream, hipStreamNonBlocking));
-  if (!e->pre_stream) AF_HIP(hipStreamCreateWithFlags(&e->pre_stream, hipStreamNonBlocking));
-  if (!e->ana_stream) AF_HIP(hipStreamCreateWithFlags(&e->ana_stream, hipStreamNonBlocking));
-  if (!e->fin_stream) AF_HIP(hipStreamCreateWithFlags(&e->fin_stream, hipStreamNonBlocking));
-  if (!e->eq_stream) AF_HIP(hipStreamCreateWithFlags(&e->eq_stream, hipStreamNonBlocking));
+  for (af::Stream *side : {&e->aux_stream, &e->pre_stream, &e->ana_stream, &e->fin_stream, &e->eq_stream})
+    if (!*side) AF_HIP(side->create());
   return AF_OK;
 }
 
 // the EQ stage's parameter block for the window about to enter the pipeline (stream-ordered behind the previous window's launch)
 int stage_diag_eq_params(af_engine *e, hipStream_t stream, bool *crossfade, int32_t *slot_out) {
-  const int n_presets = 1 + (int)e->extra_presets.size();
-  std::vector<af::ChainParams> runs((size_t)n_presets);
+  std::vector<af::ChainParams> runs = run_params(e, e->pipe.strip);
   *crossfade = false;
   bool deesser = false;
-  for (int p = 0; p < n_presets; ++p) {
-    runs[p] = preset_params(e, p);
-    runs[p].flags &= ~e->pipe.strip;
-    for (int k = 0; k < runs[p].n_eq_sections; ++k) *crossfade |= runs[p].eq[k].xf_remaining > 0;
-    if (runs[p].flags & af::kFlagDeesser) {
+  for (af::ChainParams &run : runs) {
+    for (int k = 0; k < run.n_eq_sections; ++k) *crossfade |= run.eq[k].xf_remaining > 0;
+    if (run.flags & af::kFlagDeesser) {
       deesser = true;
-      runs[p].flags &= ~(af::kFlagInputScrub | af::kFlagInputClamp);  // the de-esser's loader stage scrubbed the input already
+      run.flags &= ~(af::kFlagInputScrub | af::kFlagInputClamp);  // the de-esser's loader stage scrubbed the input already
     }
   }
   // With the de-esser every window keeps a parameter block of its own for as long as it is in the pipeline: the de-esser's
   // stages read their filters' crossfade counters as of the window's first sample up to eight launch steps after it entered.
-  constexpr int kSlots = kEqParamSlots;
-  if (!e->d_params_eq || e->eq_params_presets != n_presets) {
-    e->d_params_eq.release();
-    AF_HIP(e->d_params_eq.reserve_exact(sizeof(af::ChainParams) * n_presets * kSlots));
-    e->eq_params_presets = n_presets;
-    e->uploaded_eq.clear();
-  }
   if (deesser) {
-    const int slot = (int)(e->eq_slot_cursor++ % kSlots);
-    if (int rc = stage_upload(e, e->d_params_eq + (size_t)slot * n_presets, runs.data(), runs.size(), stream)) return rc;
-    e->uploaded_eq.clear();
-    *slot_out = slot * n_presets;
+    const size_t first = (size_t)(e->eq_slot_cursor++ % kEqParamSlots) * runs.size();
+    AF_HIP(e->d_params_eq.send(first, runs.data(), runs.size(), e->stager, stream));
+    *slot_out = (int32_t)first;
     return AF_OK;
   }
   *slot_out = 0;
-  if (e->uploaded_eq.size() != runs.size() || std::memcmp(e->uploaded_eq.data(), runs.data(), sizeof(af::ChainParams) * runs.size()) != 0) {
-    e->uploaded_eq = runs;
-    if (int rc = stage_upload(e, e->d_params_eq, runs.data(), runs.size(), stream)) return rc;
-  }
+  AF_HIP(e->d_params_eq.sync(runs.data(), runs.size(), e->stager, stream));
   return AF_OK;
 }
 
@@ -1458,7 +1355,7 @@ int af_engine_reset(af_engine *e) {
     e->retired.collect(true);
   }
   e->started = false;
-  e->uploaded_valid = e->uploaded_pre_valid = e->uploaded_de_valid = false;
+  for (af::Mirrored<af::ChainParams> *m : {&e->d_params, &e->d_params_pre, &e->d_params_de, &e->d_params_eq}) m->invalidate();
   e->pipe.decided = false;
   e->params_dirty = true;
   e->samples_processed = 0;
@@ -1470,9 +1367,9 @@ int af_engine_reset(af_engine *e) {
   // filter from its configured target (Biquad::reset, biquad.rs:341-347), not from wherever a crossfade stood
   e->retune_ops.clear();
   e->retune_span.clear();
-  for (size_t k = 0; k < e->live_retuned.size() && k <= e->extra_presets.size(); ++k) {
+  for (size_t k = 0; k < e->live_retuned.size() && k < e->presets.size(); ++k) {
     if (!e->live_retuned[k]) continue;
-    af::ChainProto &p = k == 0 ? e->proto : e->extra_presets[k - 1].proto;
+    af::ChainProto &p = e->presets[k].proto;
     p.eq.reset();
     for (auto &b : p.deesser.bands) {
       b.detector_hp.reset();
@@ -1533,17 +1430,14 @@ int af_engine_last_retune_ms(af_engine *e, double *ms) {
     return AF_OK;                    \
   } while (0)
 
-int af_engine_set_deesser_enabled(af_engine *e, int32_t on) { AF_SETTER(cur(e).deesser_enabled = cur(e).deesser.enabled = on != 0); }
-int af_engine_set_eq_enabled(af_engine *e, int32_t on) { AF_SETTER(cur(e).eq_enabled = cur(e).eq.enabled = on != 0); }
-int af_engine_set_compressor_enabled(af_engine *e, int32_t on) { AF_SETTER(cur(e).compressor_enabled = cur(e).compressor.enabled = on != 0); }
-int af_engine_set_limiter_enabled(af_engine *e, int32_t on) { AF_SETTER(cur(e).limiter_enabled = cur(e).limiter.enabled = on != 0); }
-int af_engine_set_eq_before_deesser(af_engine *e, int32_t on) { AF_SETTER(cur(e).eq_before_deesser = on != 0); }
+int af_engine_set_deesser_enabled(af_engine *e, int32_t on) { AF_SETTER(e->selected().proto.deesser_enabled = e->selected().proto.deesser.enabled = on != 0); }
+int af_engine_set_eq_enabled(af_engine *e, int32_t on) { AF_SETTER(e->selected().proto.eq_enabled = e->selected().proto.eq.enabled = on != 0); }
+int af_engine_set_compressor_enabled(af_engine *e, int32_t on) { AF_SETTER(e->selected().proto.compressor_enabled = e->selected().proto.compressor.enabled = on != 0); }
+int af_engine_set_limiter_enabled(af_engine *e, int32_t on) { AF_SETTER(e->selected().proto.limiter_enabled = e->selected().proto.limiter.enabled = on != 0); }
+int af_engine_set_eq_before_deesser(af_engine *e, int32_t on) { AF_SETTER(e->selected().proto.eq_before_deesser = on != 0); }
 // the front end belongs to the engine, not to a preset (with the suppressor on it runs in the suppressor's pre-pass)
-#define AF_ALL_PRESETS(stmt)                                     \
-  do {                                                           \
-    { af::ChainProto &p = e->proto; stmt; }                      \
-    for (af_preset &ps__ : e->extra_presets) { af::ChainProto &p = ps__.proto; stmt; } \
-  } while (0)
+#define AF_ALL_PRESETS(stmt) \
+  for (af_preset &ps__ : e->presets) { af::ChainProto &p = ps__.proto; stmt; }
 int af_engine_set_input_scrub_enabled(af_engine *e, int32_t on) { AF_SETTER(AF_ALL_PRESETS(p.input_scrub = on != 0)); }
 int af_engine_set_input_clamp_enabled(af_engine *e, int32_t on) { AF_SETTER(AF_ALL_PRESETS(p.input_clamp = on != 0)); }
 int af_engine_set_prefilter_enabled(af_engine *e, int32_t on, int32_t hp) {
@@ -1581,26 +1475,26 @@ int af_engine_set_control_block_samples(af_engine *e, int32_t n) {
     bool live__ = false;                                                 \
     if (int rc__ = setter_mode(e, &live__)) return rc__;                 \
     if (live__) {                                                        \
-      af::EqBandConfig c__ = cur(e).eq.bands[band].config;               \
+      af::EqBandConfig c__ = e->selected().proto.eq.bands[band].config;               \
       c__.field = (value);                                               \
       return live_eq_set_band(e, band, c__);                             \
     }                                                                    \
     config_call;                                                         \
     return AF_OK;                                                        \
   } while (0)
-int af_eq_set_band_frequency(af_engine *e, int32_t band, double hz) { AF_EQ_LIVE_FIELD(frequency_hz, hz, cur(e).eq.set_band_frequency(band, hz)); }
-int af_eq_set_band_gain(af_engine *e, int32_t band, double db) { AF_EQ_LIVE_FIELD(gain_db, db, cur(e).eq.set_band_gain(band, db)); }
-int af_eq_set_band_q(af_engine *e, int32_t band, double q) { AF_EQ_LIVE_FIELD(q, q, cur(e).eq.set_band_q(band, q)); }
+int af_eq_set_band_frequency(af_engine *e, int32_t band, double hz) { AF_EQ_LIVE_FIELD(frequency_hz, hz, e->selected().proto.eq.set_band_frequency(band, hz)); }
+int af_eq_set_band_gain(af_engine *e, int32_t band, double db) { AF_EQ_LIVE_FIELD(gain_db, db, e->selected().proto.eq.set_band_gain(band, db)); }
+int af_eq_set_band_q(af_engine *e, int32_t band, double q) { AF_EQ_LIVE_FIELD(q, q, e->selected().proto.eq.set_band_q(band, q)); }
 int af_eq_set_band_config(af_engine *e, int32_t band, const af_eq_band_config *c) {
   if (int rc = check_band(band)) return rc;
   if (!c) return fail(AF_ERR_INVALID_ARGUMENT, "config is null");
   bool live = false;
   if (int rc = setter_mode(e, &live)) return rc;
   if (live) return live_eq_set_band(e, band, to_cfg(*c));
-  cur(e).eq.set_band_config(band, to_cfg(*c));
+  e->selected().proto.eq.set_band_config(band, to_cfg(*c));
   return AF_OK;
 }
-int af_eq_reset(af_engine *e) { AF_SETTER(cur(e).eq.reset()); }
+int af_eq_reset(af_engine *e) { AF_SETTER(e->selected().proto.eq.reset()); }
 int af_eq_band_config_validate(const af_eq_band_config *c, int32_t index, double sample_rate) {
   if (!c) return fail(AF_ERR_INVALID_ARGUMENT, "config is null");
   if (c->filter_type < 0 || c->filter_type > 5)
@@ -1612,48 +1506,48 @@ int af_eq_band_config_validate(const af_eq_band_config *c, int32_t index, double
 
 // Live (compressor.rs:210-371 on the running compressor): what each setter edits beyond its parameters is recorded as state edits.
 int af_compressor_set_threshold(af_engine *e, double v) {
-  AF_LIVE_SETTER((void)0, cur(e).compressor.set_threshold(v), live_reset_release_envelopes(e));
+  AF_LIVE_SETTER((void)0, e->selected().proto.compressor.set_threshold(v), live_reset_release_envelopes(e));
 }
-int af_compressor_set_ratio(af_engine *e, double v) { AF_LIVE_PARAM_SETTER(cur(e).compressor.set_ratio(v)); }
-int af_compressor_set_attack_time(af_engine *e, double v) { AF_LIVE_PARAM_SETTER(cur(e).compressor.set_attack_time(v)); }
+int af_compressor_set_ratio(af_engine *e, double v) { AF_LIVE_PARAM_SETTER(e->selected().proto.compressor.set_ratio(v)); }
+int af_compressor_set_attack_time(af_engine *e, double v) { AF_LIVE_PARAM_SETTER(e->selected().proto.compressor.set_attack_time(v)); }
 int af_compressor_set_release_time(af_engine *e, double v) {
-  AF_LIVE_SETTER((void)0, cur(e).compressor.set_release_time(v),
-                 if (!cur(e).compressor.adaptive_release) live_set_release(e, cur(e).compressor));
+  AF_LIVE_SETTER((void)0, e->selected().proto.compressor.set_release_time(v),
+                 if (!e->selected().proto.compressor.adaptive_release) live_set_release(e, e->selected().proto.compressor));
 }
 int af_compressor_set_makeup_gain(af_engine *e, double v) {
-  AF_LIVE_SETTER((void)0, cur(e).compressor.set_makeup_gain(v),
-                 if (!cur(e).compressor.auto_makeup_enabled) live_set(e, af::kCompSmoothedMakeup, v));
+  AF_LIVE_SETTER((void)0, e->selected().proto.compressor.set_makeup_gain(v),
+                 if (!e->selected().proto.compressor.auto_makeup_enabled) live_set(e, af::kCompSmoothedMakeup, v));
 }
 // the stage pipeline runs every preset's stages as roles of the same dispatches: its presets take the same code paths
 #define AF_LIVE_SAME_PATHS_CHECK(what)                                                                                            \
-  if (e->pipe.active && !e->extra_presets.empty())                                                                                \
+  if (e->pipe.active && e->n_presets() > 1)                                                                                       \
     return fail(AF_ERR_UNSUPPORTED, what " cannot change live on a multi-preset engine that runs the stage pipeline: every preset " \
                                          "must take the same code paths; call af_engine_reset first")
 int af_compressor_set_adaptive_release(af_engine *e, int32_t on) {
-  AF_LIVE_SETTER(AF_LIVE_SAME_PATHS_CHECK("adaptive release"), cur(e).compressor.set_adaptive_release(on != 0), {
-    if (!on) live_set_release(e, cur(e).compressor);
+  AF_LIVE_SETTER(AF_LIVE_SAME_PATHS_CHECK("adaptive release"), e->selected().proto.compressor.set_adaptive_release(on != 0), {
+    if (!on) live_set_release(e, e->selected().proto.compressor);
     live_reset_release_envelopes(e);
   });
 }
 int af_compressor_set_base_release_time(af_engine *e, double v) {
-  AF_LIVE_SETTER((void)0, cur(e).compressor.set_base_release_time(v),
-                 if (!cur(e).compressor.adaptive_release) live_set_release(e, cur(e).compressor));
+  AF_LIVE_SETTER((void)0, e->selected().proto.compressor.set_base_release_time(v),
+                 if (!e->selected().proto.compressor.adaptive_release) live_set_release(e, e->selected().proto.compressor));
 }
 // a configuration setter: the token-ring kernel and the stage plan are built per value, and the loudness meter's rows exist only
 // when it was on at the start
-int af_compressor_set_auto_makeup_enabled(af_engine *e, int32_t on) { AF_SETTER(cur(e).compressor.set_auto_makeup_enabled(on != 0)); }
-int af_compressor_set_target_lufs(af_engine *e, double v) { AF_LIVE_PARAM_SETTER(cur(e).compressor.set_target_lufs(v)); }
+int af_compressor_set_auto_makeup_enabled(af_engine *e, int32_t on) { AF_SETTER(e->selected().proto.compressor.set_auto_makeup_enabled(on != 0)); }
+int af_compressor_set_target_lufs(af_engine *e, double v) { AF_LIVE_PARAM_SETTER(e->selected().proto.compressor.set_target_lufs(v)); }
 int af_compressor_set_sidechain_highpass_enabled(af_engine *e, int32_t on) {
-  const bool changes = e && cur(e).compressor.sidechain_highpass_enabled != (on != 0);
+  const bool changes = e && e->selected().proto.compressor.sidechain_highpass_enabled != (on != 0);
   AF_LIVE_SETTER(if (changes) AF_LIVE_SAME_PATHS_CHECK("the side-chain high-pass"),
-                 cur(e).compressor.set_sidechain_highpass_enabled(on != 0), {
+                 e->selected().proto.compressor.set_sidechain_highpass_enabled(on != 0), {
     if (changes)  // reset_sidechain_highpass_state, compressor.rs:397-404
       for (int row : {af::kCompScPrevIn, af::kCompScPrevOut, af::kCompLowEnv, af::kCompVoicedEnv, af::kCompPresenceEnv, af::kCompPlosive})
         live_set(e, row, 0.0);
   });
 }
 
-int af_compressor_set_noise_reference_reliability(af_engine *e, double v) { AF_LIVE_PARAM_SETTER(cur(e).compressor.set_noise_reference_reliability(v)); }
+int af_compressor_set_noise_reference_reliability(af_engine *e, double v) { AF_LIVE_PARAM_SETTER(e->selected().proto.compressor.set_noise_reference_reliability(v)); }
 
 int af_compressor_set_activity_evidence(af_engine *e, const double *vad_probabilities, int64_t n_blocks, int32_t per_stream,
                                         double vad_reliability, double noise_floor_db, double live_noise_reliability) {
@@ -1667,10 +1561,10 @@ int af_compressor_set_activity_evidence(af_engine *e, const double *vad_probabil
   e->vad_blocks = n_blocks;
   e->params_dirty = true;
   if (e->started) {  // ChainParams carries the three scalars
-    e->host_params.comp.vad_reliability = e->vad_reliability;
-    e->host_params.comp.noise_floor_db = e->noise_floor_db;
-    e->host_params.comp.live_noise_reliability = e->live_noise_reliability;
-    e->host_params.comp.has_evidence = e->has_evidence ? 1 : 0;
+    e->base().params.comp.vad_reliability = e->vad_reliability;
+    e->base().params.comp.noise_floor_db = e->noise_floor_db;
+    e->base().params.comp.live_noise_reliability = e->live_noise_reliability;
+    e->base().params.comp.has_evidence = e->has_evidence ? 1 : 0;
   }
   if (n_blocks == 0) return AF_OK;
   AF_HIP(e->use_device());
@@ -1686,22 +1580,22 @@ int af_compressor_set_activity_evidence(af_engine *e, const double *vad_probabil
   return AF_OK;
 }
 
-int af_limiter_set_ceiling(af_engine *e, double v) { AF_LIVE_PARAM_SETTER(cur(e).limiter.set_ceiling(v)); }  // (limiter.rs:139-152: parameters only)
-int af_limiter_set_release_time(af_engine *e, double v) { AF_LIVE_PARAM_SETTER(cur(e).limiter.set_release_time(v)); }
-int af_limiter_set_lookahead_ms(af_engine *e, double v) { AF_SETTER(cur(e).limiter.set_lookahead_ms(v)); }
-double af_limiter_ceiling_db(const af_engine *e) { return e ? cur(e).limiter.ceiling_db : 0.0; }
-int32_t af_limiter_lookahead_samples(const af_engine *e) { return e ? cur(e).limiter.lookahead_samples : 0; }
+int af_limiter_set_ceiling(af_engine *e, double v) { AF_LIVE_PARAM_SETTER(e->selected().proto.limiter.set_ceiling(v)); }  // (limiter.rs:139-152: parameters only)
+int af_limiter_set_release_time(af_engine *e, double v) { AF_LIVE_PARAM_SETTER(e->selected().proto.limiter.set_release_time(v)); }
+int af_limiter_set_lookahead_ms(af_engine *e, double v) { AF_SETTER(e->selected().proto.limiter.set_lookahead_ms(v)); }
+double af_limiter_ceiling_db(const af_engine *e) { return e ? e->selected().proto.limiter.ceiling_db : 0.0; }
+int32_t af_limiter_lookahead_samples(const af_engine *e) { return e ? e->selected().proto.limiter.lookahead_samples : 0; }
 
-int af_true_peak_limiter_set_release_ms(af_engine *e, float ms) { AF_LIVE_PARAM_SETTER(cur(e).tp_limiter.set_release_ms(ms)); }
+int af_true_peak_limiter_set_release_ms(af_engine *e, float ms) { AF_LIVE_PARAM_SETTER(e->selected().proto.tp_limiter.set_release_ms(ms)); }
 
 // Live: the de-esser's scalar settings are parameters only (deesser.rs:294-353).  Its cut frequencies move nine filters
 // (set_bounds, deesser.rs:64-73): each detector filter and each dynamic EQ gets a crossfade from its live memories, and the
 // dynamic EQ's crossfade runs from the stream's live coefficients to the new centre / Q at the stream's momentary gain --
 // per-stream values, computed on the device into the rows at dyn_pending_row.
 static void live_deesser_bounds(af_engine *e) {
-  e->live_cuts.resize(1 + e->extra_presets.size(), 0);
+  e->live_cuts.resize(e->presets.size(), 0);
   e->live_cuts[(size_t)e->current_preset] = 1;
-  const af::DeEsserParams dp = cur(e).deesser.params();
+  const af::DeEsserParams dp = e->selected().proto.deesser.params();
   for (int i = 0; i < 3; ++i) {
     const int base = af::kDeBand0 + i * af::kDeBandStride;
     for (int z_row : {base + 11, base + 15, base + 19}) live_restart_section(e, z_row);  // detector_hp, detector_lp, dynamic_eq
@@ -1711,15 +1605,15 @@ static void live_deesser_bounds(af_engine *e) {
 }
 #define AF_DEESSER_CUT_LIVE_CHECK                                                                                              \
   if (e->dyn_pending_row == 0) return fail(AF_ERR_BACKEND, "internal: live control is on but the pending-coefficient rows are missing")
-int af_deesser_set_auto_enabled(af_engine *e, int32_t on) { AF_LIVE_PARAM_SETTER(cur(e).deesser.auto_enabled = on != 0); }
-int af_deesser_set_auto_amount(af_engine *e, double v) { AF_LIVE_PARAM_SETTER(cur(e).deesser.set_auto_amount(v)); }
-int af_deesser_set_low_cut_hz(af_engine *e, double v) { AF_LIVE_SETTER(AF_DEESSER_CUT_LIVE_CHECK, cur(e).deesser.set_low_cut_hz(v), live_deesser_bounds(e)); }
-int af_deesser_set_high_cut_hz(af_engine *e, double v) { AF_LIVE_SETTER(AF_DEESSER_CUT_LIVE_CHECK, cur(e).deesser.set_high_cut_hz(v), live_deesser_bounds(e)); }
-int af_deesser_set_threshold_db(af_engine *e, double v) { AF_LIVE_PARAM_SETTER(cur(e).deesser.set_threshold_db(v)); }
-int af_deesser_set_ratio(af_engine *e, double v) { AF_LIVE_PARAM_SETTER(cur(e).deesser.set_ratio(v)); }
-int af_deesser_set_attack_ms(af_engine *e, double v) { AF_LIVE_PARAM_SETTER(cur(e).deesser.set_attack_ms(v)); }
-int af_deesser_set_release_ms(af_engine *e, double v) { AF_LIVE_PARAM_SETTER(cur(e).deesser.set_release_ms(v)); }
-int af_deesser_set_max_reduction_db(af_engine *e, double v) { AF_LIVE_PARAM_SETTER(cur(e).deesser.set_max_reduction_db(v)); }
+int af_deesser_set_auto_enabled(af_engine *e, int32_t on) { AF_LIVE_PARAM_SETTER(e->selected().proto.deesser.auto_enabled = on != 0); }
+int af_deesser_set_auto_amount(af_engine *e, double v) { AF_LIVE_PARAM_SETTER(e->selected().proto.deesser.set_auto_amount(v)); }
+int af_deesser_set_low_cut_hz(af_engine *e, double v) { AF_LIVE_SETTER(AF_DEESSER_CUT_LIVE_CHECK, e->selected().proto.deesser.set_low_cut_hz(v), live_deesser_bounds(e)); }
+int af_deesser_set_high_cut_hz(af_engine *e, double v) { AF_LIVE_SETTER(AF_DEESSER_CUT_LIVE_CHECK, e->selected().proto.deesser.set_high_cut_hz(v), live_deesser_bounds(e)); }
+int af_deesser_set_threshold_db(af_engine *e, double v) { AF_LIVE_PARAM_SETTER(e->selected().proto.deesser.set_threshold_db(v)); }
+int af_deesser_set_ratio(af_engine *e, double v) { AF_LIVE_PARAM_SETTER(e->selected().proto.deesser.set_ratio(v)); }
+int af_deesser_set_attack_ms(af_engine *e, double v) { AF_LIVE_PARAM_SETTER(e->selected().proto.deesser.set_attack_ms(v)); }
+int af_deesser_set_release_ms(af_engine *e, double v) { AF_LIVE_PARAM_SETTER(e->selected().proto.deesser.set_release_ms(v)); }
+int af_deesser_set_max_reduction_db(af_engine *e, double v) { AF_LIVE_PARAM_SETTER(e->selected().proto.deesser.set_max_reduction_db(v)); }
 
 // ---- RNNoise suppressor (rust-core/src/dsp/rnnoise.rs) ----
 int af_engine_set_suppressor_enabled(af_engine *e, int32_t on) { AF_SETTER(e->supp.enabled = on != 0); }
@@ -2037,25 +1931,26 @@ int af_suppressor_debug_pitch_search(const float *spans, int32_t n_streams, int3
 int af_engine_set_preset_count(af_engine *e, int32_t n) {
   if (n < 1 || n > 256) return fail(AF_ERR_INVALID_ARGUMENT, "preset count must be in [1, 256]");
   if (int rc = require_config(e)) return rc;
-  while ((int)e->extra_presets.size() > n - 1) e->extra_presets.pop_back();
-  while ((int)e->extra_presets.size() < n - 1) {  // a fresh OfflineDspBlockProcessor::new(sample_rate), block_processor.rs:46-60
-    e->extra_presets.emplace_back(e->proto.sample_rate);
-    af::ChainProto &np = e->extra_presets.back().proto;
-    np.control_block = e->proto.control_block;
-    np.input_scrub = e->proto.input_scrub;
-    np.input_clamp = e->proto.input_clamp;
-    np.dc_block = e->proto.dc_block;
-    np.pre_highpass = e->proto.pre_highpass;
+  while (e->n_presets() > n) e->presets.pop_back();
+  while (e->n_presets() < n) {  // a fresh OfflineDspBlockProcessor::new(sample_rate), block_processor.rs:46-60
+    e->presets.emplace_back(e->base().proto.sample_rate);  // (may reallocate: base() is taken anew below)
+    af::ChainProto &np = e->presets.back().proto;
+    const af::ChainProto &p0 = e->base().proto;
+    np.control_block = p0.control_block;
+    np.input_scrub = p0.input_scrub;
+    np.input_clamp = p0.input_clamp;
+    np.dc_block = p0.dc_block;
+    np.pre_highpass = p0.pre_highpass;
   }
   if (e->current_preset >= n) e->current_preset = 0;
   for (int32_t &g : e->group_preset)
     if (g >= n) g = 0;
   return AF_OK;
 }
-int32_t af_engine_preset_count(const af_engine *e) { return e ? 1 + (int32_t)e->extra_presets.size() : 0; }
+int32_t af_engine_preset_count(const af_engine *e) { return e ? e->n_presets() : 0; }
 int af_engine_select_preset(af_engine *e, int32_t preset) {
   if (!e) return fail(AF_ERR_INVALID_ARGUMENT, "engine is null");
-  if (preset < 0 || preset > (int32_t)e->extra_presets.size()) return fail(AF_ERR_INVALID_ARGUMENT, "preset %d does not exist", preset);
+  if (preset < 0 || preset >= e->n_presets()) return fail(AF_ERR_INVALID_ARGUMENT, "preset %d does not exist", preset);
   e->current_preset = preset;
   return AF_OK;
 }
@@ -2064,7 +1959,7 @@ int af_engine_assign_presets(af_engine *e, const int32_t *preset_of_group, int32
   if (n_groups != (e->n_streams + 63) / 64)
     return fail(AF_ERR_INVALID_ARGUMENT, "expected one preset index per group of 64 streams (%d), got %d", (e->n_streams + 63) / 64, n_groups);
   for (int32_t g = 0; g < n_groups; ++g)
-    if (preset_of_group[g] < 0 || preset_of_group[g] > (int32_t)e->extra_presets.size())
+    if (preset_of_group[g] < 0 || preset_of_group[g] >= e->n_presets())
       return fail(AF_ERR_INVALID_ARGUMENT, "group %d: preset %d does not exist", g, preset_of_group[g]);
   if (int rc = require_config(e)) return rc;
   e->group_preset.assign(preset_of_group, preset_of_group + n_groups);
@@ -2105,9 +2000,9 @@ int af_engine_set_timing_enabled(af_engine *e, int32_t on) {
 
 // a call that runs n_run samples per stream needs evidence, where evidence is pending, for exactly its control blocks
 static int check_evidence_blocks(const af_engine *e, int64_t n_run) {
-  const int cb = e->host_params.control_block;
+  const int cb = e->base().params.control_block;
   const int64_t blocks = (n_run + cb - 1) / cb;
-  if (n_run > 0 && (e->host_params.flags & af::kFlagCompressor) && e->host_params.comp.auto_makeup_enabled && e->has_evidence &&
+  if (n_run > 0 && (e->base().params.flags & af::kFlagCompressor) && e->base().params.comp.auto_makeup_enabled && e->has_evidence &&
       e->vad_blocks != blocks)
     return fail(AF_ERR_INVALID_ARGUMENT, "expected %lld VAD probabilities at the control cadence, got %lld",
                 (long long)blocks, (long long)e->vad_blocks);
@@ -2183,37 +2078,18 @@ static void supp_front_end(const af_engine *e, const af::ChainParams &hp, uint32
   sa.f32_dc_x1 = af::kDcX1;
 }
 
-// `d_params_eq` holds kEqParamSlots blocks per preset (sized as the stage pipeline sizes it)
-static int ensure_eq_params(af_engine *e, int n_presets) {
-  if (!e->d_params_eq || e->eq_params_presets != n_presets) {
-    e->d_params_eq.release();
-    AF_HIP(e->d_params_eq.reserve_exact(sizeof(af::ChainParams) * n_presets * kEqParamSlots));
-    e->eq_params_presets = n_presets;
-    e->uploaded_eq.clear();
-  }
-  return AF_OK;
-}
-
-// `d_params_eq` <- `runs`, on `stream`, unless that is what it holds
-static int upload_eq_params_if_changed(af_engine *e, const std::vector<af::ChainParams> &runs, hipStream_t stream) {
-  if (e->uploaded_eq.size() == runs.size() && std::memcmp(e->uploaded_eq.data(), runs.data(), sizeof(af::ChainParams) * runs.size()) == 0)
-    return AF_OK;
-  e->uploaded_eq = runs;
-  return stage_upload(e, e->d_params_eq, runs.data(), runs.size(), stream);
-}
-
 // ---- path 1: the chain as a pipeline of stage kernels over windows of whole control blocks (af_stages.hip)
 // (a launch step costs ~20 us, the pipeline's fill is depth x window time: 960 samples 45.7 ms per 10 s at 256 streams,
 // 1920 41.2, 2880 39.7, 4800 42.7, 9600 40.3)
 static int run_stage_pipeline(af_engine *e, const CallArgs &c) {
-  const int cb = e->host_params.control_block;
+  const int cb = e->base().params.control_block;
   const int64_t tw = whole_blocks(cb, af::switches().stage_window);
   if (int rc = stage_pipe_prepare(e, std::max<int64_t>(tw, e->pipe.tw_max))) return rc;
-  e->pipe.strip = e->host_params.flags & c.gate_strip;
+  e->pipe.strip = e->base().params.flags & c.gate_strip;
   if (int rc = stage_chain_params(e, c.stream)) return rc;  // what the stage kernels read (everything but the EQ sections)
   e->last_kernel_used = AF_KERNEL_STAGED;
   // one launch step per window on the caller's stream: step j runs every stage on the window it has reached
-  const StagePlan plan = stage_plan(e->host_params);
+  const StagePlan plan = stage_plan(e->base().params);
   std::vector<af::DiagWin> wins;
   int64_t blocks_at = 0;
   for (int64_t t0 = 0; t0 < c.n_samples; t0 += tw) {
@@ -2231,7 +2107,7 @@ static int run_stage_pipeline(af_engine *e, const CallArgs &c) {
       wins[(size_t)j].eq_crossfade = crossfade ? 1 : 0;
       advance_crossfades(e, wins[(size_t)j].n);
     }
-    if (int rc = stage_diag_step(e, e->host_params, plan, wins, j, c.stream)) return rc;
+    if (int rc = stage_diag_step(e, e->base().params, plan, wins, j, c.stream)) return rc;
   }
   e->pipe.windows += (int64_t)wins.size();
   return AF_OK;
@@ -2243,22 +2119,22 @@ static int run_stage_pipeline(af_engine *e, const CallArgs &c) {
 // the suppressor's pipeline uses).  Taken when the streams can be CU-partitioned and the EQ kernel serves the
 // configuration; everything else is the plain segment launch on the caller's stream.
 static int run_chain_launch(af_engine *e, const CallArgs &c) {
-  const int cb = e->host_params.control_block;
+  const int cb = e->base().params.control_block;
   const hipStream_t stream = c.stream;
-  af::ChainParams hp = e->host_params;  // (a copy: with the gate on, the front end is the pre-pass's)
+  af::ChainParams hp = e->base().params;  // (a copy: with the gate on, the front end is the pre-pass's)
   hp.flags &= ~c.gate_strip;
   const bool auto_mk = (hp.flags & af::kFlagCompressor) && hp.comp.auto_makeup_enabled;
   const int64_t window = whole_blocks(cb, 9600);
   // (the chain launch lays out its LDS for a crossfade only when one is pending at the call's start, as
   // launch_chain_segment sizes it: checking the crossfade layout always kept 15 and 16 sections off this form)
   bool offload = af::switches().chain_persistent && af::switches().eq_offload && (e->kernel == AF_KERNEL_AUTO || e->kernel == AF_KERNEL_PHASED) &&
-                 (e->ring_variant == 0 || e->ring_variant == 1604) && e->extra_presets.empty() && af::switches().roles == 0 &&
+                 (e->ring_variant == 0 || e->ring_variant == 1604) && e->n_presets() == 1 && af::switches().roles == 0 &&
                  c.layout == AF_LAYOUT_STREAM_MAJOR && (hp.flags & af::kFlagEq) && hp.n_eq_sections > 0 &&
                  eq_side_launch_serves(hp, af::kFlagPrePass, eq_crossfade_pending(hp)) && c.n_samples >= 2 * window &&
                  !af::switches().serial_streams;
   if (offload) {
     if (int rc = ensure_side_streams(e, stream)) return rc;
-    offload = e->partition_chain_cus > 0 && !e->borrowed_streams;
+    offload = e->partition_chain_cus > 0;
   }
   if (!offload)  // (no suppressor: everything is chain time)
     return launch_chain_segment(e, hp, c.gate_strip != 0, c.chain_in, c.out, c.n_samples, c.stream_stride, c.layout, e->samples_processed,
@@ -2278,13 +2154,11 @@ static int run_chain_launch(af_engine *e, const CallArgs &c) {
                                     e->has_evidence ? e->d_vad : nullptr, e->aux_stream, stream, /*stats_cleared=*/true,
                                     auto_mk ? e->d_block_power : nullptr, e->d_ready))
     return rc;
-  if (int rc = ensure_eq_params(e, 1)) return rc;
   int64_t blocks_done = 0;
   for (int64_t seg0 = 0; seg0 < c.n_samples; seg0 += window) {
     const int64_t seg_n = std::min<int64_t>(window, c.n_samples - seg0);
-    std::vector<af::ChainParams> run_eq(1, e->host_params);  // (as the crossfade counters stand at this window)
-    run_eq[0].flags &= ~c.gate_strip;
-    if (int rc = upload_eq_params_if_changed(e, run_eq, e->eq_stream)) return rc;
+    const std::vector<af::ChainParams> run_eq = run_params(e, c.gate_strip);  // (as the crossfade counters stand at this window)
+    AF_HIP(e->d_params_eq.sync(run_eq.data(), run_eq.size(), e->stager, e->eq_stream));
     AF_HIP(af::launch_eq_systolic(e->d_params_eq, nullptr, e->d_st64, c.chain_in + seg0, c.out + seg0, nullptr, nullptr, 0, 0,
                                   e->d_stats + blocks_done * e->n_streams, eq_crossfade_pending(run_eq[0]), seg_n, c.stream_stride, e->n_streams,
                                   e->eq_stream,
@@ -2294,7 +2168,7 @@ static int run_chain_launch(af_engine *e, const CallArgs &c) {
     advance_crossfades(e, seg_n);
     blocks_done += (seg_n + cb - 1) / cb;
   }
-  for (hipStream_t side : {e->aux_stream, e->eq_stream}) {
+  for (hipStream_t side : {e->aux_stream.get(), e->eq_stream.get()}) {
     if (int rc = engine_event(e, &ev)) return rc;
     AF_HIP(hipEventRecord(ev, side));
     AF_HIP(hipStreamWaitEvent(stream, ev, 0));
@@ -2316,12 +2190,12 @@ static int run_chain_launch(af_engine *e, const CallArgs &c) {
 static int run_suppressor_pipeline(af_engine *e, const CallArgs &c, const float *src, int64_t src_stride, bool fused_gate,
                                    const af::VadGateArgs &vad_args) {
   const af::Switches &sw = af::switches();
-  const int cb = e->host_params.control_block;
+  const int cb = e->base().params.control_block;
   const hipStream_t stream = c.stream;
   float *const out = c.out;
   const int64_t stream_stride = c.stream_stride;
   if (e->supp.weights_dirty) AF_HIP(e->supp.upload());
-  af::ChainParams run = e->host_params;
+  af::ChainParams run = e->base().params;
   bool run_modified = false;
   const uint32_t front = af::kFlagInputClamp | af::kFlagDcBlock | af::kFlagPreHighpass;
   const uint32_t front_flags = run.flags & front;
@@ -2350,7 +2224,7 @@ static int run_suppressor_pipeline(af_engine *e, const CallArgs &c, const float 
   const int64_t chain_tw = whole_blocks(cb, kStageWindowSamples);
   if (e->pipe.active) {
     if (int rc = stage_pipe_prepare(e, std::max<int64_t>(chain_tw, e->pipe.tw_max))) return rc;
-    e->pipe.strip = e->host_params.flags & ~run.flags;  // what the pre-pass has taken over
+    e->pipe.strip = e->base().params.flags & ~run.flags;  // what the pre-pass has taken over
     if (int rc = stage_chain_params(e, stream)) return rc;  // (everything but the EQ sections is read from here)
   }
   if (int rc = ensure_side_streams(e, stream)) return rc;
@@ -2381,7 +2255,7 @@ static int run_suppressor_pipeline(af_engine *e, const CallArgs &c, const float 
   // state planes' load and write-back per window, and the fill / drain of the 16-wave pipeline per launch.
   // AF_CHAIN_PERSISTENT=0 restores one launch per window (A/B runs).
   const bool persistent = sw.chain_persistent && eq_offload && e->partition_chain_cus > 0 && !e->pipe.active && !sw.diag_skip_chain &&
-                          e->extra_presets.empty() && sw.roles == 0 && (e->kernel == AF_KERNEL_AUTO || e->kernel == AF_KERNEL_PHASED) &&
+                          e->n_presets() == 1 && sw.roles == 0 && (e->kernel == AF_KERNEL_AUTO || e->kernel == AF_KERNEL_PHASED) &&
                           c.layout == AF_LAYOUT_STREAM_MAJOR && eq_side_launch_serves(run, 0, false) &&
                           (!auto_makeup_call || e->d_block_power != nullptr) && wins.size() >= 2;
   if (persistent) {
@@ -2427,7 +2301,7 @@ static int run_suppressor_pipeline(af_engine *e, const CallArgs &c, const float 
     sa.raw_protocol = e->supp.raw_protocol ? 1 : 0;
     supp_front_end(e, run, front_flags, sa);
     if (e->gate_enabled) {
-      sa.front_scrub = (front_flags || (e->host_params.flags & af::kFlagInputScrub)) ? 1 : 0;
+      sa.front_scrub = (front_flags || (e->base().params.flags & af::kFlagInputScrub)) ? 1 : 0;
       gate_args(e, sa);
     }
     if (index > 0) {  // history = tail of the previous window's buffer
@@ -2478,7 +2352,7 @@ static int run_suppressor_pipeline(af_engine *e, const CallArgs &c, const float 
   };
   // a window is behind us: crossfade bookkeeping may have moved the parameters on
   auto window_done = [&](int64_t seg_n) {
-    run = e->host_params;
+    run = e->base().params;
     if (strip_front) run.flags &= ~(front | af::kFlagInputScrub);
     blocks_done += (seg_n + cb - 1) / cb;
   };
@@ -2542,24 +2416,20 @@ static int run_suppressor_pipeline(af_engine *e, const CallArgs &c, const float 
     // ---- the window's EQ on the suppressor's side (af_eq_systolic.hip), when the chain's launch would be the plain
     // one-launch form of the token-ring kernel
     if (eq_offload && !sw.diag_skip_chain) {
-      const int n_presets = 1 + (int)e->extra_presets.size();
+      const std::vector<af::ChainParams> runs_eq = run_params(e, e->base().params.flags & ~run.flags);  // (strip: what the pre-pass has taken over)
       bool ok = true, xf_w = false;
-      std::vector<af::ChainParams> runs_eq((size_t)n_presets);
-      for (int k = 0; k < n_presets && ok; ++k) {
-        runs_eq[k] = preset_params(e, k);
-        runs_eq[k].flags &= ~(e->host_params.flags & ~run.flags);  // what the pre-pass has taken over
-        ok = eq_side_launch_serves(runs_eq[k], 0, false);
+      for (const af::ChainParams &run_eq : runs_eq) {
+        ok = ok && eq_side_launch_serves(run_eq, 0, false);
         // (a pending coefficient crossfade -- the 72 samples the legacy setters open a stream with -- runs in the systolic
         // kernel's general form; round 2 kept such windows' EQ inside the chain launch)
-        xf_w = xf_w || eq_crossfade_pending(runs_eq[k]);
+        xf_w = xf_w || eq_crossfade_pending(run_eq);
       }
       if (ok) {
         const hipStream_t es = e->eq_stream;  // behind the window's overlap-add, beside the next window's synthesis
         AF_HIP(hipStreamWaitEvent(es, syn_done[w], 0));
-        if (int rc = ensure_eq_params(e, n_presets)) return rc;
         // (always on the EQ stream, never the caller's: a copy on the legacy default stream waits for every other stream --
         // the resident chain launch included, which waits for this window: the call would run into the launch's bound)
-        if (int rc = upload_eq_params_if_changed(e, runs_eq, es)) return rc;
+        AF_HIP(e->d_params_eq.sync(runs_eq.data(), runs_eq.size(), e->stager, es));
         if (eq_needs_chain_done) {  // the previous window's EQ ran inside its chain launch: that launch owns the memories until it ends
           hipEvent_t chain_done;
           if (int rc = next_event(&chain_done)) return rc;
@@ -2568,11 +2438,11 @@ static int run_suppressor_pipeline(af_engine *e, const CallArgs &c, const float 
           eq_needs_chain_done = false;
         }
         power_w = auto_makeup_call ? e->d_block_power + blocks_done * e->n_streams : nullptr;
-        AF_HIP(af::launch_eq_systolic(e->d_params_eq, e->extra_presets.empty() ? nullptr : e->d_group_preset, e->d_st64, out + seg0, out + seg0, nullptr, nullptr, 0, 0,
+        AF_HIP(af::launch_eq_systolic(e->d_params_eq, e->n_presets() == 1 ? nullptr : e->d_group_preset, e->d_st64, out + seg0, out + seg0, nullptr, nullptr, 0, 0,
                                       e->d_stats + blocks_done * e->n_streams, xf_w, seg_n, stream_stride, e->n_streams, es, power_w,
                                       // the lane-per-stream form where the suppressor's kernels want the issue slots and nothing waits
                                       // for the EQ's own latency (an auto-makeup window's block powers do): 184.5 -> 182.4 ms per step
-                                      (n_presets == 1 && (!power_w || sw.eq_stream_power) && (runs_eq[0].flags & af::kFlagEq)) ? runs_eq[0].n_eq_sections : -1));
+                                      (e->n_presets() == 1 && (!power_w || sw.eq_stream_power) && (runs_eq[0].flags & af::kFlagEq)) ? runs_eq[0].n_eq_sections : -1));
         e->last_launches += 1;
         if (persistent) {  // the running chain launch picks the window up from here
           AF_HIP(af::launch_chain_publish_ready(e->d_ready, seg0 + seg_n, es));
@@ -2658,11 +2528,11 @@ static int process_device_impl(af_engine *e, const float *in, float *out, int64_
       return fail(AF_ERR_INVALID_ARGUMENT, "this call completes %lld samples per stream (%d were pending): stream_stride %lld is too small",
                   (long long)n_run, e->pending, (long long)stream_stride);
   }
-  const int cb = e->host_params.control_block;
+  const int cb = e->base().params.control_block;
   const int64_t blocks = (n_run + cb - 1) / cb;
   if (int rc = check_evidence_blocks(e, n_run)) return rc;
   if (n_run > 0 && !e->pipe.decided) {  // first call after a reset: which form of the chain this engine runs
-    af::ChainParams probe = e->host_params;
+    af::ChainParams probe = e->base().params;
     if (e->supp.enabled || e->gate_enabled) probe.flags &= ~(af::kFlagInputClamp | af::kFlagDcBlock | af::kFlagPreHighpass | af::kFlagInputScrub);
     const bool serves = stage_pipe_serves(e, probe, layout);
     const int env_staged = af::switches().staged;  // AF_STAGED=0 / 1: keep AUTO off / on the stage pipeline (A/B runs)
@@ -2672,7 +2542,7 @@ static int process_device_impl(af_engine *e, const float *in, float *out, int64_
     // (with the de-esser at any batch: its lane-per-stream form takes 417 ms per 2 s of audio whatever the batch)
     // (and several presets with auto-makeup: the token-ring kernel's pre-pass pair is a single-preset build)
     const bool deesser_staged = (probe.flags & af::kFlagDeesser) != 0 ||
-                                (!e->extra_presets.empty() && (probe.flags & af::kFlagCompressor) && probe.comp.auto_makeup_enabled);
+                                (e->n_presets() > 1 && (probe.flags & af::kFlagCompressor) && probe.comp.auto_makeup_enabled);
     // (the per-stream lifecycle keeps AUTO off the pipeline, whose rings are the histories: the forms above its stream limit serve)
     e->pipe.active = serves && !e->life.enabled && (e->kernel == AF_KERNEL_STAGED || (e->kernel == AF_KERNEL_AUTO && env_staged != 0 &&
                                  (deesser_staged || e->n_streams <= (e->supp.enabled ? kStagedAutoMaxStreamsBehindSuppressor : kStagedAutoMaxStreams))) ||
@@ -2744,7 +2614,7 @@ static int process_device_impl(af_engine *e, const float *in, float *out, int64_
                                   ? (af::kFlagInputScrub | af::kFlagInputClamp | af::kFlagDcBlock | af::kFlagPreHighpass) : 0u;
   const float *chain_in = in;
   if (gate_strip) {
-    const af::ChainParams &hp = e->host_params;
+    const af::ChainParams &hp = e->base().params;
     af::SuppArgs sa{};
     sa.in = in;
     sa.in_stride = stream_stride;
@@ -3065,8 +2935,8 @@ static int stream_host_resampled(af_engine *e, const float *in, int64_t n_in, fl
       e->ow_fill_dirty = false;
     }
     // limiter_enabled and the ceiling as the loop takes them from the limiter (dsp_loop.rs:535, output_writer.rs:208-215)
-    if (int rc = af_output_writer_set_limiter(e->ow, e->proto.limiter_enabled ? 1 : 0,
-                                              std::pow(10.0f, (float)e->proto.limiter.ceiling_db / 20.0f))) return rc;
+    if (int rc = af_output_writer_set_limiter(e->ow, e->base().proto.limiter_enabled ? 1 : 0,
+                                              std::pow(10.0f, (float)e->base().proto.limiter.ceiling_db / 20.0f))) return rc;
     if (int rc = af_output_writer_push_device(e->ow, res, m3, res_stride, e->d_ow_fill, 0, e->d_ow_out, ow_width, ow_width,
                                               e->d_ow_written, nullptr)) return rc;
     AF_HIP(hipStreamSynchronize(nullptr));
@@ -3220,12 +3090,12 @@ ss::Shape lifecycle_shape(af_engine *e, int k) {
     export_params(e);
     plane_heights(e, &n64, &n32, &first_live);
   }
-  const af::ChainParams &hp = preset_params(e, k);
+  const af::ChainParams &hp = e->presets[k].params;
   ss::Shape s{};
   s.sample_rate = e->sample_rate;
   s.control_block = hp.control_block;
   s.n_eq_sections = hp.n_eq_sections;
-  s.lookahead = preset_proto(e, k).limiter.lookahead_samples;
+  s.lookahead = e->presets[k].proto.limiter.lookahead_samples;
   s.meter_slots = preset_meter_slots(e, k);
   s.stage_flags = (hp.flags & ss::kStageMask) | (s.meter_slots > 0 ? ss::kStageAutoMakeup : 0u);
   s.suppressor = e->supp.enabled ? 1 : 0;
@@ -3268,12 +3138,12 @@ int lifecycle_accepts_state(af_engine *e, const char *what) {
   if (e->pending > 0)
     return fail(AF_ERR_UNSUPPORTED, "%s: %d samples per stream are pending in the suppressor's frame assembly, which all streams share; "
                                     "feed whole 480-sample frames first", what, e->pending);
-  const int cb = e->host_params.control_block;
+  const int cb = e->base().params.control_block;
   if (cb > 0 && e->samples_processed % cb != 0)
     return fail(AF_ERR_UNSUPPORTED, "%s: the engine's sample count %lld is not a whole number of %d-sample control blocks", what,
                 (long long)e->samples_processed, cb);
-  for (int k = 0; k <= (int)e->extra_presets.size(); ++k) {
-    const af::ChainParams &o = preset_params(e, k);
+  for (int k = 0; k < e->n_presets(); ++k) {
+    const af::ChainParams &o = e->presets[k].params;
     bool xf = false;
     for (int j = 0; j < o.n_eq_sections; ++j) xf = xf || o.eq[j].xf_remaining > 0;
     if (o.flags & af::kFlagDeesser)
@@ -3310,7 +3180,7 @@ void lifecycle_slots(af_engine *e, const int32_t *streams, int32_t n, std::vecto
   slots.resize((size_t)n);
   for (int32_t i = 0; i < n; ++i) {
     const int k = preset_of_stream(e, streams[i]);
-    const int W = preset_proto(e, k).limiter.lookahead_samples + 1;
+    const int W = e->presets[k].proto.limiter.lookahead_samples + 1;
     slots[(size_t)i] = ss::Slot{streams[i], k, W, (int32_t)(e->samples_processed % W)};
   }
 }
@@ -3339,7 +3209,7 @@ int af_engine_restart_streams(af_engine *e, const int32_t *streams, int32_t n) {
   AF_HIP(e->use_device());
   hipStream_t stream = e->last_stream;
   // one upload: [prototype f64 columns | slot list | prototype f32 columns], then one launch; the host waits for neither
-  const int n_presets = 1 + (int)e->extra_presets.size();
+  const int n_presets = e->n_presets();
   const size_t b64 = sizeof(double) * (size_t)n_presets * e->n_f64, bsl = sizeof(ss::Slot) * (size_t)n;
   std::vector<unsigned char> host(round16(b64) + round16(bsl) + sizeof(float) * (size_t)n_presets * af::kF32Fixed, 0);
   double *p64 = reinterpret_cast<double *>(host.data());
@@ -3480,7 +3350,7 @@ int af_eq_magnitude_response_v2(const double *freqs, size_t n, const af_eq_band_
 
 int af_engine_eq_magnitude_response(const af_engine *e, const double *freqs, size_t n, double *out_db) {
   if (!e || (!freqs && n) || (!out_db && n)) return fail(AF_ERR_INVALID_ARGUMENT, "null argument");
-  for (size_t i = 0; i < n; ++i) out_db[i] = cur(e).eq.magnitude_db(freqs[i]);
+  for (size_t i = 0; i < n; ++i) out_db[i] = e->selected().proto.eq.magnitude_db(freqs[i]);
   return AF_OK;
 }
 
@@ -3546,11 +3416,11 @@ int af_noise_suppressor_create(int32_t model, int32_t n_streams, int32_t device,
   if (model != AF_NOISE_MODEL_RNNOISE) return fail(AF_ERR_INVALID_ARGUMENT, "unknown noise model %d", model);
   af_engine *e = nullptr;
   if (int rc = af_engine_create(48000.0, n_streams, device, &e)) return rc;
-  e->proto.eq_enabled = e->proto.eq.enabled = false;
-  e->proto.compressor_enabled = e->proto.compressor.enabled = false;
-  e->proto.limiter_enabled = e->proto.limiter.enabled = false;
-  e->proto.input_scrub = false;  // scale_sample_for_model zeroes non-finite model input itself (rnnoise.rs:90-93)
-  e->proto.control_block = af::kRnnFrame;
+  e->base().proto.eq_enabled = e->base().proto.eq.enabled = false;
+  e->base().proto.compressor_enabled = e->base().proto.compressor.enabled = false;
+  e->base().proto.limiter_enabled = e->base().proto.limiter.enabled = false;
+  e->base().proto.input_scrub = false;  // scale_sample_for_model zeroes non-finite model input itself (rnnoise.rs:90-93)
+  e->base().proto.control_block = af::kRnnFrame;
   e->supp.enabled = true;
   af_noise_suppressor *s = new af_noise_suppressor();
   s->engine = e;

@@ -1,7 +1,8 @@
 // af_hip_resources.hpp -- move-only owners of what the host side of the C ABI takes from the HIP runtime: device buffers,
-// pinned staging slots, events.  Host only, header only.  Every hipMalloc / hipFree / hipHostMalloc / hipHostFree /
-// hipEventCreate / hipEventDestroy of the ABI sources is in this file.  None of the owners knows a device: the object that
-// holds them makes its device current (and synchronises it) before they are used or destroyed.
+// pinned staging slots, events, streams.  Host only, header only.  Every hipMalloc / hipFree / hipHostMalloc / hipHostFree /
+// hipEventCreate / hipEventDestroy / hipStreamCreate / hipStreamDestroy of the ABI sources is in this file.  None of the
+// owners knows a device: the object that holds them makes its device current (and synchronises it) before they are used or
+// destroyed.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -9,6 +10,7 @@
 #include <cmath>
 #include <cstdint>
 #include <cstring>
+#include <type_traits>
 #include <utility>
 #include <vector>
 
@@ -199,6 +201,92 @@ class PinnedSlots {
   Event done_[N];
   bool used_[N] = {};
   int next_ = 0;
+};
+
+// An array of T on the device beside a host copy of what was last sent to it ("the device holds what I last sent"): sync()
+// uploads only what differs.  The host copy is taken only after the upload call has succeeded, and anything that could leave
+// the two apart (a failed upload, a reallocation, a send() into a sub-range) invalidates it, so the next sync() uploads again.
+template <class T>
+class Mirrored {
+  static_assert(std::is_trivially_copyable<T>::value, "Mirrored compares and copies its elements byte-wise");
+
+ public:
+  // room for `count` elements, exactly as DeviceBuffer::reserve_exact (nothing on the device may still be reading)
+  hipError_t reserve(size_t count) {
+    if (count * sizeof(T) <= buf_.bytes()) return hipSuccess;
+    invalidate();
+    return buf_.reserve_exact(count * sizeof(T));
+  }
+  // the first `count` elements <- `src`, behind everything already queued on `stream`, unless that is what they hold
+  template <int N>
+  hipError_t sync(const T *src, size_t count, PinnedSlots<N> &slots, hipStream_t stream, bool *uploaded = nullptr) {
+    if (uploaded) *uploaded = false;
+    if (count * sizeof(T) > buf_.bytes()) return hipErrorInvalidValue;
+    if (valid_ && held_.size() == count && std::memcmp(held_.data(), src, count * sizeof(T)) == 0) return hipSuccess;
+    valid_ = false;
+    if (hipError_t err = slots.upload(buf_.get(), src, count * sizeof(T), stream); err != hipSuccess) return err;
+    held_.assign(src, src + count);
+    valid_ = true;
+    if (uploaded) *uploaded = true;
+    return hipSuccess;
+  }
+  // elements [offset, offset + count) <- `src`, always: for slots of the array that are rewritten in turn
+  template <int N>
+  hipError_t send(size_t offset, const T *src, size_t count, PinnedSlots<N> &slots, hipStream_t stream) {
+    invalidate();
+    if ((offset + count) * sizeof(T) > buf_.bytes()) return hipErrorInvalidValue;
+    return slots.upload(buf_.get() + offset, src, count * sizeof(T), stream);
+  }
+  void invalidate() { valid_ = false; }
+  T *get() const { return buf_.get(); }
+  operator T *() const { return get(); }
+
+ private:
+  DeviceBuffer<T> buf_;
+  std::vector<T> held_;  // what the device holds, while valid_
+  bool valid_ = false;
+};
+
+// A stream: empty, owned (created non-blocking or with a CU mask: destroyed with the owner), or borrowed (an alias of a
+// stream of the caller's: never destroyed).
+class Stream {
+ public:
+  Stream() = default;
+  Stream(Stream &&o) noexcept : st_(std::exchange(o.st_, nullptr)), owned_(std::exchange(o.owned_, false)) {}
+  Stream &operator=(Stream &&o) noexcept {
+    if (this != &o) { reset(); st_ = std::exchange(o.st_, nullptr); owned_ = std::exchange(o.owned_, false); }
+    return *this;
+  }
+  ~Stream() { reset(); }
+  // each of the three lets go of what was held; after a failed creation the owner is empty
+  hipError_t create() {
+    reset();
+    return adopt(hipStreamCreateWithFlags(&st_, hipStreamNonBlocking));
+  }
+  hipError_t create_with_cu_mask(uint32_t words, const uint32_t *mask) {
+    reset();
+    return adopt(hipExtStreamCreateWithCUMask(&st_, words, mask));
+  }
+  void borrow(hipStream_t st) {
+    reset();
+    st_ = st;
+  }
+  void reset() {
+    if (owned_ && st_) (void)hipStreamDestroy(st_);
+    st_ = nullptr;
+    owned_ = false;
+  }
+  hipStream_t get() const { return st_; }
+  operator hipStream_t() const { return st_; }
+
+ private:
+  hipError_t adopt(hipError_t created) {
+    owned_ = created == hipSuccess;
+    if (!owned_) st_ = nullptr;
+    return created;
+  }
+  hipStream_t st_ = nullptr;
+  bool owned_ = false;
 };
 
 // A timing bracket: two events, created at the first begin().  Unused (never begun, or begun and not ended, or a creation

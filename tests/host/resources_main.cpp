@@ -1,6 +1,6 @@
 // Stand-alone test of csrc/af_hip_resources.hpp against a fake HIP runtime defined in this file (it is not linked against
-// the real one): allocations over malloc, one stream whose copies and event records run when the test drains it, and a
-// switch that fails the k-th fallible call.  Built with -fsanitize=address,undefined by tests/test_host_resources.py.
+// the real one): allocations over malloc, one queue for every stream, whose copies and event records run when the test drains
+// it, live sets of what was created, and a switch that fails the k-th fallible call.  Built with -fsanitize=address,undefined by tests/test_host_resources.py.
 #include "af_hip_resources.hpp"
 
 #include <cstdio>
@@ -15,6 +15,8 @@ struct Op { Ev *ev; uint64_t seq; void *dst; const void *src; size_t bytes; };  
 std::deque<Op> queue;
 std::map<void *, size_t> device, pinned;  // live allocations and their sizes
 std::set<Ev *> events;
+std::set<hipStream_t> streams;  // live streams the fake created
+long stream_destroys = 0;
 uint64_t seq = 0;
 long calls = 0;           // every call into the fake
 long fallible = 0;        // the calls that can be told to fail
@@ -39,11 +41,18 @@ void reset() {
   queue.clear();
   record_log.clear();
   sync_log.clear();
-  calls = fallible = fail_at = pinned_allocs = blocking_waits = 0;
+  calls = fallible = fail_at = pinned_allocs = blocking_waits = stream_destroys = 0;
   query_fails_once = false;
   sticky = hipSuccess;
 }
-bool nothing_live() { return device.empty() && pinned.empty() && events.empty(); }
+bool nothing_live() { return device.empty() && pinned.empty() && events.empty() && streams.empty(); }
+hipError_t create_stream(hipStream_t *st) {
+  ++calls;
+  if (inject()) return hipErrorOutOfMemory;
+  *st = reinterpret_cast<hipStream_t>(new char);
+  streams.insert(*st);
+  return hipSuccess;
+}
 }  // namespace fake
 
 hipError_t hipMalloc(void **p, size_t n) {
@@ -127,6 +136,15 @@ hipError_t hipMemcpyAsync(void *dst, const void *src, size_t bytes, hipMemcpyKin
   ++fake::calls;
   if (fake::inject()) return hipErrorUnknown;
   fake::queue.push_back(fake::Op{nullptr, 0, dst, src, bytes});
+  return hipSuccess;
+}
+hipError_t hipStreamCreateWithFlags(hipStream_t *st, unsigned) { return fake::create_stream(st); }
+hipError_t hipExtStreamCreateWithCUMask(hipStream_t *st, uint32_t, const uint32_t *) { return fake::create_stream(st); }
+hipError_t hipStreamDestroy(hipStream_t st) {
+  ++fake::calls;
+  ++fake::stream_destroys;
+  if (!fake::streams.erase(st)) { std::fprintf(stderr, "hipStreamDestroy of a stream that is not live\n"); std::abort(); }
+  delete reinterpret_cast<char *>(st);
   return hipSuccess;
 }
 hipError_t hipGetLastError(void) { ++fake::calls; return std::exchange(fake::sticky, hipSuccess); }
@@ -288,6 +306,128 @@ static void test_timed_span() {
   CHECK(fake::nothing_live());
 }
 
+struct Block { int32_t a[5]; double b; };  // (padding included: sync() compares bytes, the tests fill every one)
+static Block block(int tag) {
+  Block v;
+  std::memset(&v, tag, sizeof v);
+  return v;
+}
+static bool same(const Block *dev, const Block *src, size_t count) { return std::memcmp(dev, src, count * sizeof(Block)) == 0; }
+
+static void test_mirrored_sync() {
+  fake::reset();
+  {
+    af::Mirrored<Block> m;
+    af::PinnedSlots<4> slots;
+    bool up = true;
+    Block src[3] = {block(1), block(2), block(3)};
+    CHECK(m.sync(src, 3, slots, nullptr, &up) == hipErrorInvalidValue && !up);  // no room yet: refused, nothing written
+    CHECK(m.reserve(3) == hipSuccess && m.get() && fake::device.size() == 1);
+    CHECK(m.sync(src, 3, slots, nullptr, &up) == hipSuccess && up);              // first use
+    fake::drain_all();
+    CHECK(same(m.get(), src, 3));
+    const long calls = fake::calls;
+    CHECK(m.sync(src, 3, slots, nullptr, &up) == hipSuccess && !up && fake::calls == calls);  // identical: no runtime call at all
+    src[1] = block(7);
+    CHECK(m.sync(src, 3, slots, nullptr, &up) == hipSuccess && up);              // one block differs
+    CHECK(m.sync(src, 2, slots, nullptr, &up) == hipSuccess && up);              // a different count is different contents
+    CHECK(m.sync(src, 2, slots, nullptr, &up) == hipSuccess && !up);
+    m.invalidate();
+    CHECK(m.sync(src, 2, slots, nullptr, &up) == hipSuccess && up);
+    CHECK(m.reserve(2) == hipSuccess && m.sync(src, 2, slots, nullptr, &up) == hipSuccess && !up);  // fits: the mirror holds
+    Block *before = m.get();
+    fake::drain_all();
+    CHECK(m.reserve(8) == hipSuccess && m.get() && fake::device.size() == 1 && !fake::device.count(before));
+    CHECK(m.sync(src, 2, slots, nullptr, &up) == hipSuccess && up);              // reallocated: the new buffer holds nothing yet
+    // a slot of the array rewritten in turn: the mirror of the front cannot vouch for the array any more
+    const Block window[2] = {block(9), block(10)};
+    CHECK(m.send(7, window, 2, slots, nullptr) == hipErrorInvalidValue);         // past the end: refused
+    CHECK(m.send(6, window, 2, slots, nullptr) == hipSuccess);
+    CHECK(m.sync(src, 2, slots, nullptr, &up) == hipSuccess && up);
+    fake::drain_all();
+    CHECK(same(m.get(), src, 2) && same(m.get() + 6, window, 2));
+    Block *const as_pointer = m;
+    CHECK(as_pointer == m.get());
+  }
+  CHECK(fake::nothing_live());
+}
+
+// Every fallible call inside a sync() fails in turn: the mirror must not claim what the device never received.
+static void test_mirrored_failures() {
+  const Block old_src[2] = {block(1), block(2)}, src[2] = {block(3), block(4)};
+  // `grow`: the upload also has to make the pinned allocation (a request larger than the slots so far)
+  for (int grow = 0; grow < 2; ++grow) {
+    long fallible_calls = 0;
+    for (long k = 0; k == 0 || k <= fallible_calls; ++k) {  // k = 0: the run that counts them
+      fake::reset();
+      {
+        af::Mirrored<Block> m;
+        af::PinnedSlots<2> slots;
+        bool up = false;
+        CHECK(m.reserve(2) == hipSuccess);
+        if (!grow) CHECK(m.sync(old_src, 2, slots, nullptr, &up) == hipSuccess && up);
+        const long before = fake::fallible;
+        if (k) fake::fail_at = before + k;
+        const hipError_t err = m.sync(src, 2, slots, nullptr, &up);
+        if (k == 0) {
+          CHECK(err == hipSuccess && up);
+          fallible_calls = fake::fallible - before;
+          CHECK(fallible_calls >= (grow ? 4 : 2));  // [pinned allocation, event creation,] copy, record
+        } else {
+          CHECK(err != hipSuccess && !up);
+          fake::fail_at = 0;
+          CHECK(m.sync(src, 2, slots, nullptr, &up) == hipSuccess && up);  // the same contents again: uploaded again
+        }
+        CHECK(m.sync(src, 2, slots, nullptr, &up) == hipSuccess && !up);
+        fake::drain_all();
+        CHECK(same(m.get(), src, 2));
+      }
+      CHECK(fake::nothing_live());
+    }
+  }
+}
+
+static void test_stream() {
+  fake::reset();
+  {
+    af::Stream none;  // empty: no call at all
+    CHECK(!none.get());
+  }
+  CHECK(fake::calls == 0);
+  hipStream_t callers = nullptr;
+  CHECK(fake::create_stream(&callers) == hipSuccess);  // a stream of the caller's
+  {
+    af::Stream owned;
+    CHECK(owned.create() == hipSuccess && owned.get() && fake::streams.size() == 2);
+    const hipStream_t handle = owned;
+    CHECK(handle == owned.get());
+    af::Stream moved(std::move(owned));  // the moved-from owner is empty and destroys nothing
+    CHECK(!owned.get() && moved.get() == handle);
+    owned.reset();
+    CHECK(fake::stream_destroys == 0);
+    af::Stream masked;
+    const uint32_t mask[2] = {0xffu, 0u};
+    fake::fail_at = fake::fallible + 1;
+    CHECK(masked.create_with_cu_mask(2, mask) != hipSuccess && !masked.get());  // a failed creation leaves it empty
+    CHECK(masked.create_with_cu_mask(2, mask) == hipSuccess && masked.get() && fake::streams.size() == 3);
+    masked = std::move(moved);  // what it held is destroyed, once
+    CHECK(fake::stream_destroys == 1 && fake::streams.size() == 2 && masked.get() == handle);
+    af::Stream alias;
+    alias.borrow(callers);
+    CHECK(alias.get() == callers);
+    af::Stream alias2(std::move(alias));
+    alias2.reset();  // a borrowed stream is never destroyed
+    CHECK(fake::stream_destroys == 1 && fake::streams.count(callers));
+    alias2.borrow(callers);
+    masked.borrow(callers);  // borrowing lets go of the owned stream
+    CHECK(fake::stream_destroys == 2 && !fake::streams.count(handle));
+    CHECK(masked.create() == hipSuccess && masked.get() != callers);  // ... and creating lets go of the alias, destroying nothing
+    CHECK(fake::stream_destroys == 2);
+  }
+  CHECK(fake::stream_destroys == 3 && fake::streams.size() == 1 && fake::streams.count(callers));
+  CHECK(hipStreamDestroy(callers) == hipSuccess && fake::nothing_live());
+}
+
 // construct each owner, grow twice, upload six times, retire, collect, destroy; stops at the first error
 static hipError_t script() {
 #define TRY(expr)                                        \
@@ -295,13 +435,22 @@ static hipError_t script() {
     if (hipError_t err__ = (expr); err__ != hipSuccess) return err__; \
   } while (0)
   af::DeviceBuffer<unsigned char> dst;
+  af::Mirrored<Block> mirror;  // (ahead of the slots: their destructor lets the queued copies run)
   af::RetireList retired;
   af::DeviceBuffer<> scratch;
   af::DeviceBuffer<double> staging;
   af::PinnedSlots<4> slots;
   af::TimedSpan span;
   af::EventChain chain;
+  af::Stream plain, masked;
+  const Block blocks[2] = {block(1), block(2)};
+  const uint32_t mask = 1u;
   unsigned char src[96] = {};
+  TRY(plain.create());
+  TRY(masked.create_with_cu_mask(1, &mask));
+  TRY(mirror.reserve(2));
+  TRY(mirror.sync(blocks, 2, slots, plain));
+  TRY(mirror.send(1, blocks, 1, slots, masked));
   TRY(dst.reserve_exact(1024));
   TRY(staging.reserve_exact(64));
   TRY(staging.reserve_exact(256));
@@ -348,6 +497,9 @@ int main() {
   test_reserve_exact();
   test_pinned_slots();
   test_timed_span();
+  test_mirrored_sync();
+  test_mirrored_failures();
+  test_stream();
   test_failure_sweep();
   const double samples[6] = {0.0, 1.0, HUGE_VAL, 2.0, 3.0, 4.0};  // 2 rows of 2, 3 apart: the infinity is in no row
   CHECK(af::check_finite(samples, 2, 2, 3) && !af::check_finite(samples, 2, 3, 3));

@@ -72,3 +72,20 @@ def test_one_launch_forms_equal_the_per_window_forms(mode, tmp_path):
             path = os.path.join(out, f"abfc_{t}.npz")
             if os.path.exists(path):
                 os.remove(path)
+
+
+def test_serial_streams_create_run_and_exit_cleanly(tmp_path):
+    """AF_SERIAL_STREAMS: the engine's side streams alias the caller's and must not be destroyed with the engine.  One engine is
+    created, runs one call (64 streams, suppressor on) and is closed in a child process (tests/switch_child.py), which must
+    exit with status 0 and return what the same call returns here, without the switch."""
+    import switch_child
+
+    out = str(tmp_path / "serial.npz")
+    done = subprocess.run([sys.executable, switch_child.__file__, "full_chain_one_call", out], env=dict(os.environ, AF_SERIAL_STREAMS="1"),
+                          capture_output=True, text=True, timeout=120)
+    assert done.returncode == 0, (done.returncode, done.stderr[-2000:])
+    want = switch_child.full_chain_one_call()
+    with np.load(out) as z:
+        assert z["y"].shape == want["y"].shape
+        assert np.array_equal(z["y"].view(np.uint32), want["y"].view(np.uint32)), f"max abs {np.abs(z['y'] - want['y']).max():.3e}"
+        assert z["rows"].tobytes() == want["rows"].tobytes()

@@ -3,6 +3,10 @@ feed-forward waves, LDS hand-over) against the token-ring kernel: the expression
 audio, every block row and the state the kernels leave behind must agree BIT FOR BIT -- including a stream that changes
 kernel between calls.  (The token-ring kernel itself is held to the CPU oracle by tests/test_gpu_parity.py; the variant
 `roles` of that file runs the oracle comparisons on this kernel directly.)"""
+import os
+import subprocess
+import sys
+
 import numpy as np
 import pytest
 
@@ -51,12 +55,17 @@ CONFIGS = {
 }
 
 
-@pytest.mark.parametrize("name", list(CONFIGS))
-def test_roles_equal_the_token_ring_bit_for_bit(name):
-    settings = CONFIGS[name]
+def three_calls(name="bench-chain"):
+    """(audio, cuts, settings, bands) of the comparison below"""
     audio = (S.batch_signal(70, 9) * np.float32(8.0)).astype(np.float32)  # 70 streams (64 + 6), 4320 samples, hot enough to limit
     bands = [(80.0 * 1.75**i, 3.0 if i % 2 else -2.5, 1.0) for i in range(10)]  # legacy setters: a crossfade opens the stream
     cuts = [1920, 3003]  # whole control blocks, then a call that ends inside a block and inside a tile
+    return audio, cuts, CONFIGS[name], bands
+
+
+@pytest.mark.parametrize("name", list(CONFIGS))
+def test_roles_equal_the_token_ring_bit_for_bit(name):
+    audio, cuts, settings, bands = three_calls(name)
     ring = _run([RING], audio, cuts, settings, bands)
     roles = _run([ROLES], audio, cuts, settings, bands)
     assert set(ring[2]) == {RING} and set(roles[2]) == {ROLES}
@@ -67,6 +76,21 @@ def test_roles_equal_the_token_ring_bit_for_bit(name):
     _same(ring, mixed)
     # both limiters really worked on this input
     assert float(ring[1]["limiter_peak_gain_reduction_db"].max()) > 0.5 and int(ring[1]["true_peak_limited_events"].sum()) > 0
+
+
+def test_the_ring_compressor_with_the_role_limiter_equals_the_token_ring(tmp_path):
+    """AF_ROLES=2: the token ring ends at the compressor's output and the limiter role kernel follows, so one segment uploads
+    two variants of the parameter block to the same buffer, the EQ kernel's and then the ring's.  The switch is read once per
+    process: the hybrid runs in a child (tests/switch_child.py), the token ring here."""
+    out = str(tmp_path / "roles2.npz")
+    child = os.path.join(os.path.dirname(os.path.abspath(__file__)), "switch_child.py")
+    done = subprocess.run([sys.executable, child, "roles_three_calls", out], env=dict(os.environ, AF_ROLES="2"), capture_output=True,
+                          text=True, timeout=120)
+    assert done.returncode == 0, done.stderr[-2000:]
+    ring = _run([RING], *three_calls())
+    with np.load(out) as z:
+        assert set(z["used"].tolist()) == {ROLES}
+        _same(ring, (z["y"], z["rows"]))
 
 
 def test_roles_behind_the_suppressor_equal_the_token_ring():
