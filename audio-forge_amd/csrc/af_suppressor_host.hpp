@@ -7,6 +7,7 @@
 #include <cstring>
 #include <vector>
 
+#include "af_hip_resources.hpp"
 #include "af_suppressor.h"
 #include "af_switches.hpp"
 
@@ -74,6 +75,100 @@ inline void synthetic_weights(RnnWeightsI8 &w, uint64_t seed) {
   fill_i8(w.denoise_out_b, sizeof w.denoise_out_b, &s, 40);
 }
 
+// What upload() sends to the device, built on the host alone (build_suppressor_blob makes no HIP call): the f32 blob -- each
+// of the eleven matrices of kRnnMatrixDims, padded to the matrix-core tiles ([k_pad][n_pad], a GRU's recurrent rows behind its
+// input rows, padding zero), followed by its bias, then the tables -- the same matrices as int8 in the network kernel's
+// operand order (w4_matrix_offset, af_suppressor.h), and where each part of the blob starts, in floats.
+struct SuppressorBlob {
+  std::vector<float> f32;
+  std::vector<uint32_t> w4;
+  size_t matrix[11], bias[11];  // in the order of kRnnMatrixDims: dense, vad z r h, noise z r h, denoise z r h, out
+  size_t tansig, half_window, dct, twiddle, frac, band_of_bin;
+};
+
+// matrix `i`: columns [gate n, gate n + n) of `w` (and of the recurrent `u`, if the layer has one), whose rows hold `gates` x n
+inline void append_matrix(SuppressorBlob &out, int i, const int8_t *w, const int8_t *u, const int8_t *b, int gate, int gates) {
+  const RnnLayerDims d = kRnnMatrixDims[i];
+  const int stride = gates * d.n, col0 = gate * d.n;
+  std::vector<float> &dst = out.f32;
+  const size_t off_w = out.matrix[i] = dst.size();
+  dst.resize(dst.size() + (size_t)d.k_pad * d.n_pad, 0.0f);
+  for (int k = 0; k < d.k_in; ++k)
+    for (int n = 0; n < d.n; ++n) dst[off_w + (size_t)k * d.n_pad + n] = (float)w[k * stride + col0 + n];
+  for (int k = 0; k < d.k_rec; ++k)
+    for (int n = 0; n < d.n; ++n) dst[off_w + (size_t)(d.k_in + k) * d.n_pad + n] = (float)u[k * stride + col0 + n];
+  const size_t off_b = out.bias[i] = dst.size();
+  dst.resize(dst.size() + d.n_pad, 0.0f);
+  for (int n = 0; n < d.n; ++n) dst[off_b + n] = (float)b[col0 + n];
+}
+
+inline SuppressorBlob build_suppressor_blob(const RnnWeightsI8 &weights) {
+  SuppressorBlob out;
+  std::vector<float> &blob = out.f32;
+  append_matrix(out, 0, weights.input_dense_w, nullptr, weights.input_dense_b, 0, 1);
+  for (int g = 0; g < 3; ++g) append_matrix(out, 1 + g, weights.vad_gru_w, weights.vad_gru_u, weights.vad_gru_b, g, 3);
+  for (int g = 0; g < 3; ++g) append_matrix(out, 4 + g, weights.noise_gru_w, weights.noise_gru_u, weights.noise_gru_b, g, 3);
+  for (int g = 0; g < 3; ++g) append_matrix(out, 7 + g, weights.denoise_gru_w, weights.denoise_gru_u, weights.denoise_gru_b, g, 3);
+  append_matrix(out, 10, weights.denoise_out_w, nullptr, weights.denoise_out_b, 0, 1);
+  const double pi = 3.14159265358979323846;
+  out.tansig = blob.size();
+  for (int i = 0; i <= 200; ++i) blob.push_back((float)std::tanh(0.04 * i));
+  while (blob.size() % 4) blob.push_back(0.0f);
+  out.half_window = blob.size();
+  for (int i = 0; i < kRnnFrame; ++i) {
+    const double sn = std::sin(.5 * pi * (i + .5) / kRnnFrame);
+    blob.push_back((float)std::sin(.5 * pi * sn * sn));
+  }
+  out.dct = blob.size();
+  for (int i = 0; i < kRnnBands; ++i)
+    for (int j = 0; j < kRnnBands; ++j) {
+      double v = std::cos((i + .5) * j * pi / kRnnBands);
+      if (j == 0) v *= std::sqrt(.5);
+      blob.push_back((float)v);
+    }
+  while (blob.size() % 4) blob.push_back(0.0f);
+  out.twiddle = blob.size();
+  for (int i = 0; i < kRnnWindow; ++i) {
+    blob.push_back((float)std::cos(-2.0 * pi * i / kRnnWindow));
+    blob.push_back((float)std::sin(-2.0 * pi * i / kRnnWindow));
+  }
+  while (blob.size() % 4) blob.push_back(0.0f);
+  out.frac = blob.size();
+  const int eband[kRnnBands] = {0, 1, 2, 3, 4, 5, 6, 7, 8, 10, 12, 14, 16, 20, 24, 28, 34, 40, 48, 60, 78, 100};
+  std::vector<int32_t> band_of(484, kRnnBands - 1);
+  blob.resize(blob.size() + 404, 0.0f);
+  for (int b = 0; b < kRnnBands - 1; ++b) {
+    const int size = (eband[b + 1] - eband[b]) << 2;
+    for (int j = 0; j < size; ++j) {
+      blob[out.frac + (eband[b] << 2) + j] = (float)j / (float)size;
+      band_of[(eband[b] << 2) + j] = b;
+    }
+  }
+  out.band_of_bin = blob.size();
+  blob.resize(blob.size() + 484);
+  std::memcpy(&blob[out.band_of_bin], band_of.data(), 484 * sizeof(int32_t));
+  // the eleven matrices back as int8 (every entry of the f32 blob is a small integer), each word at the place the network
+  // kernel reads it: dword [group][tile][lane] behind w4_matrix_offset(i), k padded to whole groups of 16 with zero weights
+  out.w4.assign((size_t)w4_matrix_offset(11), 0u);
+  for (int i = 0; i < 11; ++i) {
+    const RnnLayerDims d = kRnnMatrixDims[i];
+    const int tiles = d.n_pad / 16;
+    for (int at = 0; at < w4_matrix_dwords(i); ++at) {
+      const int lane = at % 64, t = at / 64 % tiles, g = at / 64 / tiles;
+      uint32_t word = 0;
+      for (int j = 0; j < 4; ++j) {
+        const int k = 16 * g + 4 * j + (lane >> 4), n = 16 * t + (lane & 15);
+        const int8_t v = k < d.k_pad ? (int8_t)blob[out.matrix[i] + (size_t)k * d.n_pad + n] : (int8_t)0;
+        word |= (uint32_t)(uint8_t)v << (8 * j);
+      }
+      out.w4[(size_t)w4_matrix_offset(i) + at] = word;
+    }
+  }
+  return out;
+}
+
+// The suppressor's settings, weights and device memory.  The buffers are owners (af_hip_resources.hpp): the engine that holds
+// this object makes its device current, and synchronises it, before they are used or destroyed.
 struct SuppressorHost {
   bool enabled = false;
   bool raw_protocol = false;
@@ -81,219 +176,118 @@ struct SuppressorHost {
   RnnWeightsI8 weights;
   bool weights_dirty = true;
   // device side
-  float *d_blob = nullptr;   // all f32 matrices + tables, one allocation
-  uint32_t *d_w4 = nullptr;  // the matrices as int8 in the network kernel's operand order (af_suppressor.h)
-  size_t blob_floats = 0;
+  DeviceBuffer<float> d_blob;   // all f32 matrices + tables, one allocation
+  DeviceBuffer<uint32_t> d_w4;  // the matrices as int8 in the network kernel's operand order (af_suppressor.h)
   RnnDeviceWeights dw{};
   SuppTables tables{};
-  float *d_state = nullptr;  // [streams][SuppState::kCount]
-  float *d_xh = nullptr;
-  float *d_ds = nullptr;
+  DeviceBuffer<float> d_state;  // [streams][SuppState::kCount]
+  DeviceBuffer<float> d_xh;
+  DeviceBuffer<float> d_ds;
   static constexpr int kXhBuffers = 4;    // model-input buffers: the pre-pass runs up to three windows ahead of the synthesis
   static constexpr int kSpecBuffers = kSuppSpecBuffers;  // spectrum / pitch-spectrum / record buffers: the analysis runs up to two windows ahead
   size_t xh_floats = 0;  // floats per model-input buffer
   size_t ws_cells = 0;   // (frame, stream) cells per spectrum / record buffer
-  float2 *d_X = nullptr, *d_P = nullptr;
-  SuppFrameRec *d_rec = nullptr;
+  DeviceBuffer<float2> d_X, d_P;
+  DeviceBuffer<SuppFrameRec> d_rec;
   int ws_frames = 0, ws_streams = 0;
   int last_xh_slot = -1, last_xh_frames = 0;  // the model-input buffer the last pre-pass wrote and its window's frames (test tap)
 
   SuppressorHost() { synthetic_weights(weights, 0x5EEDULL); }
 
-  static void expand_dense(std::vector<float> &dst, const int8_t *w, const int8_t *b, RnnLayerDims d, size_t &off_w,
-                           size_t &off_b) {
-    off_w = dst.size();
-    dst.resize(dst.size() + (size_t)d.k_pad * d.n_pad, 0.0f);
-    for (int k = 0; k < d.k_in; ++k)
-      for (int n = 0; n < d.n; ++n) dst[off_w + (size_t)k * d.n_pad + n] = (float)w[k * d.n + n];
-    off_b = dst.size();
-    dst.resize(dst.size() + d.n_pad, 0.0f);
-    for (int n = 0; n < d.n; ++n) dst[off_b + n] = (float)b[n];
-  }
-  static void expand_gru(std::vector<float> &dst, const int8_t *w, const int8_t *u, const int8_t *b, RnnLayerDims d,
-                         size_t off_w[3], size_t off_b[3]) {
-    const int stride = 3 * d.n;
-    for (int g = 0; g < 3; ++g) {
-      off_w[g] = dst.size();
-      dst.resize(dst.size() + (size_t)d.k_pad * d.n_pad, 0.0f);
-      for (int k = 0; k < d.k_in; ++k)
-        for (int n = 0; n < d.n; ++n) dst[off_w[g] + (size_t)k * d.n_pad + n] = (float)w[k * stride + g * d.n + n];
-      for (int k = 0; k < d.k_rec; ++k)
-        for (int n = 0; n < d.n; ++n)
-          dst[off_w[g] + (size_t)(d.k_in + k) * d.n_pad + n] = (float)u[k * stride + g * d.n + n];
-      off_b[g] = dst.size();
-      dst.resize(dst.size() + d.n_pad, 0.0f);
-      for (int n = 0; n < d.n; ++n) dst[off_b[g] + n] = (float)b[g * d.n + n];
-    }
-  }
-
+  // weights_dirty stays set until both copies have been made: after a failure the next call sends everything again
   hipError_t upload() {
-    std::vector<float> blob;
-    size_t dw_off, db_off, ow_off, ob_off, vw[3], vb[3], nw[3], nb[3], ew[3], eb[3];
-    expand_dense(blob, weights.input_dense_w, weights.input_dense_b, kDimDense, dw_off, db_off);
-    expand_gru(blob, weights.vad_gru_w, weights.vad_gru_u, weights.vad_gru_b, kDimVad, vw, vb);
-    expand_gru(blob, weights.noise_gru_w, weights.noise_gru_u, weights.noise_gru_b, kDimNoise, nw, nb);
-    expand_gru(blob, weights.denoise_gru_w, weights.denoise_gru_u, weights.denoise_gru_b, kDimDenoise, ew, eb);
-    expand_dense(blob, weights.denoise_out_w, weights.denoise_out_b, kDimOut, ow_off, ob_off);
-    const double pi = 3.14159265358979323846;
-    const size_t tansig_off = blob.size();
-    for (int i = 0; i <= 200; ++i) blob.push_back((float)std::tanh(0.04 * i));
-    while (blob.size() % 4) blob.push_back(0.0f);
-    const size_t win_off = blob.size();
-    for (int i = 0; i < kRnnFrame; ++i) {
-      const double sn = std::sin(.5 * pi * (i + .5) / kRnnFrame);
-      blob.push_back((float)std::sin(.5 * pi * sn * sn));
-    }
-    const size_t dct_off = blob.size();
-    for (int i = 0; i < kRnnBands; ++i)
-      for (int j = 0; j < kRnnBands; ++j) {
-        double v = std::cos((i + .5) * j * pi / kRnnBands);
-        if (j == 0) v *= std::sqrt(.5);
-        blob.push_back((float)v);
-      }
-    while (blob.size() % 4) blob.push_back(0.0f);
-    const size_t tw_off = blob.size();
-    for (int i = 0; i < kRnnWindow; ++i) {
-      blob.push_back((float)std::cos(-2.0 * pi * i / kRnnWindow));
-      blob.push_back((float)std::sin(-2.0 * pi * i / kRnnWindow));
-    }
-    while (blob.size() % 4) blob.push_back(0.0f);
-    const size_t frac_off = blob.size();
-    const int eband[kRnnBands] = {0, 1, 2, 3, 4, 5, 6, 7, 8, 10, 12, 14, 16, 20, 24, 28, 34, 40, 48, 60, 78, 100};
-    std::vector<int32_t> band_of(484, kRnnBands - 1);
-    blob.resize(blob.size() + 404, 0.0f);
-    for (int b = 0; b < kRnnBands - 1; ++b) {
-      const int size = (eband[b + 1] - eband[b]) << 2;
-      for (int j = 0; j < size; ++j) {
-        blob[frac_off + (eband[b] << 2) + j] = (float)j / (float)size;
-        band_of[(eband[b] << 2) + j] = b;
-      }
-    }
-    const size_t band_off = blob.size();
-    blob.resize(blob.size() + 484);
-    std::memcpy(&blob[band_off], band_of.data(), 484 * sizeof(int32_t));
-    if (blob.size() > blob_floats) {
-      if (d_blob) (void)hipFree(d_blob);
-      hipError_t err = hipMalloc(&d_blob, blob.size() * sizeof(float));
-      if (err != hipSuccess) return err;
-      blob_floats = blob.size();
-    }
-    hipError_t err = hipMemcpy(d_blob, blob.data(), blob.size() * sizeof(float), hipMemcpyHostToDevice);
-    if (err != hipSuccess) return err;
-    dw.dense_w = d_blob + dw_off;
-    dw.dense_b = d_blob + db_off;
-    dw.out_w = d_blob + ow_off;
-    dw.out_b = d_blob + ob_off;
+    const SuppressorBlob b = build_suppressor_blob(weights);
+    if (hipError_t err = d_blob.reserve_exact(b.f32.size() * sizeof(float)); err != hipSuccess) return err;
+    if (hipError_t err = hipMemcpy(d_blob, b.f32.data(), b.f32.size() * sizeof(float), hipMemcpyHostToDevice); err != hipSuccess) return err;
+    if (hipError_t err = d_w4.reserve_exact(b.w4.size() * sizeof(uint32_t)); err != hipSuccess) return err;
+    if (hipError_t err = hipMemcpy(d_w4, b.w4.data(), b.w4.size() * sizeof(uint32_t), hipMemcpyHostToDevice); err != hipSuccess) return err;
+    dw.dense_w = d_blob + b.matrix[0];
+    dw.dense_b = d_blob + b.bias[0];
     for (int g = 0; g < 3; ++g) {
-      dw.vad_w[g] = d_blob + vw[g];
-      dw.vad_b[g] = d_blob + vb[g];
-      dw.noise_w[g] = d_blob + nw[g];
-      dw.noise_b[g] = d_blob + nb[g];
-      dw.den_w[g] = d_blob + ew[g];
-      dw.den_b[g] = d_blob + eb[g];
+      dw.vad_w[g] = d_blob + b.matrix[1 + g];
+      dw.vad_b[g] = d_blob + b.bias[1 + g];
+      dw.noise_w[g] = d_blob + b.matrix[4 + g];
+      dw.noise_b[g] = d_blob + b.bias[4 + g];
+      dw.den_w[g] = d_blob + b.matrix[7 + g];
+      dw.den_b[g] = d_blob + b.bias[7 + g];
     }
-    {  // the eleven matrices back as int8 (every entry of the f32 blob is a small integer), same padded layout
-      const size_t offs[11] = {dw_off, vw[0], vw[1], vw[2], nw[0], nw[1], nw[2], ew[0], ew[1], ew[2], ow_off};
-      const RnnLayerDims dims[11] = {kDimDense, kDimVad, kDimVad, kDimVad, kDimNoise, kDimNoise, kDimNoise,
-                                     kDimDenoise, kDimDenoise, kDimDenoise, kDimOut};
-      std::vector<int8_t> w8;
-      int32_t off8[11];
-      for (int i = 0; i < 11; ++i) {
-        off8[i] = (int32_t)w8.size();
-        const size_t count = (size_t)dims[i].k_pad * dims[i].n_pad;
-        for (size_t j = 0; j < count; ++j) w8.push_back((int8_t)blob[offs[i] + j]);
-        while (w8.size() % 16) w8.push_back(0);
-      }
-      // ... re-ordered for the network kernel (af_suppressor.h): k padded to whole groups of 16 with zero weights
-      std::vector<uint32_t> w4;
-      for (int i = 0; i < 11; ++i) {
-        if ((int)w4.size() != w4_matrix_offset(i)) return hipErrorInvalidValue;
-        const int n_pad = dims[i].n_pad, tiles = n_pad / 16, groups = (dims[i].k_pad / 4 + 3) / 4;
-        for (int g = 0; g < groups; ++g)
-          for (int t = 0; t < tiles; ++t)
-            for (int lane = 0; lane < 64; ++lane) {
-              uint32_t word = 0;
-              for (int j = 0; j < 4; ++j) {
-                const int k = 16 * g + 4 * j + (lane >> 4), n = 16 * t + (lane & 15);
-                const int8_t v = k < dims[i].k_pad ? w8[(size_t)off8[i] + (size_t)k * n_pad + n] : (int8_t)0;
-                word |= (uint32_t)(uint8_t)v << (8 * j);
-              }
-              w4.push_back(word);
-            }
-      }
-      if (!d_w4) {
-        hipError_t e4 = hipMalloc(&d_w4, w4.size() * sizeof(uint32_t));
-        if (e4 != hipSuccess) return e4;
-      }
-      hipError_t e4 = hipMemcpy(d_w4, w4.data(), w4.size() * sizeof(uint32_t), hipMemcpyHostToDevice);
-      if (e4 != hipSuccess) return e4;
-      dw.w4 = d_w4;
-    }
-    dw.tansig = d_blob + tansig_off;
-    tables.half_window = d_blob + win_off;
-    tables.dct = d_blob + dct_off;
-    tables.twiddle = reinterpret_cast<const float2 *>(d_blob + tw_off);
-    tables.frac = d_blob + frac_off;
-    tables.band_of_bin = reinterpret_cast<const int32_t *>(d_blob + band_off);
+    dw.out_w = d_blob + b.matrix[10];
+    dw.out_b = d_blob + b.bias[10];
+    dw.tansig = d_blob + b.tansig;
+    dw.w4 = d_w4;
+    tables.half_window = d_blob + b.half_window;
+    tables.dct = d_blob + b.dct;
+    tables.twiddle = reinterpret_cast<const float2 *>(d_blob + b.twiddle);
+    tables.frac = d_blob + b.frac;
+    tables.band_of_bin = reinterpret_cast<const int32_t *>(d_blob + b.band_of_bin);
     weights_dirty = false;
     return hipSuccess;
   }
 
   hipError_t reset_state(int n_streams) {
-    if (!d_state) {
-      hipError_t err = hipMalloc(&d_state, sizeof(float) * SuppState::kCount * (size_t)n_streams);
-      if (err != hipSuccess) return err;
-    }
-    std::vector<float> row(SuppState::kCount, 0.0f);
-    row[SuppState::kSmoothedStrength] = 1.0f;  // rnnoise.rs:59
-    std::vector<float> all((size_t)SuppState::kCount * n_streams);
-    for (int s = 0; s < n_streams; ++s) std::memcpy(&all[(size_t)s * SuppState::kCount], row.data(), sizeof(float) * row.size());
+    std::vector<float> all((size_t)SuppState::kCount * n_streams, 0.0f);
+    for (int s = 0; s < n_streams; ++s) all[(size_t)s * SuppState::kCount + SuppState::kSmoothedStrength] = 1.0f;  // rnnoise.rs:59
+    if (hipError_t err = d_state.reserve_exact(all.size() * sizeof(float)); err != hipSuccess) return err;
     return hipMemcpy(d_state, all.data(), all.size() * sizeof(float), hipMemcpyHostToDevice);
   }
 
+  // No-op when the frames fit; otherwise the five buffers are freed first and allocated exactly.  After a failure there is no
+  // workspace (and no size is claimed), so the next call allocates again.
   hipError_t ensure_workspace(int n_streams, int frames) {
     if (frames <= ws_frames && n_streams == ws_streams) return hipSuccess;
-    release_workspace();
-    hipError_t err;
+    drop_workspace();
     const size_t cells = (size_t)frames * n_streams;
     // The windows of a call run as a pipeline (pre-pass | analysis | synthesis), so the buffers that cross a
     // stage boundary exist several times: the model input lives from the pre-pass to the synthesis (3 windows
     // in flight), spectra and frame records from the analysis to the synthesis (2), pitch spectra / resynthesised
     // frames from the network half of the synthesis to its resynthesis half (2).
-    xh_floats = (size_t)n_streams * (kPitchBuf + (size_t)frames * kRnnFrame);
+    const size_t xh = (size_t)n_streams * (kPitchBuf + (size_t)frames * kRnnFrame);
+    hipError_t err = d_xh.reserve_exact(sizeof(float) * kXhBuffers * xh);
+    if (err == hipSuccess) err = d_X.reserve_exact(sizeof(float2) * kSpecBuffers * cells * kRnnFreq);
+    if (err == hipSuccess) err = d_P.reserve_exact(sizeof(float2) * kSpecBuffers * cells * kRnnFreq);
+    if (err == hipSuccess) err = d_rec.reserve_exact(sizeof(SuppFrameRec) * kSpecBuffers * cells);
+    if (err == hipSuccess) err = d_ds.reserve_exact(sizeof(float) * cells * (kPitchBuf / 2));
+    if (err != hipSuccess) {
+      drop_workspace();
+      return err;
+    }
+    xh_floats = xh;
     ws_cells = cells;
-    if ((err = hipMalloc(&d_xh, sizeof(float) * kXhBuffers * xh_floats)) != hipSuccess) return err;
-    if ((err = hipMalloc(&d_X, sizeof(float2) * kSpecBuffers * cells * kRnnFreq)) != hipSuccess) return err;
-    if ((err = hipMalloc(&d_P, sizeof(float2) * kSpecBuffers * cells * kRnnFreq)) != hipSuccess) return err;
-    if ((err = hipMalloc(&d_rec, sizeof(SuppFrameRec) * kSpecBuffers * cells)) != hipSuccess) return err;
-    if ((err = hipMalloc(&d_ds, sizeof(float) * cells * (kPitchBuf / 2))) != hipSuccess) return err;
     ws_frames = frames;
     ws_streams = n_streams;
     return hipSuccess;
   }
-  void release_workspace() {
-    (void)hipFree(d_xh);
-    (void)hipFree(d_ds);
-    d_ds = nullptr;
-    (void)hipFree(d_X);
-    (void)hipFree(d_P);
-    (void)hipFree(d_rec);
-    d_xh = nullptr;
-    d_X = d_P = nullptr;
-    d_rec = nullptr;
+
+  // The pointer fields of `sa` for window `index` of a call at pipeline depth `depth`: model-input buffer index % kXhBuffers,
+  // spectrum / pitch-spectrum / record set index % depth, the single set of whitened pitch buffers, the state rows, and, behind
+  // the call's first window, the history source: the buffer of the window before, whose rows hold `prev_frames` frames.
+  void window_buffers(SuppArgs &sa, int64_t index, int depth, int64_t prev_frames) const {
+    const size_t set = (size_t)(index % depth) * ws_cells;
+    sa.xh = d_xh + (size_t)(index % kXhBuffers) * xh_floats;
+    sa.X = d_X + set * kRnnFreq;
+    sa.P = d_P + set * kRnnFreq;
+    sa.ds = d_ds;
+    sa.rec = d_rec + set;
+    sa.state = d_state;
+    if (index > 0) {  // history = tail of the previous window's buffer
+      sa.xh_prev = d_xh + (size_t)((index - 1) % kXhBuffers) * xh_floats;
+      sa.xh_prev_stride = kPitchBuf + prev_frames * kRnnFrame;
+    }
+  }
+
+ private:
+  void drop_workspace() {
+    d_xh.release();
+    d_ds.release();
+    d_X.release();
+    d_P.release();
+    d_rec.release();
+    xh_floats = ws_cells = 0;
     ws_frames = ws_streams = 0;
     last_xh_slot = -1;
     last_xh_frames = 0;
   }
-  void release_all() {
-    release_workspace();
-    (void)hipFree(d_blob);
-    (void)hipFree(d_w4);
-    d_w4 = nullptr;
-    (void)hipFree(d_state);
-    d_blob = d_state = nullptr;
-    blob_floats = 0;
-  }
 };
 
 }  // namespace af
+

@@ -280,7 +280,9 @@ int af_suppressor_set_trace_enabled(af_engine *e, int32_t enabled);
 int64_t af_suppressor_trace_frames(const af_engine *e);
 int af_suppressor_read_trace(af_engine *e, int32_t *out, int64_t capacity_frames);
 /* test tap: the analysis record (158 floats/ints) and spectra X, P (481 complex each) of one
- * (frame, stream) cell of the last suppressor window */
+ * (frame, stream) cell of the suppressor's buffer set 0.  The windows of a call rotate through the
+ * sets, so this is the call's last window only when the call had at most one window per set: valid
+ * after a one-window call */
 int af_suppressor_debug_read(af_engine *e, int32_t frame, int32_t stream, float *record, float *x_spectrum,
                              float *p_spectrum);
 /* test tap of the pitch path (synchronises): the LPC-whitened, 2x-decimated pitch buffer (864 floats) of one (frame, stream)

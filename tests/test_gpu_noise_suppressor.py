@@ -9,7 +9,7 @@ import numpy as np
 import pytest
 
 import signals as S
-from test_oracle_rnnoise_wrapper import check_soft_clip_transfer
+from test_oracle_rnnoise_wrapper import RESET_FRAMES, check_soft_clip_transfer, reset_stimulus
 
 pytestmark = pytest.mark.gpu
 
@@ -182,6 +182,46 @@ def test_trait_surface_matches_restatement_over_ragged_pushes(mi, oracle):
     assert drained.shape[1] == refs[0].pending_input()
     assert np.array_equal(drained[1], refs[1].drain_pending_input())
     assert p.pending_input() == 0
+    p.close()
+
+
+def test_reset_starts_the_model_again_and_keeps_the_smoothed_strength(mi, oracle):
+    """af_noise_suppressor_reset (rnnoise.rs:205-210): empty rings and a new DenoiseState, the wet/dry smoothing kept.  Six
+    frames at strength 0.4, a reset, six more: counts equal the oracle's RNNoiseProcessor exactly at every step, audio to
+    1e-5 (test_oracle_rnnoise_wrapper.py shows that the oracle's reset differs by more than 1e-3 from a fresh processor and
+    from a soft reset on these rows).  A reset before anything was processed succeeds and changes nothing."""
+    x = reset_stimulus()
+    n = RESET_FRAMES * 480
+    p = mi.NoiseSuppressor("rnnoise", 3, weight_seed=0x5EED)
+    p.set_strength(0.4)
+    refs = [oracle.RNNoiseProcessor(0.4, 0x5EED) for _ in range(3)]
+    p.reset()  # (the refs are not reset: what follows must be what an untouched processor gives)
+    assert p.available_samples() == 0 and p.pending_input() == 0 and p.get_strength() == np.float32(0.4) and p.is_enabled()
+
+    def step(lo, hi, what):
+        assert p.push_samples(x[:, lo:hi]) == refs[0].push_samples(x[0, lo:hi]) == hi - lo
+        for k in (1, 2):
+            refs[k].push_samples(x[k, lo:hi])
+        assert p.pending_input() == refs[0].pending_input() == hi - lo
+        p.process_frames()
+        for r in refs:
+            r.process_frames()
+        assert p.available_samples() == refs[0].available_samples() == hi - lo, what
+        assert p.pending_input() == refs[0].pending_input() == 0, what
+        got = p.pop_samples(hi - lo)
+        assert got.shape == (3, hi - lo)
+        for k in range(3):
+            want = refs[k].read_samples(hi - lo)
+            assert want.size == hi - lo
+            assert float(np.max(np.abs(got[k].astype(np.float64) - want))) <= 1e-5, (what, k)
+        assert p.available_samples() == refs[0].available_samples() == 0
+
+    step(0, n, "before the reset")
+    p.reset()
+    for r in refs:
+        r.reset()
+    assert p.available_samples() == refs[0].available_samples() == 0 and p.pending_input() == refs[0].pending_input() == 0
+    step(n, 2 * n, "after the reset")
     p.close()
 
 

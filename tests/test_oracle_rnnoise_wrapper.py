@@ -151,6 +151,45 @@ def test_streaming_in_ragged_blocks_equals_whole_frames(oracle):
     assert np.array_equal(np.concatenate(got), whole)
 
 
+RESET_FRAMES = 6  # frames on each side of the reset
+
+
+def reset_stimulus():
+    """[3][12 frames]: a 180 Hz amplitude-modulated tone plus noise per stream (the GPU reset test runs on the same rows)."""
+    return S.batch_signal(3, 2 * RESET_FRAMES)
+
+
+def push_process_read(processor, samples):
+    processor.push_samples(samples)
+    processor.process_frames()
+    return processor.read_samples(processor.available_samples())
+
+
+def test_reset_differs_from_a_fresh_processor_and_from_a_soft_reset(oracle):
+    """rnnoise.rs:205-210: reset() makes a new DenoiseState and keeps the wrapper's smoothed strength.  On the stimulus of
+    the GPU reset test that must be told apart from both of its neighbours, or the GPU test could not tell a reset that does
+    nothing (soft_reset) or too much (a fresh processor, smoothed strength back at 1) from the right one: after 6 frames at
+    strength 0.4 and a reset(), the next 6 frames differ by more than 1e-3 from either."""
+    x = reset_stimulus()
+    n = RESET_FRAMES * 480
+    for k in range(x.shape[0]):
+        hard = oracle.RNNoiseProcessor(0.4, 0x5EED)
+        push_process_read(hard, x[k, :n])
+        hard.reset()
+        assert hard.available_samples() == 0 and hard.pending_input() == 0
+        after_reset = push_process_read(hard, x[k, n:])
+        fresh = push_process_read(oracle.RNNoiseProcessor(0.4, 0x5EED), x[k, n:])
+        soft = oracle.RNNoiseProcessor(0.4, 0x5EED)
+        push_process_read(soft, x[k, :n])
+        soft.soft_reset()
+        after_soft = push_process_read(soft, x[k, n:])
+        assert after_reset.size == fresh.size == after_soft.size == n
+        from_fresh = float(np.max(np.abs(after_reset.astype(np.float64) - fresh)))
+        from_soft = float(np.max(np.abs(after_reset.astype(np.float64) - after_soft)))
+        print(f"stream {k}: reset vs fresh {from_fresh:.3f}, reset vs soft reset {from_soft:.3f}")
+        assert from_fresh > 1e-3 and from_soft > 1e-3, k
+
+
 def test_evaluation_order_independence(oracle):
     """The restatement's wavefront-native sums (order 0: what the GPU kernels evaluate) against the published scalar C's
     running sums (order 1).  Neither is "the" order of nnnoiseless (it unrolls over several accumulators), so the two
