@@ -11,123 +11,16 @@
 // cs_fold_kernel: one wave per lane folds the lane's rows and the capture's shared rows as python_api.rs:578-713 does
 //   (mic_eq_core.chain_diagnostics): maxima, dB values, the percentiles of the gain-reduction traces and the pumping score.
 //
-// CompState / comp_sample / the true-peak FIR are restated from af_kernels.hip rather than shared, so that file's code object
-// is untouched.
+// The per-sample dynamics step (compressor sample, limiter step, true-peak step, output observation, block-end makeup smoothing)
+// is af_dynamics_step.h's, shared with the streaming lane chain (af_lane_chain.hip); af_kernels.hip keeps its own copy, so that
+// file's code object is untouched.
 #include <hip/hip_runtime.h>
 
 #include "af_compressor_search_host.hpp"
 #include "af_dsp.h"
+#include "af_dynamics_step.h"
 
 namespace af {
-
-namespace {
-
-struct CsCompState {
-  double sc_prev_in, sc_prev_out, low_env, voiced_env, presence_env, plosive;
-  double peak_env_db, rms_env_sq, gr, fast_env, slow_env, cur_release_ms, target_release_ms;
-  double release_coeff, smoothed_makeup;
-};
-
-// Compressor::process_sample_impl(update_makeup_gain = false), dsp/compressor.rs:725-774 -- af_kernels.hip's comp_sample
-__device__ __forceinline__ float cs_comp_sample(const CompressorParams &p, CsCompState &s, float input, double makeup_lin) {
-  const double x = (double)input;
-  double d = x;
-  double weight_db = kDetectorUnitWeight;
-  if (p.sidechain_highpass_enabled) {
-    // process_sidechain_sample, compressor.rs:407-417
-    d = p.sidechain_highpass_coeff * (s.sc_prev_out + x - s.sc_prev_in);
-    s.sc_prev_in = x;
-    s.sc_prev_out = d;
-    // update_sidechain_band_metrics, compressor.rs:420-450
-    const double low = x - d;
-    const double voiced = d;
-    const double presence = 0.65 * d + 0.35 * (d - low);
-    const double k = p.band_env_coeff;
-    s.low_env = k * s.low_env + (1.0 - k) * low * low;
-    s.voiced_env = k * s.voiced_env + (1.0 - k) * voiced * voiced;
-    s.presence_env = k * s.presence_env + (1.0 - k) * presence * presence;
-    const double low_rms = sqrt(s.low_env);
-    const double voiced_rms = fmax(sqrt(s.voiced_env), 1e-8);
-    const double presence_rms = sqrt(s.presence_env);
-    s.plosive = dclamp(low_rms / voiced_rms, 0.0, 32.0);
-    const double plosive_amount = dclamp(div_known(s.plosive - 1.25, 3.75, 1.0 / 3.75), 0.0, 1.0);
-    const double plosive_penalty = 1.0 - plosive_amount * (1.0 - 0.35);
-    const double presence_ratio = dclamp(presence_rms / voiced_rms, 0.0, 4.0);
-    const double presence_weight = 1.0 + 0.18 * dclamp(presence_ratio - 0.75, 0.0, 1.0);
-    const double w = dclamp(plosive_penalty * presence_weight, 0.35, 1.15);
-    weight_db = detector_weight(w);
-  } else {
-    s.plosive = 0.0;
-  }
-  const double inst_peak_db = lin2db(fabs(d), 1e-10);
-  const double pk = inst_peak_db > s.peak_env_db ? p.attack_coeff : p.detector_release_coeff;
-  s.peak_env_db = pk * s.peak_env_db + (1.0 - pk) * inst_peak_db;
-
-  const double sq = d * d;
-  s.rms_env_sq = p.rms_coeff * s.rms_env_sq + (1.0 - p.rms_coeff) * sq;
-  const double rms_db = detector_rms_level(s.rms_env_sq);
-
-  const double detector_db = af::detector_db(s.peak_env_db, rms_db, weight_db);  // blended_detector_db, compressor.rs:681-686
-
-  // update_adaptive_release_time_meter + release smoothing, compressor.rs:452-466,752-761 (see af_kernels.hip on release_coeff)
-  if (p.adaptive_release) {
-    const double sustained = dclamp(div_known(s.slow_env, 6.0, 1.0 / 6.0), 0.0, 1.0);
-    const double transient_bias = dclamp(div_known(s.fast_env - s.slow_env, 7.0, 1.0 / 7.0), 0.0, 1.0);
-    const double syllabic = dclamp(sustained * sustained * (1.0 - 0.35 * transient_bias), 0.0, 1.0);
-    s.target_release_ms = 50.0 + syllabic * (400.0 - 50.0);
-  } else {
-    s.target_release_ms = p.base_release_ms;
-  }
-  const double release_diff = s.target_release_ms - s.cur_release_ms;
-  if (fabs(release_diff) > 1.0) {
-    s.cur_release_ms = p.release_smoothing_coeff * s.cur_release_ms + (1.0 - p.release_smoothing_coeff) * s.target_release_ms;
-  } else {
-    s.cur_release_ms = s.target_release_ms;
-  }
-
-  const double target = comp_gain_reduction(p, detector_db);
-  // smooth_gain_reduction, compressor.rs:468-505
-  if (!p.adaptive_release) {
-    const double k = target > s.gr ? p.attack_coeff : s.release_coeff;
-    s.gr = k * s.gr + (1.0 - k) * target;
-    s.fast_env = s.gr;
-    s.slow_env = 0.0;
-  } else {
-    if (target > s.gr) {
-      s.fast_env = p.attack_coeff * s.gr + (1.0 - p.attack_coeff) * target;
-    } else {
-      s.fast_env = p.fast_release_coeff * s.fast_env + (1.0 - p.fast_release_coeff) * target;
-    }
-    if (target > 3.0) {
-      s.slow_env = p.slow_charge_coeff * s.slow_env + (1.0 - p.slow_charge_coeff) * target;
-    } else {
-      s.slow_env *= p.slow_release_coeff;
-    }
-    s.gr = fmax(s.fast_env, s.slow_env);
-  }
-  const double output_gain = db2lin(-s.gr) * makeup_lin;
-  return (float)(x * output_gain);
-}
-
-// Bandlimited4xPeak::observe, dsp/true_peak.rs:173-186, over a 32-row ring: h[k] = sample t-k lives at row (t - k) & 31
-__device__ __forceinline__ float cs_tp_observe(const float (*ring)[kLanes], int t, int lane) {
-  float h[kTpTaps];
-#pragma unroll
-  for (int k = 0; k < kTpTaps; ++k) h[k] = ring[(t - k) & (kTpTaps - 1)][lane];
-  float peak = fabsf(h[0]);
-#pragma unroll
-  for (int p = 0; p < 4; ++p) {
-    float acc = 0.0f;
-#pragma unroll
-    for (int k = 0; k < kTpTaps; ++k) acc = __builtin_fmaf(AF_TP_FIR[p][k], h[k], acc);
-    peak = fmaxf(peak, fabsf(acc));
-  }
-  return peak;
-}
-
-static_assert((kTpTaps & (kTpTaps - 1)) == 0, "the true-peak rings index with a mask");
-
-}  // namespace
 
 // =====================================================================================
 // the sweep
@@ -158,14 +51,14 @@ extern "C" __global__ __launch_bounds__(kLanes) void cs_sweep_kernel(CsSweepArgs
   P.sidechain_highpass_enabled = (lane_flags & kCsSidechainHighpass) ? 1 : 0;
 
   // a fresh processor: af_api.cpp, upload_initial_state
-  CsCompState cs = {};
+  DynCompState cs = {};
   cs.peak_env_db = -120.0;
   cs.cur_release_ms = a.lane_f64[(int64_t)kCsCurReleaseMs * LP + g];
   cs.target_release_ms = a.lane_f64[(int64_t)kCsTargetReleaseMs * LP + g];
   cs.release_coeff = a.lane_f64[(int64_t)kCsReleaseCoeff * LP + g];
   cs.smoothed_makeup = a.lane_f64[(int64_t)kCsSmoothedMakeup * LP + g];
-  double lim_gain = 1.0;
-  float lim_prefix = 0.0f, tp_gain = 1.0f;
+  DynLimiterState lim = {1.0, 0.0f};
+  float tp_gain = 1.0f;
   for (int r = 0; r < kTpTaps; ++r) {
     tpi[r][lane] = 0.0f;
     tpo[r][lane] = 0.0f;
@@ -186,100 +79,41 @@ extern "C" __global__ __launch_bounds__(kLanes) void cs_sweep_kernel(CsSweepArgs
   int64_t block_index = 0;
   for (int64_t blk0 = 0; blk0 < n; blk0 += cb, ++block_index) {
     const int blk_len = (int)((n - blk0) < cb ? (n - blk0) : cb);
-    float out_peak = 0.0f, tp_in_peak = 0.0f, out_tp = 0.0f, tp_gmin = 1.0f;
-    double out_sq = 0.0, lim_gmin = 1.0;
-    uint32_t tp_limited = 0, non_finite = 0;
+    DynTpStats tps = {0.0f, 1.0f, 0};
+    DynOutputStats os = {0.0, 0.0f, 0.0f, 0};
+    double lim_gmin = 1.0;
     const double makeup_lin = db2lin(cs.smoothed_makeup);  // constant inside a block (compressor.rs:771-772 vs 721)
 
     for (int i = 0; i < blk_len; ++i) {
       const int64_t t64 = blk0 + i;
       const int t = (int)(t64 & 0x7fffffff);  // only its low five bits are used
       // what this sample needs from memory, asked for ahead of the compressor's arithmetic
-      const int jn = (j + 1 == W) ? 0 : j + 1;
-      const float delayed_in = ring[(int64_t)jn * LP];
-      const float sfx = (j + 1 < W) ? suf[(int64_t)(j + 1) * LP] : 0.0f;
+      const DynLimiterFetch lf = dyn_limiter_fetch(ring, suf, LP, j, W);
       const float x = x_next;
       x_next = (t64 + 1 < n) ? in[t64 + 1] : 0.0f;
 
-      // ---- compressor (compressor.rs:700-722)
-      const float xin = cs_comp_sample(P, cs, x, makeup_lin);
-
-      // ---- lookahead limiter (limiter.rs:246-284)
-      const float ax = fabsf(xin);
-      lim_prefix = (j == 0) ? ax : fmaxf(lim_prefix, ax);
-      const double peak = (double)fmaxf(sfx, lim_prefix);
-      ring[(int64_t)j * LP] = xin;
-      if (j + 1 == W) {  // block of W inputs complete: suffix maxima for the next block
-        float m = 0.0f;
-        for (int k = W - 1; k >= 0; --k) {
-          m = fmaxf(m, fabsf(ring[(int64_t)k * LP]));
-          suf[(int64_t)k * LP] = m;
-        }
-      }
-      j = jn;
-      const double target = peak > ceil_lin ? ceil_lin / peak : 1.0;
-      if (target < lim_gain) {
-        lim_gain = target;
-      } else {
-        lim_gain = rc * lim_gain + (1.0 - rc) * target;
-      }
-      lim_gmin = fmin(lim_gmin, lim_gain);
-      const double limited = (double)delayed_in * lim_gain;
-
-      // ---- 4x true-peak limiter (true_peak.rs:337-378)
-      float input = (float)dclamp(limited, -ceil_lin, ceil_lin);
-      if (!finite_f32(input)) input = 0.0f;
-      tpi[t & (kTpTaps - 1)][lane] = input;
-      const float delayed = tpi[(t - kTpDelay) & (kTpTaps - 1)][lane];
-      const float itp = cs_tp_observe(tpi, t, lane);
-      tp_in_peak = fmaxf(tp_in_peak, itp);
-      float tp_target = 1.0f;
-      if (itp > tp_ceiling) tp_target = fclamp((tp_ceiling * 0.999f) / itp, 0.0f, 1.0f);
-      if (tp_target < tp_gain) {
-        tp_gain = tp_target;
-        tp_limited = 1;
-      } else {
-        tp_gain = rel * tp_gain + (1.0f - rel) * tp_target;
-      }
-      tp_gmin = fminf(tp_gmin, tp_gain);
-      float o = fclamp(delayed * tp_gain, -tp_ceiling, tp_ceiling);
-      if (!finite_f32(o)) o = 0.0f;
-
-      // ---- block output statistics + true-peak detector (block_processor.rs:158-159)
-      if (finite_f32(o)) {
-        out_sq += (double)o * (double)o;
-        tpo[t & (kTpTaps - 1)][lane] = o;
-      } else {
-        non_finite = 1;
-        tpo[t & (kTpTaps - 1)][lane] = 0.0f;  // TruePeakDetector feeds 0 for non-finite, true_peak.rs:212
-      }
-      out_peak = fmaxf(out_peak, fabsf(o));
-      out_tp = fmaxf(out_tp, cs_tp_observe(tpo, t, lane));
+      const float xin = dyn_comp_sample(P, cs, x, makeup_lin);                                             // compressor.rs:700-722
+      const double limited = dyn_limiter_step(ring, suf, LP, j, W, lf, xin, ceil_lin, rc, lim, lim_gmin);  // limiter.rs:246-284
+      j = lf.jn;
+      const float o = dyn_tp_limiter_step(tpi, t, lane, limited, ceil_lin, tp_ceiling, rel, tp_gain, tps);  // true_peak.rs:337-378
+      dyn_output_observe(tpo, t, lane, o, os);                                                             // block_processor.rs:158-159
       if (audio) audio[t64] = o;
     }
 
-    // ---- end of block: update_auto_makeup_gain with auto-makeup off (compressor.rs:604-617)
-    const double makeup_coeff = pow(P.makeup_smoothing_coeff, (double)(blk_len < 1 ? 1 : blk_len));
-    const double makeup_target = P.makeup_gain_db;
-    const double diff = makeup_target - cs.smoothed_makeup;
-    if (fabs(diff) > 0.1) {
-      cs.smoothed_makeup = makeup_coeff * cs.smoothed_makeup + (1.0 - makeup_coeff) * makeup_target;
-    } else {
-      cs.smoothed_makeup = makeup_target;
-    }
+    dyn_block_end_makeup(P, cs, blk_len);
     if (valid) {
       CsRow st;
-      st.output_sample_peak = out_peak;
-      st.tp_limiter_input_peak = tp_in_peak;
-      st.output_true_peak = out_tp;
-      st.limiter_peak_gr_db = lim_gmin < 1.0 ? (float)(-lin2db(lim_gmin, 1e-10)) : 0.0f;  // limiter.rs:273-280
-      st.tp_limiter_gr_db = tp_gmin < 1.0f ? -20.0f * log10f(fmaxf(tp_gmin, 1e-10f)) : 0.0f;  // true_peak.rs:315-321, 363-365
+      st.output_sample_peak = os.peak;
+      st.tp_limiter_input_peak = tps.in_peak;
+      st.output_true_peak = os.tp;
+      st.limiter_peak_gr_db = dyn_limiter_gr_db(lim_gmin);
+      st.tp_limiter_gr_db = dyn_tp_gr_db(tps.gmin);
       st.compressor_gr_db = (float)cs.gr;
       st.makeup_gain_db = (float)cs.smoothed_makeup;
       st.pad = 0.0f;
-      st.output_square_sum = out_sq;
-      st.tp_limited_events = tp_limited;
-      st.non_finite_output = non_finite;
+      st.output_square_sum = os.sq;
+      st.tp_limited_events = tps.limited;
+      st.non_finite_output = os.non_finite;
       a.rows[block_index * a.n_lanes + g] = st;
     }
   }

@@ -98,8 +98,13 @@ if _core_module is not None:
 else:
     LatencyCalibration = LatencyCalibrationResult = None
     generate_probe_signal = analyze_latency = analyze_latency_batch = result_to_profile = _missing_core
+# ... and the streaming lane chain (one lane per stream, per-stream settings)
+if _core_module is not None:
+    from .lane_chain import LaneChain
+else:
+    LaneChain = None
 
-__all__ = ["CORE_AVAILABLE", "Engine", "NoiseSuppressor", "NoiseModel", "StreamResampler", "Mixdown", "VoiceSpectrum", "VoiceSpectrumResult", "NoiseReference", "NoiseReferenceAnalysis", "SpeechFeatures", "CaptureMetadata",
+__all__ = ["LaneChain", "CORE_AVAILABLE", "Engine", "NoiseSuppressor", "NoiseModel", "StreamResampler", "Mixdown", "VoiceSpectrum", "VoiceSpectrumResult", "NoiseReference", "NoiseReferenceAnalysis", "SpeechFeatures", "CaptureMetadata",
            "new_noise_suppression_engine", *_OPERATORS, "CompressorSearch", "compressor_input_batch", "simulate_compressor_candidates_batch", "calibrate_compressor",
            "calibrate_compressor_batch", "SetupVerification", "measure_setup_verification_batch", "decide_voice_setup_verification", "verify_voice_setup_batch", "validate_voice_setup_verification", "LaneEq",
            "simulate_candidate_chain", "simulate_candidate_chain_batch", "apply_headroom_validation", "apply_headroom_validation_batch", "LatencyCalibration",

@@ -300,6 +300,16 @@ class SetupOfflineResult(C.Structure):
                                                    "setup_confidence", "recommendation_uncertainty")])
 
 
+class LaneChainSettings(C.Structure):
+    """af_lane_chain_settings: one stream's settings of the streaming lane chain."""
+    _fields_ = ([("bands", (C.c_double * 3) * 10)]
+                + [(name, C.c_double) for name in ("compressor_threshold_db", "compressor_ratio", "compressor_attack_ms",
+                                                   "compressor_release_ms", "compressor_makeup_gain_db", "compressor_base_release_ms",
+                                                   "limiter_ceiling_db", "limiter_release_ms")]
+                + [(name, C.c_int32) for name in ("eq_enabled", "compressor_enabled", "limiter_enabled", "compressor_adaptive_release",
+                                                  "compressor_sidechain_highpass_enabled", "limiter_careful_output_enabled")])
+
+
 # every symbol include/audioforge_mi.h declares: name -> (restype, argtypes)
 _vp, _i32, _i64, _d, _f, _sz = C.c_void_p, C.c_int32, C.c_int64, C.c_double, C.c_float, C.c_size_t
 _fp, _dp = C.POINTER(C.c_float), C.POINTER(C.c_double)
@@ -580,6 +590,18 @@ SIGNATURES = {
     "af_lane_eq_output": (C.c_int, [_vp, C.POINTER(_vp), C.POINTER(_i64)]),
     "af_lane_eq_read_output": (C.c_int, [_vp, _fp, _i64]),
     "af_lane_eq_last_kernel_ms": (C.c_int, [_vp, _dp]),
+    # streaming lane chain
+    "af_lane_chain_default_settings": (C.c_int, [C.POINTER(LaneChainSettings)]),
+    "af_lane_chain_create": (C.c_int, [_d, _i32, _d, _i32, C.POINTER(_vp)]),
+    "af_lane_chain_destroy": (None, [_vp]),
+    "af_lane_chain_configure": (C.c_int, [_vp, C.POINTER(_i32), _i32, C.POINTER(LaneChainSettings)]),
+    "af_lane_chain_process_host": (C.c_int, [_vp, _fp, _fp, _i64, _i64]),
+    "af_lane_chain_process_device": (C.c_int, [_vp, _vp, _vp, _i64, _i64, _vp]),
+    "af_lane_chain_blocks": (_i64, [_vp]),
+    "af_lane_chain_read_rows": (C.c_int, [_vp, C.POINTER(BlockStats), _i64]),
+    "af_lane_chain_reset": (C.c_int, [_vp]),
+    "af_lane_chain_samples_processed": (C.c_int, [_vp, _i32, C.POINTER(_i64)]),
+    "af_lane_chain_last_kernel_ms": (C.c_int, [_vp, _dp]),
     # second-passage verification: the measurements
     "af_setup_verification_create": (C.c_int, [C.c_uint32, _i32, _i32, _i32, C.POINTER(_vp)]),
     "af_setup_verification_destroy": (None, [_vp]),
@@ -636,6 +658,7 @@ VALUE_FUNCTIONS = {
     "af_device_rate_features_resampled_length", "af_device_rate_features_sibilance_bins",
     "af_voice_setup_default_inputs",
     "af_compressor_search_destroy", "af_compressor_search_blocks", "af_lane_eq_destroy",
+    "af_lane_chain_destroy", "af_lane_chain_blocks",
     "af_setup_verification_destroy", "af_setup_verification_reason_text", "af_setup_offline_reason_text",
     "af_latency_destroy", "af_latency_message_text",
 }

@@ -693,7 +693,7 @@ def _is_preset_list(bands, settings) -> bool:
 
 
 def simulate_auto_eq_chain_batch(audio: np.ndarray, sample_rate: float, bands, settings=None, device: int = 0,
-                                 diagnostics: bool = True) -> tuple[np.ndarray, list[dict[str, Any]]]:
+                                 diagnostics: bool = True, route: str = "groups") -> tuple[np.ndarray, list[dict[str, Any]]]:
     """Batched form: ``audio`` is [n_streams, n] float32.
 
     ``bands`` / ``settings`` are either one preset for every stream (the reference's arguments), or one entry per
@@ -701,15 +701,37 @@ def simulate_auto_eq_chain_batch(audio: np.ndarray, sample_rate: float, bands, s
     (python/mic_eq/config_parts/settings.py:543-593).  Streams that share a preset are packed into groups of 64 (the unit
     a preset applies to on the GPU; partial groups are padded with silent streams) and handed back in the caller's order.
 
+    ``route="groups"`` (the default) is that path.  ``route="lanes"`` runs the same call on a ``LaneChain`` (lane_chain.py): one
+    lane per stream, no packing and no padding, the right choice when most streams have a preset of their own (DESIGN 4.25
+    has the measured crossover).  It returns the same values and raises NotImplementedError, naming the setting, for what a
+    lane does not run: the de-esser, auto-makeup, typed bands, and limiter lookaheads that differ between streams.
+
     Returns (output [n_streams, n] float32, one reference-shaped dict per stream).
     """
     started = time.perf_counter()
+    if route not in ("groups", "lanes"):
+        raise ValueError(f"route must be 'groups' or 'lanes', got {route!r}")
     if not np.isfinite(sample_rate) or sample_rate <= 0.0:
         raise ValueError("sample_rate must be positive and finite")
     audio = np.ascontiguousarray(audio, dtype=np.float32)
     if audio.ndim != 2:
         raise TypeError("audio must be [n_streams, n_samples]")
     n_streams, n = audio.shape
+    if route == "lanes":
+        from . import lane_chain
+
+        if not _is_preset_list(bands, settings) and len(bands) != NUM_BANDS:
+            raise ValueError(f"expected {NUM_BANDS} EQ bands, got {len(bands)}")
+        output, rows, effective = lane_chain.simulate_lanes(audio, float(sample_rate), bands, settings, device)
+        results = []
+        if diagnostics:
+            lengths = _block_lengths(n, int(min(max(round(sample_rate * 0.020), 1), 8192)))
+            runtime_ms = (time.perf_counter() - started) * 1000.0
+            for s_i in range(n_streams):
+                d = chain_diagnostics(rows[:, s_i], lengths, effective[s_i])
+                d["candidate_runtime_ms"] = runtime_ms
+                results.append(d)
+        return output, results
     if not _is_preset_list(bands, settings):
         if len(bands) != NUM_BANDS:
             raise ValueError(f"expected {NUM_BANDS} EQ bands, got {len(bands)}")

@@ -1209,6 +1209,61 @@ int af_lane_eq_output(af_lane_eq *h, float **d_out, int64_t *stride);
 int af_lane_eq_read_output(af_lane_eq *h, float *out, int64_t stride);
 int af_lane_eq_last_kernel_ms(af_lane_eq *h, double *ms);
 
+/* ---- streaming lane chain: one processor per stream, each under its own settings ------------------------------------------
+ * The reference configures one processor per caller (python/mic_eq/config_parts/settings.py:543-593).  An af_engine preset is a
+ * 64-stream group; here ONE STREAM IS ONE LANE and carries its own settings and its own state from call to call.  Every stream
+ * runs the dynamics chain simulate_auto_eq_chain configures (python_api.rs:400-487) without the de-esser, in
+ * OfflineDspBlockProcessor's order (block_processor.rs:106-161): input scrub (python_api.rs:517-520) -> ParametricEQ (ten legacy
+ * bands, with the coefficient crossfade the setters schedule) -> Compressor (auto-makeup off) -> Limiter -> TruePeakLimiter ->
+ * block output statistics and TruePeakDetector.  Every call starts a new control block of round(0.020 * sample_rate) samples
+ * clamped to 1..8192 (python_api.rs:512-514); the last block of a call may be short.  A stream's output and rows equal, bit for
+ * bit, those of a one-stream af_engine configured with the stream's settings and driven with the same calls.
+ * Not here (they stay with af_engine): the de-esser, auto-makeup, typed EQ bands, the gate, the suppressor, the front-end
+ * filters, device-rate I/O, live retune without a restart, state export and import. */
+typedef struct af_lane_chain af_lane_chain;
+/* One stream's settings: the keys of simulate_auto_eq_chain's settings dict (python_api.rs:400-487) that this object runs. */
+typedef struct af_lane_chain_settings {
+  double bands[10][3];                 /* (frequency_hz, gain_db, q): set_band_frequency / _gain / _q, python_api.rs:408-412 */
+  double compressor_threshold_db, compressor_ratio, compressor_attack_ms, compressor_release_ms; /* python_api.rs:446-456 */
+  double compressor_makeup_gain_db, compressor_base_release_ms;
+  double limiter_ceiling_db, limiter_release_ms;  /* effective ceiling min(ceiling, -1.5) under careful output, control.rs:904-910;
+                                                     the true-peak limiter's release is limiter_release_ms as an f32 */
+  int32_t eq_enabled, compressor_enabled, limiter_enabled;  /* OfflineDspBlockProcessor's stage switches, block_processor.rs:31-60 */
+  int32_t compressor_adaptive_release, compressor_sidechain_highpass_enabled, limiter_careful_output_enabled;
+} af_lane_chain_settings;
+/* simulate_auto_eq_chain's defaults (python_api.rs:400-487) with flat bands at the default frequencies (eq.rs:122-138). */
+int af_lane_chain_default_settings(af_lane_chain_settings *out);
+/* OfflineDspBlockProcessor::new per stream (block_processor.rs:31-60): host work only.  limiter_lookahead_ms is the object's
+ * (Limiter::set_lookahead_ms, limiter.rs:154-184) and sets the height of every stream's delay ring.  AF_ERR_INVALID_ARGUMENT for
+ * a null `out`, a sample_rate or limiter_lookahead_ms that is not finite and positive, n_streams <= 0, device < 0.  A stream
+ * that is never configured runs OfflineDspBlockProcessor's defaults: flat EQ, compressor off, limiter at -0.5 dB. */
+int af_lane_chain_create(double sample_rate, int32_t n_streams, double limiter_lookahead_ms, int32_t device, af_lane_chain **out);
+void af_lane_chain_destroy(af_lane_chain *h);
+/* The listed streams become fresh processors with settings[i]: OfflineDspBlockProcessor::new plus the setters in
+ * python_api.rs:400-487's order, which leaves the EQ's coefficient crossfade pending.  Every other stream continues
+ * undisturbed.  Host work only (the streams' columns are uploaded with the next process call).  AF_ERR_INVALID_ARGUMENT, with
+ * nothing changed, for a null pointer, n <= 0, a stream index out of range or listed twice, a value that is not finite. */
+int af_lane_chain_configure(af_lane_chain *h, const int32_t *streams, int32_t n, const af_lane_chain_settings *settings);
+/* OfflineDspBlockProcessor::process_block_inplace (block_processor.rs:106-161) per control block over [n_streams][stride]
+ * float32, n_samples per row; out may equal in.  n_samples == 0 is a no-op.  AF_ERR_INVALID_ARGUMENT before any device work
+ * for a null pointer, n_samples < 0, stride < n_samples.  _host returns when the output is in `out`; _device enqueues on
+ * `hip_stream` (a hipStream_t, NULL = default stream) and keeps no reference to the buffers after the kernel has run; columns
+ * waiting from af_lane_chain_configure / _reset go first on the same stream, through pinned staging, without a host wait.  The
+ * host waits only when the stream differs from the last call's (for that call) or a buffer of the object has to grow.  The
+ * caller's current device is the same after every af_lane_chain_* call as before it. */
+int af_lane_chain_process_host(af_lane_chain *h, const float *in, float *out, int64_t n_samples, int64_t stride);
+int af_lane_chain_process_device(af_lane_chain *h, const float *d_in, float *d_out, int64_t n_samples, int64_t stride,
+                                 void *hip_stream);
+/* Control blocks of the last process call, and their rows as [blocks][n_streams] af_block_stats (BlockStats of
+ * block_processor.rs:106-161, input fields included; capacity in rows; waits for the call). */
+int64_t af_lane_chain_blocks(const af_lane_chain *h);
+int af_lane_chain_read_rows(af_lane_chain *h, af_block_stats *rows, int64_t capacity);
+/* OfflineDspBlockProcessor::new for EVERY stream with its current settings (as af_lane_chain_configure of all streams). */
+int af_lane_chain_reset(af_lane_chain *h);
+/* Samples the stream has processed since it was last configured or reset. */
+int af_lane_chain_samples_processed(const af_lane_chain *h, int32_t stream, int64_t *out);
+int af_lane_chain_last_kernel_ms(af_lane_chain *h, double *ms);
+
 /* ---- second-passage verification, the measurements: python/mic_eq/analysis/voice_setup.py:1446-1679 ---------------------
  * validate_voice_setup_verification renders a second passage and the room tone through the recommended chain and measures both
  * sides.  This object takes what the other analyses leave (the median spectra of the original, the verification and the
